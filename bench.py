@@ -14,11 +14,16 @@ dense slates, 256 slates per GPU by default (the reference's batch_size 64 point
 `--workload fc_listnet` runs configs[1] (FCModel[96] + ListNet).  Weak scaling: every rank gets its own
 `--slates-per-gpu` slates, losses are normalised by the global batch and gradients summed over RCCL.
 
-Prints ONE JSON line (rank 0).  `roofline` describes the dominant hand-written kernel of the step (timed live with
-HIP events on the launch stream, in a side pass after the timed region; FC-only workloads: the whole step against the
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times `--steps` steps and prints the headline (`value`,
+`ms_per_step`, ...); everything else is measured only with `--full`, after the timed region: `roofline` describes the dominant
+hand-written kernel of the step (timed live with HIP events on the launch stream; FC-only workloads: the whole step against the
 HBM roof; NeuralNDCG workloads add `roofline_loss_kernels` against the fp32 vector peak); `cpu_baseline` is the reference step
 restated with the torch CPU operators the reference itself calls (oracle/torch_port.py, kind "port", pinned to the numpy oracle;
-losses it does not cover: the numpy oracle) on a bounded sample of the same workload.
+losses it does not cover: the numpy oracle) on a bounded sample of the same workload; the side points (64 slates, ragged,
+dropout, other arithmetics, end to end, host batches) and, with several ranks, `comm`.
+
+`--dump-outputs DIR` writes what the last timed step computed -- the loss, the scores and the updated parameters -- as
+DIR/<name>.npy (float32, at most 64 MB in all), so that two builds can be compared output for output on identical inputs.
 """
 import argparse
 import json
@@ -457,6 +462,26 @@ def gemm_error_vs_fp64(w, B, L, device, gemm):
     return float(((C_[rows].double() - ref).abs().max() / scale).item())
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(dirpath, arrays, budget=DUMP_BUDGET_BYTES):
+    """Write every tensor of ``arrays`` as DIR/<name>.npy in float32.  If they exceed ``budget`` bytes together, every array
+    keeps the same fraction of its elements: a fixed, seeded choice of flat indices (in increasing order), identical from run to
+    run for the same shapes."""
+    os.makedirs(dirpath, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    room = budget - 4096 * len(host)                         # (headroom for the .npy headers)
+    frac = min(1.0, room / float(total)) if total else 1.0
+    for k, a in host.items():
+        if frac < 1.0:
+            n = max(1, int(a.size * frac))
+            pick = np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))
+            a = a.reshape(-1)[pick]
+        np.save(os.path.join(dirpath, k + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -484,6 +509,10 @@ def main():
                          "8-GPU run exercised on the one GPU a build box has; `comm` is filled in")
     ap.add_argument("--engine", default="fused", choices=["fused", "autograd"],
                     help="fused: explicit hipGraph-captured step (engine.FusedTrainer); autograd: nn.Module + torch autograd/Adam")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the rooflines, kernel times, side points, comm and cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the loss, scores and updated parameters of the last timed step as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -607,11 +636,17 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # before anything below runs another step on this trainer
+        scores = trainer.scores if args.engine == "fused" else trainer.last_scores
+        outs = {"loss": loss, "scores": scores}
+        outs.update(("param." + k, v) for k, v in model.state_dict().items())
+        dump_outputs(args.dump_outputs, outs)
 
     # the roofline kernel (FFN-1 GEMM) timed where it runs: HIP events around its launches inside eager training steps that
     # follow the timed region (same stream, same neighbours, same clocks as the step; a replayed hipGraph has no place for them)
     probe_us, wgrad_us = None, None
-    if args.engine == "fused" and w["N"]:
+    if args.full and args.engine == "fused" and w["N"]:
         use_graph = trainer.use_graph
         trainer.use_graph, trainer.probe, trainer.probe_wgrad = False, [], []
         for i in range(6):
@@ -626,7 +661,7 @@ def main():
 
     # multi-rank: how much of the gradient all-reduce is exposed = timed step - the same step with the collective skipped
     comm = None
-    if (world > 1 or forced) and args.engine == "fused":
+    if args.full and (world > 1 or forced) and args.engine == "fused":
         trainer.comm_enabled = False
         for i in range(2):
             one_step(i)
@@ -653,112 +688,115 @@ def main():
         items = args.steps * B * L * world
         value = items / dt
         fl_item = train_flops_per_item(w, L)
-        kern = time_kernels(w, B, L, device)
-        for kn, kv in kern.items():
-            if kn.endswith("@FFN1") and probe_us is not None and not args.compact:
-                kv["sec_back_to_back"], kv["sec"] = kv["sec"], probe_us * 1e-6
-        # dominant hand-written kernel by time per step
-        name, k = max(kern.items(), key=lambda kv: kv[1]["sec"] * kv[1]["launches_per_step"])
-        if name.startswith("ltrx_gemm"):
-            alg = k["flops"] / k["sec"] / 1e12            # algorithmic: the 2*M*N*K flop of the fp32 GEMM it replaces
-            traffic, traffic_detail = (None, "skipped (--no-side-pass)")
-            if not args.no_side_pass and world == 1 and name.endswith("@FFN1"):
-                traffic, traffic_detail = measure_hbm_traffic(B * L, w["d_ff"], w["fc_sizes"][-1])
-            roof = dict(kernel=name, bound="mfma", achieved=round(alg, 1), peak=PEAK_BF16_MFMA_TFLOPS, unit="TFLOP/s",
-                        frac=round(alg / PEAK_BF16_MFMA_TFLOPS, 4), traffic=traffic,
-                        traffic_detail=traffic_detail,
-                        algorithmic_bytes_per_launch=4.0 * (B * L * w["fc_sizes"][-1] + w["d_ff"] * w["fc_sizes"][-1] + B * L * w["d_ff"]),
-                        traffic_source="live: measure_hbm_traffic() (rocprofv3 --pmc child passes); committed copy of the same passes: profiles/r03_pmc_gemm256.md",
-                        avg_launch_us=round(k["sec"] * 1e6, 1),
-                        timing="HIP events around the %d FFN-1 launches of 5 eager training steps after the timed region" % (5 * w["N"]),
-                        back_to_back_launch_us=round(k.get("sec_back_to_back", k["sec"]) * 1e6, 1),
-                        algorithmic_flops_per_launch=k["flops"], arithmetic="bf16 MFMA, fp32 accumulate, 3 products per fp32 product (split-bf16)",
-                        executed_mfma_tflops=round(3 * alg, 1), executed_frac=round(3 * alg / PEAK_BF16_MFMA_TFLOPS, 4),
-                        vs_exact_fp32_mfma_peak=round(alg / PEAK_FP32_MFMA_TFLOPS, 3))
-        elif "flops" in k:
-            ach = k["flops"] / k["sec"] / 1e12
-            roof = dict(kernel=name, bound="mfma", achieved=round(ach, 2), peak=PEAK_FP32_MFMA_TFLOPS, unit="TFLOP/s",
-                        frac=round(ach / PEAK_FP32_MFMA_TFLOPS, 4), traffic=None,
-                        avg_launch_us=round(k["sec"] * 1e6, 1), algorithmic_flops_per_launch=k["flops"])
-        else:
-            by = k.get("bytes", 12.0 * B * L)
-            ach = by / k["sec"] / 1e9
-            roof = dict(kernel=name, bound="hbm", achieved=round(ach, 1), peak=PEAK_HBM_GBPS, unit="GB/s",
-                        frac=round(ach / PEAK_HBM_GBPS, 4), traffic=None, avg_launch_us=round(k["sec"] * 1e6, 1),
-                        algorithmic_bytes_per_launch=by)
-        if not w["N"]:
-            # FCModel-only workloads (BASELINE configs[1]): 53 kFLOP per item against 552 B -- the HBM roofline binds.  Algorithmic bytes
-            # per step = SURVEY 8(d)'s per-item figure (features once, label, score) x items per step; the step is the two launches of
-            # ltrx_fc_listnet_step (slate-resident forward / loss / backward kernel + partial reduce with Adam), timed with HIP events
-            # on the launch stream over steps that follow the timed region
-            by = float(4 * w["n_features"] + 8) * B * L
-            fcstep = bool(getattr(trainer, "fcstep", False))
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            for i in range(20):
-                one_step(args.warmup + args.steps + i)
-            e1.record()
-            torch.cuda.synchronize()
-            step_us = e0.elapsed_time(e1) / 20 * 1e3
-            traffic, traffic_detail = (None, "skipped")
-            if fcstep and not args.no_side_pass and world == 1:
-                traffic, traffic_detail = measure_hbm_traffic(0, 0, 0, script="fc_one.py", kernels=("ltrx_fc_listnet_kernel", "ltrx_fc_reduce_kernel"),
-                                                              env_extra=dict(FB=str(B), FL=str(L), FF=str(w["n_features"]), FH=str(w["fc_sizes"][0])))
-            ach = by / (step_us * 1e-6) / 1e9
-            roof = dict(kernel=("ltrx_fc_listnet_kernel + ltrx_fc_reduce_kernel (the whole step: two launches; per-kernel split in "
-                                "profiles/r04_bench_fc_listnet_kernel_stats.md)" if fcstep else
-                                "whole step (FC GEMMs + score head + ListNet + Adam: ~15 launches)"),
-                        bound="hbm", achieved=round(ach, 1), peak=PEAK_HBM_GBPS, unit="GB/s", frac=round(ach / PEAK_HBM_GBPS, 4),
-                        traffic=traffic, traffic_detail=traffic_detail, algorithmic_bytes_per_launch=by, avg_launch_us=round(step_us, 1),
-                        timing="HIP events around 20 training steps after the timed region (both launches of a step)",
-                        host_bound_note="wall-clock per step in the timed region: %.1f us" % (dt / args.steps * 1e6))
-        wg_roof = None
-        if wgrad_us:
-            d_, dff_ = w["fc_sizes"][-1], w["d_ff"]
-            flw = 2.0 * B * L * (3 * d_ * d_ + d_ * d_ + 2 * d_ * dff_)          # 2 M (N K) summed over the four projections of a layer
-            tfw = flw / (wgrad_us * 1e-6) / 1e12
-            wg_roof = dict(kernel="ltrx_gemm_tn256_kernel (ltrx_gemm_tn_group: the four weight gradients of an encoder layer in one launch)",
-                           bound="mfma", achieved=round(tfw, 1), peak=PEAK_BF16_MFMA_TFLOPS, unit="TFLOP/s", frac=round(tfw / PEAK_BF16_MFMA_TFLOPS, 4),
-                           executed_mfma_tflops=round(3 * tfw, 1), executed_frac=round(3 * tfw / PEAK_BF16_MFMA_TFLOPS, 4),
-                           avg_launch_us=round(wgrad_us, 1), launches_per_step=w["N"], algorithmic_flops_per_launch=flw,
-                           algorithmic_bytes_per_launch=4.0 * B * L * (8 * d_ + 2 * dff_),     # dY and X of the four problems, read once
-                           timing="HIP events around the grouped launch inside 5 eager training steps after the timed region")
-        att_roof = None
-        if w["N"] and "ltrx_mha_fwd (res split-bf16)" in kern:
-            # the attention kernels against the matrix-core roof: algorithmic flops 4 L^2 d_k per (slate, head)
-            # forward, 10 L^2 d_k backward (five tile products: S, dP, dV, dK in the dK/dV kernel, dQ in the second kernel), each
-            # contraction executed as 3 bf16 MFMA products; HBM side: the compulsory tensors and the dS hand-over between the two
-            # backward kernels (fp32 [B, h, LK, LK], written once and read once).  Timed back to back after the timed region.
-            d_, h_ = w["fc_sizes"][-1], w["h"]
-            LK = (L + 63) // 64 * 64
-            kf, kb = kern["ltrx_mha_fwd (res split-bf16)"], kern["ltrx_mha_bwd (dq+dkdv, res split-bf16)"]
-            def _ar(k_, io_bytes, extra=None):
-                tf = k_["flops"] / k_["sec"] / 1e12
-                r_ = dict(avg_launch_us=round(k_["sec"] * 1e6, 1), algorithmic_flops_per_launch=k_["flops"], achieved=round(tf, 1), unit="TFLOP/s",
-                          peak=PEAK_BF16_MFMA_TFLOPS, frac=round(tf / PEAK_BF16_MFMA_TFLOPS, 4), executed_mfma_tflops=round(3 * tf, 1),
-                          executed_frac=round(3 * tf / PEAK_BF16_MFMA_TFLOPS, 4), algorithmic_bytes_per_launch=io_bytes,
-                          hbm_gbps_if_compulsory_only=round(io_bytes / k_["sec"] / 1e9, 1))
-                r_.update(extra or {})
-                return r_
-            ds_b = 2.0 * 4.0 * B * h_ * LK * LK
-            att_roof = dict(bound="mfma (issue-side: the softmax / split arithmetic and the LDS fragment reads ADD to the matrix time, they do not hide behind it)", launches_per_step=w["N"],
-                            forward=_ar(kf, 4.0 * B * L * 4 * d_ + 4.0 * B * h_ * L),
-                            backward=_ar(kb, 4.0 * B * L * 8 * d_ + 4.0 * B * h_ * L,
-                                         dict(ds_handover_bytes=ds_b, hbm_gbps_with_ds_handover=round((4.0 * B * L * 8 * d_ + ds_b) / kb["sec"] / 1e9, 1),
-                                              kernels="ltrx_mha_bwd_dkdv_res_kernel + ltrx_mha_bwd_dq_res_kernel")),
-                            notes="profiles/r06_attention_forward_experiments.md (round 6: the tile period is the SUM of its MFMA, vector, LDS and staging parts; 64-query forward and phase shift slower; instruction diet: forward 182 -> 162 us, dK/dV 343 -> 325 us), profiles/r04_pmc_step_bytes_256.md (PMC traffic of both backward kernels), profiles/NOTES.md (chunked / 24-bit dS hand-over: measured slower)")
-        loss_roof = None
-        if w["loss"].startswith("neuralNDCG"):
-            # the Sinkhorn kernels are VALU bound (no contraction): algorithmic flops = n^2 x (4 per forward step + 6 per backward step)
-            # x max_iter + ~10 n^2 for NeuralSort / softmax and its backward, against the fp32 vector peak
-            it_ = int(w.get("loss_args", {}).get("max_iter", 50))
-            fl = float(B) * L * L * (10.0 * it_ + 10.0)
-            sec = kern["loss_fwd_bwd"]["sec"]
-            loss_roof = dict(kernel="ltrx_neural_forward_blk_kernel + ltrx_neural_backward_blk_kernel (whole plugin call)", bound="valu",
-                             achieved=round(fl / sec / 1e12, 2), peak=PEAK_FP32_MFMA_TFLOPS, unit="TFLOP/s",
-                             frac=round(fl / sec / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4), algorithmic_flops_per_launch=fl,
-                             avg_launch_us=round(sec * 1e6, 1))
+        roof = wg_roof = att_roof = loss_roof = None
+        kern = {}
+        if args.full:
+            kern = time_kernels(w, B, L, device)
+            for kn, kv in kern.items():
+                if kn.endswith("@FFN1") and probe_us is not None and not args.compact:
+                    kv["sec_back_to_back"], kv["sec"] = kv["sec"], probe_us * 1e-6
+            # dominant hand-written kernel by time per step
+            name, k = max(kern.items(), key=lambda kv: kv[1]["sec"] * kv[1]["launches_per_step"])
+            if name.startswith("ltrx_gemm"):
+                alg = k["flops"] / k["sec"] / 1e12            # algorithmic: the 2*M*N*K flop of the fp32 GEMM it replaces
+                traffic, traffic_detail = (None, "skipped (--no-side-pass)")
+                if not args.no_side_pass and world == 1 and name.endswith("@FFN1"):
+                    traffic, traffic_detail = measure_hbm_traffic(B * L, w["d_ff"], w["fc_sizes"][-1])
+                roof = dict(kernel=name, bound="mfma", achieved=round(alg, 1), peak=PEAK_BF16_MFMA_TFLOPS, unit="TFLOP/s",
+                            frac=round(alg / PEAK_BF16_MFMA_TFLOPS, 4), traffic=traffic,
+                            traffic_detail=traffic_detail,
+                            algorithmic_bytes_per_launch=4.0 * (B * L * w["fc_sizes"][-1] + w["d_ff"] * w["fc_sizes"][-1] + B * L * w["d_ff"]),
+                            traffic_source="live: measure_hbm_traffic() (rocprofv3 --pmc child passes); committed copy of the same passes: profiles/r03_pmc_gemm256.md",
+                            avg_launch_us=round(k["sec"] * 1e6, 1),
+                            timing="HIP events around the %d FFN-1 launches of 5 eager training steps after the timed region" % (5 * w["N"]),
+                            back_to_back_launch_us=round(k.get("sec_back_to_back", k["sec"]) * 1e6, 1),
+                            algorithmic_flops_per_launch=k["flops"], arithmetic="bf16 MFMA, fp32 accumulate, 3 products per fp32 product (split-bf16)",
+                            executed_mfma_tflops=round(3 * alg, 1), executed_frac=round(3 * alg / PEAK_BF16_MFMA_TFLOPS, 4),
+                            vs_exact_fp32_mfma_peak=round(alg / PEAK_FP32_MFMA_TFLOPS, 3))
+            elif "flops" in k:
+                ach = k["flops"] / k["sec"] / 1e12
+                roof = dict(kernel=name, bound="mfma", achieved=round(ach, 2), peak=PEAK_FP32_MFMA_TFLOPS, unit="TFLOP/s",
+                            frac=round(ach / PEAK_FP32_MFMA_TFLOPS, 4), traffic=None,
+                            avg_launch_us=round(k["sec"] * 1e6, 1), algorithmic_flops_per_launch=k["flops"])
+            else:
+                by = k.get("bytes", 12.0 * B * L)
+                ach = by / k["sec"] / 1e9
+                roof = dict(kernel=name, bound="hbm", achieved=round(ach, 1), peak=PEAK_HBM_GBPS, unit="GB/s",
+                            frac=round(ach / PEAK_HBM_GBPS, 4), traffic=None, avg_launch_us=round(k["sec"] * 1e6, 1),
+                            algorithmic_bytes_per_launch=by)
+            if not w["N"]:
+                # FCModel-only workloads (BASELINE configs[1]): 53 kFLOP per item against 552 B -- the HBM roofline binds.  Algorithmic bytes
+                # per step = SURVEY 8(d)'s per-item figure (features once, label, score) x items per step; the step is the two launches of
+                # ltrx_fc_listnet_step (slate-resident forward / loss / backward kernel + partial reduce with Adam), timed with HIP events
+                # on the launch stream over steps that follow the timed region
+                by = float(4 * w["n_features"] + 8) * B * L
+                fcstep = bool(getattr(trainer, "fcstep", False))
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                for i in range(20):
+                    one_step(args.warmup + args.steps + i)
+                e1.record()
+                torch.cuda.synchronize()
+                step_us = e0.elapsed_time(e1) / 20 * 1e3
+                traffic, traffic_detail = (None, "skipped")
+                if fcstep and not args.no_side_pass and world == 1:
+                    traffic, traffic_detail = measure_hbm_traffic(0, 0, 0, script="fc_one.py", kernels=("ltrx_fc_listnet_kernel", "ltrx_fc_reduce_kernel"),
+                                                                  env_extra=dict(FB=str(B), FL=str(L), FF=str(w["n_features"]), FH=str(w["fc_sizes"][0])))
+                ach = by / (step_us * 1e-6) / 1e9
+                roof = dict(kernel=("ltrx_fc_listnet_kernel + ltrx_fc_reduce_kernel (the whole step: two launches; per-kernel split in "
+                                    "profiles/r04_bench_fc_listnet_kernel_stats.md)" if fcstep else
+                                    "whole step (FC GEMMs + score head + ListNet + Adam: ~15 launches)"),
+                            bound="hbm", achieved=round(ach, 1), peak=PEAK_HBM_GBPS, unit="GB/s", frac=round(ach / PEAK_HBM_GBPS, 4),
+                            traffic=traffic, traffic_detail=traffic_detail, algorithmic_bytes_per_launch=by, avg_launch_us=round(step_us, 1),
+                            timing="HIP events around 20 training steps after the timed region (both launches of a step)",
+                            host_bound_note="wall-clock per step in the timed region: %.1f us" % (dt / args.steps * 1e6))
+            wg_roof = None
+            if wgrad_us:
+                d_, dff_ = w["fc_sizes"][-1], w["d_ff"]
+                flw = 2.0 * B * L * (3 * d_ * d_ + d_ * d_ + 2 * d_ * dff_)          # 2 M (N K) summed over the four projections of a layer
+                tfw = flw / (wgrad_us * 1e-6) / 1e12
+                wg_roof = dict(kernel="ltrx_gemm_tn256_kernel (ltrx_gemm_tn_group: the four weight gradients of an encoder layer in one launch)",
+                               bound="mfma", achieved=round(tfw, 1), peak=PEAK_BF16_MFMA_TFLOPS, unit="TFLOP/s", frac=round(tfw / PEAK_BF16_MFMA_TFLOPS, 4),
+                               executed_mfma_tflops=round(3 * tfw, 1), executed_frac=round(3 * tfw / PEAK_BF16_MFMA_TFLOPS, 4),
+                               avg_launch_us=round(wgrad_us, 1), launches_per_step=w["N"], algorithmic_flops_per_launch=flw,
+                               algorithmic_bytes_per_launch=4.0 * B * L * (8 * d_ + 2 * dff_),     # dY and X of the four problems, read once
+                               timing="HIP events around the grouped launch inside 5 eager training steps after the timed region")
+            att_roof = None
+            if w["N"] and "ltrx_mha_fwd (res split-bf16)" in kern:
+                # the attention kernels against the matrix-core roof: algorithmic flops 4 L^2 d_k per (slate, head)
+                # forward, 10 L^2 d_k backward (five tile products: S, dP, dV, dK in the dK/dV kernel, dQ in the second kernel), each
+                # contraction executed as 3 bf16 MFMA products; HBM side: the compulsory tensors and the dS hand-over between the two
+                # backward kernels (fp32 [B, h, LK, LK], written once and read once).  Timed back to back after the timed region.
+                d_, h_ = w["fc_sizes"][-1], w["h"]
+                LK = (L + 63) // 64 * 64
+                kf, kb = kern["ltrx_mha_fwd (res split-bf16)"], kern["ltrx_mha_bwd (dq+dkdv, res split-bf16)"]
+                def _ar(k_, io_bytes, extra=None):
+                    tf = k_["flops"] / k_["sec"] / 1e12
+                    r_ = dict(avg_launch_us=round(k_["sec"] * 1e6, 1), algorithmic_flops_per_launch=k_["flops"], achieved=round(tf, 1), unit="TFLOP/s",
+                              peak=PEAK_BF16_MFMA_TFLOPS, frac=round(tf / PEAK_BF16_MFMA_TFLOPS, 4), executed_mfma_tflops=round(3 * tf, 1),
+                              executed_frac=round(3 * tf / PEAK_BF16_MFMA_TFLOPS, 4), algorithmic_bytes_per_launch=io_bytes,
+                              hbm_gbps_if_compulsory_only=round(io_bytes / k_["sec"] / 1e9, 1))
+                    r_.update(extra or {})
+                    return r_
+                ds_b = 2.0 * 4.0 * B * h_ * LK * LK
+                att_roof = dict(bound="mfma (issue-side: the softmax / split arithmetic and the LDS fragment reads ADD to the matrix time, they do not hide behind it)", launches_per_step=w["N"],
+                                forward=_ar(kf, 4.0 * B * L * 4 * d_ + 4.0 * B * h_ * L),
+                                backward=_ar(kb, 4.0 * B * L * 8 * d_ + 4.0 * B * h_ * L,
+                                             dict(ds_handover_bytes=ds_b, hbm_gbps_with_ds_handover=round((4.0 * B * L * 8 * d_ + ds_b) / kb["sec"] / 1e9, 1),
+                                                  kernels="ltrx_mha_bwd_dkdv_res_kernel + ltrx_mha_bwd_dq_res_kernel")),
+                                notes="profiles/r06_attention_forward_experiments.md (round 6: the tile period is the SUM of its MFMA, vector, LDS and staging parts; 64-query forward and phase shift slower; instruction diet: forward 182 -> 162 us, dK/dV 343 -> 325 us), profiles/r04_pmc_step_bytes_256.md (PMC traffic of both backward kernels), profiles/NOTES.md (chunked / 24-bit dS hand-over: measured slower)")
+            loss_roof = None
+            if w["loss"].startswith("neuralNDCG"):
+                # the Sinkhorn kernels are VALU bound (no contraction): algorithmic flops = n^2 x (4 per forward step + 6 per backward step)
+                # x max_iter + ~10 n^2 for NeuralSort / softmax and its backward, against the fp32 vector peak
+                it_ = int(w.get("loss_args", {}).get("max_iter", 50))
+                fl = float(B) * L * L * (10.0 * it_ + 10.0)
+                sec = kern["loss_fwd_bwd"]["sec"]
+                loss_roof = dict(kernel="ltrx_neural_forward_blk_kernel + ltrx_neural_backward_blk_kernel (whole plugin call)", bound="valu",
+                                 achieved=round(fl / sec / 1e12, 2), peak=PEAK_FP32_MFMA_TFLOPS, unit="TFLOP/s",
+                                 frac=round(fl / sec / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4), algorithmic_flops_per_launch=fl,
+                                 avg_launch_us=round(sec * 1e6, 1))
         out = {
             "metric": "slate-items/sec training (WEB30K synth, slate 240)", "value": round(value, 1),
             "unit": "slate-items/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -781,9 +819,9 @@ def main():
             "roofline_weight_gradient": wg_roof,
             "roofline_attention": att_roof,
             "roofline_loss_kernels": loss_roof,
-            "kernel_times_us": {n: round(v["sec"] * 1e6, 1) for n, v in kern.items()},
+            "kernel_times_us": {n: round(v["sec"] * 1e6, 1) for n, v in kern.items()} if args.full else None,
         }
-        if world == 1 and B != 64 and args.engine == "fused" and not args.no_side_pass:
+        if args.full and world == 1 and B != 64 and args.engine == "fused" and not args.no_side_pass:
             try:
                 m64 = build_model(w, device, args.dropout)
                 t64 = FusedTrainer(m64, w["loss"], w.get("loss_args", {}), 64, L, lr=1e-3, world_size=1, use_graph=True, gemm=args.gemm)
@@ -797,7 +835,7 @@ def main():
                 out["value_at_64_slates_per_gpu"] = round(20 * 64 * L / (time.perf_counter() - t0), 1)
             except Exception as e:      # never let the side measurement break the contract line
                 out["value_at_64_slates_per_gpu"] = "failed: %r" % (e,)
-        if world == 1 and w["N"] and args.engine == "fused" and not args.no_side_pass and not args.ragged and args.dropout == 0.0:
+        if args.full and world == 1 and w["N"] and args.engine == "fused" and not args.no_side_pass and not args.ragged and args.dropout == 0.0:
             # "a second number uses WEB30K-like lengths counting VALID items only" and the shipped configs train with
             # dropout 0.1 (reproducibility/configs/neuralndcg_web30k/approxndcg.json) -- both measured inside the default run, so the
             # driver's record carries them: (i) ragged slates (lognormal lengths, ~47 % of the slots valid) through the variable-length
@@ -837,7 +875,7 @@ def main():
                 del td, md
             except Exception as e:
                 out["value_dropout_0.1"] = "failed: %r" % (e,)
-        if world == 1 and not w["N"] and args.engine == "fused" and not args.no_side_pass:
+        if args.full and world == 1 and not w["N"] and args.engine == "fused" and not args.no_side_pass:
             try:           # the large-batch point ("and a large-batch point, e.g. 2048/GPU"): 8 slates per workgroup
                 Bl = 2048
                 xl, yl, il = synth_batch(2 * Bl, L, w["n_features"], 4242, device)
@@ -906,7 +944,7 @@ def main():
             except Exception as e:
                 out["value_gemm_launch_sequence"] = "failed: %r" % (e,)
         out["comm"] = comm
-        if world == 1 and not args.no_side_pass:
+        if args.full and world == 1 and not args.no_side_pass:
             try:          # what a caller that hands over HOST batches (the reference's DataLoader, train_utils.py:95) would add per step
                 hx, hy, hi = (t[:B].cpu().pin_memory() for t in (x, y, idx))
                 dx, dy, di = torch.empty_like(x[:B]), torch.empty_like(y[:B]), torch.empty_like(idx[:B])
@@ -925,7 +963,7 @@ def main():
                                        "note": "pinned host memory -> HBM of one batch (features, labels, indices); `value` itself is measured with the batch resident in HBM"}
             except Exception as e:
                 out["host_batches"] = "failed: %r" % (e,)
-        if world == 1 and args.engine == "fused" and not args.no_side_pass and not args.ragged and L == 240 and w["n_features"] <= 136:
+        if args.full and world == 1 and args.engine == "fused" and not args.no_side_pass and not args.ragged and L == 240 and w["n_features"] <= 136:
             # VERDICT r5 item 1 / SURVEY 8(d) "time the reference's own loop once": the drop-in path END TO END -- what an unmodified
             # main.py runs after install(fit=True): libsvm files -> device parse -> HBM-resident slates -> DeviceLoader -> fit().
             # (i) a WEB30K-shaped ragged job (2048 queries, lognormal lengths): valid items/s over the training pass, beside
@@ -950,13 +988,13 @@ def main():
                 out["end_to_end_main_items_per_s"] = "failed: %r" % (e,)
             finally:
                 shutil.rmtree(e2e_dir, ignore_errors=True)
-        if w["N"] and args.engine == "fused":
+        if args.full and w["N"] and args.engine == "fused":
             try:                               # measured arithmetic error of the benchmarked GEMM (and of the alternatives)
                 out["gemm_max_rel_err_vs_fp64"] = {g_: gemm_error_vs_fp64(w, B, L, device, g_) for g_ in
                                                    sorted({args.gemm, "split_bf16_strict", "hipblaslt", "bf16"})}
             except Exception as e:
                 out["gemm_max_rel_err_vs_fp64"] = "failed: %r" % (e,)
-        if world == 1 and args.engine == "fused" and w["N"] and not args.no_side_pass and not args.compact:
+        if args.full and world == 1 and args.engine == "fused" and w["N"] and not args.no_side_pass and not args.compact:
             for key, gm in (("value_strict_fp32", "split_bf16_strict"), ("value_hipblaslt_fp32", "hipblaslt")):
                 if gm == args.gemm:
                     continue
@@ -974,7 +1012,7 @@ def main():
                     del t2, m2
                 except Exception as e:
                     out[key] = "failed: %r" % (e,)
-        if world == 1 and args.engine == "fused" and w["N"] and not args.no_side_pass and not args.compact and args.gemm == "split_bf16":
+        if args.full and world == 1 and args.engine == "fused" and w["N"] and not args.no_side_pass and not args.compact and args.gemm == "split_bf16":
             # SURVEY.md §8(d) "strict fp32 mode for parity, bf16 mode for throughput ... report both": the same step with ONE bf16
             # product per contraction (GEMMs + attention).  Its loss error is measured here against the parity arithmetic at
             # identical weights (same seed -> same initial model, first step of the same batch); it is NOT `value`.
@@ -1001,7 +1039,7 @@ def main():
                 del ta, tb, ma, mb
             except Exception as e:
                 out["throughput_mode_bf16"] = "failed: %r" % (e,)
-        if world == 1 and args.engine == "fused" and w["N"] and not args.no_side_pass and not args.compact:
+        if args.full and world == 1 and args.engine == "fused" and w["N"] and not args.no_side_pass and not args.compact:
             # the PLAIN drop-in: allrank_amd.install() without fit=True -- the reference's own loss_batch (train_utils.py:18-29):
             # nn.Module forward, torch autograd, torch.optim.Adam -- around the same HIP kernels (ops.linear / feed_forward /
             # attention_packed / layer_norm / the fused loss)
@@ -1021,7 +1059,7 @@ def main():
                 del t3, o3, m3
             except Exception as e:
                 out["value_plain_dropin_autograd"] = "failed: %r" % (e,)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(w, L)
             if args.engine == "fused" and not args.no_side_pass and not args.ragged and L == 240 and w["n_features"] <= 136:
                 out["cpu_baseline"]["reference_loader"] = reference_loader_leg(w, B, L, device, args.gemm, out.get("end_to_end_main"))

@@ -1,12 +1,16 @@
 """The torch restatement of FixLength / ToTensor inside allrank_amd/data.py (``DeviceSlates.batch_torch``; device-agnostic torch
 ops) == allrank/data/dataset_loading.py:19-93, checked on CPU tensors.  The product path (``DeviceSlates.batch`` -> the HIP kernels of
 ltrx_data.hip) is compared with this restatement on the GPU (tests/test_gpu_data.py) and refuses CPU tensors."""
+import os
+
 import numpy as np
 import pytest
 import torch
 
 from allrank_amd.data import DeviceSlates
-from oracle.ref_loader import reference_available
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "cpu_golden.npz")
+FIXLENGTH_L = 64
 
 
 def _batches(ds, batch_size, slate_length=None, shuffle=False, generator=None):
@@ -89,22 +93,19 @@ def test_epoch_iterator_covers_every_slate_once():
     assert xv.shape == (40, 50, 6)
 
 
-@pytest.mark.skipif(not reference_available(), reason="reference tree only exists in the build container")
 def test_against_reference_fixlength_pad_and_libsvm_roundtrip(tmp_path):
-    from oracle.ref_loader import load_reference
-    load_reference()
-    from allrank.data.dataset_loading import FixLength, ToTensor
+    """the reference's FixLength + ToTensor of these slates (dataset_loading.py:19-93) are stored in tests/golden/cpu_golden.npz
+    (tests/golden/make_golden_cpu.py)"""
     from sklearn.datasets import dump_svmlight_file
+    g = np.load(GOLDEN, allow_pickle=False)
     X, y, qid, lens = _toy(seed=4, n_q=12)
     path = str(tmp_path / "train.txt")
     dump_svmlight_file(X, y, path, query_id=qid)
     ds = DeviceSlates.from_svm_file(path, device="cpu")
-    L = 64
+    L = FIXLENGTH_L
     xb, yb, idx = next(_batches(ds, 12, L))
-    off = np.concatenate([[0], np.cumsum(lens)])
-    fl, tt = FixLength(L), ToTensor()
     for s in range(12):
-        rx, ry, ri = tt(fl((X[off[s]:off[s + 1]].astype(np.float64), y[off[s]:off[s + 1]], None)))
+        rx, ry, ri = (torch.from_numpy(g["fixlength.%d.%s" % (s, k)]) for k in "xyi")
         assert torch.allclose(xb[s], rx, atol=1e-6) and torch.equal(yb[s], ry) and torch.equal(idx[s], ri)
 
 

@@ -3,7 +3,7 @@ names of allrank/data/dataset_loading.py:197-248 / main.py:8,57-68.
 
 CPU half (no GPU here):
   * oracle/loader_oracle.py (the restated host loader the GPU tests and the bench compare with) == the reference's own loaders, every
-    batch of two epochs bit for bit, padding and sampling branch, under main.py:36-38's seeds            [needs /root/reference]
+    batch of two epochs bit for bit, padding and sampling branch, under main.py:36-38's seeds (stored: tests/golden/cpu_golden.npz)
   * DeviceLoader's batch ORDER, its draws from torch's global generator, ``burn()`` and the rank blocks == the reference loader's
     behaviour.  The batch assembly itself is the HIP kernels' job (tests/test_gpu_loader.py); here the torch restatement
     ``DeviceSlates.batch_torch`` (pinned to the reference's FixLength by tests/test_data_cpu.py) is injected in their place.
@@ -75,15 +75,17 @@ def _same(a, b, canon=False):
             assert s.dtype == t.dtype and s.shape == t.shape and torch.equal(s.cpu(), t.cpu())
 
 
-@pytest.mark.skipif(not reference_available(), reason="needs a checkout of allegro/allRank (ALLRANK_REFERENCE)")
-@pytest.mark.parametrize("slate_length", [40, 12])          # 40: padding only; 12: sampling branch incl. the relevance rules
+LOADER_SLATE_LENGTHS = [40, 12]                              # 40: padding only; 12: sampling branch incl. the relevance rules
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "cpu_golden.npz")
+
+
+@pytest.mark.parametrize("slate_length", LOADER_SLATE_LENGTHS)
 def test_oracle_loader_equals_the_reference_loader(tmp_path, slate_length):
-    from oracle.ref_loader import load_reference
-    load_reference(stable_sort=False)
-    import allrank.data.dataset_loading as RD
+    """every batch of the reference's own loaders on this data is stored in tests/golden/cpu_golden.npz (tests/golden/make_golden_cpu.py)"""
+    g = np.load(GOLDEN, allow_pickle=False)
+    ref = [tuple(torch.from_numpy(g["loader%d.%d.%s" % (slate_length, j, k)]) for k in "xyi")
+           for j in range(int(g["loader%d.n" % slate_length]))]
     path = _write(tmp_path, long={3: 33, 8: 12})
-    _seed()
-    ref = _epochs(*RD.create_data_loaders(*RD.load_libsvm_dataset(path, slate_length, "vali"), num_workers=0, batch_size=8))
     _seed()
     mine = _epochs(*LO.create_data_loaders(*LO.load_libsvm_dataset(path, slate_length, "vali"), num_workers=0, batch_size=8))
     _same(ref, mine)

@@ -1,9 +1,12 @@
-"""CPU checks of the model plugin surface: same parameter names/shapes/count as the reference and -- when the
-reference tree is present (build container only) -- bit-identical initial weights under the same seed."""
+"""CPU checks of the model plugin surface: same parameter names/shapes/count as the reference and bit-identical initial
+weights under the same seed (the reference's weights are stored in tests/golden/cpu_golden.npz, tests/golden/make_golden_cpu.py)."""
+import os
+
+import numpy as np
 import pytest
 import torch
 
-from oracle.ref_loader import reference_available
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "cpu_golden.npz")
 
 
 def _engine(cfgkw):
@@ -36,34 +39,33 @@ def test_make_model_mutates_sizes_like_reference():
     assert kw["fc_model"]["sizes"] == [20, 16]                     # model.py:25
 
 
-@pytest.mark.skipif(not reference_available(), reason="reference tree only exists in the build container")
-@pytest.mark.parametrize("kw", [_kw(N=2, h=4, d_ff=64, sizes=(32,), nf=20), _kw(N=0, sizes=(24, 16), nf=20, act="ReLU", norm=True),
-                                _kw(N=1, h=1, d_ff=48, sizes=(24,), nf=12, oact="Sigmoid"),
-                                _kw(N=1, h=2, d_ff=48, sizes=(24,), nf=12, pos=dict(strategy="learned", max_indices=30)),
-                                _kw(N=1, h=2, d_ff=48, sizes=(24,), nf=12, pos=dict(strategy="fixed", max_indices=30))])
+SEED_CONFIGS = [_kw(N=2, h=4, d_ff=64, sizes=(32,), nf=20), _kw(N=0, sizes=(24, 16), nf=20, act="ReLU", norm=True),
+                _kw(N=1, h=1, d_ff=48, sizes=(24,), nf=12, oact="Sigmoid"),
+                _kw(N=1, h=2, d_ff=48, sizes=(24,), nf=12, pos=dict(strategy="learned", max_indices=30)),
+                _kw(N=1, h=2, d_ff=48, sizes=(24,), nf=12, pos=dict(strategy="fixed", max_indices=30))]
+
+
+def position_inputs(kw):
+    """a fixed input of the position module: features [3, 7, d] and item indices with padding (-1) and indices past max_indices"""
+    x = torch.randn(3, 7, kw["fc_model"]["sizes"][-1], generator=torch.Generator().manual_seed(7))
+    idx = torch.tensor([[0, 1, 2, 3, 4, 5, 6], [5, 40, 2, -1, -1, -1, -1], [29, 30, 31, 0, 1, -1, -1]])
+    return x, idx
+
+
+@pytest.mark.parametrize("kw", SEED_CONFIGS)
 def test_same_seed_gives_reference_initial_weights(kw):
     import copy
-    from oracle.ref_loader import load_reference
-    load_reference()
-    from allrank.models.model import make_model as ref_make
-    from allrank.config import TransformerConfig
-    k1, k2 = copy.deepcopy(kw), copy.deepcopy(kw)
-    if k1["transformer"]:
-        from allrank.config import PositionalEncoding
-        if k1["transformer"]["positional_encoding"]:
-            k1["transformer"]["positional_encoding"] = PositionalEncoding(**k1["transformer"]["positional_encoding"])
-        k1["transformer"] = TransformerConfig(**k1["transformer"])
+    i = next(j for j, c in enumerate(SEED_CONFIGS) if c is kw)
+    g = np.load(GOLDEN, allow_pickle=False)
     torch.manual_seed(42)
-    ref = ref_make(**k1)
-    torch.manual_seed(42)
-    eng = _engine(k2)
-    rs, es = ref.state_dict(), eng.state_dict()
-    assert list(rs.keys()) == list(es.keys())
-    for k in rs:
-        assert torch.equal(rs[k], es[k]), k
-    assert [n for n, _ in ref.named_parameters()] == [n for n, _ in eng.named_parameters()]
+    eng = _engine(copy.deepcopy(kw))
+    es = eng.state_dict()
+    assert list(g["model.%d.keys" % i]) == list(es.keys())
+    for j, k in enumerate(es):
+        assert torch.equal(torch.from_numpy(g["model.%d.sd.%d" % (i, j)]), es[k]), k
+    assert list(g["model.%d.params" % i]) == [n for n, _ in eng.named_parameters()]
     if kw["transformer"] and kw["transformer"]["positional_encoding"]:      # the position module computes the same thing
-        x = torch.randn(3, 7, kw["fc_model"]["sizes"][-1])
-        idx = torch.tensor([[0, 1, 2, 3, 4, 5, 6], [5, 40, 2, -1, -1, -1, -1], [29, 30, 31, 0, 1, -1, -1]])
+        x, idx = position_inputs(kw)
+        assert torch.equal(torch.from_numpy(g["model.%d.pos_x" % i]), x)
         mask = idx == -1
-        assert torch.equal(ref.encoder.position(x, mask, idx.clone()), eng.encoder.position(x, mask, idx.clone()))
+        assert torch.equal(torch.from_numpy(g["model.%d.pos_out" % i]), eng.encoder.position(x, mask, idx.clone()))
