@@ -143,10 +143,19 @@ __device__ __forceinline__ int load_slate(const SlateLds& t, const float* __rest
     t.dk[c] = (i < kk) ? 1.0f / log2f((float)i + 2.0f) : 0.f;
   }
   __syncthreads();
+  // Bsum_j = sum_m |s_j - s_m|, compensated (Kahan): the logits (L+1-2i) s_j - Bsum_j subtract two numbers of size ~ L |s|, so at
+  // trained score scales (|s| ~ 30, L = 1024) the error of a plain serial fp32 sum (~ sqrt(L) ulp of Bsum) became a logit error of
+  // ~ 0.05 and a NeuralNDCG gradient 5x further from fp64 than the reference's own (tests/test_gpu_score_scale.py).  The terms are
+  // non-negative, so the compensated sum is within ~1 ulp of Bsum at any L.  contract(off) above keeps the compensation exact.
   for (int j = threadIdx.x; j < n; j += blockDim.x) {
     const float sj = t.sc[j];
-    float a = 0.f;
-    for (int m = 0; m < n; ++m) a += fabsf(sj - t.sc[m]);
+    float a = 0.f, c = 0.f;
+    for (int m = 0; m < n; ++m) {
+      const float v = fabsf(sj - t.sc[m]) - c;
+      const float s = a + v;
+      c = (s - a) - v;
+      a = s;
+    }
     t.bs[j] = a;
   }
   __syncthreads();

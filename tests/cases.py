@@ -135,3 +135,87 @@ def mrr_kats():
             ([[0.2, 0.5], [0.5, 0.2]], [[0.0, 1.0], [0.0, 1.0]], [1, 2], [[1.0, 1.0], [0.0, 0.5]]),
             ([[0.5, 0.2]], [[0.0, 0.0]], [10], [[0.0]]),
             ([[0.5, 0.2, 1.0]], [[1.0, 0.0, P]], [10], [[1.0]]), ([[0.5, 0.2, 1.0]], [[0.0, 1.0, P]], [10], [[0.5]])]
+
+
+# ---- score-scale fixtures (tests/golden/scale_golden.npz, made by make_golden_scale.py) ----
+# A model in training does not emit N(0, 1) scores: the slates above, multiplied by these factors, reach the clamp / eps branches
+# of every listwise loss (sigmoid(alpha * diff) saturating, log(P + eps), q^w >= eps, near one-hot NeuralSort).
+SCALES = (1, 8, 30, 100, 1000)
+# (name, B, L, seed, tie_scores, full case matrix?)
+SCALE_SETS = (("main", 4, 240, 13, False, True), ("ties", 3, 33, 14, True, True), ("outlier", 3, 50, 15, False, True),
+              ("tiny", 6, 3, 16, False, True), ("long", 2, 1024, 17, False, False))
+
+
+def scale_inputs(B, L, seed, ties, name):
+    """the unscaled slate of a set: make_inputs, plus for "outlier" one item per slate 50 above the rest of it"""
+    from tests.golden.make_inputs import make_inputs
+    s, y = make_inputs(B, L, seed, ties)
+    if name == "outlier":
+        for b in range(B):
+            nv = int((y[b] != -1).sum())
+            s[b, (7 * b + 3) % nv] += 50.0
+    return s, y
+
+
+def scale_loss_cases(full):
+    """[(case name, kind, kwargs)] -- the perm of listMLE and the binary labels of binary listNet come from the fixture"""
+    cases = [("listnet", "listnet", {}), ("listmle", "listmle", {}), ("approxndcg.a1", "approxndcg", dict(alpha=1.0))]
+    if full:
+        cases.append(("approxndcg.a2.5", "approxndcg", dict(alpha=2.5)))
+    lam = [(si, None, "sum", "binary") for si in range(len(LAMBDA_SCHEMES))] + [(si, 5, "mean", "natural") for si in range(len(LAMBDA_SCHEMES))]
+    if not full:
+        lam = [(3, None, "sum", "binary"), (4, 5, "mean", "natural")]
+    for si, kk, red, lg in lam:
+        cases.append(("lambda.s%d.k%s.%s.%s" % (si, kk, red, lg), "lambdaloss",
+                      dict(weighing_scheme=LAMBDA_SCHEMES[si], k=kk, reduction=red, reduction_log=lg, sigma=1.3, mu=7.0)))
+    neural = [(tr, tau, kk, True) for tr in (False, True) for tau in (1.0, 0.1) for kk in (None, 5)] + \
+             [(False, 1.0, None, False), (True, 1.0, None, False)]
+    if not full:
+        neural = [(False, 1.0, None, True), (True, 0.1, 5, True)]
+    for tr, tau, kk, pw in neural:
+        cases.append(("neural.t%d.tau%g.k%s.p%d" % (int(tr), tau, kk, int(pw)), "neuralndcg",
+                      dict(transposed=tr, temperature=tau, k=kk, powered_relevancies=pw)))
+    if full:
+        for m, kw in enumerate((dict(), dict(weight_by_diff=True), dict(weight_by_diff_powed=True))):
+            cases.append(("ranknet.m%d" % m, "ranknet", kw))
+        cases.append(("blistnet", "binary_listnet", {}))
+    return cases
+
+
+SCALE_NDCG_ATS = (1, 5, 10)         # + L
+SCALE_MRR_ATS = (1, 10)
+
+
+def iter_scale_cases(gold):
+    """yields (set name, scale, case name, kind, kwargs, s, y, ref_loss, ref_grad): s already multiplied by the scale, y the binary
+    labels for binary listNet; kwargs of listMLE carry the recorded perm"""
+    for name, B, L, seed, ties, full in SCALE_SETS:
+        for sc in SCALES:
+            pre = "%s.x%d." % (name, sc)
+            s, y = gold[pre + "s"], gold[name + ".y"]
+            for cname, kind, kw in scale_loss_cases(full):
+                kw = dict(kw)
+                yy = y
+                if kind == "listmle":
+                    kw["perm"] = gold[name + ".perm"]
+                elif kind == "binary_listnet":
+                    yy = gold[name + ".yb"]
+                yield name, sc, cname, kind, kw, s, yy, gold[pre + cname + ".loss"], gold[pre + cname + ".grad"]
+
+
+def neural_scale_check(loss, grad, ref_loss, ref_grad, loss64, grad64):
+    """the conditioning-aware NeuralNDCG bar at score scale: at |s| >> 1 the NeuralSort logits (L+1-2i) s_j - sum_k |s_j - s_k|
+    cancel and the reference's own fp32 gradient moves away from the fp64 oracle by up to ~10x its largest entry, so the anchor is
+    the fp64 oracle and the bar grows with the reference's own fp32 error:
+        max|g - g64| <= max(5e-4 max|g64|, 4 max|g_ref32 - g64|) + 1e-12,   |l - l64| <= max(1e-5 (1 + |l64|), 4 |l_ref32 - l64|).
+    returns (ok, row of the measured errors)"""
+    import numpy as np
+    g, g64 = np.asarray(grad, np.float64), np.asarray(grad64, np.float64)
+    e_ref = float(np.abs(np.asarray(ref_grad, np.float64) - g64).max())
+    err = float(np.abs(g - g64).max())
+    gbar = max(5e-4 * float(np.abs(g64).max()), 4 * e_ref) + 1e-12
+    l_ref = abs(float(ref_loss) - float(loss64))
+    lerr = abs(float(loss) - float(loss64))
+    lbar = max(1e-5 * (1 + abs(float(loss64))), 4 * l_ref)
+    ok = bool(np.isfinite(g).all() and np.isfinite(loss) and err <= gbar and lerr <= lbar)
+    return ok, dict(gerr=err, gbar=gbar, e_ref=e_ref, g64max=float(np.abs(g64).max()), lerr=lerr, lbar=lbar, l_ref=l_ref)

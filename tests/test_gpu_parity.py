@@ -619,6 +619,54 @@ def test_fused_trainer_matches_oracle_and_autograd_path(loss_name, loss_args, ge
     assert torch.isfinite(s1).all()
 
 
+@pytest.mark.parametrize("gemm", ["split_bf16", "hipblaslt"])
+@pytest.mark.parametrize("loss_name,loss_args", [("approxNDCGLoss", {}), ("listNet", {}),
+                                                  ("lambdaLoss", dict(weighing_scheme="lambdaRank_scheme", k=10)),
+                                                  ("neuralNDCG", dict(temperature=1.0))])
+def test_fused_trainer_matches_oracle_and_autograd_path_at_trained_score_scale(loss_name, loss_args, gemm):
+    """the step above started where training runs: the output layer's weight x 8 puts the initial scores at |s| ~ 30, where the
+    losses' clamp / eps branches are live; step 0 at the 1e-5 bar, the later steps at the same 2e-3 bar"""
+    import copy
+    from allrank_amd import losses as E
+    from allrank_amd.engine import FusedTrainer, Trainer
+    cfg = dict(n_features=20, fc_sizes=[32], fc_activation=None, fc_input_norm=False, N=2, d_ff=64, h=4, output_activation=None)
+    params = M.init_params(cfg, seed=11)
+    params["output_layer.w_1.weight"] = params["output_layer.w_1.weight"] * np.float32(8)
+    rng = np.random.default_rng(12)
+    B, L = 4, 70
+    x = rng.standard_normal((B, L, 20)).astype(np.float32)
+    y = rng.integers(0, 5, (B, L)).astype(np.float32)
+    y[2, 40:] = -1
+    x[2, 40:] = 0
+    s0, _ = M.forward(params, cfg, x, y == -1)
+    smax = float(np.abs(s0[y != -1]).max())
+    assert 20 <= smax <= 40, smax
+    m1 = _make_engine_model(cfg, params)
+    m2 = copy.deepcopy(m1)
+    xt, yt = _t(x), _t(y)
+    ft = FusedTrainer(m1, loss_name, loss_args, B, L, lr=1e-3, use_graph=True, gemm=gemm)
+    lossfn = (lambda s, t: getattr(E, loss_name)(s, t, **loss_args))
+    tr = Trainer(m2, lossfn, torch.optim.Adam(m2.parameters(), lr=1e-3))
+    ofn = {"approxNDCGLoss": lambda s, t: O.approxndcg(s, t), "listNet": lambda s, t: O.listnet(s, t),
+           "lambdaLoss": lambda s, t: O.lambdaloss(s, t, **loss_args), "neuralNDCG": lambda s, t: O.neuralndcg(s, t, **loss_args)}[loss_name]
+    oopt = M.Adam(params, lr=1e-3)
+    rows = []
+    for step in range(5):                       # steps 0,1 eager warm-up, step 2 captures + replays, 3,4 replay
+        lf = float(ft.step(xt, yt).item())
+        la = float(tr.step(xt, yt).item())
+        lo = float(M.train_step(params, cfg, oopt, x, y, ofn)[0])
+        rows.append((lf, la, lo))
+        tol = 1e-5 if step == 0 else 2e-3
+        assert np.isfinite(lf) and abs(lf - la) <= tol * (1 + abs(la)) and abs(lf - lo) <= tol * (1 + abs(lo)), rows
+    _log("fused_trainer_scale_%s_%s" % (loss_name, gemm), dict(max_abs_score=smax, losses=rows))
+    sd1, sd2 = m1.state_dict(), m2.state_dict()
+    for k in sd1:
+        assert (sd1[k] - sd2[k]).abs().max().item() <= 1.01e-2, k
+    with torch.no_grad():
+        s1 = m1.score(xt, yt == -1, None)
+    assert torch.isfinite(s1).all()
+
+
 def test_fused_trainer_fc_only_relu():
     from allrank_amd.engine import FusedTrainer
     cfg = dict(n_features=20, fc_sizes=[24, 16], fc_activation="ReLU", fc_input_norm=False, N=0, d_ff=0, h=1, output_activation=None)
