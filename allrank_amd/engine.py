@@ -118,8 +118,9 @@ class FusedTrainer(object):
         (Round 6: the two opt-in NEGATIVE RESULTS of round 5 -- ``overlap_wgrad`` (fork / join of the weight-gradient launches on a
         second stream: 1-2 % slower, profiles/r05_wgrad_overlap_ab.md) and ``act_images`` (activations as pre-split operand images:
         VALU -6 ... -28 % in the consumers, cycles unchanged, step -1 %, profiles/r05_act_images_ab.md) -- no longer live in this class;
-        tools/lab/patches/r06_engine_overlap_wgrad_act_images.patch re-adds them; the image-form kernel entry points they drove (ltrx_gemm_nt_img,
-        ltrx_gemm_tn_group_img, ltrx_layernorm_fwd_image) stay in the library with their kernel-level bit-identity test.)
+        tools/lab/patches/r06_engine_overlap_wgrad_act_images.patch re-adds them; the image-form kernel entry points that act_images drove
+        (ltrx_gemm_nt_img, ltrx_gemm_tn_group_img, ltrx_layernorm_fwd_image) have left the library too: the patch's act_images half
+        needs the library of commit 68005e3.)
         force_dist=True: see ``self.sharded`` below."""
         import torch.nn as nn
         from . import _lib as LB
