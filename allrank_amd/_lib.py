@@ -59,6 +59,9 @@ SIGNATURES = {
     "ltrx_gather_rows": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _i, _vp]),
     "ltrx_packed_row_index": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "ltrx_scatter_rows": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _vp]),
+    "ltrx_assemble_packed": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "ltrx_gather_rows_cu": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "ltrx_scatter_rows_cu": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "ltrx_transpose_batch": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
     "ltrx_bias_act": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "ltrx_score_head_fwd": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),

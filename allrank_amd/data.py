@@ -260,6 +260,16 @@ class ShardBatch(tuple):
         return self
 
 
+class SlateIds(object):
+    """One batch of ``DeviceLoader.id_batches``: this rank's block of a global batch as slate ids of the resident set ``slates``
+    (``ids``: host int64) with their host item counts (``lengths``, clamped to the slate length) -- plus ``global_slates``,
+    ``offset`` and ``order_tag`` with the meaning they have in ``ShardBatch``."""
+
+    def __init__(self, slates, ids, lengths, global_slates, offset, order_tag):
+        self.slates, self.ids, self.lengths = slates, ids, lengths
+        self.global_slates, self.offset, self.order_tag = int(global_slates), int(offset), int(order_tag)
+
+
 class _SlateIds(torch.utils.data.Dataset):
     """dataset of the numbers 0 .. n-1: a torch DataLoader over it yields the slate ids of every batch, i.e. the sampler /
     batch-sampler behaviour of the reference's loader (dataset_loading.py:245-246) without touching any data"""
@@ -348,6 +358,29 @@ class DeviceLoader(object):
         s, L = self.dataset.slates, self.dataset.slate_length
         valid = float(s.lengths.clamp(max=L).double().sum().item()) / max(1.0, float(s.n_slates) * L)
         return self.batch_size, L, valid
+
+    @property
+    def packable(self):
+        """True when no slate is longer than the loader's slate length -- every non-training role, which the reference pads to its
+        longest slate (:212-227) -- i.e. only FixLength's padding branch changes the content of a batch (a slate of exactly
+        ``slate_length`` items is permuted by the sampling branch; its items, labels and positions are the same)"""
+        return self.dataset.slate_length >= self.dataset.longest_query_length
+
+    def id_batches(self):
+        """The batches of ``__iter__`` -- same generator draws, same slates, same rank blocks -- as ``SlateIds`` instead of assembled
+        tensors: for a consumer that builds the packed batch itself (engine.FusedScorer.run_resident).  Slates keep their stored item
+        order (the padding branch of FixLength)."""
+        from .parallel import shard_slates
+        ds, L = self.dataset, self.dataset.slate_length
+        chunks = [c.to(torch.int64) for c in self._ids]                # the epoch's draws from torch's global generator, as __iter__
+        if ds.samples:
+            np.random.randint(0, 2 ** 31 - 1)                          # ... and the sampling seed __iter__ draws from numpy's
+        weights = torch.arange(1, self.batch_size + 1, dtype=torch.int64)
+        for c in chunks:
+            n = int(c.numel())
+            a, b = shard_slates(n, self.rank, self.world)
+            tag = int((c * weights[:n]).sum().item()) & 0x7FFFFFFFFFFF
+            yield SlateIds(ds.slates, c[a:b], ds.slates.lengths_host[c[a:b]].clamp(max=L), n, a, tag)
 
     def __iter__(self):
         from .parallel import shard_slates

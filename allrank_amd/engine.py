@@ -512,11 +512,12 @@ class FusedTrainer(object):
         x = ((x ^ (x >> 15)) * 0x846CA68B) & 0xFFFFFFFF
         return x ^ (x >> 16)
 
-    def _ln_fwd(self, x, res, a, b, xsum, y, mean, rstd, p=0.0, seed=0):
-        """y = LN(x + drop_p(res)); xsum = x + drop_p(res)"""
+    def _ln_fwd(self, x, res, a, b, xsum, y, mean, rstd, p=0.0, seed=0, rows=None):
+        """y = LN(x + drop_p(res)); xsum = x + drop_p(res)   (over ``rows`` rows, default the step's)"""
         P = self.LB.ptr
-        self.LB.check(self.lib.ltrx_layernorm_fwd(P(x), P(res), P(a), P(b), self.rows, self.d, float(self.ln_eps), P(xsum), P(y),
-                                                  P(mean), P(rstd), float(p), seed, P(self.drop_step), self._st()), "layernorm_fwd")
+        self.LB.check(self.lib.ltrx_layernorm_fwd(P(x), P(res), P(a), P(b), self.rows if rows is None else rows, self.d,
+                                                  float(self.ln_eps), P(xsum), P(y), P(mean), P(rstd), float(p), seed, P(self.drop_step),
+                                                  self._st()), "layernorm_fwd")
 
     def _drop_apply(self, src, dst, p, seed):
         """dst = src * keep-mask/(1-p) of the site (the backward of a dropped branch)"""
@@ -647,12 +648,14 @@ class FusedTrainer(object):
         need = self.lib.ltrx_gemm_nt_relu_bits_bytes(self.rows, self.dff, self.d)
         return buf if 0 < need <= buf.numel() else None
 
-    def _lin_fwd(self, x, w, b, out, act=0, p=0.0, seed=0, res=None, bits=None):
+    def _lin_fwd(self, x, w, b, out, act=0, p=0.0, seed=0, res=None, bits=None, rows=None):
         """out = drop_p(act(x w^T + b)) [+ res]   (nn.Linear forward, act 1 = ReLU; dropout in the epilogue; ``res`` = the
         residual stream of the SublayerConnection this projection closes, transformer.py:98-106: added in the epilogue, so the
-        sum is written once by the GEMM instead of being re-read and re-written by the LayerNorm that follows)"""
+        sum is written once by the GEMM instead of being re-read and re-written by the LayerNorm that follows; ``rows``: the row
+        count of the pass, default the step's)"""
+        M = self.rows if rows is None else rows
         if self.gemm == "hipblaslt":
-            n = self.rows
+            n = M
             torch.addmm(b, x[:n], w.t(), out=out[:n])
             if act == 1:
                 torch.relu_(out[:n])
@@ -663,11 +666,11 @@ class FusedTrainer(object):
             return
         P = self.LB.ptr
         if bits is not None and act == 1:                         # ReLU + its one-bit mask for the backward (act 4)
-            self.LB.check(self.lib.ltrx_gemm_nt(P(x), x.stride(0), P(w), w.stride(0), self._img(w), P(out), out.stride(0), self.rows,
+            self.LB.check(self.lib.ltrx_gemm_nt(P(x), x.stride(0), P(w), w.stride(0), self._img(w), P(out), out.stride(0), M,
                                                 w.shape[0], x.shape[1], P(b), 4, P(bits), 0, float(p), seed, P(self.drop_step), self._prec, 0,
                                                 self._st()), "gemm_nt(fwd, relu bits)")
             return
-        self.LB.check(self.lib.ltrx_gemm_nt(P(x), x.stride(0), P(w), w.stride(0), self._img(w), P(out), out.stride(0), self.rows, w.shape[0],
+        self.LB.check(self.lib.ltrx_gemm_nt(P(x), x.stride(0), P(w), w.stride(0), self._img(w), P(out), out.stride(0), M, w.shape[0],
                                             x.shape[1], P(b), 3 if res is not None else act, P(res), res.stride(0) if res is not None else 0,
                                             float(p), seed, P(self.drop_step), self._prec, 0, self._st()), "gemm_nt(fwd)")
 
@@ -771,86 +774,92 @@ class FusedTrainer(object):
         q.clear()
 
     # ---- the step body (capturable) ----------------------------------------------------------------------------
-    def _forward(self, train=True):
-        """input buffers -> scores (self.scores_raw [B, L, n_out], self.scores [B, L]); ``train=False`` is model.eval(): every
-        dropout rate is 0 (the saved activations are written all the same, nothing reads them).  Returns (feat, sc_rows)."""
+    def _forward(self, train=True, bs=None):
+        """input buffers -> scores (scores_raw [B, L, n_out], scores [B, L]) of the buffer set ``bs``: the step's own buffers (``bs``
+        None = self) or a FusedScorer's (forward-only, packed, its own B / L / row count; the valid-row count is read from its
+        device cu_seqlens).  ``train=False`` is model.eval(): every dropout rate is 0 (the saved activations are written all the same,
+        nothing reads them).  Returns (feat, sc_rows)."""
+        bs = self if bs is None else bs
         P = self.LB.ptr
-        lib, M, d, B, L = self.lib, self.rows, self.d, self.B, self.L
-        kpm = None if self.compact else self.mask                 # packed rows are all valid keys
+        lib, M, d, B, L = self.lib, bs.rows, self.d, bs.B, bs.L
+        kpm = None if bs.compact else bs.mask                     # packed rows are all valid keys
         W = self.W
         fc = self.model.input_layer
         dp = (lambda p: p) if train else (lambda p: 0.0)          # dropout rate of a site in this pass
-        h = self.x_in
+        h = bs.x_in
         if self.in_norm is not None:                              # FCModel.input_norm (model.py:39)
             self.LB.check(lib.ltrx_layernorm_torch_fwd(P(h), P(W(self.in_norm.weight)), P(W(self.in_norm.bias)), M, self.fc_sizes[0],
-                                                       float(self.in_norm.eps), P(self.x_norm), P(self.mean_in), P(self.rstd_in),
+                                                       float(self.in_norm.eps), P(bs.x_norm), P(bs.mean_in), P(bs.rstd_in),
                                                        self._st()), "layernorm_torch_fwd")
-            h = self.x_norm
+            h = bs.x_norm
         for i, lyr in enumerate(fc.layers):
             w_i = W(lyr.weight)
             if i == 0 and self._x_pad:                             # F rounded up to the GEMM's K step: padded rows x padded W_0
-                h, w_i = self.x_in_k, self.w0_pad
+                h, w_i = bs.x_in_k, self.w0_pad
             if self.fc_act >= 3:                                   # Sigmoid / Tanh: GEMM + bias, then the activation in place
-                self._lin_fwd(h, w_i, W(lyr.bias), self.fc_out[i])
-                self.LB.check(lib.ltrx_out_act_fwd(P(self.fc_out[i]), M * self.fc_out[i].shape[1], self.fc_act - 2, P(self.fc_out[i]),
+                self._lin_fwd(h, w_i, W(lyr.bias), bs.fc_out[i], rows=M)
+                self.LB.check(lib.ltrx_out_act_fwd(P(bs.fc_out[i]), M * bs.fc_out[i].shape[1], self.fc_act - 2, P(bs.fc_out[i]),
                                                    self._st()), "fc_act_fwd")
             else:
-                self._lin_fwd(h, w_i, W(lyr.bias), self.fc_out[i], self.fc_act, dp(self.p_fc), self._site(1000 + i))
-            h = self.fc_out[i]
+                self._lin_fwd(h, w_i, W(lyr.bias), bs.fc_out[i], self.fc_act, dp(self.p_fc), self._site(1000 + i), rows=M)
+            h = bs.fc_out[i]
         if self.pos is not None:                                  # transformer.py:51-52: x = sqrt(d) x + pe[rank]
-            self.LB.check(lib.ltrx_posenc_fwd(P(h), P(self._pos_table()), P(self.idx_rows), P(kpm), M, d, self.pos_pad, float(d) ** 0.5,
-                                              P(self.x_pe), self._st()), "posenc_fwd")
-            h = self.x_pe
+            self.LB.check(lib.ltrx_posenc_fwd(P(h), P(self._pos_table()), P(bs.idx_rows), P(kpm), M, d, self.pos_pad, float(d) ** 0.5,
+                                              P(bs.x_pe), self._st()), "posenc_fwd")
+            h = bs.x_pe
         x = h                                                     # residual stream
-        for i, st in enumerate(self.layers):
+        for i, st in enumerate(bs.layers):
             lay = st["mod"]
             n0, n1 = lay.sublayer[0].norm, lay.sublayer[1].norm
-            self._ln_fwd(x, None, W(n0.a_2), W(n0.b_2), None, st["xn0"], st["mean0"], st["rstd0"])
+            self._ln_fwd(x, None, W(n0.a_2), W(n0.b_2), None, st["xn0"], st["mean0"], st["rstd0"], rows=M)
             st["xin"] = x
-            self._lin_fwd(st["xn0"], st["wqkv"], st["bqkv"], st["qkv"])
+            self._lin_fwd(st["xn0"], st["wqkv"], st["bqkv"], st["qkv"], rows=M)
             qkv = st["qkv"]
             self.LB.check(lib.ltrx_mha_fwd(P(qkv), qkv.data_ptr() + 4 * d, qkv.data_ptr() + 8 * d, P(kpm), B, L, self.h,
                                            d // self.h, 3 * d, P(st["o"]), d, P(st["lse"]), dp(st["p_att"]), st["s_att"],
-                                           P(self.drop_step), P(self.cu), P(self.order), self._mha_mode, self._st()), "mha_fwd")
+                                           P(self.drop_step), P(bs.cu), P(bs.order), self._mha_mode, self._st()), "mha_fwd")
             lo = lay.self_attn.linears[3]
             # x1 = x + dropout(attention branch): the residual sum is the out-projection's epilogue (act 3)
-            self._lin_fwd(st["o"], W(lo.weight), W(lo.bias), st["x1"], 0, dp(st["p_s0"]), st["s_s0"], res=x)
-            self._ln_fwd(st["x1"], None, W(n1.a_2), W(n1.b_2), None, st["xn1"], st["mean1"], st["rstd1"])
+            self._lin_fwd(st["o"], W(lo.weight), W(lo.bias), st["x1"], 0, dp(st["p_s0"]), st["s_s0"], res=x, rows=M)
+            self._ln_fwd(st["x1"], None, W(n1.a_2), W(n1.b_2), None, st["xn1"], st["mean1"], st["rstd1"], rows=M)
             ff = lay.feed_forward
             if self.probe is not None and train:                  # bench.py: HIP events around the roofline kernel, in the step
                 ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 ev0.record()
             self._lin_fwd(st["xn1"], W(ff.w_1.weight), W(ff.w_1.bias), st["r"], 1, dp(st["p_ff"]), st["s_ff"],
-                          bits=self._relu_bits(st) if train else None)
+                          bits=self._relu_bits(st) if train else None, rows=M)
             if self.probe is not None and train:
                 ev1.record()
                 self.probe.append((ev0, ev1))
             # x(next layer) = x1 + dropout(feed-forward branch), again in the epilogue of the projection that closes the sublayer
-            nxt = self.layers[i + 1]["xsum0"] if i + 1 < len(self.layers) else self.xsum_f
-            self._lin_fwd(st["r"], W(ff.w_2.weight), W(ff.w_2.bias), nxt, 0, dp(st["p_s1"]), st["s_s1"], res=st["x1"])
+            nxt = bs.layers[i + 1]["xsum0"] if i + 1 < len(bs.layers) else bs.xsum_f
+            self._lin_fwd(st["r"], W(ff.w_2.weight), W(ff.w_2.bias), nxt, 0, dp(st["p_s1"]), st["s_s1"], res=st["x1"], rows=M)
             x = nxt
         out = self.model.output_layer
         if self.N:
             nf = self.enc.norm
-            self._ln_fwd(x, None, W(nf.a_2), W(nf.b_2), None, self.xf, self.mean_f, self.rstd_f)
-            feat = self.xf
+            self._ln_fwd(x, None, W(nf.a_2), W(nf.b_2), None, bs.xf, bs.mean_f, bs.rstd_f, rows=M)
+            feat = bs.xf
         else:
             feat = x
         no = self.n_out
-        sc_rows = self.scores_c if self.compact else self.scores_raw
+        sc_rows = bs.scores_c if bs.compact else bs.scores_raw
         if no == 1:
             self.LB.check(lib.ltrx_score_head_fwd(P(feat), P(W(out.w_1.weight)), P(W(out.w_1.bias)), M, d, P(sc_rows), self._st()),
                           "score_head_fwd")
         else:                                                     # Linear(d, d_output) as a GEMM (model.py:117)
-            self._lin_fwd(feat, W(out.w_1.weight), W(out.w_1.bias), sc_rows.view(-1, no))
+            self._lin_fwd(feat, W(out.w_1.weight), W(out.w_1.bias), sc_rows.view(-1, no), rows=M)
         if self.out_act:                                          # OutputLayer activation (model.py:117), in place
             self.LB.check(lib.ltrx_out_act_fwd(P(sc_rows), M * no, self.out_act, P(sc_rows), self._st()), "out_act_fwd")
-        if self.compact:                                          # packed scores -> the padded [B, L] grid of the loss kernels
+        if bs is not self:                                        # scorer: packed scores -> padded grid, padding 0, count from cu[B]
+            self.LB.check(lib.ltrx_scatter_rows_cu(P(sc_rows), no, P(bs.cu), B, L, no, M, P(bs.scores_raw), no, self._st()),
+                          "scatter_rows_cu")
+        elif self.compact:                                        # packed scores -> the padded [B, L] grid of the loss kernels
             self.scores_raw.zero_()
             self.LB.check(lib.ltrx_scatter_rows(P(self.scores_c), no, P(self.idx), self.n_valid, no, P(self.scores_raw), no, self._st()),
                           "scatter_rows")
         if no > 1:
-            torch.sum(self.scores_raw, dim=-1, out=self.scores)   # model.score (model.py:127)
+            torch.sum(bs.scores_raw, dim=-1, out=bs.scores)       # model.score (model.py:127)
         return feat, sc_rows
 
     def _body(self):
@@ -1309,6 +1318,240 @@ class FusedTrainer(object):
                 self._fwd_only()
         self.graph_fwd.replay()
         return self.scores
+
+    def scorer(self, B, L, use_graph=True, max_graphs=8):
+        """a FusedScorer for validation batches of ``B`` slates padded to ``L`` items (any L up to LTRX_MAX_METRIC_SLATE_LEN)"""
+        return FusedScorer(self, B, L, use_graph=use_graph, max_graphs=max_graphs)
+
+
+def row_bucket(n, cap=None):
+    """The rung of the scorer's row ladder that holds ``n`` packed rows: 32, 64, ..., 256, then steps of max(32, rung // 8 rounded
+    down to a multiple of 32) -- every rung a multiple of 32, each at most 1/8 above the one below from 256 on, so a batch runs at
+    most 31 rows (below 256) or 1/8 of its rows (above) of alignment padding.  ``cap`` (a multiple of 32): the largest rung."""
+    b = 32
+    while b < n:
+        b += max(32, (b // 8) // 32 * 32)
+    return b if cap is None else min(b, cap)
+
+
+class FusedScorer(object):
+    """``model.eval(); model.score(...)`` for batches of up to ``B`` slates padded to ``L`` items -- the validation shape, where the
+    reference pads every slate to the longest one of the set (dataset_loading.py:185-194) -- through the forward kernels of a
+    FusedTrainer (``FusedTrainer._forward`` over this object's buffers), on the VALID rows only:
+
+      * the batch's valid items are packed into consecutive rows (``run_resident``: straight from the resident CSR set,
+        ltrx_assemble_packed -- the padded [B, L, F] features are never written; ``run``: gathered from a padded batch,
+        ltrx_gather_rows_cu), attention runs per slate from cu_seqlens, and the packed scores go back to the padded grid with 0 on
+        padded slots (ltrx_scatter_rows_cu) -- the value compact training leaves there;
+      * the weights are the trainer's (flat parameters, weight images and transposes), re-synced before every call as ``score()``
+        does, so every optimizer step is seen;
+      * nothing is saved for a backward: one encoder layer's activation buffers serve every layer (bytes: ``self.nbytes``);
+      * the row count is rounded up the ladder of ``row_bucket``; the forward of a bucket is captured in a hipGraph after two eager
+        calls at that bucket (``score()``'s warm-up rule) and replayed for every later batch that falls in it -- the kernels read the
+        valid-row count from device memory, so a graph is right for every batch of its bucket.  The graphs form an LRU of
+        ``max_graphs`` buckets: a new bucket beyond that evicts the least recently used one (``evictions`` counts them);
+      * per batch the host only picks the bucket from the host lengths and uploads the B+1 prefix sums, the launch order and the slate
+        ids from pinned staging (a ring of 4, as ``FusedTrainer._pack`` does): no host sync.  ``run`` without host lengths counts
+        the valid items on the device -- one sync, as compact training does.
+    Results (``scores_raw`` [B, L] or [B, L, d_output], ``scores`` [B, L], labels ``y`` [B, L] of ``run_resident``) stay valid until
+    the next call."""
+
+    def __init__(self, trainer, B, L, use_graph=True, max_graphs=8):
+        import collections
+        from . import _lib as LB
+        t = trainer
+        B, L = int(B), int(L)
+        if B <= 0 or L <= 0:
+            raise ValueError("FusedScorer: B and L must be positive")
+        if L > LB.MAX_METRIC_SLATE_LEN:
+            raise ValueError("FusedScorer: slate length %d above LTRX_MAX_METRIC_SLATE_LEN = %d" % (L, LB.MAX_METRIC_SLATE_LEN))
+        self.t, self.LB, self.B, self.L = t, LB, B, L
+        self.compact, self.mask = True, None              # (what FusedTrainer._forward reads of a buffer set)
+        dev = t.dev
+        self.cap = (B * L + 31) // 32 * 32                 # the largest rung: every slot of the batch valid
+        Mc = self.cap
+        f32 = dict(dtype=torch.float32, device=dev)
+        # device staging of one batch: slate ids (i64, as int32 pairs), cu_seqlens [B+1], launch order [B] -- one upload
+        self._stage = torch.zeros(4 * B + 1, dtype=torch.int32, device=dev)
+        self.ids = self._stage[:2 * B].view(torch.int64)
+        self.cu = self._stage[2 * B:3 * B + 1]
+        self.order = self._stage[3 * B + 1:]
+        self._ring = [(torch.zeros(4 * B + 1, dtype=torch.int32).pin_memory(), torch.cuda.Event()) for _ in range(4)]
+        self._turn = 0
+        self.rows, self.n_valid = 32, 0
+        self.idx = torch.full((Mc,), -1, dtype=torch.int32, device=dev)     # packed row -> b * L + j
+        F0 = t.fc_sizes[0]
+        if t._x_pad:                                       # the trainer's first GEMM reads 256-float padded rows and a padded W_0
+            self.x_in_buf = torch.zeros((Mc, t.x_in_buf.shape[1]), **f32)
+            self.x_in = self.x_in_buf[:, :F0]
+            self.x_in_k = self.x_in_buf[:, :t.x_in_k.shape[1]]
+        else:
+            self.x_in = torch.zeros((Mc, F0), **f32)
+        if t.in_norm is not None:
+            self.x_norm = torch.zeros((Mc, F0), **f32)
+            self.mean_in, self.rstd_in = torch.zeros(Mc, **f32), torch.zeros(Mc, **f32)
+        self.fc_out = [torch.zeros((Mc, s), **f32) for s in t.fc_sizes[1:]]
+        if t.pos is not None:
+            self.idx_rows = torch.full((Mc,), -1, dtype=torch.int64, device=dev)
+        d = t.d
+        self.layers = []
+        if t.N:
+            # the residual stream ping-pongs between two buffers (a layer's input is dead once its out-projection has added it);
+            # one LayerNorm output / statistics set serves LN0, LN1 and the final norm (each is consumed before the next is written)
+            ping = [torch.zeros((Mc, d), **f32) for _ in range(2)]
+            xn, mean, rstd = torch.zeros((Mc, d), **f32), torch.zeros(Mc, **f32), torch.zeros(Mc, **f32)
+            act = dict(xn0=xn, xn1=xn, mean0=mean, rstd0=rstd, mean1=mean, rstd1=rstd, qkv=torch.zeros((Mc, 3 * d), **f32),
+                       o=torch.zeros((Mc, d), **f32), x1=torch.zeros((Mc, d), **f32), r=torch.zeros((Mc, t.dff), **f32),
+                       lse=torch.zeros((B, t.h, L), **f32))
+            keys = ("wqkv", "bqkv", "mod", "p_att", "p_ff", "p_s0", "p_s1", "s_att", "s_ff", "s_s0", "s_s1")
+            for i, st in enumerate(t.layers):
+                self.layers.append(dict({k: st[k] for k in keys}, xsum0=ping[i % 2], **act))
+            self.xsum_f = ping[t.N % 2]
+            self.xf, self.mean_f, self.rstd_f = xn, mean, rstd
+            if t.pos is not None:
+                self.x_pe = ping[0]                         # layer 0 reads it and writes ping[1]
+        elif t.pos is not None:
+            self.x_pe = torch.zeros((Mc, d), **f32)
+        no = t.n_out
+        self.scores_c = torch.zeros(Mc if no == 1 else (Mc, no), **f32)
+        self.scores_raw = torch.zeros((B, L) if no == 1 else (B, L, no), **f32)
+        self.scores = self.scores_raw if no == 1 else torch.zeros((B, L), **f32)
+        self.y = torch.full((B, L), float(PADDED_Y_VALUE), **f32)
+        seen, nb = set(), 0
+        for v in list(vars(self).values()) + [v for st in self.layers for v in st.values()]:
+            if torch.is_tensor(v) and v.is_cuda and v.untyped_storage().data_ptr() not in seen:
+                seen.add(v.untyped_storage().data_ptr())
+                nb += v.untyped_storage().nbytes()
+        self.nbytes = nb
+        self.use_graph, self.max_graphs = bool(use_graph), int(max_graphs)
+        self._graphs = collections.OrderedDict()           # row bucket -> captured forward
+        self._visits = collections.Counter()
+        self._pool = None
+        self.evictions = 0
+        self.last_mode = None                              # "eager" / "capture" / "replay" of the last call (tests)
+
+    def _upload(self, ids, lengths):
+        """host lengths (and slate ids) of one batch -> cu_seqlens, longest-first launch order (and ids) on the device through the
+        pinned ring; returns the valid-row count"""
+        B, L = self.B, self.L
+        k = self._turn % len(self._ring)
+        self._turn += 1
+        host, ev = self._ring[k]
+        ev.synchronize()                                   # (the copy that last used this slot has completed)
+        lens = torch.as_tensor(lengths, dtype=torch.int32)
+        if lens.is_cuda:                                   # (a device tensor costs the sync the host lengths are meant to avoid)
+            lens = lens.cpu()
+        lens = lens.reshape(-1)
+        n = int(lens.numel())
+        if n > B:
+            raise ValueError("FusedScorer: %d slates in a batch of a %d-slate scorer" % (n, B))
+        if n and int(lens.max()) > L:
+            raise ValueError("FusedScorer: a slate of %d items in a scorer for slate length %d" % (int(lens.max()), L))
+        full = torch.zeros(B, dtype=torch.int32)
+        full[:n] = lens.clamp(min=0)
+        host[2 * B] = 0
+        torch.cumsum(full, 0, dtype=torch.int32, out=host[2 * B + 1:3 * B + 1])
+        host[3 * B + 1:] = torch.argsort(full, descending=True, stable=True)
+        if ids is not None:
+            h64 = host[:2 * B].view(torch.int64)
+            h64.zero_()                                    # (slates past n: id 0, length 0 -- never read)
+            h64[:n] = torch.as_tensor(ids, dtype=torch.int64).cpu().reshape(-1)
+        self._stage.copy_(host, non_blocking=True)
+        ev.record()
+        return int(host[3 * B])
+
+    def _set_rows(self, n):
+        self.n_valid = n
+        self.rows = row_bucket(max(n, 1), self.cap)
+
+    def _sync(self):
+        self.t._reattach()
+        self.t._sync_weights()
+
+    def run_resident(self, slates, ids, lengths):
+        """scores of the slates ``ids`` (host int64, at most B) of the resident set ``slates`` (a data.DeviceSlates) padded to L;
+        ``lengths``: their item counts (host; every one <= L -- the padding branch of FixLength).  Also fills ``self.y`` with the
+        padded labels.  Returns ``scores_raw``."""
+        P, LB = self.LB.ptr, self.LB
+        t = self.t
+        ids_h = torch.as_tensor(ids, dtype=torch.int64).cpu().reshape(-1)
+        if ids_h.numel() and (int(ids_h.min()) < 0 or int(ids_h.max()) >= slates.n_slates):
+            raise ValueError("FusedScorer.run_resident: slate id outside the set")
+        if slates.n_features != t.fc_sizes[0]:
+            raise ValueError("FusedScorer.run_resident: %d features, the model takes %d" % (slates.n_features, t.fc_sizes[0]))
+        LB.require_device(slates.x_items)
+        self._sync()
+        self._set_rows(self._upload(ids_h, lengths))
+        LB.check(t.lib.ltrx_assemble_packed(P(slates.x_items), P(slates.y_items), P(slates.offsets), P(self.ids), P(self.cu), self.B,
+                                            self.L, slates.n_features, self.rows, P(self.x_in), self.x_in.stride(0), P(self.y),
+                                            P(self.idx), P(self.idx_rows) if t.pos is not None else None, t._st()), "assemble_packed")
+        self._run()
+        return self.scores_raw
+
+    def run(self, xb, yb, indices=None, lengths=None):
+        """scores of a padded batch ``xb`` [n, L, F] (n <= B; valid items first in every slate, labels ``yb`` == -1 on padding, as
+        dataset.py:28-38 pads); ``lengths``: host item counts per slate (None: counted on the device, one host sync).  Returns
+        ``scores_raw``."""
+        P, LB = self.LB.ptr, self.LB
+        t, B, L = self.t, self.B, self.L
+        n_sl = int(xb.shape[0])
+        if n_sl > B or int(xb.shape[1]) != L:
+            raise ValueError("FusedScorer.run: batch %s, scorer for %d slates of %d items" % (tuple(xb.shape), B, L))
+        if t.pos is not None and indices is None:
+            raise ValueError("FusedScorer.run: the model has a positional encoding, run() needs `indices`")
+        xb = xb.to(t.dev, torch.float32).contiguous()
+        yb = yb.to(t.dev, torch.float32)
+        self._sync()
+        if lengths is not None:
+            n = self._upload(None, lengths)
+        else:
+            full = torch.zeros(B, dtype=torch.int32, device=t.dev)
+            full[:n_sl] = (yb != PADDED_Y_VALUE).sum(1, dtype=torch.int32)
+            self.cu[0] = 0
+            torch.cumsum(full, 0, dtype=torch.int32, out=self.cu[1:])
+            self.order.copy_(torch.argsort(full, descending=True, stable=True))
+            n = int(self.cu[B])                            # (host sync: the row count picks the bucket)
+        self._set_rows(n)
+        self.y[:n_sl].copy_(yb)
+        self.y[n_sl:].fill_(float(PADDED_Y_VALUE))
+        F = int(xb.shape[2])
+        LB.check(t.lib.ltrx_gather_rows_cu(P(xb), F, P(self.cu), B, L, F, self.rows, P(self.x_in), self.x_in.stride(0), P(self.idx),
+                                           t._st()), "gather_rows_cu(x)")
+        if t.pos is not None:                              # int64 positions move as pairs of 32-bit words
+            ib = indices.to(t.dev, torch.int64).contiguous()
+            LB.check(t.lib.ltrx_gather_rows_cu(P(ib), 2, P(self.cu), B, L, 2, self.rows, P(self.idx_rows), 2, None, t._st()),
+                     "gather_rows_cu(indices)")
+            self.idx_rows[n:self.rows].fill_(-1)           # alignment rows -> the padding position
+        self._run()
+        return self.scores_raw
+
+    def _run(self):
+        t, key = self.t, self.rows
+        if not self.use_graph:
+            self.last_mode = "eager"
+            t._forward(False, self)
+            return
+        g = self._graphs.get(key)
+        if g is None:
+            self._visits[key] += 1
+            if self._visits[key] <= 2:                     # warm-up outside capture (lazy module loads, kernel attributes)
+                self.last_mode = "eager"
+                t._forward(False, self)
+                return
+            if len(self._graphs) >= self.max_graphs:
+                self._graphs.popitem(last=False)
+                self.evictions += 1
+            if self._pool is None:
+                self._pool = torch.cuda.graph_pool_handle()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, pool=self._pool):
+                t._forward(False, self)
+            self._graphs[key] = g
+            self.last_mode = "capture"
+        else:
+            self._graphs.move_to_end(key)
+            self.last_mode = "replay"
+        g.replay()
 
 
 class _null(object):

@@ -18,7 +18,8 @@ What changes (all outside the arithmetic of a step):
     stream in front of every step (train_utils.py:95);
   * no ``loss.item()`` per step: the running loss is accumulated on the device, one host sync per epoch (train_utils.py:29);
   * the validation pass runs through ``FusedTrainer.score`` (the forward half of the explicit step, dropout off, its own hipGraph)
-    instead of the nn.Module forward;
+    instead of the nn.Module forward; with ``val_scorer="packed"`` (or ALLRANK_AMD_VAL_SCORER=packed) every validation batch,
+    whatever its slate length, runs the packed, captured forward-only scorer (engine.FusedScorer) on its valid items only;
   * train metrics come from the scores of the training forward itself instead of a second full pass over ``train_dl`` in train()
     mode (train_utils.py:99; same mode, same data).  ``train_metrics="reference"`` (or the environment variable
     ALLRANK_AMD_TRAIN_METRICS=reference -- main.py passes only config.training's keys) runs the reference's second pass instead: one
@@ -262,36 +263,77 @@ def _burn(dl, times=1):
     return True
 
 
-def _evaluate(model, loss_func, dl, device, metrics, trainer=None, world=1, rank=0):
+def _packed_blocker(loss_func, fused, reason):
+    """why the packed validation scorer cannot serve this job ("" if it can)"""
+    name = getattr(getattr(loss_func, "func", None), "__name__", "")
+    if name in ("neuralNDCG", "neuralNDCG_transposed") and (getattr(loss_func, "keywords", None) or {}).get("stochastic"):
+        # loss_utils.py:102 takes the batch-wide minimum over the PADDED scores too (and draws noise at validation): the value depends
+        # on what sits in the padded slots, which the packed scorer sets to 0 and the nn.Module forward does not
+        return "stochastic NeuralNDCG reads padded scores (batch-wide min, loss_utils.py:102)"
+    if not fused:
+        return "no FusedTrainer (%s)" % (reason or "autograd step")
+    return ""
+
+
+def _val_scorer(scorers, trainer, n, L):
+    """the FusedScorer for validation batches of up to n slates of L items (one per slate length, grown if a batch is larger)"""
+    s = scorers.get(L)
+    if s is None or s.B < n:
+        s = scorers[L] = trainer.scorer(max(n, 1), L)
+    return s
+
+
+def _evaluate(model, loss_func, dl, device, metrics, trainer=None, world=1, rank=0, scorers=None):
     """validation pass of train_utils.py:101-107: mean loss (weighted by batch size) and metric means, no autograd.  With a
     FusedTrainer the scores come from its forward-only pass (``FusedTrainer.score``: the kernels of the training step, dropout
     off, hipGraph replay) instead of the nn.Module forward (fp32 library GEMMs).
+    ``scorers`` (a dict, fit(val_scorer="packed")): EVERY batch goes through a packed, captured FusedScorer of its slate length
+    (kept in the dict across epochs) -- straight from the resident set when the loader is a packable DeviceLoader
+    (``id_batches``), else from the padded batch; slates above LTRX_MAX_METRIC_SLATE_LEN take the nn.Module path and
+    ``last_run["val_scorer_reason"]`` says so.
     Sharded (``world`` > 1, round 5): every rank scores its contiguous block of each validation batch -- the same partition as the
     training step -- under ``shard_context(global batch)``, so its loss is its share of the reference's loss on the whole batch
     (global divisors / normalisers); shares, slate counts and per-slate metric sums are all-reduced once at the end, and
     every rank returns the same numbers (scheduler and early stopping stay in step).  Before, every rank evaluated the whole set."""
     import torch.distributed as dist
-    from . import sharding
+    from . import _lib as LB, sharding
     tot, num = torch.zeros((), device=device), 0
     acc = {name: None for name in metrics}
     pf = dl if isinstance(dl, _Prefetcher) else _Prefetcher(dl, device)
+    loader = pf.loader
+    resident = (scorers is not None and getattr(loader, "packable", False) and getattr(loader, "world", 1) == world
+                and loader.slate_length <= LB.MAX_METRIC_SLATE_LEN)
     with torch.no_grad():
-        for batch in pf:
-            xb, yb, idx, n_glob, pre = _my_block(batch, pf.loader, rank, world)
-            n = int(xb.shape[0])
-            if trainer is not None and n <= trainer.B and tuple(xb.shape[1:2]) == (trainer.L,):
-                xs, ys, ids = _pad_batch(xb, yb, idx, trainer.B)
-                sc = trainer.score(xs, ys, ids, lengths=_host_lengths(batch, trainer, n, pre, world))[:n]
-                # (an empty shard of a short last batch still enters the loss -- its normaliser all-reduce is a collective -- with
-                #  one fully padded slate: value 0, count 0)
-                out, yl = trainer.scores_raw[:max(n, 1)], ys[:max(n, 1)]
+        for batch in (loader.id_batches() if resident else pf):
+            if resident:                                              # packed straight from the resident set: no padded features
+                n, n_glob = len(batch.ids), batch.global_slates
+                scorer = _val_scorer(scorers, trainer, -(-loader.batch_size // world), loader.slate_length)
+                scorer.run_resident(batch.slates, batch.ids, batch.lengths)
+                sc, out, yl, yb = scorer.scores[:n], scorer.scores_raw[:max(n, 1)], scorer.y[:max(n, 1)], scorer.y
             else:
-                if n == 0:
-                    xb, yb, idx = _pad_batch(xb, yb, idx, 1)
-                mask = yb == PADDED_Y_VALUE
-                out = model(xb, mask, idx)
-                sc = (out if out.dim() == 2 else model.score(xb, mask, idx))[:n]
-                yl = yb
+                xb, yb, idx, n_glob, pre = _my_block(batch, loader, rank, world)
+                n = int(xb.shape[0])
+                if scorers is not None and int(xb.shape[1]) <= LB.MAX_METRIC_SLATE_LEN:
+                    scorer = _val_scorer(scorers, trainer, n, int(xb.shape[1]))
+                    lens = getattr(batch, "lengths", None) if (pre is not None or world == 1) else None
+                    scorer.run(xb, yb, idx, lengths=lens if lens is not None and int(lens.numel()) == n else None)
+                    sc, out, yl = scorer.scores[:n], scorer.scores_raw[:max(n, 1)], scorer.y[:max(n, 1)]
+                elif trainer is not None and scorers is None and n <= trainer.B and tuple(xb.shape[1:2]) == (trainer.L,):
+                    xs, ys, ids = _pad_batch(xb, yb, idx, trainer.B)
+                    sc = trainer.score(xs, ys, ids, lengths=_host_lengths(batch, trainer, n, pre, world))[:n]
+                    # (an empty shard of a short last batch still enters the loss -- its normaliser all-reduce is a collective -- with
+                    #  one fully padded slate: value 0, count 0)
+                    out, yl = trainer.scores_raw[:max(n, 1)], ys[:max(n, 1)]
+                else:
+                    if scorers is not None:
+                        last_run["val_scorer_reason"] = ("a slate length of %d is above LTRX_MAX_METRIC_SLATE_LEN = %d: module path"
+                                                         % (int(xb.shape[1]), LB.MAX_METRIC_SLATE_LEN))
+                    if n == 0:
+                        xb, yb, idx = _pad_batch(xb, yb, idx, 1)
+                    mask = yb == PADDED_Y_VALUE
+                    out = model(xb, mask, idx)
+                    sc = (out if out.dim() == 2 else model.score(xb, mask, idx))[:n]
+                    yl = yb
             if loss_func is None:                                     # (metrics only: the reference's compute_metrics pass)
                 share = tot.new_zeros(())
             elif world > 1:
@@ -344,12 +386,16 @@ def _assert_finite(trainer, fused, loss, epoch, step, model):
 
 def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, config, gradient_clipping_norm, early_stopping_patience,
         device, output_dir, tensorboard_output_path, use_fused=True, compact=None, gemm="split_bf16", train_metrics=None,
-        check_finite=None):
+        check_finite=None, val_scorer=None):
     """Same positional / keyword arguments as the reference ``fit``; ``use_fused`` / ``compact`` / ``gemm`` / ``train_metrics`` /
     ``check_finite`` are extensions (compact=None: variable-length execution when less than 80 % of the first batch's slots are valid
     items; gemm: the arithmetic of the fused step, "split_bf16" = fp32-class parity arithmetic, "bf16" = the one-product throughput
     mode, see FusedTrainer; train_metrics: "fused" (default) = from the training forward, "reference" = the reference's second pass,
-    train_utils.py:99; check_finite: None = ``config.detect_anomaly`` or LTRX_CHECK_FINITE=1, see the module docstring)."""
+    train_utils.py:99; check_finite: None = ``config.detect_anomaly`` or LTRX_CHECK_FINITE=1, see the module docstring; val_scorer:
+    "module" (default) = the validation batches of another slate length than the training step's run the nn.Module forward,
+    "packed" = every validation batch runs the packed, captured forward-only scorer of the fused step (engine.FusedScorer; the
+    environment variable ALLRANK_AMD_VAL_SCORER=packed does the same under main.py), ``last_run["val_scorer"]`` says which one ran
+    and ``last_run["val_scorer_reason"]`` why the packed one could not)."""
     import torch.distributed as dist
     device = torch.device(device)
     world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
@@ -369,6 +415,9 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
     train_metrics_mode = (train_metrics or os.environ.get("ALLRANK_AMD_TRAIN_METRICS") or "fused").lower()
     if train_metrics_mode not in ("fused", "reference"):
         raise ValueError("train_metrics must be 'fused' or 'reference', got %r" % (train_metrics_mode,))
+    val_scorer_mode = (val_scorer or os.environ.get("ALLRANK_AMD_VAL_SCORER") or "module").lower()
+    if val_scorer_mode not in ("module", "packed"):
+        raise ValueError("val_scorer must be 'module' or 'packed', got %r" % (val_scorer_mode,))
     if check_finite is None:
         check_finite = bool(getattr(config, "detect_anomaly", False)) or os.environ.get("LTRX_CHECK_FINITE", "0") not in ("", "0")
     writer = _tensorboard(tensorboard_output_path) if tensorboard_output_path else None
@@ -395,6 +444,11 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
     last_run.update(engine="fused" if fused else "autograd", compact=bool(trainer.compact) if fused else False, reason=reason,
                     fcstep=getattr(trainer, "fcstep", False))
     log.info("allrank_amd.fit: %s step%s", last_run["engine"], (" (" + reason + ")") if reason else "")
+    vs_reason = _packed_blocker(loss_func, fused, reason) if val_scorer_mode == "packed" else ""
+    scorers = {} if val_scorer_mode == "packed" and not vs_reason else None
+    last_run.update(val_scorer="packed" if scorers is not None else "module", val_scorer_reason=vs_reason)
+    if vs_reason:
+        log.info("allrank_amd.fit: validation through the nn.Module forward (%s)", vs_reason)
 
     epoch, train_metrics, val_metrics = -1, {}, {}
     train_pf, valid_pf = _Prefetcher(train_dl, device), _Prefetcher(valid_dl, device)     # one per loader: stream and staging sets persist
@@ -461,10 +515,10 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
 
         model.eval()
         t_val = time.perf_counter()
-        val_loss, val_metrics = _evaluate(model, loss_func, valid_pf, device, metrics, trainer if fused else None, world, rank)
+        val_loss, val_metrics = _evaluate(model, loss_func, valid_pf, device, metrics, trainer if fused else None, world, rank, scorers)
         _burn(valid_dl, len(metrics))                              # train_utils.py:107 iterates valid_dl once more per metric name
         last_run["epoch_log"].append({"train_s": t_train, "val_s": time.perf_counter() - t_val, "slates": int(stats[1]),
-                                      "slots": int(slots)})
+                                      "slots": int(slots), "val_loss": val_loss})
 
         lr_now = optimizer.param_groups[0]["lr"]
         if writer is not None:

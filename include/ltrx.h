@@ -302,6 +302,25 @@ int ltrx_packed_row_index(const int32_t* cu_seqlens, int B, int L, int n, int32_
 int ltrx_scatter_rows(const float* src, int ld_src, const int32_t* idx, int n, int cols, float* dst, int ld_dst,
                       ltrx_stream_t stream);
 
+/* Packed batches whose row count lives in DEVICE memory (graph-replayable: no launch argument depends on the batch).
+ * n = cu_seqlens[B] (i32[B+1], device memory; slate b = packed rows cu[b] .. cu[b+1]-1, cu[b+1]-cu[b] <= L); `rows` >= n is the
+ * host row bucket the outputs hold.  Rows move as 32-bit words, 16 bytes per access when cols / strides / addresses allow.
+ *   ltrx_assemble_packed: from a CSR set resident in HBM (ltrx_assemble_batch's arrays) and B slate ids: x_out[r, :F] = the
+ *       features of item j of slate b for r = cu[b] + j < n, zero rows for n <= r < rows (columns F .. ld_x-1 untouched);
+ *       y_out[B, L] = labels, -1 on padding; idx_out[r] = b*L + j and pos_out[r] = j (both -1 for r >= n; either may be NULL).
+ *       The padding branch of FixLength followed by packing.
+ *   ltrx_gather_rows_cu: the same packing of a padded batch src[B', L, ld_src] (valid items first in every slate; slates past
+ *       B' must have length 0): dst[r] = src[b*L + j] for r < n, zero for n <= r < rows; idx_out (or NULL) as above.
+ *   ltrx_scatter_rows_cu: dst[b*L + j] = src[cu[b] + j] for j < cu[b+1]-cu[b] (and cu[b] + j < rows), 0 in every other slot
+ *       of dst[B, L, ld_dst]. */
+int ltrx_assemble_packed(const float* x_items, const float* y_items, const int64_t* offsets, const int64_t* slates,
+                         const int32_t* cu_seqlens, int B, int L, int F, int rows, float* x_out, int ld_x, float* y_out,
+                         int32_t* idx_out, int64_t* pos_out, ltrx_stream_t stream);
+int ltrx_gather_rows_cu(const float* src, int ld_src, const int32_t* cu_seqlens, int B, int L, int cols, int rows, float* dst,
+                        int ld_dst, int32_t* idx_out, ltrx_stream_t stream);
+int ltrx_scatter_rows_cu(const float* src, int ld_src, const int32_t* cu_seqlens, int B, int L, int cols, int rows, float* dst,
+                         int ld_dst, ltrx_stream_t stream);
+
 /* y = act(y + bias) in place over a contiguous [M,N] matrix (model.py:42-43); act 0 = identity, 1 = ReLU; N % 4 == 0. */
 int ltrx_bias_act(float* y_inout, const float* bias, int M, int N, int act, ltrx_stream_t stream);
 
