@@ -2,102 +2,47 @@
 kernels fails loudly (the product path never routes through a CPU implementation)."""
 import ctypes
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LTRX_LIB_PATH") or os.path.join(_HERE, "libltrx.so")     # (override: A/B runs of two builds)
 
-_c_float_p = ctypes.c_void_p   # device pointers are passed as raw addresses
-_vp = ctypes.c_void_p
-_i = ctypes.c_int
-_f = ctypes.c_float
-_sz = ctypes.c_size_t
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ltrx.h")
 
-SIGNATURES = {
-    "ltrx_version": (_i, []),
-    "ltrx_listnet_workspace_bytes": (_sz, [_i, _i]),
-    "ltrx_listnet_fwd_bwd": (_i, [_vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp]),
-    "ltrx_listmle_workspace_bytes": (_sz, [_i, _i]),
-    "ltrx_listmle_fwd_bwd": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "ltrx_approxndcg_workspace_bytes": (_sz, [_i, _i]),
-    "ltrx_approxndcg_fwd_bwd": (_i, [_vp, _vp, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp]),
-    "ltrx_lambdaloss_workspace_bytes": (_sz, [_i, _i]),
-    "ltrx_lambdaloss_fwd_bwd": (_i, [_vp, _vp, _i, _i, _f, _f, _i, _i, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "ltrx_neuralndcg_workspace_bytes": (_sz, [_i, _i, _i]),
-    "ltrx_neuralndcg_prepare": (_i, [_vp, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp]),
-    "ltrx_neuralndcg_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _f, _i, _i, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
-    "ltrx_ranknet_workspace_bytes": (_sz, [_i, _i]),
-    "ltrx_ranknet_fwd_bwd": (_i, [_vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "ltrx_bce_workspace_bytes": (_sz, [_i, _i, _i]),
-    "ltrx_bce_fwd_bwd": (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "ltrx_pointwise_rmse_workspace_bytes": (_sz, [_i, _i]),
-    "ltrx_pointwise_rmse_fwd_bwd": (_i, [_vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp]),
-    "ltrx_binary_listnet_workspace_bytes": (_sz, [_i, _i]),
-    "ltrx_binary_listnet_fwd_bwd": (_i, [_vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp]),
-    "ltrx_mrr_workspace_bytes": (_sz, [_i, _i, _i]),
-    "ltrx_mrr_at": (_i, [_vp, _vp, _i, _i, ctypes.POINTER(ctypes.c_int), _i, _f, _vp, _vp, _vp]),
-    "ltrx_ndcg_workspace_bytes": (_sz, [_i, _i]),
-    "ltrx_ndcg_at": (_i, [_vp, _vp, _i, _i, ctypes.POINTER(ctypes.c_int), _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
-    "ltrx_ndcg_at_gains": (_i, [_vp, _vp, _vp, _i, _i, ctypes.POINTER(ctypes.c_int), _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
-    "ltrx_layernorm_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _f, ctypes.c_uint32, _vp, _vp]),
-    "ltrx_layernorm_bwd_workspace_bytes": (_sz, [_i, _i]),
-    "ltrx_layernorm_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
-    "ltrx_layernorm_bwd_partial": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp]),
-    "ltrx_mha_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _f, ctypes.c_uint32, _vp, _vp, _vp, _i, _vp]),
-    "ltrx_mha_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "ltrx_adam_step": (_i, [_vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _f, _i, _vp, _f, _vp, _vp]),
-    "ltrx_sgd_step": (_i, [_vp, _vp, _vp, _sz, _f, _f, _i, _f, _f, _vp, _vp]),
-    "ltrx_clip_workspace_bytes": (_sz, [_sz]),
-    "ltrx_clip_grad_norm_scale": (_i, [_vp, _sz, _f, _vp, _vp, _vp, _vp]),
-    "ltrx_colsum_workspace_bytes": (_sz, [_i, _i]),
-    "ltrx_colsum": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
-    "ltrx_relu_bwd": (_i, [_vp, _vp, _sz, _f, _vp]),
-    "ltrx_dropout_apply": (_i, [_vp, _vp, _sz, _f, ctypes.c_uint32, _vp, _vp]),
-    "ltrx_bump_u32": (_i, [_vp, _vp]),
-    "ltrx_first_nonfinite": (_i, [_vp, _sz, _vp, _i, _vp, _vp]),
-    "ltrx_gather_rows": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _i, _vp]),
-    "ltrx_packed_row_index": (_i, [_vp, _i, _i, _i, _vp, _vp]),
-    "ltrx_scatter_rows": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _vp]),
-    "ltrx_assemble_packed": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
-    "ltrx_gather_rows_cu": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
-    "ltrx_scatter_rows_cu": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
-    "ltrx_transpose_batch": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
-    "ltrx_bias_act": (_i, [_vp, _vp, _i, _i, _i, _vp]),
-    "ltrx_score_head_fwd": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
-    "ltrx_score_head_bwd_workspace_bytes": (_sz, [_i, _i]),
-    "ltrx_score_head_bwd": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "ltrx_gemm_nt_relu_bits_bytes": (_sz, [_i, _i, _i]),
-    "ltrx_gemm_nt": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _f, ctypes.c_uint32, _vp, _i, _i, _vp]),
-    "ltrx_split_image": (_i, [_vp, _vp, _sz, _vp]),
-    "ltrx_weight_images": (_i, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp]),
-    "ltrx_ingest_batch": (_i, [_vp, _vp, _sz, _sz, _i, _i, _f, _vp, _vp, _vp, _vp]),
-    "ltrx_gemm_tn_workspace_bytes": (_sz, [_i, _i, _i]),
-    "ltrx_gemm_tn_splits": (_i, [_i, _i, _i]),
-    "ltrx_gemm_tn": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "ltrx_gemm_tn_group_workspace_bytes": (_sz, [_i, _i, _vp, _vp]),
-    "ltrx_gemm_tn_group": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
-    "ltrx_reduce_group": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "ltrx_debug_tn_group_map": (_i, [_i, _i, _vp, _vp, _vp, _vp]),
-    "ltrx_layernorm_torch_fwd": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp]),
-    "ltrx_posenc_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),
-    "ltrx_posenc_table_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
-    "ltrx_scale_inplace": (_i, [_vp, _sz, _f, _vp]),
-    "ltrx_out_act_fwd": (_i, [_vp, _sz, _i, _vp, _vp]),
-    "ltrx_out_act_bwd": (_i, [_vp, _vp, _sz, _i, _vp, _vp]),
-    "ltrx_fixlength_positions": (_i, [_vp, _vp, _vp, _i, _i, _i, ctypes.c_uint64, _vp, _vp]),
-    "ltrx_assemble_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "ltrx_libsvm_parse": (_i, [_vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
-    "ltrx_selftest_mfma32x32x2": (_i, [_vp, _vp, _vp, _vp]),
-    "ltrx_fc_listnet_supported": (_i, [_i, _i, _i]),
-    "ltrx_fc_listnet_workspace_bytes": (_sz, [_i, _i, _i, _i, _sz]),
-    "ltrx_fc_linear_listnet_workspace_bytes": (_sz, [_i, _i]),
-    "ltrx_fc_linear_listnet_step": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _sz, _sz, _sz, _sz, _sz, _f, _f, _f, _vp, _vp, _vp, _vp,
-                                         _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _vp, _vp]),
-    "ltrx_fc_listnet_step": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _sz, _sz, _sz, _sz, _f, _f, _f, _vp, _vp, _vp, _vp, _vp,
-                                  _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _vp, _vp]),
-    "ltrx_mha_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _f, ctypes.c_uint32, _vp, _vp, _vp, _i, _vp, _vp]),
-}
+# C type -> ctypes type.  "*" stands for any pointer, device or host: like ltrx_stream_t it is passed as a raw address.
+_CTYPES = {"*": ctypes.c_void_p, "ltrx_stream_t": ctypes.c_void_p, "int": ctypes.c_int, "float": ctypes.c_float,
+           "size_t": ctypes.c_size_t, "uint32_t": ctypes.c_uint32, "uint64_t": ctypes.c_uint64, "int64_t": ctypes.c_int64}
+
+
+def _ctype_name(decl, where):
+    """the key into ``_CTYPES`` of one C declarator (``const float* x`` -> ``*``, ``int n`` -> ``int``)"""
+    words = ["*"] if "*" in decl else [w for w in decl.split() if w != "const"]
+    if not 1 <= len(words) <= 2 or words[0] not in _CTYPES:
+        raise TypeError("include/ltrx.h: no ctypes mapping for %r in %r" % (decl.strip(), where))
+    return words[0]
+
+
+def parse_header(text):
+    """{name: (return type, [parameter types])}, as keys of ``_CTYPES``, of every ``ltrx_*`` prototype in the text of
+    include/ltrx.h.  An ``ltrx_name(`` outside a readable prototype, or a type outside ``_CTYPES``, raises: the table never guesses."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#(?:[^\n]*\\\n)*[^\n]*", " ", text, flags=re.M)
+    protos = {m.start(2): m for m in re.finditer(r"([\w\s\*]+?)\b(ltrx_\w+)\s*\(([^()]*)\)\s*;", text)}
+    out = {}
+    for use in re.finditer(r"\bltrx_\w+\s*\(", text):
+        if use.start() not in protos:
+            raise TypeError("include/ltrx.h: cannot read the declaration at %r" % " ".join(text[use.start():use.start() + 160].split()))
+        ret, name, params = protos[use.start()].groups()
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        out[name] = (_ctype_name(ret, name), [_ctype_name(q, name) for q in params])
+    return out
+
+
+with open(HEADER_PATH) as _f:
+    PROTOTYPES = parse_header(_f.read())
+SIGNATURES = {name: (_CTYPES[ret], [_CTYPES[q] for q in params]) for name, (ret, params) in PROTOTYPES.items()}
 
 _lib = None
 MAX_SLATE_LEN = 2048            # LTRX_MAX_SLATE_LEN (include/ltrx.h; checked against the header by tests/test_abi.py)
@@ -144,8 +89,7 @@ def lib():
             fn = getattr(h, name)     # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
-            launches = res is _i and args and args[-1] is _vp and not name.endswith("_bytes")
-            setattr(b, name, _on_stream_device(fn) if launches else fn)
+            setattr(b, name, _on_stream_device(fn) if PROTOTYPES[name][1][-1:] == ["ltrx_stream_t"] else fn)
         _lib = b
     return _lib
 

@@ -648,6 +648,14 @@ class FusedTrainer(object):
         need = self.lib.ltrx_gemm_nt_relu_bits_bytes(self.rows, self.dff, self.d)
         return buf if 0 < need <= buf.numel() else None
 
+    def _gemm_nt(self, a, b, out, M, bias, act, aux, ldaux, p, seed, what):
+        """the one ltrx_gemm_nt call of the step: out[:M] = epi_act(a b^T + bias), dropout (p, site ``seed``) in the epilogue;
+        ``aux`` / ``ldaux`` as the act code reads them (include/ltrx.h); ``b``'s split image is passed along where one exists"""
+        P = self.LB.ptr
+        self.LB.check(self.lib.ltrx_gemm_nt(P(a), a.stride(0), P(b), b.stride(0), self._img(b), P(out), out.stride(0), M, b.shape[0],
+                                            a.shape[1], P(bias), act, P(aux), ldaux, float(p), seed, P(self.drop_step), self._prec, 0,
+                                            self._st()), what)
+
     def _lin_fwd(self, x, w, b, out, act=0, p=0.0, seed=0, res=None, bits=None, rows=None):
         """out = drop_p(act(x w^T + b)) [+ res]   (nn.Linear forward, act 1 = ReLU; dropout in the epilogue; ``res`` = the
         residual stream of the SublayerConnection this projection closes, transformer.py:98-106: added in the epilogue, so the
@@ -664,15 +672,12 @@ class FusedTrainer(object):
             if res is not None:
                 out[:n].add_(res[:n])
             return
-        P = self.LB.ptr
         if bits is not None and act == 1:                         # ReLU + its one-bit mask for the backward (act 4)
-            self.LB.check(self.lib.ltrx_gemm_nt(P(x), x.stride(0), P(w), w.stride(0), self._img(w), P(out), out.stride(0), M,
-                                                w.shape[0], x.shape[1], P(b), 4, P(bits), 0, float(p), seed, P(self.drop_step), self._prec, 0,
-                                                self._st()), "gemm_nt(fwd, relu bits)")
-            return
-        self.LB.check(self.lib.ltrx_gemm_nt(P(x), x.stride(0), P(w), w.stride(0), self._img(w), P(out), out.stride(0), M, w.shape[0],
-                                            x.shape[1], P(b), 3 if res is not None else act, P(res), res.stride(0) if res is not None else 0,
-                                            float(p), seed, P(self.drop_step), self._prec, 0, self._st()), "gemm_nt(fwd)")
+            self._gemm_nt(x, w, out, M, b, 4, bits, 0, p, seed, "gemm_nt(fwd, relu bits)")
+        elif res is not None:
+            self._gemm_nt(x, w, out, M, b, 3, res, res.stride(0), p, seed, "gemm_nt(fwd)")
+        else:
+            self._gemm_nt(x, w, out, M, b, act, None, 0, p, seed, "gemm_nt(fwd)")
 
     def _lin_dgrad(self, dy, w, wT, out, relu_of=None, p=0.0, seed=0, bits=None):
         """out = dy w   (input gradient of nn.Linear); wT = w^T contiguous.  With ``relu_of`` (the saved post-ReLU,
@@ -685,16 +690,12 @@ class FusedTrainer(object):
             elif p:
                 self._drop_apply(out, out, p, seed)
             return
-        P = self.LB.ptr
-        if bits is not None and relu_of is not None:              # the mask written by the forward launch (act 5): 1/32 of the bytes
-            self.LB.check(self.lib.ltrx_gemm_nt(P(dy), dy.stride(0), P(wT), wT.stride(0), self._img(wT), P(out), out.stride(0), self.rows,
-                                                wT.shape[0], dy.shape[1], None, 5, P(bits), 0, float(p), seed, P(self.drop_step),
-                                                self._prec, 0, self._st()), "gemm_nt(dgrad, relu bits)")
-            return
-        self.LB.check(self.lib.ltrx_gemm_nt(P(dy), dy.stride(0), P(wT), wT.stride(0), self._img(wT), P(out), out.stride(0), self.rows,
-                                            wT.shape[0], dy.shape[1], None, 2 if relu_of is not None else 0, P(relu_of),
-                                            relu_of.stride(0) if relu_of is not None else 0, float(p), seed, P(self.drop_step),
-                                            self._prec, 0, self._st()), "gemm_nt(dgrad)")
+        if relu_of is None:
+            self._gemm_nt(dy, wT, out, self.rows, None, 0, None, 0, p, seed, "gemm_nt(dgrad)")
+        elif bits is not None:                                    # the mask written by the forward launch (act 5): 1/32 of the bytes
+            self._gemm_nt(dy, wT, out, self.rows, None, 5, bits, 0, p, seed, "gemm_nt(dgrad, relu bits)")
+        else:
+            self._gemm_nt(dy, wT, out, self.rows, None, 2, relu_of, relu_of.stride(0), p, seed, "gemm_nt(dgrad)")
 
     def _lin_wgrad(self, dy, x, gw, gb, defer=False):
         """gw = dy^T x, gb = column sums of dy   (weight and bias gradients of nn.Linear).  ``defer``: an encoder-layer projection

@@ -38,6 +38,28 @@ def test_binding_table_matches_header(libpath):
     assert _lib.lib().ltrx_version() == 130
 
 
+def test_binding_table_is_derived_from_the_header_prototypes():
+    """every declared symbol has an entry, every entry has as many argtypes as its prototype has parameters (counted here from
+    the header text, not by the parser under test), and a type the map does not know stops the import instead of being guessed"""
+    from allrank_amd import _lib
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ltrx.h")).read(), flags=re.S)
+    assert sorted(_lib.SIGNATURES) == _declared_symbols()
+    for name, (res, args) in _lib.SIGNATURES.items():
+        (params,) = re.findall(r"\b%s\s*\(([^)]*)\)" % name, src)
+        want = 0 if params.strip() in ("", "void") else params.count(",") + 1
+        assert len(args) == want, (name, len(args), want)
+        assert (_lib.PROTOTYPES[name][1][-1:] == ["ltrx_stream_t"]) == bool(re.search(r"ltrx_stream_t\s+\w+\s*$", params)), name
+    assert _lib.SIGNATURES["ltrx_gemm_nt"][1][14:16] == [ctypes.c_float, ctypes.c_uint32]
+    assert _lib.SIGNATURES["ltrx_listnet_workspace_bytes"] == (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int])
+    ok = "int ltrx_probe(const float* x, int n, ltrx_stream_t stream);"
+    assert _lib.parse_header(ok) == {"ltrx_probe": ("int", ["*", "int", "ltrx_stream_t"])}
+    for bad in ("int ltrx_probe(const float* x, double scale, ltrx_stream_t stream);",      # unmapped parameter type
+                "long ltrx_probe(int n);",                                                  # unmapped return type
+                "int ltrx_probe(int (*callback)(int), ltrx_stream_t stream);"):             # a prototype the parser cannot read
+        with pytest.raises(TypeError, match="ltrx_probe"):
+            _lib.parse_header(bad)
+
+
 def test_slate_length_limits_are_stated_once_and_reported(libpath):
     """the limits of include/ltrx.h, the constants the Python error message quotes, and the status code of an over-long slate
     (returned before any HIP call, so this runs without a GPU)"""

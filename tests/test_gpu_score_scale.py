@@ -80,23 +80,44 @@ def test_neuralndcg_both_paths_within_the_conditioning_bar_at_score_scale(scale,
 
 @pytest.mark.parametrize("scale", [30, 1000])
 def test_fused_loss_equals_the_plugin_call_at_score_scale(scale, scale_golden):
-    """FusedLoss (the explicit training step's loss launcher) == the autograd plugin call, bit for bit, on trained-scale scores"""
+    """FusedLoss (the explicit training step's loss launcher) == the autograd plugin call, bit for bit, for every loss name FusedLoss
+    accepts.  The ranking losses on trained-scale scores (listMLE with one explicit permutation on both paths, binary listNet on the
+    binary labels); bce, ordinal and pointwise_rmse take probabilities: a fixed-seed draw strictly inside (0, 1), not squashed
+    scores, whose saturated 0 / 1 would exercise the clamp instead of the launcher."""
     from allrank_amd import losses as E
     jobs = [("approxNDCGLoss", {}), ("listNet", {}),
             ("lambdaLoss", dict(weighing_scheme="lambdaRank_scheme", sigma=1.3, mu=7.0)),
             ("lambdaLoss", dict(weighing_scheme="ndcgLoss2PP_scheme", k=5, reduction="mean", reduction_log="natural", sigma=1.3, mu=7.0)),
-            ("neuralNDCG", dict(temperature=1.0)), ("neuralNDCG_transposed", dict(temperature=0.1, k=5))]
+            ("neuralNDCG", dict(temperature=1.0)), ("neuralNDCG_transposed", dict(temperature=0.1, k=5)),
+            ("listMLE", {}), ("rankNet", {}), ("rankNet_weightByGTDiff", {}), ("rankNet_weightByGTDiff_pow", {}), ("binary_listNet", {}),
+            ("bce", {}), ("ordinal", dict(n=4)), ("pointwise_rmse", dict(no_of_levels=4))]
+    seen = set()
     for st in ("main", "outlier"):
         B, L = SETS[st]
-        s, y = scale_golden["%s.x%d.s" % (st, scale)], scale_golden[st + ".y"]
+        g = torch.Generator().manual_seed(1000 * scale + L)
+        perm = torch.randperm(L, generator=g)
+        prob = (0.02 + 0.96 * torch.rand((B, L, 4), generator=g)).numpy()
+        assert prob.min() > 0.0 and prob.max() < 1.0
         for name, kw in jobs:
+            s, y = scale_golden["%s.x%d.s" % (st, scale)], scale_golden[st + ".y"]
+            if name in ("bce", "ordinal", "pointwise_rmse"):
+                s = prob if name == "ordinal" else np.ascontiguousarray(prob[:, :, 0])
+            if name in ("bce", "binary_listNet"):
+                y = scale_golden[st + ".yb"]
             fl = E.FusedLoss(name, B, L, "cuda:0", **kw)
+            pkw = dict(kw)
+            if name == "listMLE":
+                fl.set_perm(perm)
+                pkw["perm"] = perm
             loss, grad = fl.run(_t(s), _t(y), float(B))
             sp = _t(s, True)
-            l2 = getattr(E, name)(sp, _t(y), **kw)
+            l2 = getattr(E, name)(sp, _t(y), **pkw)
             l2.backward()
-            assert torch.isfinite(grad).all(), (st, name)
+            print("fused-vs-plugin", st, scale, name, float(loss), float(l2), float((grad - sp.grad).abs().max()))
+            assert grad.shape == sp.grad.shape and torch.isfinite(grad).all(), (st, name)
             assert torch.equal(loss.reshape(()), l2.detach().reshape(())) and torch.equal(grad, sp.grad), (st, name, kw)
+            seen.add(name)
+    assert seen == set(E._LOSSES)                              # every name FusedLoss accepts
 
 
 @pytest.mark.parametrize("scale", SCALES)
