@@ -7,7 +7,10 @@ Differences from the reference driver (all outside the arithmetic): no ``loss.it
 the device; call ``.item()`` when you want it), gradients live in one flat buffer (allrank_amd.parallel), and under
 ``world_size > 1`` the loss is normalised by the global batch and gradients are summed over RCCL.
 """
+import collections
 import ctypes
+import logging
+import warnings
 
 import torch
 from torch.nn.utils import clip_grad_norm_
@@ -50,6 +53,163 @@ class Trainer(object):
         self.opt.step()
         self.flat.zero()          # == opt.zero_grad(set_to_none=False): grads stay views of the flat buffer
         return loss
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# shared by FusedTrainer and FusedScorer: the forward-buffer plan, the batch stager, the forward-graph cache
+# ------------------------------------------------------------------------------------------------------------------
+def _alloc_forward(owner, t, rows, B, L, saved, compact):
+    """Create on ``owner`` the buffer set that ``FusedTrainer._forward`` of trainer ``t`` runs over (``B`` slates of ``L`` items, up to
+    ``rows`` rows), every buffer zero-initialised.  The only place that makes forward buffers, and the list of what ``_forward`` reads
+    from a buffer set ``bs``:
+      B, L, compact (rows = the packed valid items, else the padded grid); rows (of THIS pass: kept current by the owner, not here)
+      mask [B, L] u8 key padding (None in the scorer's form: packed rows are all valid keys)
+      cu [B+1], order [B] (views of the owner's ``_stager`` tensor), idx [rows] packed row -> grid slot: compact only, else None
+      x_in [rows, F] -- with t._x_pad a view of x_in_buf (rows padded to 256 floats; the pad columns are never written again and
+      must stay zero) next to x_in_k (F rounded up to 32 columns); x_norm, mean_in, rstd_in (input_norm only); fc_out[i]
+      idx_rows (i64 rank of every row, -1 = none) and x_pe: positional encoding only
+      layers[i]: wqkv, bqkv, mod, p_*, s_* (the trainer's parameter views and dropout sites; its own dicts also hold gwqkv / gbqkv
+      and later rbits / wqkvT), xsum0 (the residual stream entering layer i > 0), xn0, mean0, rstd0, qkv, o, lse, x1, xn1, mean1,
+      rstd1, r;  xsum_f, xf, mean_f, rstd_f (the final norm);  scores_c (compact only), scores_raw [B, L(, n_out)], scores [B, L]
+    ``saved=True``, the trainer's form: the backward reads the activations, so every layer has its own.  ``saved=False``, the scorer's:
+    ONE activation set serves every layer -- the residual stream ping-pongs between two buffers (a layer's input is dead once its
+    out-projection has added it: xsum0 of layer i = ping[i % 2], xsum_f = ping[N % 2], x_pe = ping[0], which layer 0 reads while
+    writing ping[1]) and one LayerNorm output / statistics set serves LN0, LN1 and the final norm (each is consumed before the next is
+    written)."""
+    dev, d, no, F0 = t.dev, t.d, t.n_out, t.fc_sizes[0]
+
+    def z(*shape):
+        return torch.zeros(shape, dtype=torch.float32, device=dev)
+
+    def ln():
+        return z(rows, d), z(rows), z(rows)
+
+    def acts(ln0, ln1):
+        return dict(xn0=ln0[0], mean0=ln0[1], rstd0=ln0[2], xn1=ln1[0], mean1=ln1[1], rstd1=ln1[2], qkv=z(rows, 3 * d), o=z(rows, d),
+                    lse=z(B, t.h, L), x1=z(rows, d), r=z(rows, t.dff))
+
+    owner.B, owner.L, owner.compact = B, L, compact
+    owner.mask = torch.zeros((B, L), dtype=torch.uint8, device=dev) if saved else None
+    owner._stager = _Stager(dev, B, with_ids=not saved) if compact else None
+    owner.cu, owner.order = (owner._stager.cu, owner._stager.order) if compact else (None, None)
+    owner.idx = torch.full((rows,), 0 if saved else -1, dtype=torch.int32, device=dev) if compact else None
+    if t._x_pad:
+        owner.x_in_buf = z(rows, (F0 + 255) // 256 * 256)
+        owner.x_in, owner.x_in_k = owner.x_in_buf[:, :F0], owner.x_in_buf[:, :(F0 + 31) // 32 * 32]
+    else:
+        owner.x_in = z(rows, F0)
+    if t.in_norm is not None:
+        owner.x_norm, owner.mean_in, owner.rstd_in = z(rows, F0), z(rows), z(rows)
+    owner.fc_out = [z(rows, s) for s in t.fc_sizes[1:]]
+    if t.pos is not None:
+        owner.idx_rows = torch.full((rows,), -1, dtype=torch.int64, device=dev)
+    heads, owner.layers = t.layers, []                        # (owner may be t: its dicts hold the parameter views so far)
+    if t.N and saved:
+        for i, st in enumerate(heads):
+            owner.layers.append(dict(st, xsum0=z(rows, d) if i else None, **acts(ln(), ln())))
+        owner.xsum_f = z(rows, d)
+        owner.xf, owner.mean_f, owner.rstd_f = ln()
+    elif t.N:
+        ping, one = [z(rows, d), z(rows, d)], ln()
+        shared = acts(one, one)
+        for i, st in enumerate(heads):
+            owner.layers.append(dict({k: st[k] for k in ("wqkv", "bqkv", "mod", "p_att", "p_ff", "p_s0", "p_s1", "s_att", "s_ff", "s_s0",
+                                                          "s_s1")}, xsum0=ping[i % 2], **shared))
+        owner.xsum_f = ping[t.N % 2]
+        owner.xf, owner.mean_f, owner.rstd_f = one
+    if t.pos is not None:
+        owner.x_pe = ping[0] if (t.N and not saved) else z(rows, d)
+    if compact:
+        owner.scores_c = z(rows) if no == 1 else z(rows, no)
+    owner.scores_raw = z(B, L) if no == 1 else z(B, L, no)    # what the loss sees (model.forward)
+    owner.scores = owner.scores_raw if no == 1 else z(B, L)   # model.score (sum over the output units)
+
+
+def _stage_host(host, B, lengths, ids=None):
+    """Pure host half of the stager: write ``[ids as int32 pairs, 2B |] cu_seqlens [B+1], stable longest-first order [B]`` of up to
+    ``B`` slate ``lengths`` into the int32 buffer ``host`` (slates past the given ones: length 0, id 0); returns the valid-row count."""
+    o = 2 * B if ids is not None else 0
+    lens = torch.as_tensor(lengths, dtype=torch.int32).reshape(-1)
+    full = torch.zeros(B, dtype=torch.int32)
+    full[:lens.numel()] = lens
+    host[o] = 0
+    torch.cumsum(full, 0, dtype=torch.int32, out=host[o + 1:o + B + 1])
+    host[o + B + 1:o + 2 * B + 1] = torch.argsort(full, descending=True, stable=True)
+    if ids is not None:
+        h64 = host[:o].view(torch.int64)
+        h64.zero_()
+        h64[:lens.numel()] = torch.as_tensor(ids, dtype=torch.int64).reshape(-1)
+    return int(host[o + B])
+
+
+class _Stager(object):
+    """Device staging of one batch -- [slate ids (i64, as int32 pairs) |] cu_seqlens [B+1], launch order [B] in ONE tensor -- filled by
+    one non-blocking upload from a ring of 4 pinned host buffers (a slot is reused after the copy that last used it has completed):
+    only these few words cross PCIe per batch, and nothing syncs."""
+
+    def __init__(self, dev, B, with_ids):
+        self.B, o = B, 2 * B if with_ids else 0
+        self.stage = torch.zeros(o + 2 * B + 1, dtype=torch.int32, device=dev)
+        self.ids = self.stage[:o].view(torch.int64) if with_ids else None
+        self.cu, self.order = self.stage[o:o + B + 1], self.stage[o + B + 1:]
+        self._ring = [(torch.zeros(o + 2 * B + 1, dtype=torch.int32).pin_memory(), torch.cuda.Event()) for _ in range(4)]
+        self._turn = 0
+
+    def upload(self, lengths, ids=None):
+        """``lengths`` (host or device ints, at most B, range-checked by the caller) and, if given, slate ``ids`` -> device; the row count"""
+        host, ev = self._ring[self._turn % len(self._ring)]
+        self._turn += 1
+        ev.synchronize()
+        if lengths.is_cuda:                                   # (a device tensor costs the sync the host lengths are meant to avoid)
+            lengths = lengths.cpu()
+        n = _stage_host(host if ids is not None else host[-(2 * self.B + 1):], self.B, lengths, ids)
+        self.stage.copy_(host, non_blocking=True)
+        ev.record()
+        return n
+
+
+class _GraphLRU(object):
+    """The forward-graph rule: a key runs eagerly on its first two visits (warm-up outside capture: lazy module loads, kernel
+    attributes), is captured in a hipGraph on the third and replayed afterwards.  The captures form an LRU of ``max_graphs`` keys
+    (``graphs``: least recently used first); a new key beyond that evicts the oldest (``evictions`` counts them)."""
+
+    def __init__(self, max_graphs, own_pool=False):
+        self.graphs, self._visits = collections.OrderedDict(), collections.Counter()
+        self.max_graphs, self.evictions = int(max_graphs), 0
+        self._own_pool, self._pool = own_pool, None
+
+    def run(self, key, fn):
+        """run, capture and replay, or replay ``fn`` for ``key``; returns "eager", "capture" or "replay" """
+        g = self.graphs.get(key)
+        if g is not None:
+            self.graphs.move_to_end(key)
+            g.replay()
+            return "replay"
+        self._visits[key] += 1
+        if self._visits[key] <= 2:
+            fn()
+            return "eager"
+        if len(self.graphs) >= self.max_graphs:
+            self.graphs.popitem(last=False)
+            self.evictions += 1
+        if self._own_pool and self._pool is None:
+            self._pool = torch.cuda.graph_pool_handle()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, pool=self._pool):
+            fn()
+        self.graphs[key] = g
+        g.replay()
+        return "capture"
+
+
+def pad_batch(xb, yb, idx, B):
+    """top a short batch up to ``B`` slates with fully padded ones (features 0, label -1, index -1: no loss, no gradient)"""
+    n = B - xb.shape[0]
+    if n <= 0:
+        return xb, yb, idx
+    return (torch.cat([xb, xb.new_zeros((n,) + tuple(xb.shape[1:]))]),
+            torch.cat([yb, yb.new_full((n, yb.shape[1]), float(PADDED_Y_VALUE))]),
+            torch.cat([idx, idx.new_full((n, idx.shape[1]), -1)]))
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -122,10 +282,8 @@ class FusedTrainer(object):
         (ltrx_gemm_nt_img, ltrx_gemm_tn_group_img, ltrx_layernorm_fwd_image) have left the library too: the patch's act_images half
         needs the library of commit 68005e3.)
         force_dist=True: see ``self.sharded`` below."""
-        import torch.nn as nn
         from . import _lib as LB
         from .losses import FusedLoss
-        from .model import FCModel, Encoder, LTRModel, LearnedPositionalEncoding
         self.LB = LB
         self.lib = LB.lib()
         if gemm not in ("split_bf16", "split_bf16_strict", "hipblaslt", "bf16"):
@@ -156,6 +314,76 @@ class FusedTrainer(object):
         # ``force_dist`` asks for it on a one-rank group: the whole collective path, RCCL included, on the one GPU a build box has
         # (bench.py --force-dist, tests/test_gpu_rccl.py).  Needs an initialised process group.
         self.sharded = bool(world_size > 1 or force_dist)
+        self.clip = float(gradient_clipping_norm) if gradient_clipping_norm else None
+        seed = self._read_model(model, dropout, seed)
+        offs = self._layout_parameters(dropout)
+        # slate-resident FC + ListNet step (csrc/ltrx_fcstep.hip): eligibility.  It reads the padded batch in place and masks padded
+        # items itself, so a request for variable-length execution is moot for such a job (and would only route it to the slower
+        # GEMM launch sequence): compact is dropped.
+        fc_ok = bool(
+            fc_step and self.N == 0 and self.nfc == 1 and self.in_norm is None and self.pos is None and self.fc_act in (0, 1)
+            and self.p_fc == 0.0 and self.n_out == 1 and self.out_act == 0 and loss_name == "listNet"
+            and gemm == "split_bf16" and optimizer in ("Adam", "AdamW")
+            and self.lib.ltrx_fc_listnet_supported(L, self.fc_sizes[0], self.fc_sizes[1]))
+        if fc_ok:
+            if compact or not use_graph:
+                logging.getLogger("allrank_amd.engine").info(
+                    "FusedTrainer: the slate-resident FC + ListNet step is taken (two launches per step, the padded batch read in place): "
+                    "compact=%s / use_graph=%s do not apply to it; scores / labels of the last step alias the caller's tensors until the "
+                    "next step()", compact, use_graph)
+            compact = False
+        # forward buffers (the trainer is its own buffer set).  Input rows are padded to a multiple of 256 floats where the first FC
+        # layer can then run the large-tile GEMMs: the forward projection contracts over F rounded up to the kernel's 32-column step
+        # against a row-padded copy of W_0 (refreshed with the weight images), the weight gradient reads the padded rows as tiles.
+        F0 = self.fc_sizes[0]
+        self._x_pad = bool(pad_input and self.in_norm is None and gemm in ("split_bf16", "bf16") and F0 % 4 == 0 and F0 % 256 != 0
+                           and F0 <= 1024 and self.fc_sizes[1] % 256 == 0 and self.M >= 2048)
+        _alloc_forward(self, self, self.M, B, L, saved=True, compact=bool(compact))
+        self.rows = B * L                                                     # rows the row-wise kernels run over
+        self.n_valid = B * L
+        self.y_in = torch.zeros((B, L), dtype=torch.float32, device=self.dev)
+        self._alloc_backward(relu_bits)
+        self._fused_images = False
+        if self.gemm != "hipblaslt":
+            self._init_weight_images()
+        self.loss = FusedLoss(loss_name, B, L, self.dev, **(loss_args or {}))
+        if (self.n_out > 1) != (loss_name == "ordinal") or (loss_name == "ordinal" and int(loss_args["n"]) != self.n_out):
+            raise NotImplementedError("FusedTrainer: d_output > 1 goes with the ordinal loss of the same n (and only with it)")
+        # ListMLE: the reference draws torch.randperm(L) on every call (listMLE.py:17).  shuffle_ties=True (default) does
+        # the same with a device generator; tests that compare with the oracle set shuffle_ties=False and an explicit
+        # permutation via ``trainer.loss.set_perm``.
+        self.shuffle_ties = True
+        self._perm_gen = torch.Generator(device=self.dev)
+        self._perm_gen.manual_seed(int(seed) & 0x7FFFFFFF)
+        self.use_graph = use_graph and not compact
+        self._fwd_graphs = _GraphLRU(1)                       # score(): one key, captured into the default pool
+        self.probe = None                                     # list collecting (start, end) events of the FFN1 GEMM (eager steps only)
+        self.probe_wgrad = None                               # ... of the grouped weight-gradient launch (bench.py, eager steps only)
+        # captured steps: {(batch divisor, collectives on?): [(hipGraph segment, collective to launch after it | None), ...]}
+        self._graphs = collections.OrderedDict()
+        self.max_graphs = 4
+        self._warned_evict = False
+        self.capture_fallback = None                          # repr of the capture error if a sharded run fell back to eager steps
+        self._seg_break = None                                # set while capturing: ends the current segment (see _capture)
+        self._graph_pool = None
+        self._cap_stream = None
+        self._warm = 0
+        self._wver = [p._version for p in self._order]
+        self._images_stale = False
+        self.y_cur = self.y_in                                # labels of the last step() (the caller's tensor in the fcstep path)
+        self.keep_fc_out = False                              # tests: also write the FC activations to fc_out[0]
+        self.keep_loss_grad = False                           # tests: also write d loss / d scores to self.loss.grad (4 B per item)
+        self.fcstep = fc_ok
+        if self.fcstep and fc_step == "collapse" and self.fc_act == 0:
+            self.fcstep = "collapse"
+        if self.fcstep:
+            self._init_fc_step(offs)
+
+    # ---- the named steps of __init__ ---------------------------------------------------------------------------
+    def _read_model(self, model, dropout, seed):
+        """the model family check and what the step reads off the nn.Module (sizes, activations, dropout); returns the resolved seed"""
+        import torch.nn as nn
+        from .model import FCModel, Encoder, LTRModel, LearnedPositionalEncoding
         if not isinstance(model, LTRModel) or not isinstance(model.input_layer, FCModel):
             raise NotImplementedError("FusedTrainer needs an allrank_amd LTRModel with an FCModel input block")
         fc = model.input_layer
@@ -166,7 +394,7 @@ class FusedTrainer(object):
             # loaders' shuffle order comes from that generator, and a draw here would shift every epoch's batches away from the
             # reference's (round 6: the trajectory fixtures of tests/golden/make_golden_trajectory.py)
             seed = int(torch.initial_seed() & 0x7FFFFFFF)
-        self._seed = (int(seed) * 0x9E3779B1 + 0x7F4A7C15 * (1 + self._rank(group, world_size))) & 0xFFFFFFFF
+        self._seed = (int(seed) * 0x9E3779B1 + 0x7F4A7C15 * (1 + self._rank(self.group, self.world))) & 0xFFFFFFFF
         if isinstance(fc.activation, nn.Identity):
             self.fc_act = 0
         elif isinstance(fc.activation, nn.ReLU):
@@ -180,6 +408,11 @@ class FusedTrainer(object):
         enc = model.encoder if isinstance(model.encoder, Encoder) else None
         self.pos = enc.position if (enc is not None and enc.position is not None) else None
         self.pos_learned = isinstance(self.pos, LearnedPositionalEncoding)
+        if self.pos is not None:
+            if self.pos_learned:
+                self.pos_pad = int(self.pos.pe.padding_idx)
+            else:
+                self.pos_pad = int(self.pos.padding_idx)
         out = model.output_layer
         self.n_out = int(out.d_output)                # > 1: ordinal configs (model.py:111-128: forward [B, L, d_output], score = sum)
         if isinstance(out.activation, nn.Identity):
@@ -190,8 +423,7 @@ class FusedTrainer(object):
             self.out_act = 2
         else:
             raise NotImplementedError("FusedTrainer: output activation %r" % (out.activation,))
-        dev = next(model.parameters()).device
-        self.dev = dev
+        self.dev = next(model.parameters()).device
         self.enc = enc
         self.nfc = len(fc.layers)
         self.fc_sizes = [fc.layers[0].in_features] + [l.out_features for l in fc.layers]
@@ -202,8 +434,13 @@ class FusedTrainer(object):
             self.h = l0.self_attn.h
             self.dff = l0.feed_forward.w_1.out_features
             self.ln_eps = enc.norm.eps
+        return seed
 
-        # ---- flat parameter layout (16-byte aligned segments; q,k,v weights and biases adjacent) ----
+    def _layout_parameters(self, dropout):
+        """the flat parameter / gradient / moment buffers (16-byte aligned segments; q,k,v weights and biases adjacent) with the module's
+        parameters re-pointed at them, the gradient buckets, and the parameter views and dropout sites of every encoder layer in
+        ``self.layers`` (_alloc_forward adds the activations); returns the segment offsets"""
+        model, fc, enc, out, dev = self.model, self.model.input_layer, self.enc, self.model.output_layer, self.dev
         order = []
         if self.in_norm is not None:
             order += [self.in_norm.weight, self.in_norm.bias]
@@ -231,38 +468,10 @@ class FusedTrainer(object):
         self.flat_m = torch.zeros(n, dtype=torch.float32, device=dev)
         self.flat_v = torch.zeros(n, dtype=torch.float32, device=dev)
         self.step_count = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.clip = float(gradient_clipping_norm) if gradient_clipping_norm else None
         self.clip_scale = torch.ones(1, dtype=torch.float32, device=dev)
         self.grad_norm = torch.zeros(1, dtype=torch.float32, device=dev)
         self.ws_clip = torch.empty(max(self.lib.ltrx_clip_workspace_bytes(n), 64), dtype=torch.uint8, device=dev)
         self.drop_step = torch.zeros(1, dtype=torch.int32, device=dev)       # u32 word folded into every dropout seed
-        # slate-resident FC + ListNet step (csrc/ltrx_fcstep.hip): eligibility.  It reads the padded batch in place and masks padded
-        # items itself, so a request for variable-length execution is moot for such a job (and would only route it to the slower
-        # GEMM launch sequence): compact is dropped.
-        fc_ok = bool(
-            fc_step and self.N == 0 and self.nfc == 1 and self.in_norm is None and self.pos is None and self.fc_act in (0, 1)
-            and self.p_fc == 0.0 and self.n_out == 1 and self.out_act == 0 and loss_name == "listNet"
-            and gemm == "split_bf16" and optimizer in ("Adam", "AdamW")
-            and self.lib.ltrx_fc_listnet_supported(L, self.fc_sizes[0], self.fc_sizes[1]))
-        if fc_ok:
-            if compact or not use_graph:
-                import logging
-                logging.getLogger("allrank_amd.engine").info(
-                    "FusedTrainer: the slate-resident FC + ListNet step is taken (two launches per step, the padded batch read in place): "
-                    "compact=%s / use_graph=%s do not apply to it; scores / labels of the last step alias the caller's tensors until the "
-                    "next step()", compact, use_graph)
-            compact = False
-        self.compact = bool(compact)
-        self.rows = B * L                                                     # rows the row-wise kernels run over
-        self.n_valid = B * L
-        # cu_seqlens of the packed batch and the attention launch order (longest slate first), one buffer / one copy
-        self._cuord = torch.zeros(2 * B + 1, dtype=torch.int32, device=dev) if compact else None
-        self.cu = self._cuord[:B + 1] if compact else None
-        self.order = self._cuord[B + 1:] if compact else None
-        self.idx = torch.zeros(B * L, dtype=torch.int32, device=dev) if compact else None  # packed row -> padded row
-        if compact:
-            self._cu_ring = [(torch.zeros(2 * B + 1, dtype=torch.int32).pin_memory(), torch.cuda.Event()) for _ in range(4)]
-            self._pack_turn = 0
         # gradient buckets for the multi-GPU all-reduce, in the order the backward completes them: the tail of the flat
         # buffer (last encoder layer + final norm + head) first, then one bucket per earlier layer, the FC stack last
         offs_of = {id(p): o for p, o in zip(order, offs)}
@@ -303,52 +512,14 @@ class FusedTrainer(object):
                 return buf[o:o + count_rows]
             return buf[o:o + count_rows * cols].view(count_rows, cols)
 
-        M, d = self.M, self.d
-        f32 = dict(dtype=torch.float32, device=dev)
-        # The input features: rows of F floats, or -- where the first FC layer can then run the large-tile GEMMs -- rows padded to a
-        # multiple of 256 floats (zeros): the forward projection contracts over F rounded up to the kernel's 32-column step against a
-        # row-padded copy of W_0 (refreshed with the weight images), the weight gradient reads the padded rows as operand tiles.
-        F0 = self.fc_sizes[0]
-        self._x_pad = bool(pad_input and self.in_norm is None and gemm in ("split_bf16", "bf16") and F0 % 4 == 0 and F0 % 256 != 0
-                           and F0 <= 1024 and self.fc_sizes[1] % 256 == 0 and M >= 2048)
-        if self._x_pad:
-            self.x_in_buf = torch.zeros((M, (F0 + 255) // 256 * 256), **f32)
-            self.x_in = self.x_in_buf[:, :F0]
-            kp = (F0 + 31) // 32 * 32
-            self.x_in_k = self.x_in_buf[:, :kp]
-            self.w0_pad = torch.zeros((self.fc_sizes[1], kp), **f32)
-            self.w0_pad_i = torch.zeros_like(self.w0_pad)
-        else:
-            self.x_in = torch.zeros((M, F0), **f32)
-        if self.in_norm is not None:
-            F_ = self.fc_sizes[0]
-            self.x_norm = torch.zeros((M, F_), **f32)
-            self.mean_in = torch.zeros(M, **f32)
-            self.rstd_in = torch.zeros(M, **f32)
-            self.d_in = torch.zeros((M, F_), **f32)
-            self.ws_ln_in = torch.empty(max(self.lib.ltrx_layernorm_bwd_workspace_bytes(M, F_), 64), dtype=torch.uint8, device=dev)
-        if self.pos is not None:
-            self.x_pe = torch.zeros((M, d), **f32)
-            self.idx_rows = torch.full((M,), -1, dtype=torch.int64, device=dev)      # original rank of every row (-1: none)
-            if self.pos_learned:
-                self.pos_pad = int(self.pos.pe.padding_idx)
-            else:
-                self.pos_pad = int(self.pos.padding_idx)
-        self.y_in = torch.zeros((B, L), **f32)
-        self.mask = torch.zeros((B, L), dtype=torch.uint8, device=dev)
-        self.fc_out = [torch.zeros((M, s), **f32) for s in self.fc_sizes[1:]]
+        d = self.d
         self.layers = []
         for i in range(self.N):
             lay = enc.layers[i]
             lin = lay.self_attn.linears
             st = dict(
                 wqkv=fused_view(self.flat_p, lin[0].weight, 3 * d, d), bqkv=fused_view(self.flat_p, lin[0].bias, 3 * d),
-                gwqkv=fused_view(self.flat_g, lin[0].weight, 3 * d, d), gbqkv=fused_view(self.flat_g, lin[0].bias, 3 * d),
-                xsum0=None if i == 0 else torch.zeros((M, d), **f32),      # residual stream entering the layer
-                xn0=torch.zeros((M, d), **f32), mean0=torch.zeros(M, **f32), rstd0=torch.zeros(M, **f32),
-                qkv=torch.zeros((M, 3 * d), **f32), o=torch.zeros((M, d), **f32), lse=torch.zeros((B, self.h, L), **f32),
-                x1=torch.zeros((M, d), **f32), xn1=torch.zeros((M, d), **f32), mean1=torch.zeros(M, **f32),
-                rstd1=torch.zeros(M, **f32), r=torch.zeros((M, self.dff), **f32), mod=lay,
+                gwqkv=fused_view(self.flat_g, lin[0].weight, 3 * d, d), gbqkv=fused_view(self.flat_g, lin[0].bias, 3 * d), mod=lay,
                 # dropout sites (transformer.py:105,155,227): probabilities and seeds
                 p_att=float(lay.self_attn.dropout.p) if dropout else 0.0,
                 p_ff=float(lay.feed_forward.dropout.p) if dropout else 0.0,
@@ -356,17 +527,23 @@ class FusedTrainer(object):
                 p_s1=float(lay.sublayer[1].dropout.p) if dropout else 0.0,
                 s_att=self._site(4 * i), s_ff=self._site(4 * i + 1), s_s0=self._site(4 * i + 2), s_s1=self._site(4 * i + 3))
             self.layers.append(st)
+        # (no active dropout site -> no mask counter to advance: one launch less per step)
+        self._any_dropout = bool(self.p_fc or any(st[k] for st in self.layers for k in ("p_att", "p_ff", "p_s0", "p_s1")))
+        return offs
+
+    def _alloc_backward(self, relu_bits):
+        """gradient buffers and kernel workspaces of the backward (what _body and its helpers use beyond the forward buffer set)"""
+        B, L, M, d, dev, compact, gemm = self.B, self.L, self.M, self.d, self.dev, self.compact, self.gemm
+        f32 = dict(dtype=torch.float32, device=dev)
+        if self.in_norm is not None:
+            F_ = self.fc_sizes[0]
+            self.d_in = torch.zeros((M, F_), **f32)
+            self.ws_ln_in = torch.empty(max(self.lib.ltrx_layernorm_bwd_workspace_bytes(M, F_), 64), dtype=torch.uint8, device=dev)
         if relu_bits and self.N and self.dff % 256 == 0 and d % 32 == 0 and gemm not in ("hipblaslt", "split_bf16_strict"):
             # one bit per feed-forward activation (written by the forward GEMM, read by the input-gradient GEMM instead of r)
             for st in self.layers:
                 st["rbits"] = torch.zeros(((M + 255) // 256) * (self.dff // 256) * 8192, dtype=torch.uint8, device=dev)
-        # (no active dropout site -> no mask counter to advance: one launch less per step)
-        self._any_dropout = bool(self.p_fc or any(st[k] for st in self.layers for k in ("p_att", "p_ff", "p_s0", "p_s1")))
         if self.N:
-            self.xsum_f = torch.zeros((M, d), **f32)
-            self.xf = torch.zeros((M, d), **f32)
-            self.mean_f = torch.zeros(M, **f32)
-            self.rstd_f = torch.zeros(M, **f32)
             self.d_r = torch.zeros((M, self.dff), **f32)
             self.dqkv = torch.zeros((M, 3 * d), **f32)
             self.d_o = torch.zeros((M, d), **f32)
@@ -377,10 +554,7 @@ class FusedTrainer(object):
             self.ws_ln_g = [self.ws_ln] + [torch.empty_like(self.ws_ln) for _ in range(2)]
             self.ws_mha = torch.empty(max(self.lib.ltrx_mha_bwd_workspace_bytes(B, L, self.h, self.d // self.h, self._mha_mode), 64), dtype=torch.uint8, device=dev)
         no = self.n_out
-        self.scores_raw = torch.zeros((B, L) if no == 1 else (B, L, no), **f32)      # what the loss sees (model.forward)
-        self.scores = self.scores_raw if no == 1 else torch.zeros((B, L), **f32)      # model.score (sum over the output units)
         if compact:
-            self.scores_c = torch.zeros(M if no == 1 else (M, no), **f32)
             self.dsc_c = torch.zeros(M if no == 1 else (M, no), **f32)
         if no > 1:
             npad = (no + 3) // 4 * 4
@@ -393,8 +567,6 @@ class FusedTrainer(object):
         self.ws_col = torch.empty(max(self.lib.ltrx_colsum_workspace_bytes(M, maxn), 64), dtype=torch.uint8, device=dev)
         self.ws_head = torch.empty(max(self.lib.ltrx_score_head_bwd_workspace_bytes(M, d), 64), dtype=torch.uint8, device=dev)
         self.fc_dgrad = [torch.zeros((M, s), **f32) for s in self.fc_sizes[1:-1]]
-        big = max([(3 * d) * d, (self.dff * d) if self.N else 0] + [a * b for a, b in zip(self.fc_sizes[:-1], self.fc_sizes[1:])])
-        self._fused_images = False
         if self.gemm != "hipblaslt":
             nb = 0
             shapes = [(s1, s0) for s0, s1 in zip(self.fc_sizes[:-1], self.fc_sizes[1:])]
@@ -417,82 +589,61 @@ class FusedTrainer(object):
                     kpa = (ctypes.c_int * len(comp))(*[c[1] for c in comp])
                     nb = max(nb, self.lib.ltrx_gemm_tn_group_workspace_bytes(len(comp), M, npa, kpa))
             self.ws_tn = torch.empty(max(nb, 64), dtype=torch.uint8, device=dev)
-            # transposed weight copies for the input-gradient GEMMs (refreshed after every optimizer step by ONE batched
-            # transpose launch): all copies live in one flat buffer, the descriptor table is built once
-            tw = [l.weight for l in (fc.layers if self.in_norm is not None else fc.layers[1:])]
-            srcs = [(self._pv[id(p)][0], p.shape[0], p.shape[1], ("w", id(p))) for p in tw]
-            if enc is not None:
-                for li, st in enumerate(self.layers):
-                    lay = st["mod"]
-                    for p in (lay.self_attn.linears[3].weight, lay.feed_forward.w_1.weight, lay.feed_forward.w_2.weight):
-                        srcs.append((self._pv[id(p)][0], p.shape[0], p.shape[1], ("w", id(p))))
-                    srcs.append((self._pv[id(lay.self_attn.linears[0].weight)][0], 3 * d, d, ("qkv", li)))
-            tot = sum((r * c + 3) // 4 * 4 for _, r, c, _ in srcs)
-            self.flat_t = torch.zeros(max(tot, 4), **f32)
-            desc, tstart, o = [], [0], 0
-            for (so, r, c, key) in srcs:
-                view = self.flat_t[o:o + r * c].view(c, r)
-                if key[0] == "w":
-                    self._wT[key[1]] = view
-                else:
-                    self.layers[key[1]]["wqkvT"] = view
-                desc += [so, o, r, c]
-                tstart.append(tstart[-1] + ((r + 31) // 32) * ((c + 31) // 32))
-                o += (r * c + 3) // 4 * 4
-            self._tdesc = torch.tensor(desc if desc else [0, 0, 0, 0], dtype=torch.int64, device=dev)
-            self._tstart = torch.tensor(tstart, dtype=torch.int32, device=dev)
-            self._tn, self._ttiles = len(srcs), tstart[-1]
-            # pre-split bf16 hi / lo IMAGES of the weights and of their transposes (same offsets as flat_p / flat_t): what the
-            # large-tile NT GEMMs stage as operand B without splitting it again in every tile (ltrx_split_image, include/ltrx.h)
-            self.flat_pi = torch.empty_like(self.flat_p)
-            self.flat_ti = torch.zeros_like(self.flat_t)
-            # one-launch refresh (ltrx_weight_images) when every transposed matrix keeps image groups of 4 inside a row
-            self._fused_images = self.nflat % 4 == 0 and all(r % 4 == 0 for _, r, _, _ in srcs)
-            self._refresh_transposes()
-        self.loss = FusedLoss(loss_name, B, L, dev, **(loss_args or {}))
-        if (self.n_out > 1) != (loss_name == "ordinal") or (loss_name == "ordinal" and int(loss_args["n"]) != self.n_out):
-            raise NotImplementedError("FusedTrainer: d_output > 1 goes with the ordinal loss of the same n (and only with it)")
-        # ListMLE: the reference draws torch.randperm(L) on every call (listMLE.py:17).  shuffle_ties=True (default) does
-        # the same with a device generator; tests that compare with the oracle set shuffle_ties=False and an explicit
-        # permutation via ``trainer.loss.set_perm``.
-        self.shuffle_ties = True
-        self._perm_gen = torch.Generator(device=dev)
-        self._perm_gen.manual_seed(int(seed) & 0x7FFFFFFF)
-        self.use_graph = use_graph and not compact
-        self.graph_fwd, self._warm_fwd = None, 0
-        self.probe = None                                     # list collecting (start, end) events of the FFN1 GEMM (eager steps only)
-        self.probe_wgrad = None                               # ... of the grouped weight-gradient launch (bench.py, eager steps only)
-        # captured steps: {(batch divisor, collectives on?): [(hipGraph segment, collective to launch after it | None), ...]}
-        import collections
-        self._graphs = collections.OrderedDict()
-        self.max_graphs = 4
-        self._warned_evict = False
-        self.capture_fallback = None                          # repr of the capture error if a sharded run fell back to eager steps
-        self._seg_break = None                                # set while capturing: ends the current segment (see _capture)
-        self._graph_pool = None
-        self._cap_stream = None
-        self._warm = 0
-        self._wver = [p._version for p in self._order]
-        self._images_stale = False
-        self.y_cur = self.y_in                                # labels of the last step() (the caller's tensor in the fcstep path)
-        self.keep_fc_out = False                              # tests: also write the FC activations to fc_out[0]
-        self.keep_loss_grad = False                           # tests: also write d loss / d scores to self.loss.grad (4 B per item)
-        self.fcstep = fc_ok
-        if self.fcstep and fc_step == "collapse" and self.fc_act == 0:
-            self.fcstep = "collapse"
-        if self.fcstep:
-            F_, H_ = self.fc_sizes[0], self.fc_sizes[1]
-            H4 = (H_ + 3) // 4 * 4
-            offs_fc = (0, H_ * F_, H_ * F_ + H4, H_ * F_ + 2 * H4)
-            assert tuple(offs) == offs_fc and self.nflat == offs_fc[3] + 4, (offs, self.nflat)
-            self._fc_ws = torch.empty(max(self.lib.ltrx_fc_listnet_workspace_bytes(B, L, F_, H_, self.nflat), 64), dtype=torch.uint8, device=dev)
-            P = LB.ptr
-            self._fc_a = (B, L, F_, H_, self.fc_act, P(self.flat_p), offs_fc[0], offs_fc[1], offs_fc[2], offs_fc[3], self.nflat,
-                          float(self.loss.eps), float(self.loss.pad))
-            if self.fcstep == "collapse":
-                self._fc_ws = torch.empty(max(self.lib.ltrx_fc_linear_listnet_workspace_bytes(B, F_), 64), dtype=torch.uint8, device=dev)
-                self._fc_a = self._fc_a[:4] + self._fc_a[5:]          # (no activation argument)
-            self._fc_b = (P(self.scores_raw), P(self.loss.grad))
+
+    def _init_weight_images(self):
+        """transposed weight copies for the input-gradient GEMMs (one flat buffer, one descriptor table, refreshed after every optimizer
+        step by ONE batched transpose launch) and the pre-split images of the weights and of the copies"""
+        fc, enc, d, dev = self.model.input_layer, self.enc, self.d, self.dev
+        f32 = dict(dtype=torch.float32, device=dev)
+        if self._x_pad:                                           # the row-padded copy of W_0 the padded input rows multiply
+            self.w0_pad = torch.zeros((self.fc_sizes[1], self.x_in_k.shape[1]), **f32)
+            self.w0_pad_i = torch.zeros_like(self.w0_pad)
+        tw = [l.weight for l in (fc.layers if self.in_norm is not None else fc.layers[1:])]
+        srcs = [(self._pv[id(p)][0], p.shape[0], p.shape[1], ("w", id(p))) for p in tw]
+        if enc is not None:
+            for li, st in enumerate(self.layers):
+                lay = st["mod"]
+                for p in (lay.self_attn.linears[3].weight, lay.feed_forward.w_1.weight, lay.feed_forward.w_2.weight):
+                    srcs.append((self._pv[id(p)][0], p.shape[0], p.shape[1], ("w", id(p))))
+                srcs.append((self._pv[id(lay.self_attn.linears[0].weight)][0], 3 * d, d, ("qkv", li)))
+        tot = sum((r * c + 3) // 4 * 4 for _, r, c, _ in srcs)
+        self.flat_t = torch.zeros(max(tot, 4), **f32)
+        desc, tstart, o = [], [0], 0
+        for (so, r, c, key) in srcs:
+            view = self.flat_t[o:o + r * c].view(c, r)
+            if key[0] == "w":
+                self._wT[key[1]] = view
+            else:
+                self.layers[key[1]]["wqkvT"] = view
+            desc += [so, o, r, c]
+            tstart.append(tstart[-1] + ((r + 31) // 32) * ((c + 31) // 32))
+            o += (r * c + 3) // 4 * 4
+        self._tdesc = torch.tensor(desc if desc else [0, 0, 0, 0], dtype=torch.int64, device=dev)
+        self._tstart = torch.tensor(tstart, dtype=torch.int32, device=dev)
+        self._tn, self._ttiles = len(srcs), tstart[-1]
+        # pre-split bf16 hi / lo IMAGES of the weights and of their transposes (same offsets as flat_p / flat_t): what the
+        # large-tile NT GEMMs stage as operand B without splitting it again in every tile (ltrx_split_image, include/ltrx.h)
+        self.flat_pi = torch.empty_like(self.flat_p)
+        self.flat_ti = torch.zeros_like(self.flat_t)
+        # one-launch refresh (ltrx_weight_images) when every transposed matrix keeps image groups of 4 inside a row
+        self._fused_images = self.nflat % 4 == 0 and all(r % 4 == 0 for _, r, _, _ in srcs)
+        self._refresh_transposes()
+
+    def _init_fc_step(self, offs):
+        """the slate-resident FC + ListNet step: its workspace and the launch arguments that never change"""
+        B, L, dev = self.B, self.L, self.dev
+        F_, H_ = self.fc_sizes[0], self.fc_sizes[1]
+        H4 = (H_ + 3) // 4 * 4
+        offs_fc = (0, H_ * F_, H_ * F_ + H4, H_ * F_ + 2 * H4)
+        assert tuple(offs) == offs_fc and self.nflat == offs_fc[3] + 4, (offs, self.nflat)
+        self._fc_ws = torch.empty(max(self.lib.ltrx_fc_listnet_workspace_bytes(B, L, F_, H_, self.nflat), 64), dtype=torch.uint8, device=dev)
+        P = self.LB.ptr
+        self._fc_a = (B, L, F_, H_, self.fc_act, P(self.flat_p), offs_fc[0], offs_fc[1], offs_fc[2], offs_fc[3], self.nflat,
+                      float(self.loss.eps), float(self.loss.pad))
+        if self.fcstep == "collapse":
+            self._fc_ws = torch.empty(max(self.lib.ltrx_fc_linear_listnet_workspace_bytes(B, F_), 64), dtype=torch.uint8, device=dev)
+            self._fc_a = self._fc_a[:4] + self._fc_a[5:]          # (no activation argument)
+        self._fc_b = (P(self.scores_raw), P(self.loss.grad))
 
     # ---- thin launch helpers -----------------------------------------------------------------------------------
     def _st(self):
@@ -535,7 +686,6 @@ class FusedTrainer(object):
         P = self.LB.ptr
         if self.group_wgrad and self.gemm != "hipblaslt" and self._ln_slot < len(self.ws_ln_g):
             # dx now; the (da, db) partials join the layer's one reducing launch (_reduce_flush)
-            import ctypes
             buf = self.ws_ln_g[self._ln_slot]
             self._ln_slot += 1
             rows_out = ctypes.c_int(0)
@@ -721,7 +871,6 @@ class FusedTrainer(object):
         q = self._wg_pending
         if not q:
             return
-        import ctypes
         n = len(q)
         vp, ci = ctypes.c_void_p * n, ctypes.c_int * n
         A = vp(*[t[0].data_ptr() for t in q])
@@ -766,7 +915,6 @@ class FusedTrainer(object):
         self._ln_slot = 0
         if not q:
             return
-        import ctypes
         n = len(q)
         vp = ctypes.c_void_p * n
         self.LB.check(self.lib.ltrx_reduce_group(n, vp(*[t[0] for t in q]), (ctypes.c_int * n)(*[t[1] for t in q]),
@@ -776,10 +924,9 @@ class FusedTrainer(object):
 
     # ---- the step body (capturable) ----------------------------------------------------------------------------
     def _forward(self, train=True, bs=None):
-        """input buffers -> scores (scores_raw [B, L, n_out], scores [B, L]) of the buffer set ``bs``: the step's own buffers (``bs``
-        None = self) or a FusedScorer's (forward-only, packed, its own B / L / row count; the valid-row count is read from its
-        device cu_seqlens).  ``train=False`` is model.eval(): every dropout rate is 0 (the saved activations are written all the same,
-        nothing reads them).  Returns (feat, sc_rows)."""
+        """input buffers -> scores of the buffer set ``bs`` (what that is: ``_alloc_forward``): the step's own (``bs`` None = self) or
+        a FusedScorer's (the valid-row count is then read from its device cu_seqlens).  ``train=False`` is model.eval(): every dropout
+        rate is 0 (the activations are written all the same).  Returns (feat, sc_rows)."""
         bs = self if bs is None else bs
         P = self.LB.ptr
         lib, M, d, B, L = self.lib, bs.rows, self.d, bs.B, bs.L
@@ -1034,22 +1181,8 @@ class FusedTrainer(object):
         valid items on the device costs."""
         B, L = self.B, self.L
         if lengths is not None:
-            # only the B+1 prefix sums cross PCIe, from a ring of pinned staging buffers (a slot is reused after its copy
-            # has completed); the packed-row index is derived on the device
-            k = self._pack_turn % len(self._cu_ring)
-            self._pack_turn += 1
-            host, ev = self._cu_ring[k]
-            ev.synchronize()
-            lens = torch.as_tensor(lengths, dtype=torch.int32)
-            if lens.is_cuda:                                      # (a device tensor costs the sync the host lengths are meant to avoid)
-                lens = lens.cpu()
-            lens = lens.reshape(B).clamp(min=0, max=L)
-            host[0] = 0
-            torch.cumsum(lens, 0, dtype=torch.int32, out=host[1:B + 1])
-            host[B + 1:] = torch.argsort(lens, descending=True, stable=True)
-            n = int(host[B])
-            self._cuord.copy_(host, non_blocking=True)
-            ev.record()
+            # only the B+1 prefix sums and the launch order cross PCIe (_Stager); the packed-row index is derived on the device
+            n = self._stager.upload(torch.as_tensor(lengths, dtype=torch.int32).reshape(B).clamp(min=0, max=L))
             self.LB.check(self.lib.ltrx_packed_row_index(self.LB.ptr(self.cu), B, L, n, self.LB.ptr(self.idx), self._st()),
                           "packed_row_index")
         else:
@@ -1083,18 +1216,10 @@ class FusedTrainer(object):
             if p.grad is None or p.grad.data_ptr() != g.data_ptr():
                 p.grad = g
 
-    def step(self, xb, yb, indices=None, global_batch=None, lengths=None):
-        """copy the batch into the static input buffers and run (or replay) the step; returns the device loss [1]."""
-        self._reattach()
-        if self.fcstep:
-            return self._fc_step(xb, yb, global_batch)
-        self._sync_weights()
+    def _stage_batch(self, xb, yb, indices, lengths, who):
+        """the batch of ``step()`` / ``score()`` into the static input buffers: labels, padding mask and features (one launch where
+        the caller's tensors allow it), the packed rows when compact, the rank of every row when the model has a positional encoding"""
         self.y_cur = self.y_in
-        if self.loss.name == "listMLE" and self.shuffle_ties:
-            # listMLE.py:17: a fresh random column order per call breaks ties among equal labels at random; the
-            # permutation lives in a persistent device buffer, so the refresh is safe under hipGraph replay
-            self.loss.perm.copy_(torch.randperm(self.L, device=self.dev, generator=self._perm_gen))
-        self._divisor = float(global_batch if global_batch is not None else self.B * self.world)
         direct = (yb.dtype == torch.float32 and yb.is_contiguous() and yb.is_cuda and yb.numel() == self.M
                   and (self.compact or (xb.dtype == torch.float32 and xb.is_contiguous() and xb.is_cuda
                                         and xb.numel() == self.x_in.numel())))
@@ -1113,12 +1238,25 @@ class FusedTrainer(object):
             self.x_in.copy_(xb.reshape(self.M, -1))
         if self.pos is not None:
             if indices is None:
-                raise ValueError("FusedTrainer: the model has a positional encoding, step() needs `indices`")
+                raise ValueError("FusedTrainer: the model has a positional encoding, %s() needs `indices`" % who)
             if self.compact:                                      # rank of every packed row; alignment rows -> padding row
                 self.idx_rows.fill_(-1)
                 self.idx_rows[:self.n_valid] = indices.reshape(-1)[self.idx[:self.n_valid].long()]
             else:
                 self.idx_rows.copy_(indices.reshape(-1))
+
+    def step(self, xb, yb, indices=None, global_batch=None, lengths=None):
+        """copy the batch into the static input buffers and run (or replay) the step; returns the device loss [1]."""
+        self._reattach()
+        if self.fcstep:
+            return self._fc_step(xb, yb, global_batch)
+        self._sync_weights()
+        if self.loss.name == "listMLE" and self.shuffle_ties:
+            # listMLE.py:17: a fresh random column order per call breaks ties among equal labels at random; the
+            # permutation lives in a persistent device buffer, so the refresh is safe under hipGraph replay
+            self.loss.perm.copy_(torch.randperm(self.L, device=self.dev, generator=self._perm_gen))
+        self._divisor = float(global_batch if global_batch is not None else self.B * self.world)
+        self._stage_batch(xb, yb, indices, lengths, "step")
         if not self.use_graph:
             return self._eager()
         # The batch divisor is a by-value launch argument of the loss kernels (include/ltrx.h: `batch_divisor`), i.e. a captured
@@ -1136,7 +1274,6 @@ class FusedTrainer(object):
                 old_key = next(iter(self._graphs))
                 del self._graphs[old_key]
                 if not self._warned_evict:
-                    import warnings
                     self._warned_evict = True
                     warnings.warn("allrank_amd: more than %d distinct batch divisors in flight -- evicting the least recently used captured "
                                   "step (divisor %g); every new divisor costs one re-capture" % (self.max_graphs, old_key[0]))
@@ -1149,7 +1286,6 @@ class FusedTrainer(object):
                 msg = str(exc)
                 if not self.sharded or not any(t in msg for t in ("capture", "Capture", "hipErrorStreamCapture", "cudaErrorStreamCapture")):
                     raise
-                import warnings
                 warnings.warn("allrank_amd: hipGraph capture of the sharded step failed (%r); running eagerly" % (exc,))
                 self.capture_fallback = repr(exc)     # queryable: tests/dist_equiv_worker.py asserts it stays None
                 self.use_graph = False
@@ -1280,44 +1416,19 @@ class FusedTrainer(object):
         return segs
 
 
-    def _fwd_only(self):
-        self._forward(False)
-
     def score(self, xb, yb, indices=None, lengths=None):
         """``model.score(xb, yb == PADDED_Y_VALUE, indices)`` in eval mode (model.py:82-92) through the kernels of the training
         step -- the forward half only, every dropout off, replayed from its own hipGraph -- for the validation / metric passes of
         an epoch (train_utils.py:32-56, 101-107).  The nn.Module forward computes the same scores with fp32 library GEMMs at
-        less than half the rate.  ``yb`` only provides the padding mask; the batch must have the trainer's [B, L] shape (top up
-        a short last batch with all-padded slates).  Returns the trainer's score buffer [B, L] (valid until the next call)."""
+        less than half the rate.  ``yb`` only provides the padding mask; the batch must have the trainer's [B, L] shape
+        (``pad_batch``) and is staged as ``step()`` stages it.  Returns the trainer's ``scores`` [B, L] (valid until the next call)."""
         self._reattach()
         self._sync_weights()
-        self.y_in.copy_(yb)
-        self.y_cur = self.y_in
-        self.mask.copy_(yb == PADDED_Y_VALUE)
-        if self.compact:
-            self._pack(xb.reshape(self.M, -1).contiguous(), lengths)
+        self._stage_batch(xb, yb, indices, lengths, "score")
+        if self.use_graph:
+            self._fwd_graphs.run(0, lambda: self._forward(False))
         else:
-            self.x_in.copy_(xb.reshape(self.M, -1))
-        if self.pos is not None:
-            if indices is None:
-                raise ValueError("FusedTrainer: the model has a positional encoding, score() needs `indices`")
-            if self.compact:
-                self.idx_rows.fill_(-1)
-                self.idx_rows[:self.n_valid] = indices.reshape(-1)[self.idx[:self.n_valid].long()]
-            else:
-                self.idx_rows.copy_(indices.reshape(-1))
-        if not self.use_graph:
-            self._fwd_only()
-            return self.scores
-        if self.graph_fwd is None:
-            if self._warm_fwd < 2:
-                self._warm_fwd += 1
-                self._fwd_only()
-                return self.scores
-            self.graph_fwd = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph_fwd):
-                self._fwd_only()
-        self.graph_fwd.replay()
+            self._forward(False)
         return self.scores
 
     def scorer(self, B, L, use_graph=True, max_graphs=8):
@@ -1346,19 +1457,17 @@ class FusedScorer(object):
         padded slots (ltrx_scatter_rows_cu) -- the value compact training leaves there;
       * the weights are the trainer's (flat parameters, weight images and transposes), re-synced before every call as ``score()``
         does, so every optimizer step is seen;
-      * nothing is saved for a backward: one encoder layer's activation buffers serve every layer (bytes: ``self.nbytes``);
-      * the row count is rounded up the ladder of ``row_bucket``; the forward of a bucket is captured in a hipGraph after two eager
-        calls at that bucket (``score()``'s warm-up rule) and replayed for every later batch that falls in it -- the kernels read the
-        valid-row count from device memory, so a graph is right for every batch of its bucket.  The graphs form an LRU of
-        ``max_graphs`` buckets: a new bucket beyond that evicts the least recently used one (``evictions`` counts them);
-      * per batch the host only picks the bucket from the host lengths and uploads the B+1 prefix sums, the launch order and the slate
-        ids from pinned staging (a ring of 4, as ``FusedTrainer._pack`` does): no host sync.  ``run`` without host lengths counts
-        the valid items on the device -- one sync, as compact training does.
+      * nothing is saved for a backward: the ``saved=False`` buffer set of ``_alloc_forward`` (bytes: ``self.nbytes``);
+      * the row count is rounded up the ladder of ``row_bucket``, and the bucket keys the forward-graph rule of ``_GraphLRU`` (LRU of
+        ``max_graphs`` buckets) -- the kernels read the valid-row count from device memory, so a graph is right for every batch of
+        its bucket;
+      * per batch the host only picks the bucket from the host lengths and uploads prefix sums, launch order and slate ids
+        (``_Stager``): no host sync.  ``run`` without host lengths counts the valid items on the device -- one sync, as compact
+        training does.
     Results (``scores_raw`` [B, L] or [B, L, d_output], ``scores`` [B, L], labels ``y`` [B, L] of ``run_resident``) stay valid until
     the next call."""
 
     def __init__(self, trainer, B, L, use_graph=True, max_graphs=8):
-        import collections
         from . import _lib as LB
         t = trainer
         B, L = int(B), int(L)
@@ -1366,58 +1475,12 @@ class FusedScorer(object):
             raise ValueError("FusedScorer: B and L must be positive")
         if L > LB.MAX_METRIC_SLATE_LEN:
             raise ValueError("FusedScorer: slate length %d above LTRX_MAX_METRIC_SLATE_LEN = %d" % (L, LB.MAX_METRIC_SLATE_LEN))
-        self.t, self.LB, self.B, self.L = t, LB, B, L
-        self.compact, self.mask = True, None              # (what FusedTrainer._forward reads of a buffer set)
-        dev = t.dev
+        self.t, self.LB = t, LB
         self.cap = (B * L + 31) // 32 * 32                 # the largest rung: every slot of the batch valid
-        Mc = self.cap
-        f32 = dict(dtype=torch.float32, device=dev)
-        # device staging of one batch: slate ids (i64, as int32 pairs), cu_seqlens [B+1], launch order [B] -- one upload
-        self._stage = torch.zeros(4 * B + 1, dtype=torch.int32, device=dev)
-        self.ids = self._stage[:2 * B].view(torch.int64)
-        self.cu = self._stage[2 * B:3 * B + 1]
-        self.order = self._stage[3 * B + 1:]
-        self._ring = [(torch.zeros(4 * B + 1, dtype=torch.int32).pin_memory(), torch.cuda.Event()) for _ in range(4)]
-        self._turn = 0
+        _alloc_forward(self, t, self.cap, B, L, saved=False, compact=True)
+        self.ids = self._stager.ids
         self.rows, self.n_valid = 32, 0
-        self.idx = torch.full((Mc,), -1, dtype=torch.int32, device=dev)     # packed row -> b * L + j
-        F0 = t.fc_sizes[0]
-        if t._x_pad:                                       # the trainer's first GEMM reads 256-float padded rows and a padded W_0
-            self.x_in_buf = torch.zeros((Mc, t.x_in_buf.shape[1]), **f32)
-            self.x_in = self.x_in_buf[:, :F0]
-            self.x_in_k = self.x_in_buf[:, :t.x_in_k.shape[1]]
-        else:
-            self.x_in = torch.zeros((Mc, F0), **f32)
-        if t.in_norm is not None:
-            self.x_norm = torch.zeros((Mc, F0), **f32)
-            self.mean_in, self.rstd_in = torch.zeros(Mc, **f32), torch.zeros(Mc, **f32)
-        self.fc_out = [torch.zeros((Mc, s), **f32) for s in t.fc_sizes[1:]]
-        if t.pos is not None:
-            self.idx_rows = torch.full((Mc,), -1, dtype=torch.int64, device=dev)
-        d = t.d
-        self.layers = []
-        if t.N:
-            # the residual stream ping-pongs between two buffers (a layer's input is dead once its out-projection has added it);
-            # one LayerNorm output / statistics set serves LN0, LN1 and the final norm (each is consumed before the next is written)
-            ping = [torch.zeros((Mc, d), **f32) for _ in range(2)]
-            xn, mean, rstd = torch.zeros((Mc, d), **f32), torch.zeros(Mc, **f32), torch.zeros(Mc, **f32)
-            act = dict(xn0=xn, xn1=xn, mean0=mean, rstd0=rstd, mean1=mean, rstd1=rstd, qkv=torch.zeros((Mc, 3 * d), **f32),
-                       o=torch.zeros((Mc, d), **f32), x1=torch.zeros((Mc, d), **f32), r=torch.zeros((Mc, t.dff), **f32),
-                       lse=torch.zeros((B, t.h, L), **f32))
-            keys = ("wqkv", "bqkv", "mod", "p_att", "p_ff", "p_s0", "p_s1", "s_att", "s_ff", "s_s0", "s_s1")
-            for i, st in enumerate(t.layers):
-                self.layers.append(dict({k: st[k] for k in keys}, xsum0=ping[i % 2], **act))
-            self.xsum_f = ping[t.N % 2]
-            self.xf, self.mean_f, self.rstd_f = xn, mean, rstd
-            if t.pos is not None:
-                self.x_pe = ping[0]                         # layer 0 reads it and writes ping[1]
-        elif t.pos is not None:
-            self.x_pe = torch.zeros((Mc, d), **f32)
-        no = t.n_out
-        self.scores_c = torch.zeros(Mc if no == 1 else (Mc, no), **f32)
-        self.scores_raw = torch.zeros((B, L) if no == 1 else (B, L, no), **f32)
-        self.scores = self.scores_raw if no == 1 else torch.zeros((B, L), **f32)
-        self.y = torch.full((B, L), float(PADDED_Y_VALUE), **f32)
+        self.y = torch.full((B, L), float(PADDED_Y_VALUE), dtype=torch.float32, device=t.dev)
         seen, nb = set(), 0
         for v in list(vars(self).values()) + [v for st in self.layers for v in st.values()]:
             if torch.is_tensor(v) and v.is_cuda and v.untyped_storage().data_ptr() not in seen:
@@ -1425,41 +1488,20 @@ class FusedScorer(object):
                 nb += v.untyped_storage().nbytes()
         self.nbytes = nb
         self.use_graph, self.max_graphs = bool(use_graph), int(max_graphs)
-        self._graphs = collections.OrderedDict()           # row bucket -> captured forward
-        self._visits = collections.Counter()
-        self._pool = None
-        self.evictions = 0
-        self.last_mode = None                              # "eager" / "capture" / "replay" of the last call (tests)
+        self._fwd_graphs = _GraphLRU(max_graphs, own_pool=True)
+        self._graphs = self._fwd_graphs.graphs             # row bucket -> captured forward, least recently used first
+        self.last_mode, self.evictions = None, 0           # "eager" / "capture" / "replay" of the last call; buckets evicted so far
 
     def _upload(self, ids, lengths):
         """host lengths (and slate ids) of one batch -> cu_seqlens, longest-first launch order (and ids) on the device through the
         pinned ring; returns the valid-row count"""
-        B, L = self.B, self.L
-        k = self._turn % len(self._ring)
-        self._turn += 1
-        host, ev = self._ring[k]
-        ev.synchronize()                                   # (the copy that last used this slot has completed)
-        lens = torch.as_tensor(lengths, dtype=torch.int32)
-        if lens.is_cuda:                                   # (a device tensor costs the sync the host lengths are meant to avoid)
-            lens = lens.cpu()
-        lens = lens.reshape(-1)
+        lens = torch.as_tensor(lengths, dtype=torch.int32).reshape(-1)
         n = int(lens.numel())
-        if n > B:
-            raise ValueError("FusedScorer: %d slates in a batch of a %d-slate scorer" % (n, B))
-        if n and int(lens.max()) > L:
-            raise ValueError("FusedScorer: a slate of %d items in a scorer for slate length %d" % (int(lens.max()), L))
-        full = torch.zeros(B, dtype=torch.int32)
-        full[:n] = lens.clamp(min=0)
-        host[2 * B] = 0
-        torch.cumsum(full, 0, dtype=torch.int32, out=host[2 * B + 1:3 * B + 1])
-        host[3 * B + 1:] = torch.argsort(full, descending=True, stable=True)
-        if ids is not None:
-            h64 = host[:2 * B].view(torch.int64)
-            h64.zero_()                                    # (slates past n: id 0, length 0 -- never read)
-            h64[:n] = torch.as_tensor(ids, dtype=torch.int64).cpu().reshape(-1)
-        self._stage.copy_(host, non_blocking=True)
-        ev.record()
-        return int(host[3 * B])
+        if n > self.B:
+            raise ValueError("FusedScorer: %d slates in a batch of a %d-slate scorer" % (n, self.B))
+        if n and int(lens.max()) > self.L:
+            raise ValueError("FusedScorer: a slate of %d items in a scorer for slate length %d" % (int(lens.max()), self.L))
+        return self._stager.upload(lens.clamp(min=0), None if ids is None else torch.as_tensor(ids, dtype=torch.int64).cpu())
 
     def _set_rows(self, n):
         self.n_valid = n
@@ -1527,32 +1569,13 @@ class FusedScorer(object):
         return self.scores_raw
 
     def _run(self):
-        t, key = self.t, self.rows
-        if not self.use_graph:
-            self.last_mode = "eager"
-            t._forward(False, self)
-            return
-        g = self._graphs.get(key)
-        if g is None:
-            self._visits[key] += 1
-            if self._visits[key] <= 2:                     # warm-up outside capture (lazy module loads, kernel attributes)
-                self.last_mode = "eager"
-                t._forward(False, self)
-                return
-            if len(self._graphs) >= self.max_graphs:
-                self._graphs.popitem(last=False)
-                self.evictions += 1
-            if self._pool is None:
-                self._pool = torch.cuda.graph_pool_handle()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=self._pool):
-                t._forward(False, self)
-            self._graphs[key] = g
-            self.last_mode = "capture"
+        fwd = lambda: self.t._forward(False, self)
+        if self.use_graph:
+            self.last_mode = self._fwd_graphs.run(self.rows, fwd)
+            self.evictions = self._fwd_graphs.evictions
         else:
-            self._graphs.move_to_end(key)
-            self.last_mode = "replay"
-        g.replay()
+            self.last_mode = "eager"
+            fwd()
 
 
 class _null(object):
@@ -1617,10 +1640,7 @@ def fit_device(model, loss_name, loss_args, train_ds, val_ds, epochs, batch_size
                 # the last batch of an epoch (DataLoader drop_last=False, dataset_loading.py:245): the fused step has static
                 # shapes, so the batch is topped up with fully padded slates (label -1, features 0: no loss, no gradient) and
                 # the loss is normalised by the REAL slate count, exactly what the reference computes on the short batch
-                padn = batch_size - real
-                xb = torch.cat([xb, xb.new_zeros((padn,) + tuple(xb.shape[1:]))])
-                yb = torch.cat([yb, yb.new_full((padn, yb.shape[1]), float(PADDED_Y_VALUE))])
-                idx = torch.cat([idx, idx.new_full((padn, idx.shape[1]), -1)])
+                xb, yb, idx = pad_batch(xb, yb, idx, batch_size)
                 loss = trainer.step(xb, yb, idx, global_batch=real)
             else:
                 loss = trainer.step(xb, yb, idx)

@@ -52,7 +52,7 @@ import torch
 from . import losses as E
 from . import metrics as EM
 from .data import ShardBatch
-from .engine import FusedTrainer, Trainer, PADDED_Y_VALUE
+from .engine import FusedTrainer, Trainer, PADDED_Y_VALUE, pad_batch as _pad_batch
 from .parallel import shard_slates
 
 log = logging.getLogger("allrank_amd.fit")
@@ -105,15 +105,6 @@ def _fused_spec(model, loss_func, optimizer):
     else:
         return None, "optimizer %s is not one of the fused Adam / AdamW / SGD" % type(optimizer).__name__
     return (loss_func.func.__name__, dict(loss_func.keywords or {}), float(g["lr"]), opt), ""
-
-
-def _pad_batch(xb, yb, idx, B):
-    n = B - xb.shape[0]
-    if n <= 0:
-        return xb, yb, idx
-    return (torch.cat([xb, xb.new_zeros((n,) + tuple(xb.shape[1:]))]),
-            torch.cat([yb, yb.new_full((n, yb.shape[1]), float(PADDED_Y_VALUE))]),
-            torch.cat([idx, idx.new_full((n, idx.shape[1]), -1)]))
 
 
 class _Prefetcher(object):

@@ -52,6 +52,9 @@ def _bar(ref, valid):
 MODELS = {
     "pe_fixed": dict(pe=dict(strategy="fixed", max_indices=1300)),
     "pe_learned": dict(pe=dict(strategy="learned", max_indices=1300)),
+    # odd depths: the scorer's residual ping-pong ends in the other buffer (xsum_f = ping[N % 2], x_pe = ping[0])
+    "pe_fixed_n1": dict(N=1, pe=dict(strategy="fixed", max_indices=1300)),
+    "pe_learned_n3": dict(N=3, pe=dict(strategy="learned", max_indices=1300)),
     "input_norm_tanh": dict(input_norm=True, act="Tanh", out_act="Tanh"),
     "ordinal3": dict(d_output=3, out_act="Sigmoid"),
     "fc_only": dict(N=0, sizes=[48, 32], act="ReLU"),

@@ -1,10 +1,11 @@
-"""Host logic of the packed validation scorer (engine.FusedScorer): the row-bucket ladder, and the argument checks of the
-device-count pack / unpack entry points (returned before any HIP call, so this runs without a GPU)."""
+"""Host logic of the packed validation scorer (engine.FusedScorer): the row-bucket ladder, the host half of the batch stager, and
+the argument checks of the device-count pack / unpack entry points (returned before any HIP call, so this runs without a GPU)."""
 import ctypes
 
 import pytest
+import torch
 
-from allrank_amd.engine import row_bucket
+from allrank_amd.engine import row_bucket, _stage_host
 
 
 def test_row_bucket_ladder():
@@ -20,6 +21,24 @@ def test_row_bucket_ladder():
         prev = b
     assert row_bucket(0) == 32
     assert row_bucket(10 ** 6, cap=4096) == 4096 and row_bucket(100, cap=4096) == 128
+
+
+def test_stage_host_layout():
+    """[ids as int32 pairs, 2B |] cu_seqlens [B+1], stable longest-first order [B]; missing slates count as length 0 / id 0"""
+    B, lens, ids = 5, [3, 0, 7, 7, 1], [9, 2, 4, 4, 0]
+    host = torch.full((4 * B + 1,), -7, dtype=torch.int32)
+    assert _stage_host(host, B, lens, ids) == 18
+    assert host[:2 * B].view(torch.int64).tolist() == ids                            # the ids: an int64 view at offset 0
+    assert host[2 * B:3 * B + 1].tolist() == [0, 3, 3, 10, 17, 18]
+    assert host[3 * B + 1:].tolist() == [2, 3, 0, 4, 1]                              # ties keep their original order
+    host.fill_(-7)
+    assert _stage_host(host, B, lens[:3], ids[:3]) == 10                             # only 3 slates given: the rest length 0, id 0
+    assert host[:2 * B].view(torch.int64).tolist() == [9, 2, 4, 0, 0]
+    assert host[2 * B:3 * B + 1].tolist() == [0, 3, 3, 10, 10, 10]
+    assert host[3 * B + 1:].tolist() == [2, 0, 1, 3, 4]
+    host = torch.full((2 * B + 1,), -7, dtype=torch.int32)                           # without ids: cu then order
+    assert _stage_host(host, B, lens) == 18
+    assert host[:B + 1].tolist() == [0, 3, 3, 10, 17, 18] and host[B + 1:].tolist() == [2, 3, 0, 4, 1]
 
 
 @pytest.fixture(scope="module")
