@@ -3,13 +3,17 @@
 //
 // Why: gfx950 has no TF32/xf32 path and its exact-fp32 MFMA runs at the fp32 vector rate (157 TF), 1/16 of the bf16
 // MFMA rate (2.5 PF).  Every fp32 operand is therefore split ON THE FLY, while it is staged into LDS, into two bf16
-// terms x = hi + lo (hi = bf16(x), lo = bf16(x - hi); |x - hi - lo| <= 2^-18 |x|) and the product is evaluated as
+// terms x = hi + lo (hi = bf16(x), lo = bf16(x - hi); bf16 keeps 8 significand bits, unit round-off u = 2^-8, so
+// |x - hi| <= 2^-8 |x| and |x - hi - lo| <= 2^-16 |x|; 2^-9 and 2^-18 are the TYPICAL sizes) and the product is evaluated as
 //        A B^T  ~=  Ahi Bhi^T + Ahi Blo^T + Alo Bhi^T            (three v_mfma_f32_32x32x16_bf16, fp32 accumulate)
-// bf16 x bf16 products are exact in fp32; the dropped terms (lo*lo and the split residuals) are <= 3 * 2^-18 relative
-// per product with pseudo-random sign, i.e. the same order as the round-off an fp32 accumulation over K = 512 carries
-// anyway.  3 MFMAs at the bf16 rate = 833 TF "fp32-equivalent" ceiling, 5.3x the fp32-MFMA roof, and each pair of
+// bf16 x bf16 products are exact in fp32; the dropped terms (lo*lo and the split residuals) are BOUNDED by
+// 3 * 2^-16 (1 + 2^-7) = 4.6e-5 of |a||b| per product and are TYPICALLY 3 * 2^-18 with pseudo-random sign (worst entry seen
+// on unnormalised operands: 1.2e-5 of sum_k |a||b|), i.e. the same order as the round-off an fp32 accumulation over K = 512
+// carries anyway.  3 MFMAs at the bf16 rate = 833 TF "fp32-equivalent" ceiling, 5.3x the fp32-MFMA roof, and each pair of
 // fragment loads feeds 3 MFMAs, so the LDS traffic per MFMA is a third of a plain bf16 GEMM's.
-// (NTERMS = 3 adds lo2 and uses 6 MFMAs for a 2^-26 product error: the strict mode.)
+// (NTERMS = 3 adds lo2 and uses 6 MFMAs: product error bounded by 4 * 2^-24 (1 + 2^-7) = 2.4e-7, typically 2^-26 -- the strict
+//  mode.  ONE product, hi*hi alone: bounded by 2 * 2^-8 (1 + 2^-8) = 7.8e-3, typically 2^-9.  The three bounds are derived and
+//  proved entrywise in tests/test_split_bf16_cpu.py.)
 //
 //   ltrx_gemm_nt : C[M,N] = A[M,K] * B[N,K]^T (+ bias[N]) (+ ReLU)        both operands K-contiguous
 //                  -> forward of nn.Linear (B = weight [out,in]) and its input gradient (B = weight^T, kept transposed)

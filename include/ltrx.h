@@ -335,7 +335,12 @@ int ltrx_score_head_bwd(const float* dscores, const float* x, const float* w, in
  * while staged into LDS; A B^T ~= Ahi Bhi^T + Ahi Blo^T + Alo Bhi^T with fp32 accumulation).  `strict` is the precision
  * code of a call: 0 = the three products above (parity arithmetic, default); 1 = a 3-term split and 6 products (true-fp32
  * error); 2 = ONE product Ahi Bhi^T (plain bf16 operands, fp32 accumulate: the throughput mode, about 2^-9 relative error
- * per product -- outside the parity contract, reported separately by bench.py).  Replaces the nn.Linear GEMMs of model.py:35-44 and transformer.py:193-203,221-227.
+ * per product -- outside the parity contract, reported separately by bench.py).
+ * Error of the split itself, per product and hence per entry relative to sum_k |a||b| (bf16: 8 significand bits, unit round-off 2^-8;
+ * derived and proved on operands spanning 2^+-46 in tests/test_split_bf16_cpu.py), on top of the fp32 accumulation:
+ *   code 0: BOUND 3 * 2^-16 (1 + 2^-7) = 4.6e-5, typical 3 * 2^-18;   code 1: BOUND 4 * 2^-24 (1 + 2^-7) = 2.4e-7, typical 2^-26;
+ *   code 2: BOUND 2 * 2^-8 (1 + 2^-8) = 7.8e-3, typical 2^-9.
+ * Replaces the nn.Linear GEMMs of model.py:35-44 and transformer.py:193-203,221-227.
  *   ltrx_gemm_nt: C[M,N] (ld ldc) = epi( A[M,K] (ld lda) * B[N,K]^T (ld ldb) + bias[N] )
  *                 -- forward (B = weight) and input gradient (B = weight^T);  K, lda, ldb multiples of 4.
  *                 epilogue `act`: 0 none, 1 ReLU (transformer.py:227 fused), 2 multiply by (aux[m,n] > 0): the ReLU

@@ -714,7 +714,8 @@ def test_fused_trainer_fc_sigmoid_tanh(act):
 @pytest.mark.parametrize("strict", [0, 1])
 def test_split_bf16_gemm_matches_fp64(strict):
     """fp32-accurate GEMMs on the bf16 MFMA: error relative to sum_k |a||b| must be fp32-class
-    (2-term split: <= 3*2^-18 per product worst case; 3-term 'strict': <= 2^-24-ish)."""
+    (2-term split: typically 3*2^-18 per product, bounded by 3*2^-16 (1 + 2^-7); 3-term 'strict': 2^-26 typical, 4*2^-24 bound --
+    tests/test_split_bf16_cpu.py; the entrywise contract of every arm is tests/test_gpu_gemm_contract.py)."""
     from allrank_amd import _lib as LB
     lib = LB.lib()
     rng = np.random.default_rng(0)
