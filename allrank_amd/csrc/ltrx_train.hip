@@ -4,7 +4,6 @@
 //                         shipped config) -- 4 streams in, 3 out, 16-B accesses; bias correction on the device step count
 //   ltrx_colsum           bias gradients: out[n] = sum_m dY[m][n]   (nn.Linear backward; deterministic two-stage)
 //   ltrx_relu_bwd         dz = dr * (r > 0) in place                 (transformer.py:227 / FCModel activation)
-//   ltrx_bias_act         y = act(y + bias) in place                 (model.py:42-43: activation after every FC layer)
 //   ltrx_score_head_fwd/bwd  OutputLayer with d_output == 1 (model.py:111-117): s[m] = <x[m,:], w> + b, and its backward
 #include "ltrx_device.h"
 
@@ -180,33 +179,6 @@ extern "C" int ltrx_relu_bwd(float* dr_inout, const float* r_post_act, size_t n,
   size_t blocks = (n / 4 + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(ltrx_relu_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, dr_inout, r_post_act, n / 4, scale);
-  LTRX_LAUNCH_CHECK();
-  return LTRX_OK;
-}
-
-// y = act(y + bias) in place; act: 0 identity, 1 ReLU.  [M, N] contiguous, N % 4 == 0.
-__global__ void __launch_bounds__(256) ltrx_bias_act_kernel(float* __restrict__ y, const float* __restrict__ bias, size_t M,
-                                                            int N4, int act) {
-  const size_t total = M * (size_t)N4;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    const int c4 = (int)(i % N4);
-    float4 v = reinterpret_cast<float4*>(y)[i];
-    const float4 b = reinterpret_cast<const float4*>(bias)[c4];
-    v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w;
-    if (act == 1) {
-      v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-    }
-    reinterpret_cast<float4*>(y)[i] = v;
-  }
-}
-
-extern "C" int ltrx_bias_act(float* y_inout, const float* bias, int M, int N, int act, ltrx_stream_t stream) {
-  if (!y_inout || !bias || M <= 0 || N <= 0 || (N & 3) || act < 0 || act > 1) return LTRX_EINVAL;
-  size_t total = (size_t)M * (N / 4);
-  size_t blocks = (total + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(ltrx_bias_act_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, y_inout, bias, (size_t)M, N / 4, act);
   LTRX_LAUNCH_CHECK();
   return LTRX_OK;
 }

@@ -253,7 +253,14 @@ int ltrx_mha_bwd(const float* q, const float* k, const float* v, const uint8_t* 
  * incremented first and used for the bias corrections.  ltrx_sgd_step = torch.optim.SGD.step with dampening 0 (momentum_buf may be
  * NULL when momentum == 0).  Gradients are multiplied by grad_scale (1.0 normally) and, when given, by grad_scale_dev[0] (device; the
  * clipping coefficient) on the fly.  (amsgrad / maximize / foreach variants: not implemented -- the Python layer keeps those jobs
- * on torch's optimizer.) */
+ * on torch's optimizer.)
+ * lr, the betas, eps and weight_decay arrive as fp32 and the bias corrections 1 - beta^t are computed in fp32 (powf) from the device
+ * step count: against the same rule in fp64 one update is off by the usual few roundings plus about
+ * 2 u (beta1^t / (1 - beta1^t) + beta2^t / (2 (1 - beta2^t))) of the update, u = 2^-24 -- about 1000 u at t = 1 and 500 u at t = 2 for
+ * beta2 = 0.999, under 2 u from t = 693 on (tests/step_ref.py derives and tests/test_gpu_step_kernels.py holds that bound).
+ * torch keeps the same hyperparameters as doubles; MEASURED, typical, not a bound: with the default betas and random gradients the
+ * largest relative difference of one parameter update between the two over 1,000 steps is 1.6e-5 (it is float(0.999f) != 0.999 in
+ * 1 - beta2; tests/test_step_ref_cpu.py prints the figure and does not assert it). */
 int ltrx_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1,
                    float beta2, float eps, float weight_decay, int decoupled, float* step_count, float grad_scale,
                    const float* grad_scale_dev, ltrx_stream_t stream);
@@ -320,9 +327,6 @@ int ltrx_gather_rows_cu(const float* src, int ld_src, const int32_t* cu_seqlens,
                         int ld_dst, int32_t* idx_out, ltrx_stream_t stream);
 int ltrx_scatter_rows_cu(const float* src, int ld_src, const int32_t* cu_seqlens, int B, int L, int cols, int rows, float* dst,
                          int ld_dst, ltrx_stream_t stream);
-
-/* y = act(y + bias) in place over a contiguous [M,N] matrix (model.py:42-43); act 0 = identity, 1 = ReLU; N % 4 == 0. */
-int ltrx_bias_act(float* y_inout, const float* bias, int M, int N, int act, ltrx_stream_t stream);
 
 /* OutputLayer with d_output == 1 (model.py:111-117): scores[m] = <x[m,:], w> + b, and its backward
  * (dx[m,:] = dscores[m] * w; dw = sum_m dscores[m] x[m,:]; db = sum_m dscores[m]). */
@@ -433,7 +437,8 @@ int ltrx_reduce_group(int n, const float* const* src, const int* splits, const s
 
 /* Model options around the encoder on the explicit step (allrank_amd/csrc/ltrx_extras.hip):
  *   ltrx_layernorm_torch_fwd: FCModel.input_norm = nn.LayerNorm(n_features) (model.py:27,39): biased variance, eps inside the
- *       sqrt; saves mean and rstd.  Its parameter gradients come from ltrx_layernorm_bwd called with these statistics.
+ *       sqrt; saves mean and rstd.  Its parameter gradients come from ltrx_layernorm_bwd called with these statistics (D >= 2
+ *       there: ltrx_layernorm_bwd refuses D == 1, which this forward accepts).
  *   ltrx_posenc_fwd: positional encoding (positional.py:15-77, transformer.py:51-52): y = scale * x + table[row(m)],
  *       row = padding_idx for masked items and ranks outside [0, padding_idx), else indices[m]; mask may be NULL.
  *   ltrx_posenc_table_bwd: gradient of a LEARNED table: dtable[r] = sum of dx[m] over the rows m with row(m) == r; the padding
