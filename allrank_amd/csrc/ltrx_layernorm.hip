@@ -246,6 +246,147 @@ __global__ void __launch_bounds__(64 * WPB) ltrx_layernorm_bwd_vec_kernel(const 
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// Final norm + score head in one pass each way (D = 256 * NV, the register-resident row layout above).  The normalised
+// row xf = LN(x) and its gradient d_xf = ds * w never reach HBM: the forward reduces xf against the head's weight row
+// from registers, the backward forms ds * w in registers.  (The head's own two gradients need the rows in ltrx_score_head_bwd's
+// order to keep their bits: ltrx_norm_head_wgrad, csrc/ltrx_train.hip, recomputes xf for them.)
+// ------------------------------------------------------------------------------------------------------------------
+// Statistics and o: the expressions and order of ltrx_layernorm_fwd_vec_kernel (res = NULL).  The score repeats
+// ltrx_score_head_fwd_kernel's order -- lane l accumulates columns l, l + 64, ... in turn, then wave_sum -- so a wave
+// passes its row through a private LDS slab to turn the float4 layout into that one: the scores keep their bits.
+// The hand-over between lanes needs no workgroup barrier on wave64 hardware only (gfx9: one wave's DS instructions execute in
+// program order and the wave is the whole slab's owner); __builtin_amdgcn_wave_barrier() keeps the compiler from moving them.
+// Same bits as the two-kernel path also means the same fma contraction of a * t + b here, in ltrx_layernorm_fwd_vec_kernel and in
+// ltrx_norm_head_wgrad_kernel (all three are this one expression under the build's default -ffp-contract): tests/test_gpu_norm_head.py
+// compares y, the scores and the head's gradients bit for bit, so a compiler that chose differently would be caught there.
+template <int NV>
+__global__ void __launch_bounds__(256) ltrx_norm_head_fwd_kernel(const float* __restrict__ x, const float* __restrict__ a,
+                                                                 const float* __restrict__ b, const float* __restrict__ w,
+                                                                 const float* __restrict__ bias, int rows, float eps,
+                                                                 float* __restrict__ scores, float* __restrict__ y,
+                                                                 float* __restrict__ mean_out, float* __restrict__ rstd_out) {
+  constexpr int D = 256 * NV;
+  __shared__ __attribute__((aligned(16))) float lds[4][D];
+  const int lane = lane_id(), wpb = blockDim.x >> 6;
+  float* mine = lds[wave_id()];
+  float4 av[NV], bv[NV];
+  float wc[4 * NV];
+#pragma unroll
+  for (int t = 0; t < NV; ++t) {
+    av[t] = reinterpret_cast<const float4*>(a)[lane + 64 * t];
+    bv[t] = reinterpret_cast<const float4*>(b)[lane + 64 * t];
+  }
+#pragma unroll
+  for (int j = 0; j < 4 * NV; ++j) wc[j] = w[lane + 64 * j];
+  for (int row = blockIdx.x * wpb + wave_id(); row < rows; row += gridDim.x * wpb) {
+    const float4* xr = reinterpret_cast<const float4*>(x + (size_t)row * D);
+    float4 v[NV];
+    float sum = 0.f;
+#pragma unroll
+    for (int t = 0; t < NV; ++t) {
+      v[t] = xr[lane + 64 * t];
+      sum += (v[t].x + v[t].y) + (v[t].z + v[t].w);
+    }
+    const float mean = wave_sum(sum) / (float)D;
+    float sq = 0.f;
+#pragma unroll
+    for (int t = 0; t < NV; ++t) {
+      const float dx = v[t].x - mean, dy = v[t].y - mean, dz = v[t].z - mean, dw = v[t].w - mean;
+      sq += (dx * dx + dy * dy) + (dz * dz + dw * dw);
+    }
+    const float stdv = sqrtf(wave_sum(sq) / (float)(D - 1));
+    const float r = 1.0f / (stdv + eps);
+#pragma unroll
+    for (int t = 0; t < NV; ++t) {
+      float4 o;
+      o.x = av[t].x * ((v[t].x - mean) * r) + bv[t].x;
+      o.y = av[t].y * ((v[t].y - mean) * r) + bv[t].y;
+      o.z = av[t].z * ((v[t].z - mean) * r) + bv[t].z;
+      o.w = av[t].w * ((v[t].w - mean) * r) + bv[t].w;
+      if (y) reinterpret_cast<float4*>(y + (size_t)row * D)[lane + 64 * t] = o;
+      reinterpret_cast<float4*>(mine)[lane + 64 * t] = o;
+    }
+    __builtin_amdgcn_wave_barrier();   // the slab is this wave's alone: its LDS accesses complete in order, no workgroup barrier
+    float acc = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4 * NV; ++j) acc += mine[lane + 64 * j] * wc[j];
+    __builtin_amdgcn_wave_barrier();
+    acc = wave_sum(acc);
+    if (lane == 0) {
+      scores[row] = acc + bias[0];
+      mean_out[row] = mean;
+      rstd_out[row] = r;
+    }
+  }
+}
+
+// ltrx_layernorm_bwd_vec_kernel (dres = NULL) fed with dy = ds[row] * w from registers -- the fp32 product ltrx_score_head_bwd
+// stores.  Everything else is that kernel's: workgroup shapes, row walk, partial rows [da(D) | db(D)] and their combine.
+template <int NV, int WPB>
+__global__ void __launch_bounds__(64 * WPB) ltrx_norm_head_bwd_kernel(const float* __restrict__ ds, const float* __restrict__ xsum,
+                                                                      const float* __restrict__ a, const float* __restrict__ wh,
+                                                                      const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
+                                                                      int rows, float eps, float* __restrict__ dx,
+                                                                      float* __restrict__ partial) {
+  constexpr int D = 256 * NV;
+  __shared__ __attribute__((aligned(16))) float lds[WPB * 2 * D];
+  const int lane = lane_id(), w = wave_id(), wpb = WPB;
+  float4 av[NV], wv[NV], da[NV], db[NV];
+#pragma unroll
+  for (int t = 0; t < NV; ++t) {
+    av[t] = reinterpret_cast<const float4*>(a)[lane + 64 * t];
+    wv[t] = reinterpret_cast<const float4*>(wh)[lane + 64 * t];
+    da[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+    db[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  for (int row = blockIdx.x * wpb + w; row < rows; row += gridDim.x * wpb) {
+    const float mean = mean_in[row], r = rstd_in[row], dsr = ds[row];
+    float4 g[NV], xc[NV];
+    float gsum = 0.f, dot = 0.f;
+#pragma unroll
+    for (int t = 0; t < NV; ++t) {
+      g[t] = make_float4(dsr * wv[t].x, dsr * wv[t].y, dsr * wv[t].z, dsr * wv[t].w);
+      // the product is rounded here, as the stored d_xf was: nothing below may fold the multiplication into an fma
+      asm volatile("" : "+v"(g[t].x), "+v"(g[t].y), "+v"(g[t].z), "+v"(g[t].w));
+      xc[t] = reinterpret_cast<const float4*>(xsum + (size_t)row * D)[lane + 64 * t];
+      xc[t].x -= mean; xc[t].y -= mean; xc[t].z -= mean; xc[t].w -= mean;
+      // da/db use the raw dy; then g becomes dy * a
+      da[t].x += g[t].x * (xc[t].x * r); da[t].y += g[t].y * (xc[t].y * r);
+      da[t].z += g[t].z * (xc[t].z * r); da[t].w += g[t].w * (xc[t].w * r);
+      db[t].x += g[t].x; db[t].y += g[t].y; db[t].z += g[t].z; db[t].w += g[t].w;
+      g[t].x *= av[t].x; g[t].y *= av[t].y; g[t].z *= av[t].z; g[t].w *= av[t].w;
+      gsum += (g[t].x + g[t].y) + (g[t].z + g[t].w);
+      dot += (g[t].x * xc[t].x + g[t].y * xc[t].y) + (g[t].z * xc[t].z + g[t].w * xc[t].w);
+    }
+    const float gm = wave_sum(gsum) / (float)D;
+    dot = wave_sum(dot);
+    const float stdv = 1.0f / r - eps;
+    const float tc = (stdv > 0.f) ? r * r * dot / ((float)(D - 1) * stdv) : 0.f;
+#pragma unroll
+    for (int t = 0; t < NV; ++t) {
+      float4 o;
+      o.x = r * (g[t].x - gm) - tc * xc[t].x;
+      o.y = r * (g[t].y - gm) - tc * xc[t].y;
+      o.z = r * (g[t].z - gm) - tc * xc[t].z;
+      o.w = r * (g[t].w - gm) - tc * xc[t].w;
+      reinterpret_cast<float4*>(dx + (size_t)row * D)[lane + 64 * t] = o;
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < NV; ++t) {
+    reinterpret_cast<float4*>(lds + (size_t)w * 2 * D)[lane + 64 * t] = da[t];
+    reinterpret_cast<float4*>(lds + (size_t)w * 2 * D + D)[lane + 64 * t] = db[t];
+  }
+  __syncthreads();
+  float* pa = partial + (size_t)blockIdx.x * 2 * D;
+  for (int c = threadIdx.x; c < 2 * D; c += blockDim.x) {
+    float sacc = 0.f;
+    for (int ww = 0; ww < wpb; ++ww) sacc += lds[(size_t)ww * 2 * D + c];
+    pa[c] = sacc;
+  }
+}
+
 // One workgroup per 64 columns; its 16 waves split the partial rows, lanes own consecutive columns (coalesced),
 // the wave partials are combined through LDS in a fixed order (deterministic).
 __global__ void __launch_bounds__(1024) ltrx_layernorm_bwd_reduce_kernel(const float* __restrict__ partial, int nblk,
@@ -390,4 +531,54 @@ extern "C" int ltrx_layernorm_bwd_partial(const float* dy, const float* xsum, co
                                           int* partial_rows_out, ltrx_stream_t stream) {
   if (!partial_rows_out) return LTRX_EINVAL;
   return ln_bwd_main(dy, xsum, a, mean, rstd, dres_in, rows, D, eps, dx_out, ws, partial_rows_out, (hipStream_t)stream);
+}
+
+// ---- final norm + score head (kernels above): only the register-resident widths; anything else is LTRX_EUNSUPPORTED and the caller
+// keeps ltrx_layernorm_* + ltrx_score_head_* ----
+extern "C" int ltrx_norm_head_fwd(const float* x, const float* a, const float* b, const float* w, const float* bias, int rows, int D,
+                                  float eps, float* scores_out, float* mean_out, float* rstd_out, float* y_out, ltrx_stream_t stream) {
+  if (!x || !a || !b || !w || !bias || !scores_out || !mean_out || !rstd_out || rows <= 0 || D < 2) return LTRX_EINVAL;
+  if (!ln_vec_ok(D, x, a, b) || !ln_vec_ok(D, w, y_out, nullptr)) return LTRX_EUNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 g(ln_fwd_vec_grid(rows));
+#define LTRX_NH_FWD(NV) hipLaunchKernelGGL(ltrx_norm_head_fwd_kernel<NV>, g, dim3(256), 0, s, x, a, b, w, bias, rows, eps, scores_out, y_out, mean_out, rstd_out)
+  switch (D / 256) {
+    case 1: LTRX_NH_FWD(1); break;
+    case 2: LTRX_NH_FWD(2); break;
+    case 3: LTRX_NH_FWD(3); break;
+    default: LTRX_NH_FWD(4); break;
+  }
+#undef LTRX_NH_FWD
+  LTRX_LAUNCH_CHECK();
+  return LTRX_OK;
+}
+
+extern "C" size_t ltrx_norm_head_bwd_workspace_bytes(int rows, int D) { return ltrx_layernorm_bwd_workspace_bytes(rows, D); }
+
+// dx_out is final; ws holds *partial_rows_out rows of [da(D) | db(D)] partials (row stride 2 D) for the caller to sum, exactly as
+// ltrx_layernorm_bwd_partial leaves them.  Grid and row walk: ln_bwd_main's, both arms.  The head's own gradients: ltrx_norm_head_wgrad.
+extern "C" int ltrx_norm_head_bwd_partial(const float* dscores, const float* xsum, const float* a, const float* w, const float* mean,
+                                          const float* rstd, int rows, int D, float eps, float* dx_out, void* ws, int* partial_rows_out,
+                                          ltrx_stream_t stream) {
+  if (!dscores || !xsum || !a || !w || !mean || !rstd || !dx_out || !ws || !partial_rows_out || rows <= 0 || D < 2) return LTRX_EINVAL;
+  if (!ln_vec_ok(D, xsum, dx_out, ws) || !ln_vec_ok(D, a, w, nullptr)) return LTRX_EUNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  int grid = ln_bwd_grid(rows);
+#define LTRX_NH_BWD(NV, WPB) \
+  hipLaunchKernelGGL((ltrx_norm_head_bwd_kernel<NV, WPB>), dim3(grid), dim3(64 * WPB), 0, s, dscores, xsum, a, w, mean, rstd, rows, eps, dx_out, (float*)ws)
+  if (ln_bwd_wide(rows, D)) {
+    grid = LTRX_LN_BWD_G16;
+    if (D / 256 == 1) LTRX_NH_BWD(1, 16); else LTRX_NH_BWD(2, 16);
+  } else {
+    switch (D / 256) {
+      case 1: LTRX_NH_BWD(1, 4); break;
+      case 2: LTRX_NH_BWD(2, 4); break;
+      case 3: LTRX_NH_BWD(3, 4); break;
+      default: LTRX_NH_BWD(4, 4); break;
+    }
+  }
+#undef LTRX_NH_BWD
+  LTRX_LAUNCH_CHECK();
+  *partial_rows_out = grid;
+  return LTRX_OK;
 }

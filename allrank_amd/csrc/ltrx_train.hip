@@ -273,6 +273,60 @@ __global__ void __launch_bounds__(256) ltrx_score_head_bwd_vec_kernel(const floa
   for (int c = threadIdx.x; c <= D; c += blockDim.x) pa[c] = (lds[0][c] + lds[1][c]) + (lds[2][c] + lds[3][c]);
 }
 
+// The parameter gradients of the kernel above where the head's input is xf = LN(xsum) and only xsum and the statistics are kept (the
+// fused final norm + head, csrc/ltrx_layernorm.hip): xf is recomputed by the forward's expression, nothing is written but the
+// partials.  Grid, row walk, accumulation and combine are ltrx_score_head_bwd's, so dw / db keep the bits they have on the stored xf;
+// NV = 3 is the one width that ltrx_score_head_bwd gives to its scalar kernel, whose workgroup combine runs wave by wave.
+template <int NV>
+__global__ void __launch_bounds__(256) ltrx_norm_head_wgrad_kernel(const float* __restrict__ ds, const float* __restrict__ xsum,
+                                                                   const float* __restrict__ a, const float* __restrict__ b,
+                                                                   const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
+                                                                   int M, float* __restrict__ partial) {
+  constexpr int D = 256 * NV;
+  __shared__ float lds[4][D + 4];
+  const int lane = lane_id(), wv = wave_id(), wpb = blockDim.x >> 6;
+  float4 av[NV], bv[NV], acc[NV];
+#pragma unroll
+  for (int t = 0; t < NV; ++t) {
+    av[t] = reinterpret_cast<const float4*>(a)[lane + 64 * t];
+    bv[t] = reinterpret_cast<const float4*>(b)[lane + 64 * t];
+    acc[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  float dbacc = 0.f;
+  for (int row = blockIdx.x * wpb + wv; row < M; row += gridDim.x * wpb) {
+    const float g = ds[row], mean = mean_in[row], r = rstd_in[row];
+    const float4* xr = reinterpret_cast<const float4*>(xsum + (size_t)row * D);
+#pragma unroll
+    for (int t = 0; t < NV; ++t) {
+      const float4 v = xr[lane + 64 * t];
+      float4 y;
+      y.x = av[t].x * ((v.x - mean) * r) + bv[t].x;
+      y.y = av[t].y * ((v.y - mean) * r) + bv[t].y;
+      y.z = av[t].z * ((v.z - mean) * r) + bv[t].z;
+      y.w = av[t].w * ((v.w - mean) * r) + bv[t].w;
+      acc[t].x += g * y.x;
+      acc[t].y += g * y.y;
+      acc[t].z += g * y.z;
+      acc[t].w += g * y.w;
+    }
+    dbacc += g;
+  }
+#pragma unroll
+  for (int t = 0; t < NV; ++t) *reinterpret_cast<float4*>(&lds[wv][4 * (lane + 64 * t)]) = acc[t];
+  if (lane == 0) lds[wv][D] = dbacc;
+  __syncthreads();
+  float* pa = partial + (size_t)blockIdx.x * (D + 1);
+  for (int c = threadIdx.x; c <= D; c += blockDim.x) {
+    if (NV == 3) {
+      float s = 0.f;
+      for (int k = 0; k < 4; ++k) s += lds[k][c];
+      pa[c] = s;
+    } else {
+      pa[c] = (lds[0][c] + lds[1][c]) + (lds[2][c] + lds[3][c]);
+    }
+  }
+}
+
 // dw[c] = sum_k partial[k][c] (c < D), db = column D; 64 columns x 16 row groups (waves) per workgroup, fixed combine order
 // (16 waves: with 4 the 512 partial rows were 128 dependent-latency iterations per wave, 21 us for 1 MB)
 __global__ void __launch_bounds__(1024) ltrx_score_head_reduce_kernel(const float* __restrict__ partial, int nblk, int D,
@@ -335,6 +389,28 @@ extern "C" int ltrx_score_head_bwd(const float* dscores, const float* x, const f
   else
     hipLaunchKernelGGL(ltrx_score_head_bwd_kernel, dim3(g), dim3(256), (size_t)(4 * D + 4) * sizeof(float), s, dscores, x, w, M,
                        D, dx, (float*)ws);
+  LTRX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(ltrx_score_head_reduce_kernel, dim3((D + 1 + 63) / 64), dim3(1024), 0, s, (const float*)ws, g, D, dw, db);
+  LTRX_LAUNCH_CHECK();
+  return LTRX_OK;
+}
+
+// dw / db of ltrx_score_head_bwd for x = LN(xsum; a, b) given by xsum and the saved statistics, bit for bit (ws: the same bytes)
+extern "C" int ltrx_norm_head_wgrad(const float* dscores, const float* xsum, const float* a, const float* b, const float* mean,
+                                    const float* rstd, int M, int D, float* dw, float* db, void* ws, ltrx_stream_t stream) {
+  if (!dscores || !xsum || !a || !b || !mean || !rstd || !dw || !db || !ws || M <= 0 || D < 2) return LTRX_EINVAL;
+  if (D % 256 != 0 || D > 1024 || ((((uintptr_t)xsum) | ((uintptr_t)a) | ((uintptr_t)b)) & 15) != 0) return LTRX_EUNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  const int g = head_grid(M);
+#define LTRX_NH_WGRAD(NV) \
+  hipLaunchKernelGGL(ltrx_norm_head_wgrad_kernel<NV>, dim3(g), dim3(256), 0, s, dscores, xsum, a, b, mean, rstd, M, (float*)ws)
+  switch (D / 256) {
+    case 1: LTRX_NH_WGRAD(1); break;
+    case 2: LTRX_NH_WGRAD(2); break;
+    case 3: LTRX_NH_WGRAD(3); break;
+    default: LTRX_NH_WGRAD(4); break;
+  }
+#undef LTRX_NH_WGRAD
   LTRX_LAUNCH_CHECK();
   hipLaunchKernelGGL(ltrx_score_head_reduce_kernel, dim3((D + 1 + 63) / 64), dim3(1024), 0, s, (const float*)ws, g, D, dw, db);
   LTRX_LAUNCH_CHECK();

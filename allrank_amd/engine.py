@@ -70,7 +70,8 @@ def _alloc_forward(owner, t, rows, B, L, saved, compact):
       idx_rows (i64 rank of every row, -1 = none) and x_pe: positional encoding only
       layers[i]: wqkv, bqkv, mod, p_*, s_* (the trainer's parameter views and dropout sites; its own dicts also hold gwqkv / gbqkv
       and later rbits / wqkvT), xsum0 (the residual stream entering layer i > 0), xn0, mean0, rstd0, qkv, o, lse, x1, xn1, mean1,
-      rstd1, r;  xsum_f, xf, mean_f, rstd_f (the final norm);  scores_c (compact only), scores_raw [B, L(, n_out)], scores [B, L]
+      rstd1, r;  xsum_f, xf, mean_f, rstd_f (the final norm; xf is None where t.norm_head holds: the fused final norm + score head
+      keeps the normalised rows in registers);  scores_c (compact only), scores_raw [B, L(, n_out)], scores [B, L]
     ``saved=True``, the trainer's form: the backward reads the activations, so every layer has its own.  ``saved=False``, the scorer's:
     ONE activation set serves every layer -- the residual stream ping-pongs between two buffers (a layer's input is dead once its
     out-projection has added it: xsum0 of layer i = ping[i % 2], xsum_f = ping[N % 2], x_pe = ping[0], which layer 0 reads while
@@ -108,7 +109,7 @@ def _alloc_forward(owner, t, rows, B, L, saved, compact):
         for i, st in enumerate(heads):
             owner.layers.append(dict(st, xsum0=z(rows, d) if i else None, **acts(ln(), ln())))
         owner.xsum_f = z(rows, d)
-        owner.xf, owner.mean_f, owner.rstd_f = ln()
+        owner.xf, owner.mean_f, owner.rstd_f = (None, z(rows), z(rows)) if t.norm_head else ln()
     elif t.N:
         ping, one = [z(rows, d), z(rows, d)], ln()
         shared = acts(one, one)
@@ -116,7 +117,7 @@ def _alloc_forward(owner, t, rows, B, L, saved, compact):
             owner.layers.append(dict({k: st[k] for k in ("wqkv", "bqkv", "mod", "p_att", "p_ff", "p_s0", "p_s1", "s_att", "s_ff", "s_s0",
                                                           "s_s1")}, xsum0=ping[i % 2], **shared))
         owner.xsum_f = ping[t.N % 2]
-        owner.xf, owner.mean_f, owner.rstd_f = one
+        owner.xf, owner.mean_f, owner.rstd_f = (None,) + one[1:] if t.norm_head else one
     if t.pos is not None:
         owner.x_pe = ping[0] if (t.N and not saved) else z(rows, d)
     if compact:
@@ -246,7 +247,8 @@ class FusedTrainer(object):
     def __init__(self, model, loss_name, loss_args, B, L, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, world_size=1, group=None,
                  optimizer="Adam", weight_decay=0.0, momentum=0.0, nesterov=False,
                  use_graph=True, gemm="split_bf16", dropout=True, seed=None, gradient_clipping_norm=None, compact=False,
-                 weight_images=True, fc_step=True, group_wgrad=True, relu_bits=True, pad_input=True, force_dist=False):
+                 weight_images=True, fc_step=True, group_wgrad=True, relu_bits=True, pad_input=True, force_dist=False,
+                 _norm_head=True):
         """gemm: "split_bf16" -- libltrx fp32-accurate GEMMs on the bf16 MFMA (3 products), "split_bf16_strict" (6
         products), "hipblaslt" (torch.mm/addmm, exact-fp32 library GEMMs), or "bf16" -- the THROUGHPUT mode: one bf16
         product per contraction in the dense projections AND in attention (fp32 storage, accumulation, LayerNorm, softmax,
@@ -281,7 +283,10 @@ class FusedTrainer(object):
         tools/lab/patches/r06_engine_overlap_wgrad_act_images.patch re-adds them; the image-form kernel entry points that act_images drove
         (ltrx_gemm_nt_img, ltrx_gemm_tn_group_img, ltrx_layernorm_fwd_image) have left the library too: the patch's act_images half
         needs the library of commit 68005e3.)
-        force_dist=True: see ``self.sharded`` below."""
+        force_dist=True: see ``self.sharded`` below.
+        _norm_head=True: the encoder's final norm and the d_output == 1 score head run as one kernel each way (ltrx_norm_head_fwd /
+        ltrx_norm_head_bwd_partial / ltrx_norm_head_wgrad: the normalised rows and their gradient never reach HBM) where ``self.norm_head`` says so; False keeps
+        ltrx_layernorm_* + ltrx_score_head_* (A/B runs, tests: the same bits everywhere)."""
         from . import _lib as LB
         from .losses import FusedLoss
         self.LB = LB
@@ -316,6 +321,10 @@ class FusedTrainer(object):
         self.sharded = bool(world_size > 1 or force_dist)
         self.clip = float(gradient_clipping_norm) if gradient_clipping_norm else None
         seed = self._read_model(model, dropout, seed)
+        # final norm + score head fused: an encoder, one output unit, a register-resident width (D = 256 NV <= 1024), and the deferred
+        # reduction of the LayerNorm partials (_reduce_flush), whose sums the two-kernel path's (a_2, b_2) gradients have there
+        self.norm_head = bool(_norm_head and self.N > 0 and self.n_out == 1 and self.d % 256 == 0 and self.d <= 1024
+                              and self.group_wgrad and gemm != "hipblaslt")
         offs = self._layout_parameters(dropout)
         # slate-resident FC + ListNet step (csrc/ltrx_fcstep.hip): eligibility.  It reads the padded batch in place and masks padded
         # items itself, so a request for variable-length execution is moot for such a job (and would only route it to the slower
@@ -682,18 +691,28 @@ class FusedTrainer(object):
         self._drop_apply(ds, self.d_br, p, seed)
         return self.d_br
 
+    def _ln_partial_slot(self):
+        """the next free workspace for deferred (da, db) partial rows of a LayerNorm backward, or None: no deferred reduction in this
+        configuration, or the layer has used its slots (the reduction then runs at once)"""
+        if self.group_wgrad and self.gemm != "hipblaslt" and self._ln_slot < len(self.ws_ln_g):
+            self._ln_slot += 1
+            return self.ws_ln_g[self._ln_slot - 1]
+        return None
+
+    def _ln_partials_queue(self, buf, nrows, da, db):
+        """``nrows`` partial rows [da(d) | db(d)] in ``buf`` join the layer's one reducing launch (_reduce_flush)"""
+        self._red_pending.append((buf.data_ptr(), nrows, 2 * self.d, self.d, da.data_ptr()))
+        self._red_pending.append((buf.data_ptr() + 4 * self.d, nrows, 2 * self.d, self.d, db.data_ptr()))
+
     def _ln_bwd(self, dy, xsum, a, mean, rstd, dres, dx, da, db):
         P = self.LB.ptr
-        if self.group_wgrad and self.gemm != "hipblaslt" and self._ln_slot < len(self.ws_ln_g):
-            # dx now; the (da, db) partials join the layer's one reducing launch (_reduce_flush)
-            buf = self.ws_ln_g[self._ln_slot]
-            self._ln_slot += 1
+        buf = self._ln_partial_slot()
+        if buf is not None:                                       # dx now, the parameter gradients with the layer's reductions
             rows_out = ctypes.c_int(0)
             self.LB.check(self.lib.ltrx_layernorm_bwd_partial(P(dy), P(xsum), P(a), P(mean), P(rstd), P(dres), self.rows, self.d,
                                                               float(self.ln_eps), P(dx), P(buf), ctypes.byref(rows_out), self._st()),
                           "layernorm_bwd_partial")
-            self._red_pending.append((buf.data_ptr(), rows_out.value, 2 * self.d, self.d, da.data_ptr()))
-            self._red_pending.append((buf.data_ptr() + 4 * self.d, rows_out.value, 2 * self.d, self.d, db.data_ptr()))
+            self._ln_partials_queue(buf, rows_out.value, da, db)
             return
         self.LB.check(self.lib.ltrx_layernorm_bwd(P(dy), P(xsum), P(a), P(mean), P(rstd), P(dres), self.rows, self.d,
                                                   float(self.ln_eps), P(dx), P(da), P(db), P(self.ws_ln), self._st()),
@@ -984,15 +1003,19 @@ class FusedTrainer(object):
             self._lin_fwd(st["r"], W(ff.w_2.weight), W(ff.w_2.bias), nxt, 0, dp(st["p_s1"]), st["s_s1"], res=st["x1"], rows=M)
             x = nxt
         out = self.model.output_layer
-        if self.N:
+        no = self.n_out
+        sc_rows = bs.scores_c if bs.compact else bs.scores_raw
+        feat = x
+        if self.N and not self.norm_head:
             nf = self.enc.norm
             self._ln_fwd(x, None, W(nf.a_2), W(nf.b_2), None, bs.xf, bs.mean_f, bs.rstd_f, rows=M)
             feat = bs.xf
-        else:
-            feat = x
-        no = self.n_out
-        sc_rows = bs.scores_c if bs.compact else bs.scores_raw
-        if no == 1:
+        if self.norm_head:                                        # final norm + score head in one pass: LN(x) stays in registers
+            nf, feat = self.enc.norm, None
+            self.LB.check(lib.ltrx_norm_head_fwd(P(x), P(W(nf.a_2)), P(W(nf.b_2)), P(W(out.w_1.weight)), P(W(out.w_1.bias)), M, d,
+                                                 float(self.ln_eps), P(sc_rows), P(bs.mean_f), P(bs.rstd_f), None, self._st()),
+                          "norm_head_fwd")
+        elif no == 1:
             self.LB.check(lib.ltrx_score_head_fwd(P(feat), P(W(out.w_1.weight)), P(W(out.w_1.bias)), M, d, P(sc_rows), self._st()),
                           "score_head_fwd")
         else:                                                     # Linear(d, d_output) as a GEMM (model.py:117)
@@ -1032,7 +1055,21 @@ class FusedTrainer(object):
             dsc = self.dsc_c
         if self.out_act:                                          # d loss / d pre-activation = d loss / d score * act'(score)
             self.LB.check(lib.ltrx_out_act_bwd(P(dsc), P(sc_rows), M * no, self.out_act, P(dsc), self._st()), "out_act_bwd")
-        if no == 1:
+        if self.norm_head:
+            # backward of the fused pair.  The head's own gradients first, in ltrx_score_head_bwd's row order (their bits), from the
+            # recomputed LN(x); then d_xf = dsc w is formed in registers and dx lands where _ln_bwd put it, the (a_2, b_2) partials
+            # joining the last layer's one reducing launch as _ln_bwd's do
+            nf = self.enc.norm
+            self.LB.check(lib.ltrx_norm_head_wgrad(P(dsc), P(self.xsum_f), P(W(nf.a_2)), P(W(nf.b_2)), P(self.mean_f), P(self.rstd_f), M, d,
+                                                   P(G(out.w_1.weight)), P(G(out.w_1.bias)), P(self.ws_head), self._st()),
+                          "norm_head_wgrad")
+            buf = self._ln_partial_slot()                         # (never None: norm_head implies the deferred reduction, slot 0)
+            rows_out = ctypes.c_int(0)
+            self.LB.check(lib.ltrx_norm_head_bwd_partial(P(dsc), P(self.xsum_f), P(W(nf.a_2)), P(W(out.w_1.weight)), P(self.mean_f),
+                                                         P(self.rstd_f), M, d, float(self.ln_eps), P(gb), P(buf), ctypes.byref(rows_out),
+                                                         self._st()), "norm_head_bwd_partial")
+            self._ln_partials_queue(buf, rows_out.value, G(nf.a_2), G(nf.b_2))
+        elif no == 1:
             self.LB.check(lib.ltrx_score_head_bwd(P(dsc), P(feat), P(W(out.w_1.weight)), M, d, P(ga), P(G(out.w_1.weight)),
                                                   P(G(out.w_1.bias)), P(self.ws_head), self._st()), "score_head_bwd")
         else:                                                     # the d_output-wide head: weight / bias / input gradients as GEMMs
@@ -1041,7 +1078,8 @@ class FusedTrainer(object):
             self._lin_dgrad(self.dz_pad, W(out.w_1.weight), self.woutT_pad, ga)
         if self.N:
             nf = self.enc.norm
-            self._ln_bwd(ga, self.xsum_f, W(nf.a_2), self.mean_f, self.rstd_f, None, gb, G(nf.a_2), G(nf.b_2))
+            if not self.norm_head:
+                self._ln_bwd(ga, self.xsum_f, W(nf.a_2), self.mean_f, self.rstd_f, None, gb, G(nf.a_2), G(nf.b_2))
             ds = gb                                               # d loss / d (x1_last + ffn_last)
             other = ga
             for i in range(self.N - 1, -1, -1):

@@ -203,6 +203,25 @@ int ltrx_layernorm_bwd_partial(const float* dy, const float* xsum, const float* 
                                const float* dres_in, int rows, int D, float eps, float* dx_out, void* ws, int* partial_rows_out,
                                ltrx_stream_t stream);
 
+/* The encoder's final norm and the d_output == 1 score head (model.py:111-117) without the normalised rows or their gradient ds * w
+ * in memory.  D % 256 == 0, D <= 1024 and 16-byte aligned row / parameter pointers, else LTRX_EUNSUPPORTED (the caller keeps
+ * ltrx_layernorm_* + ltrx_score_head_*).  Every output has the bits the two-kernel sequence gives it.
+ * Forward: mean_out / rstd_out as ltrx_layernorm_fwd saves them, scores_out[r] = <LN(x[r]), w> + bias[0] as ltrx_score_head_fwd
+ * computes it on ltrx_layernorm_fwd's output; y_out (may be NULL) receives LN(x).
+ * Backward: dx_out = what ltrx_score_head_bwd followed by ltrx_layernorm_bwd_partial (dres_in NULL) writes; ws (at least
+ * ltrx_norm_head_bwd_workspace_bytes) holds *partial_rows_out rows of [da(D) | db(D)] partials, row stride 2 D, as
+ * ltrx_layernorm_bwd_partial leaves them for ltrx_reduce_group.
+ * ltrx_norm_head_wgrad: the head's own gradients dw[D], db[1] of ltrx_score_head_bwd, with its input LN(xsum) recomputed from xsum
+ * and the saved statistics in that call's row order; ws: ltrx_score_head_bwd_workspace_bytes(M, D). */
+int ltrx_norm_head_fwd(const float* x, const float* a, const float* b, const float* w, const float* bias, int rows, int D, float eps,
+                       float* scores_out, float* mean_out, float* rstd_out, float* y_out, ltrx_stream_t stream);
+size_t ltrx_norm_head_bwd_workspace_bytes(int rows, int D);
+int ltrx_norm_head_bwd_partial(const float* dscores, const float* xsum, const float* a, const float* w, const float* mean,
+                               const float* rstd, int rows, int D, float eps, float* dx_out, void* ws, int* partial_rows_out,
+                               ltrx_stream_t stream);
+int ltrx_norm_head_wgrad(const float* dscores, const float* xsum, const float* a, const float* b, const float* mean, const float* rstd,
+                         int M, int D, float* dw, float* db, void* ws, ltrx_stream_t stream);
+
 /* transformer.py:137-156 attention() as used by MultiHeadedAttention.forward (:178-203), fused flash-style:
  * q,k,v,o are [B, L, h, d_k] views of the projection outputs (element (b,l,head,c) at ((b*L+l)*h+head)*d_k + c
  * scaled by the given row stride), key_pad_mask u8[B,L] (1 = padded key, filled with -inf, transformer.py:150-151);
