@@ -9,7 +9,8 @@
 // Backward:  g = dy * a;  dx = r (g - mean(g)) - r^2 <g, xc> / ((n-1) std) * xc  (+ dres),  r = 1/(std+eps);
 // da = sum_rows dy * xhat, db = sum_rows dy via per-block partial rows in `ws` + a second tiny kernel (fixed
 // summation order -> deterministic, no atomics).
-#include "ltrx_device.h"
+#include "ltrx_rowreg.h"
+#include <cassert>
 
 using namespace ltrx;
 
@@ -119,7 +120,7 @@ __global__ void __launch_bounds__(256) ltrx_layernorm_bwd_kernel(const float* __
 // ------------------------------------------------------------------------------------------------------------------
 // Fast path, D = 256 * NV (NV = 1..4): the row lives in registers (NV float4 per lane, 16-byte coalesced accesses),
 // one HBM read per input, statistics from registers; the backward keeps the per-lane column partials of da/db in
-// registers across all rows of the wave and spills them once at the end.
+// registers across all rows of the wave and spills them once at the end.  The arithmetic is ltrx_rowreg.h's.
 // ------------------------------------------------------------------------------------------------------------------
 template <int NV>
 __global__ void __launch_bounds__(256) ltrx_layernorm_fwd_vec_kernel(const float* __restrict__ x, const float* __restrict__ res,
@@ -155,24 +156,12 @@ __global__ void __launch_bounds__(256) ltrx_layernorm_fwd_vec_kernel(const float
       }
       sum += (v[t].x + v[t].y) + (v[t].z + v[t].w);
     }
-    const float mean = wave_sum(sum) / (float)D;
-    float sq = 0.f;
-#pragma unroll
-    for (int t = 0; t < NV; ++t) {
-      const float dx = v[t].x - mean, dy = v[t].y - mean, dz = v[t].z - mean, dw = v[t].w - mean;
-      sq += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-    }
-    const float stdv = sqrtf(wave_sum(sq) / (float)(D - 1));
-    const float r = 1.0f / (stdv + eps);
+    float mean, r;
+    rowreg_stats<NV>(v, sum, eps, mean, r);
 #pragma unroll
     for (int t = 0; t < NV; ++t) {
       if (xsum_out) reinterpret_cast<float4*>(xsum_out + (size_t)row * D)[lane + 64 * t] = v[t];
-      float4 o;
-      o.x = av[t].x * ((v[t].x - mean) * r) + bv[t].x;
-      o.y = av[t].y * ((v[t].y - mean) * r) + bv[t].y;
-      o.z = av[t].z * ((v[t].z - mean) * r) + bv[t].z;
-      o.w = av[t].w * ((v[t].w - mean) * r) + bv[t].w;
-      reinterpret_cast<float4*>(y + (size_t)row * D)[lane + 64 * t] = o;
+      reinterpret_cast<float4*>(y + (size_t)row * D)[lane + 64 * t] = rowreg_affine(av[t], v[t], mean, r, bv[t]);
     }
     if (lane == 0) {
       mean_out[row] = mean;
@@ -206,25 +195,13 @@ __global__ void __launch_bounds__(64 * WPB) ltrx_layernorm_bwd_vec_kernel(const 
       g[t] = reinterpret_cast<const float4*>(dy + (size_t)row * D)[lane + 64 * t];
       xc[t] = reinterpret_cast<const float4*>(xsum + (size_t)row * D)[lane + 64 * t];
       xc[t].x -= mean; xc[t].y -= mean; xc[t].z -= mean; xc[t].w -= mean;
-      // da/db use the raw dy; then g becomes dy * a
-      da[t].x += g[t].x * (xc[t].x * r); da[t].y += g[t].y * (xc[t].y * r);
-      da[t].z += g[t].z * (xc[t].z * r); da[t].w += g[t].w * (xc[t].w * r);
-      db[t].x += g[t].x; db[t].y += g[t].y; db[t].z += g[t].z; db[t].w += g[t].w;
-      g[t].x *= av[t].x; g[t].y *= av[t].y; g[t].z *= av[t].z; g[t].w *= av[t].w;
-      gsum += (g[t].x + g[t].y) + (g[t].z + g[t].w);
-      dot += (g[t].x * xc[t].x + g[t].y * xc[t].y) + (g[t].z * xc[t].z + g[t].w * xc[t].w);
+      LTRX_ROWREG_BWD_ACC(g[t], xc[t], av[t], r, da[t], db[t], gsum, dot);
     }
-    const float gm = wave_sum(gsum) / (float)D;
-    dot = wave_sum(dot);
-    const float stdv = 1.0f / r - eps;
-    const float tc = (stdv > 0.f) ? r * r * dot / ((float)(D - 1) * stdv) : 0.f;
+    float gm, tc;
+    rowreg_bwd_coef<NV>(gsum, dot, r, eps, gm, tc);
 #pragma unroll
     for (int t = 0; t < NV; ++t) {
-      float4 o;
-      o.x = r * (g[t].x - gm) - tc * xc[t].x;
-      o.y = r * (g[t].y - gm) - tc * xc[t].y;
-      o.z = r * (g[t].z - gm) - tc * xc[t].z;
-      o.w = r * (g[t].w - gm) - tc * xc[t].w;
+      float4 o = rowreg_bwd_dx(g[t], xc[t], r, gm, tc);
       if (dres) {
         const float4 d = reinterpret_cast<const float4*>(dres + (size_t)row * D)[lane + 64 * t];
         o.x += d.x; o.y += d.y; o.z += d.z; o.w += d.w;
@@ -232,18 +209,7 @@ __global__ void __launch_bounds__(64 * WPB) ltrx_layernorm_bwd_vec_kernel(const 
       reinterpret_cast<float4*>(dx + (size_t)row * D)[lane + 64 * t] = o;
     }
   }
-#pragma unroll
-  for (int t = 0; t < NV; ++t) {
-    reinterpret_cast<float4*>(lds + (size_t)w * 2 * D)[lane + 64 * t] = da[t];
-    reinterpret_cast<float4*>(lds + (size_t)w * 2 * D + D)[lane + 64 * t] = db[t];
-  }
-  __syncthreads();
-  float* pa = partial + (size_t)blockIdx.x * 2 * D;
-  for (int c = threadIdx.x; c < 2 * D; c += blockDim.x) {
-    float sacc = 0.f;
-    for (int ww = 0; ww < wpb; ++ww) sacc += lds[(size_t)ww * 2 * D + c];
-    pa[c] = sacc;
-  }
+  LTRX_ROWREG_LN_COMBINE(NV, WPB, lds, lane, w, da, db, partial + (size_t)blockIdx.x * 2 * D);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -252,14 +218,11 @@ __global__ void __launch_bounds__(64 * WPB) ltrx_layernorm_bwd_vec_kernel(const 
 // from registers, the backward forms ds * w in registers.  (The head's own two gradients need the rows in ltrx_score_head_bwd's
 // order to keep their bits: ltrx_norm_head_wgrad, csrc/ltrx_train.hip, recomputes xf for them.)
 // ------------------------------------------------------------------------------------------------------------------
-// Statistics and o: the expressions and order of ltrx_layernorm_fwd_vec_kernel (res = NULL).  The score repeats
+// Statistics and o are ltrx_layernorm_fwd_vec_kernel's (rowreg_stats, rowreg_affine).  The score repeats
 // ltrx_score_head_fwd_kernel's order -- lane l accumulates columns l, l + 64, ... in turn, then wave_sum -- so a wave
 // passes its row through a private LDS slab to turn the float4 layout into that one: the scores keep their bits.
 // The hand-over between lanes needs no workgroup barrier on wave64 hardware only (gfx9: one wave's DS instructions execute in
 // program order and the wave is the whole slab's owner); __builtin_amdgcn_wave_barrier() keeps the compiler from moving them.
-// Same bits as the two-kernel path also means the same fma contraction of a * t + b here, in ltrx_layernorm_fwd_vec_kernel and in
-// ltrx_norm_head_wgrad_kernel (all three are this one expression under the build's default -ffp-contract): tests/test_gpu_norm_head.py
-// compares y, the scores and the head's gradients bit for bit, so a compiler that chose differently would be caught there.
 template <int NV>
 __global__ void __launch_bounds__(256) ltrx_norm_head_fwd_kernel(const float* __restrict__ x, const float* __restrict__ a,
                                                                  const float* __restrict__ b, const float* __restrict__ w,
@@ -288,22 +251,11 @@ __global__ void __launch_bounds__(256) ltrx_norm_head_fwd_kernel(const float* __
       v[t] = xr[lane + 64 * t];
       sum += (v[t].x + v[t].y) + (v[t].z + v[t].w);
     }
-    const float mean = wave_sum(sum) / (float)D;
-    float sq = 0.f;
+    float mean, r;
+    rowreg_stats<NV>(v, sum, eps, mean, r);
 #pragma unroll
     for (int t = 0; t < NV; ++t) {
-      const float dx = v[t].x - mean, dy = v[t].y - mean, dz = v[t].z - mean, dw = v[t].w - mean;
-      sq += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-    }
-    const float stdv = sqrtf(wave_sum(sq) / (float)(D - 1));
-    const float r = 1.0f / (stdv + eps);
-#pragma unroll
-    for (int t = 0; t < NV; ++t) {
-      float4 o;
-      o.x = av[t].x * ((v[t].x - mean) * r) + bv[t].x;
-      o.y = av[t].y * ((v[t].y - mean) * r) + bv[t].y;
-      o.z = av[t].z * ((v[t].z - mean) * r) + bv[t].z;
-      o.w = av[t].w * ((v[t].w - mean) * r) + bv[t].w;
+      const float4 o = rowreg_affine(av[t], v[t], mean, r, bv[t]);
       if (y) reinterpret_cast<float4*>(y + (size_t)row * D)[lane + 64 * t] = o;
       reinterpret_cast<float4*>(mine)[lane + 64 * t] = o;
     }
@@ -322,7 +274,7 @@ __global__ void __launch_bounds__(256) ltrx_norm_head_fwd_kernel(const float* __
 }
 
 // ltrx_layernorm_bwd_vec_kernel (dres = NULL) fed with dy = ds[row] * w from registers -- the fp32 product ltrx_score_head_bwd
-// stores.  Everything else is that kernel's: workgroup shapes, row walk, partial rows [da(D) | db(D)] and their combine.
+// stores; workgroup shapes and row walk are that kernel's, the row arithmetic and the combine the shared ones of ltrx_rowreg.h.
 template <int NV, int WPB>
 __global__ void __launch_bounds__(64 * WPB) ltrx_norm_head_bwd_kernel(const float* __restrict__ ds, const float* __restrict__ xsum,
                                                                       const float* __restrict__ a, const float* __restrict__ wh,
@@ -351,40 +303,14 @@ __global__ void __launch_bounds__(64 * WPB) ltrx_norm_head_bwd_kernel(const floa
       asm volatile("" : "+v"(g[t].x), "+v"(g[t].y), "+v"(g[t].z), "+v"(g[t].w));
       xc[t] = reinterpret_cast<const float4*>(xsum + (size_t)row * D)[lane + 64 * t];
       xc[t].x -= mean; xc[t].y -= mean; xc[t].z -= mean; xc[t].w -= mean;
-      // da/db use the raw dy; then g becomes dy * a
-      da[t].x += g[t].x * (xc[t].x * r); da[t].y += g[t].y * (xc[t].y * r);
-      da[t].z += g[t].z * (xc[t].z * r); da[t].w += g[t].w * (xc[t].w * r);
-      db[t].x += g[t].x; db[t].y += g[t].y; db[t].z += g[t].z; db[t].w += g[t].w;
-      g[t].x *= av[t].x; g[t].y *= av[t].y; g[t].z *= av[t].z; g[t].w *= av[t].w;
-      gsum += (g[t].x + g[t].y) + (g[t].z + g[t].w);
-      dot += (g[t].x * xc[t].x + g[t].y * xc[t].y) + (g[t].z * xc[t].z + g[t].w * xc[t].w);
+      LTRX_ROWREG_BWD_ACC(g[t], xc[t], av[t], r, da[t], db[t], gsum, dot);
     }
-    const float gm = wave_sum(gsum) / (float)D;
-    dot = wave_sum(dot);
-    const float stdv = 1.0f / r - eps;
-    const float tc = (stdv > 0.f) ? r * r * dot / ((float)(D - 1) * stdv) : 0.f;
+    float gm, tc;
+    rowreg_bwd_coef<NV>(gsum, dot, r, eps, gm, tc);
 #pragma unroll
-    for (int t = 0; t < NV; ++t) {
-      float4 o;
-      o.x = r * (g[t].x - gm) - tc * xc[t].x;
-      o.y = r * (g[t].y - gm) - tc * xc[t].y;
-      o.z = r * (g[t].z - gm) - tc * xc[t].z;
-      o.w = r * (g[t].w - gm) - tc * xc[t].w;
-      reinterpret_cast<float4*>(dx + (size_t)row * D)[lane + 64 * t] = o;
-    }
+    for (int t = 0; t < NV; ++t) reinterpret_cast<float4*>(dx + (size_t)row * D)[lane + 64 * t] = rowreg_bwd_dx(g[t], xc[t], r, gm, tc);
   }
-#pragma unroll
-  for (int t = 0; t < NV; ++t) {
-    reinterpret_cast<float4*>(lds + (size_t)w * 2 * D)[lane + 64 * t] = da[t];
-    reinterpret_cast<float4*>(lds + (size_t)w * 2 * D + D)[lane + 64 * t] = db[t];
-  }
-  __syncthreads();
-  float* pa = partial + (size_t)blockIdx.x * 2 * D;
-  for (int c = threadIdx.x; c < 2 * D; c += blockDim.x) {
-    float sacc = 0.f;
-    for (int ww = 0; ww < wpb; ++ww) sacc += lds[(size_t)ww * 2 * D + c];
-    pa[c] = sacc;
-  }
+  LTRX_ROWREG_LN_COMBINE(NV, WPB, lds, lane, w, da, db, partial + (size_t)blockIdx.x * 2 * D);
 }
 
 // One workgroup per 64 columns; its 16 waves split the partial rows, lanes own consecutive columns (coalesced),
@@ -439,6 +365,21 @@ static int ln_bwd_grid(int rows) {
 #define LTRX_LN_BWD_WIDE_ROWS (16 * 4 * LTRX_LN_BWD_G16)
 #endif
 static bool ln_bwd_wide(int rows, int D) { return D <= 512 && rows >= LTRX_LN_BWD_WIDE_ROWS; }
+// launch shape of the register-resident backward kernels (plain and norm + head): grid and waves per workgroup
+struct LnBwdShape { int grid, wpb; };
+static LnBwdShape ln_bwd_shape(int rows, int D) {
+  return ln_bwd_wide(rows, D) ? LnBwdShape{LTRX_LN_BWD_G16, 16} : LnBwdShape{ln_bwd_grid(rows), 4};
+}
+// f(NV, WPB as integral constants) for that shape; the wide arm exists at NV 1 and 2 only (D <= 512)
+template <typename F>
+static void ln_bwd_dispatch(const LnBwdShape& sh, int D, F&& f) {
+  assert(sh.wpb == 4 || D <= 512);
+  ltrx_rowreg_dispatch(D, [&](auto nv) {
+    if constexpr (decltype(nv)::value <= 2)
+      if (sh.wpb == 16) return f(nv, std::integral_constant<int, 16>{});
+    f(nv, std::integral_constant<int, 4>{});
+  });
+}
 static int ln_fwd_vec_grid(int rows) {
   int g = (rows + 7) / 8;
   return g > 1024 ? 1024 : (g < 1 ? 1 : g);
@@ -457,14 +398,10 @@ extern "C" int ltrx_layernorm_fwd(const float* x, const float* res, const float*
   hipStream_t s = (hipStream_t)stream;
   if (ln_vec_ok(D, x, y_out, res) && ln_vec_ok(D, a, b, xsum_out)) {
     const dim3 g(ln_fwd_vec_grid(rows));
-#define LTRX_LN_FWD(NV) hipLaunchKernelGGL(ltrx_layernorm_fwd_vec_kernel<NV>, g, dim3(256), 0, s, x, res, a, b, rows, eps, xsum_out, y_out, mean_out, rstd_out, drop, drop_step)
-    switch (D / 256) {
-      case 1: LTRX_LN_FWD(1); break;
-      case 2: LTRX_LN_FWD(2); break;
-      case 3: LTRX_LN_FWD(3); break;
-      default: LTRX_LN_FWD(4); break;
-    }
-#undef LTRX_LN_FWD
+    ltrx_rowreg_dispatch(D, [&](auto nv) {
+      hipLaunchKernelGGL(ltrx_layernorm_fwd_vec_kernel<decltype(nv)::value>, g, dim3(256), 0, s, x, res, a, b, rows, eps, xsum_out, y_out,
+                         mean_out, rstd_out, drop, drop_step);
+    });
   } else {
     hipLaunchKernelGGL(ltrx_layernorm_fwd_kernel, dim3(ln_grid(rows)), dim3(256), 0, s, x, res, a, b, rows, D, eps, xsum_out,
                        y_out, mean_out, rstd_out, drop, drop_step);
@@ -484,28 +421,19 @@ static int ln_bwd_main(const float* dy, const float* xsum, const float* a, const
                        int rows, int D, float eps, float* dx_out, void* ws, int* grid_out, hipStream_t s) {
   if (!dy || !xsum || !a || !mean || !rstd || !dx_out || !ws || rows <= 0 || D < 2) return LTRX_EINVAL;
   if ((size_t)4 * 2 * D * sizeof(float) > 64 * 1024) return LTRX_EUNSUPPORTED;   // D <= 2048
-  int grid = ln_bwd_grid(rows);
-  if (ln_vec_ok(D, dy, xsum, dx_out) && ln_vec_ok(D, a, dres_in, ws)) {
-#define LTRX_LN_BWD(NV, WPB) \
-  hipLaunchKernelGGL((ltrx_layernorm_bwd_vec_kernel<NV, WPB>), dim3(grid), dim3(64 * WPB), 0, s, dy, xsum, a, mean, rstd, dres_in, rows, eps, dx_out, (float*)ws)
-    if (ln_bwd_wide(rows, D)) {
-      grid = LTRX_LN_BWD_G16;
-      if (D / 256 == 1) LTRX_LN_BWD(1, 16); else LTRX_LN_BWD(2, 16);
-    } else {
-      switch (D / 256) {
-        case 1: LTRX_LN_BWD(1, 4); break;
-        case 2: LTRX_LN_BWD(2, 4); break;
-        case 3: LTRX_LN_BWD(3, 4); break;
-        default: LTRX_LN_BWD(4, 4); break;
-      }
-    }
-#undef LTRX_LN_BWD
+  const bool vec = ln_vec_ok(D, dy, xsum, dx_out) && ln_vec_ok(D, a, dres_in, ws);
+  const LnBwdShape sh = vec ? ln_bwd_shape(rows, D) : LnBwdShape{ln_bwd_grid(rows), 4};
+  if (vec) {
+    ln_bwd_dispatch(sh, D, [&](auto nv, auto wpb) {
+      hipLaunchKernelGGL((ltrx_layernorm_bwd_vec_kernel<decltype(nv)::value, decltype(wpb)::value>), dim3(sh.grid),
+                         dim3(64 * decltype(wpb)::value), 0, s, dy, xsum, a, mean, rstd, dres_in, rows, eps, dx_out, (float*)ws);
+    });
   } else {
-    hipLaunchKernelGGL(ltrx_layernorm_bwd_kernel, dim3(grid), dim3(256), (size_t)4 * 2 * D * sizeof(float), s, dy, xsum, a,
+    hipLaunchKernelGGL(ltrx_layernorm_bwd_kernel, dim3(sh.grid), dim3(256), (size_t)4 * 2 * D * sizeof(float), s, dy, xsum, a,
                        mean, rstd, dres_in, rows, D, eps, dx_out, (float*)ws);
   }
   LTRX_LAUNCH_CHECK();
-  *grid_out = grid;
+  *grid_out = sh.grid;
   return LTRX_OK;
 }
 
@@ -541,14 +469,10 @@ extern "C" int ltrx_norm_head_fwd(const float* x, const float* a, const float* b
   if (!ln_vec_ok(D, x, a, b) || !ln_vec_ok(D, w, y_out, nullptr)) return LTRX_EUNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   const dim3 g(ln_fwd_vec_grid(rows));
-#define LTRX_NH_FWD(NV) hipLaunchKernelGGL(ltrx_norm_head_fwd_kernel<NV>, g, dim3(256), 0, s, x, a, b, w, bias, rows, eps, scores_out, y_out, mean_out, rstd_out)
-  switch (D / 256) {
-    case 1: LTRX_NH_FWD(1); break;
-    case 2: LTRX_NH_FWD(2); break;
-    case 3: LTRX_NH_FWD(3); break;
-    default: LTRX_NH_FWD(4); break;
-  }
-#undef LTRX_NH_FWD
+  ltrx_rowreg_dispatch(D, [&](auto nv) {
+    hipLaunchKernelGGL(ltrx_norm_head_fwd_kernel<decltype(nv)::value>, g, dim3(256), 0, s, x, a, b, w, bias, rows, eps, scores_out, y_out,
+                       mean_out, rstd_out);
+  });
   LTRX_LAUNCH_CHECK();
   return LTRX_OK;
 }
@@ -556,29 +480,19 @@ extern "C" int ltrx_norm_head_fwd(const float* x, const float* a, const float* b
 extern "C" size_t ltrx_norm_head_bwd_workspace_bytes(int rows, int D) { return ltrx_layernorm_bwd_workspace_bytes(rows, D); }
 
 // dx_out is final; ws holds *partial_rows_out rows of [da(D) | db(D)] partials (row stride 2 D) for the caller to sum, exactly as
-// ltrx_layernorm_bwd_partial leaves them.  Grid and row walk: ln_bwd_main's, both arms.  The head's own gradients: ltrx_norm_head_wgrad.
+// ltrx_layernorm_bwd_partial leaves them (the same ln_bwd_shape).  The head's own gradients: ltrx_norm_head_wgrad.
 extern "C" int ltrx_norm_head_bwd_partial(const float* dscores, const float* xsum, const float* a, const float* w, const float* mean,
                                           const float* rstd, int rows, int D, float eps, float* dx_out, void* ws, int* partial_rows_out,
                                           ltrx_stream_t stream) {
   if (!dscores || !xsum || !a || !w || !mean || !rstd || !dx_out || !ws || !partial_rows_out || rows <= 0 || D < 2) return LTRX_EINVAL;
   if (!ln_vec_ok(D, xsum, dx_out, ws) || !ln_vec_ok(D, a, w, nullptr)) return LTRX_EUNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
-  int grid = ln_bwd_grid(rows);
-#define LTRX_NH_BWD(NV, WPB) \
-  hipLaunchKernelGGL((ltrx_norm_head_bwd_kernel<NV, WPB>), dim3(grid), dim3(64 * WPB), 0, s, dscores, xsum, a, w, mean, rstd, rows, eps, dx_out, (float*)ws)
-  if (ln_bwd_wide(rows, D)) {
-    grid = LTRX_LN_BWD_G16;
-    if (D / 256 == 1) LTRX_NH_BWD(1, 16); else LTRX_NH_BWD(2, 16);
-  } else {
-    switch (D / 256) {
-      case 1: LTRX_NH_BWD(1, 4); break;
-      case 2: LTRX_NH_BWD(2, 4); break;
-      case 3: LTRX_NH_BWD(3, 4); break;
-      default: LTRX_NH_BWD(4, 4); break;
-    }
-  }
-#undef LTRX_NH_BWD
+  const LnBwdShape sh = ln_bwd_shape(rows, D);
+  ln_bwd_dispatch(sh, D, [&](auto nv, auto wpb) {
+    hipLaunchKernelGGL((ltrx_norm_head_bwd_kernel<decltype(nv)::value, decltype(wpb)::value>), dim3(sh.grid),
+                       dim3(64 * decltype(wpb)::value), 0, s, dscores, xsum, a, w, mean, rstd, rows, eps, dx_out, (float*)ws);
+  });
   LTRX_LAUNCH_CHECK();
-  *partial_rows_out = grid;
+  *partial_rows_out = sh.grid;
   return LTRX_OK;
 }

@@ -5,7 +5,7 @@
 //   ltrx_colsum           bias gradients: out[n] = sum_m dY[m][n]   (nn.Linear backward; deterministic two-stage)
 //   ltrx_relu_bwd         dz = dr * (r > 0) in place                 (transformer.py:227 / FCModel activation)
 //   ltrx_score_head_fwd/bwd  OutputLayer with d_output == 1 (model.py:111-117): s[m] = <x[m,:], w> + b, and its backward
-#include "ltrx_device.h"
+#include "ltrx_rowreg.h"
 
 using namespace ltrx;
 
@@ -265,18 +265,12 @@ __global__ void __launch_bounds__(256) ltrx_score_head_bwd_vec_kernel(const floa
     }
     dbacc += g;
   }
-#pragma unroll
-  for (int t = 0; t < NV; ++t) *reinterpret_cast<float4*>(&lds[wv][4 * (lane + 64 * t)]) = acc[t];
-  if (lane == 0) lds[wv][D] = dbacc;
-  __syncthreads();
-  float* pa = partial + (size_t)blockIdx.x * (D + 1);
-  for (int c = threadIdx.x; c <= D; c += blockDim.x) pa[c] = (lds[0][c] + lds[1][c]) + (lds[2][c] + lds[3][c]);
+  LTRX_ROWREG_HEAD_COMBINE(NV, lds, lane, wv, acc, dbacc, partial + (size_t)blockIdx.x * (D + 1));
 }
 
 // The parameter gradients of the kernel above where the head's input is xf = LN(xsum) and only xsum and the statistics are kept (the
-// fused final norm + head, csrc/ltrx_layernorm.hip): xf is recomputed by the forward's expression, nothing is written but the
-// partials.  Grid, row walk, accumulation and combine are ltrx_score_head_bwd's, so dw / db keep the bits they have on the stored xf;
-// NV = 3 is the one width that ltrx_score_head_bwd gives to its scalar kernel, whose workgroup combine runs wave by wave.
+// fused final norm + head, csrc/ltrx_layernorm.hip): xf is recomputed by the forward's rowreg_affine, nothing is written but the
+// partials.  Grid, row walk and accumulation are ltrx_score_head_bwd's, the combine is shared, so dw / db keep the bits of the stored xf.
 template <int NV>
 __global__ void __launch_bounds__(256) ltrx_norm_head_wgrad_kernel(const float* __restrict__ ds, const float* __restrict__ xsum,
                                                                    const float* __restrict__ a, const float* __restrict__ b,
@@ -299,11 +293,7 @@ __global__ void __launch_bounds__(256) ltrx_norm_head_wgrad_kernel(const float* 
 #pragma unroll
     for (int t = 0; t < NV; ++t) {
       const float4 v = xr[lane + 64 * t];
-      float4 y;
-      y.x = av[t].x * ((v.x - mean) * r) + bv[t].x;
-      y.y = av[t].y * ((v.y - mean) * r) + bv[t].y;
-      y.z = av[t].z * ((v.z - mean) * r) + bv[t].z;
-      y.w = av[t].w * ((v.w - mean) * r) + bv[t].w;
+      const float4 y = rowreg_affine(av[t], v, mean, r, bv[t]);
       acc[t].x += g * y.x;
       acc[t].y += g * y.y;
       acc[t].z += g * y.z;
@@ -311,20 +301,7 @@ __global__ void __launch_bounds__(256) ltrx_norm_head_wgrad_kernel(const float* 
     }
     dbacc += g;
   }
-#pragma unroll
-  for (int t = 0; t < NV; ++t) *reinterpret_cast<float4*>(&lds[wv][4 * (lane + 64 * t)]) = acc[t];
-  if (lane == 0) lds[wv][D] = dbacc;
-  __syncthreads();
-  float* pa = partial + (size_t)blockIdx.x * (D + 1);
-  for (int c = threadIdx.x; c <= D; c += blockDim.x) {
-    if (NV == 3) {
-      float s = 0.f;
-      for (int k = 0; k < 4; ++k) s += lds[k][c];
-      pa[c] = s;
-    } else {
-      pa[c] = (lds[0][c] + lds[1][c]) + (lds[2][c] + lds[3][c]);
-    }
-  }
+  LTRX_ROWREG_HEAD_COMBINE(NV, lds, lane, wv, acc, dbacc, partial + (size_t)blockIdx.x * (D + 1));
 }
 
 // dw[c] = sum_k partial[k][c] (c < D), db = column D; 64 columns x 16 row groups (waves) per workgroup, fixed combine order
@@ -402,15 +379,10 @@ extern "C" int ltrx_norm_head_wgrad(const float* dscores, const float* xsum, con
   if (D % 256 != 0 || D > 1024 || ((((uintptr_t)xsum) | ((uintptr_t)a) | ((uintptr_t)b)) & 15) != 0) return LTRX_EUNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   const int g = head_grid(M);
-#define LTRX_NH_WGRAD(NV) \
-  hipLaunchKernelGGL(ltrx_norm_head_wgrad_kernel<NV>, dim3(g), dim3(256), 0, s, dscores, xsum, a, b, mean, rstd, M, (float*)ws)
-  switch (D / 256) {
-    case 1: LTRX_NH_WGRAD(1); break;
-    case 2: LTRX_NH_WGRAD(2); break;
-    case 3: LTRX_NH_WGRAD(3); break;
-    default: LTRX_NH_WGRAD(4); break;
-  }
-#undef LTRX_NH_WGRAD
+  ltrx_rowreg_dispatch(D, [&](auto nv) {
+    hipLaunchKernelGGL(ltrx_norm_head_wgrad_kernel<decltype(nv)::value>, dim3(g), dim3(256), 0, s, dscores, xsum, a, b, mean, rstd, M,
+                       (float*)ws);
+  });
   LTRX_LAUNCH_CHECK();
   hipLaunchKernelGGL(ltrx_score_head_reduce_kernel, dim3((D + 1 + 63) / 64), dim3(1024), 0, s, (const float*)ws, g, D, dw, db);
   LTRX_LAUNCH_CHECK();
