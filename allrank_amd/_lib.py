@@ -13,7 +13,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ltrx.h")
 
 # C type -> ctypes type.  "*" stands for any pointer, device or host: like ltrx_stream_t it is passed as a raw address.
 _CTYPES = {"*": ctypes.c_void_p, "ltrx_stream_t": ctypes.c_void_p, "int": ctypes.c_int, "float": ctypes.c_float,
-           "size_t": ctypes.c_size_t, "uint32_t": ctypes.c_uint32, "uint64_t": ctypes.c_uint64, "int64_t": ctypes.c_int64}
+           "size_t": ctypes.c_size_t, "int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "uint64_t": ctypes.c_uint64, "int64_t": ctypes.c_int64}
 
 
 def _ctype_name(decl, where):

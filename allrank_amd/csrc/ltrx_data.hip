@@ -13,6 +13,10 @@
 //     random order -- label sums by workgroup reductions.  No host round trip, no data-dependent launch sizes.
 //   ltrx_assemble_batch : xb[b][l][:] = x_items[offsets[slate_b] + pos] (zeros for pos = -1), yb = label or -1,
 //       indices = pos (the original rank, what positional encodings consume) -- float4-coalesced reads and writes.
+//   ltrx_assemble_batch_picked : the same batch in ONE launch from positions chosen on the host (the reference's own
+//       np.random.choice draws, allrank_amd/data.py DeviceLoader(sampling="reference")): a row with pick_row >= 0 takes its L
+//       positions from that row of `picks`, every other row its stored order (the padding branch above; the first L items of a
+//       longer slate).  The [B, L] int64 positions tensor of the two-launch path is never written or read; same access shape.
 #include "ltrx_device.h"
 
 using namespace ltrx;
@@ -160,6 +164,61 @@ extern "C" int ltrx_assemble_batch(const float* x_items, const float* y_items, c
   else
     hipLaunchKernelGGL(ltrx_assemble_batch_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, x_items, y_items, offsets, slates, positions,
                        L, F, total, xb, yb, indices);
+  LTRX_LAUNCH_CHECK();
+  return LTRX_OK;
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(256) ltrx_assemble_batch_picked_kernel(const float* __restrict__ x_items, const float* __restrict__ y_items,
+                                                                         const int64_t* __restrict__ offsets,
+                                                                         const int64_t* __restrict__ slates,
+                                                                         const int32_t* __restrict__ pick_row,
+                                                                         const int32_t* __restrict__ picks, int n_pick_rows, int L, int F,
+                                                                         size_t total, float* __restrict__ xb, float* __restrict__ yb,
+                                                                         int64_t* __restrict__ idx) {
+  const int per_row = VEC ? F / 4 : F;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const size_t row = i / per_row;                   // b * L + l
+  const int c = (int)(i % per_row);
+  const size_t b = row / L;
+  const int l = (int)(row - b * L);
+  const int64_t s = slates[b];
+  const int64_t base = offsets[s];
+  const int64_t len = offsets[s + 1] - base;
+  const int pr = pick_row[b];
+  // pick_row < 0: stored order.  A pick row the table does not have, or a pick outside the slate, is padding: nothing outside
+  // [base, base + len) is ever read.
+  int64_t pos = pr < 0 ? (int64_t)l : (pr < n_pick_rows ? (int64_t)picks[(size_t)pr * L + l] : (int64_t)-1);
+  if (pos < 0 || pos >= len) pos = -1;
+  const int64_t item = pos >= 0 ? base + pos : 0;
+  if (VEC) {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (pos >= 0) v = reinterpret_cast<const float4*>(x_items + (size_t)item * F)[c];
+    reinterpret_cast<float4*>(xb + row * F)[c] = v;
+  } else {
+    xb[row * F + c] = pos >= 0 ? x_items[(size_t)item * F + c] : 0.f;
+  }
+  if (c == 0) {
+    yb[row] = pos >= 0 ? y_items[item] : -1.0f;      // PADDED_Y_VALUE
+    idx[row] = pos;                                   // PADDED_INDEX_VALUE = -1
+  }
+}
+
+extern "C" int ltrx_assemble_batch_picked(const float* x_items, const float* y_items, const int64_t* offsets, const int64_t* slates,
+                                          const int32_t* pick_row, const int32_t* picks, int n_pick_rows, int B, int L, int F, float* xb,
+                                          float* yb, int64_t* indices, ltrx_stream_t stream) {
+  if (!x_items || !y_items || !offsets || !slates || !pick_row || !xb || !yb || !indices || B <= 0 || L <= 0 || F <= 0) return LTRX_EINVAL;
+  if (n_pick_rows < 0 || (!picks && n_pick_rows != 0)) return LTRX_EINVAL;
+  const bool vec = (F % 4 == 0) && ((((uintptr_t)x_items | (uintptr_t)xb) & 15) == 0);
+  const size_t total = (size_t)B * L * (vec ? F / 4 : F);
+  const dim3 grid((unsigned)((total + 255) / 256));
+  if (vec)
+    hipLaunchKernelGGL(ltrx_assemble_batch_picked_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, x_items, y_items, offsets, slates,
+                       pick_row, picks, n_pick_rows, L, F, total, xb, yb, indices);
+  else
+    hipLaunchKernelGGL(ltrx_assemble_batch_picked_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, x_items, y_items, offsets, slates,
+                       pick_row, picks, n_pick_rows, L, F, total, xb, yb, indices);
   LTRX_LAUNCH_CHECK();
   return LTRX_OK;
 }

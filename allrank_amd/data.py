@@ -27,6 +27,11 @@ signatures of allrank/data/dataset_loading.py:197-248 and are what ``allrank_amd
 slate length of its role) and ``DeviceLoader`` (batch order drawn from torch's global generator exactly as the reference's
 ``DataLoader(shuffle=True)`` draws it -- same seeds, same slates per batch; under a process group a rank assembles ONLY its
 contiguous block of each global batch: no full-batch collation, no host-to-device copy at all).
+
+``sampling="reference"`` (opt-in; ALLRANK_AMD_SAMPLING=reference under main.py): the sampling branch is drawn on the HOST with the
+reference's own numpy calls from the reference's own generator stream (``reference_picks``; labels of the long slates only, no
+features), a few KB of picks are uploaded per batch and ``ltrx_assemble_batch_picked`` gathers the batch in one launch -- the same
+items, ``indices`` and generator states as the reference's loader, for ``num_workers`` 0 and >= 1.
 """
 import logging
 
@@ -37,6 +42,34 @@ log = logging.getLogger("allrank_amd.data")
 
 PADDED_Y_VALUE = -1
 PADDED_INDEX_VALUE = -1
+SAMPLING_MODES = ("device", "reference")
+
+
+def sampling_mode(value=None):
+    """the sampling mode named by ``value`` or, without one, by the environment variable ALLRANK_AMD_SAMPLING (default "device")"""
+    import os
+    mode = (value if value is not None else os.environ.get("ALLRANK_AMD_SAMPLING") or "device")
+    mode = str(mode).lower()
+    if mode not in SAMPLING_MODES:
+        raise ValueError("allrank_amd.data: sampling must be 'device' or 'reference', got %r" % (mode,))
+    return mode
+
+
+def reference_picks(y, L, rng):
+    """The L positions FixLength._sample (dataset_loading.py:61-79) picks from a slate with labels ``y`` (len(y) >= L), drawn from
+    ``rng`` -- the numpy module (its global generator) or a RandomState -- with the reference's calls in the reference's order:
+    choice without replacement (:70); no relevant item sampled -> the slate's only relevant item replaces a re-drawn last slot
+    (:72-74), or, with other relevance in the slate, the draw is repeated (:75-76)."""
+    n = len(y)
+    while True:
+        pick = rng.choice(n, L, replace=False)
+        if y[pick].sum() == 0:
+            total = y.sum()
+            if total == 1:
+                pick = np.concatenate([rng.choice(pick, L - 1, replace=False), [np.argmax(y)]])
+            elif total > 0:
+                continue
+        return pick
 
 
 def parse_svm_file_on_device(path, device="cuda", n_features=None):
@@ -108,6 +141,7 @@ class DeviceSlates(object):
         ypad = torch.where(self.item_of >= 0, self.y_items[self.item_of.clamp(min=0)], torch.zeros((), device=self.device))
         self.label_sum = ypad.sum(1)
         self.argmax_pos = ypad.argmax(1)
+        self._host_labels = {}                 # L -> {slate id: float64 labels} of the slates with >= L items (host_labels)
 
     @classmethod
     def from_svm_file(cls, path, device="cuda", parser="device"):
@@ -192,6 +226,80 @@ class DeviceSlates(object):
         LB.check(LB.lib().ltrx_assemble_batch(LB.ptr(self.x_items), LB.ptr(self.y_items), LB.ptr(self.offsets), LB.ptr(slates), LB.ptr(pos),
                                               B, L, self.n_features, LB.ptr(xb), LB.ptr(yb), LB.ptr(idx), LB.stream_of(xb)),
                  "assemble_batch")
+        return xb, yb, idx
+
+    def host_labels(self, L):
+        """{slate id: labels as float64 (the reference's label dtype)} of the slates that take FixLength's sampling branch at slate
+        length ``L`` (>= L items) -- all the host needs to make the reference's draws.  Built on first use per ``L``: one download."""
+        L = int(L)
+        if L not in self._host_labels:
+            lens = self.lengths_host.numpy()
+            ids = np.flatnonzero(lens >= L)
+            out = {}
+            if len(ids):
+                ids_d = torch.from_numpy(ids).to(self.device)
+                n = self.lengths[ids_d]
+                pos = torch.arange(int(n.max()), device=self.device)[None, :]
+                items = (self.offsets[ids_d][:, None] + pos)[pos < n[:, None]]           # the long slates' items, slate after slate
+                flat = self.y_items[items].cpu().numpy().astype(np.float64)
+                cuts = np.cumsum(lens[ids])[:-1]
+                out = dict(zip(ids.tolist(), np.split(flat, cuts)))
+            self._host_labels[L] = out
+        return self._host_labels[L]
+
+    def _picked_args(self, slates, pick_row, picks):
+        slates = slates.to(device=self.device, dtype=torch.int64).contiguous()
+        pick_row = pick_row.to(device=self.device, dtype=torch.int32).contiguous()
+        if picks is not None and picks.numel() == 0:
+            picks = None
+        if picks is not None:
+            picks = picks.to(device=self.device, dtype=torch.int32).contiguous()
+        return slates, pick_row, picks
+
+    def _empty_batch(self, L):
+        return (torch.empty((0, L, self.n_features), dtype=torch.float32, device=self.device),
+                torch.empty((0, L), dtype=torch.float32, device=self.device), torch.empty((0, L), dtype=torch.int64, device=self.device))
+
+    def batch_picked(self, slates, slate_length, pick_row, picks=None):
+        """slates: i64[B] slate ids, pick_row: i32[B], picks: i32[n, L] or None -> (xb [B,L,F], yb [B,L], indices [B,L]) in ONE launch
+        (ltrx_assemble_batch_picked): row b takes the positions ``picks[pick_row[b]]``, or its stored order where ``pick_row[b]`` < 0."""
+        from . import _lib as LB
+        LB.require_device(self.x_items)
+        L = int(slate_length)
+        slates, pick_row, picks = self._picked_args(slates, pick_row, picks)
+        B = int(slates.numel())
+        if B == 0:
+            return self._empty_batch(L)
+        if int(pick_row.numel()) != B or (picks is not None and (picks.dim() != 2 or int(picks.shape[1]) != L)):
+            raise ValueError("batch_picked: pick_row must have one entry per slate and picks must be [n, %d]" % L)
+        xb = torch.empty((B, L, self.n_features), dtype=torch.float32, device=self.device)
+        yb = torch.empty((B, L), dtype=torch.float32, device=self.device)
+        idx = torch.empty((B, L), dtype=torch.int64, device=self.device)
+        LB.check(LB.lib().ltrx_assemble_batch_picked(LB.ptr(self.x_items), LB.ptr(self.y_items), LB.ptr(self.offsets), LB.ptr(slates),
+                                                     LB.ptr(pick_row), LB.ptr(picks), 0 if picks is None else int(picks.shape[0]), B, L,
+                                                     self.n_features, LB.ptr(xb), LB.ptr(yb), LB.ptr(idx), LB.stream_of(xb)),
+                 "assemble_batch_picked")
+        return xb, yb, idx
+
+    def batch_picked_torch(self, slates, slate_length, pick_row, picks=None):
+        """the batch of ``batch_picked`` through torch ops (tests; the counterpart of ``batch_torch``)"""
+        L = int(slate_length)
+        slates, pick_row, picks = self._picked_args(slates, pick_row, picks)
+        if slates.numel() == 0:
+            return self._empty_batch(L)
+        lens = self.lengths[slates][:, None]
+        pos = torch.arange(L, device=self.device)[None, :].expand(slates.numel(), L)
+        if picks is not None:
+            known = (pick_row >= 0) & (pick_row < picks.shape[0])
+            taken = picks[pick_row.long().clamp(0, picks.shape[0] - 1)].to(torch.int64)
+            pos = torch.where(known[:, None], taken, torch.where(pick_row[:, None] < 0, pos, torch.full_like(pos, -1)))
+        else:
+            pos = torch.where(pick_row[:, None] < 0, pos, torch.full_like(pos, -1))
+        valid = (pos >= 0) & (pos < lens)
+        item = torch.where(valid, self.offsets[slates][:, None] + pos, torch.zeros_like(pos))
+        xb = self.x_items[item] * valid[:, :, None]
+        yb = torch.where(valid, self.y_items[item], torch.full((), float(PADDED_Y_VALUE), device=self.device))
+        idx = torch.where(valid, pos, torch.full_like(pos, PADDED_INDEX_VALUE))
         return xb, yb, idx
 
     def batch_torch(self, slates, slate_length, generator=None):
@@ -290,13 +398,14 @@ class DeviceLibSVMDataset(object):
     slate for every other role (:212-227).  ``shape`` / ``longest_query_length`` / ``len()`` / indexing keep the reference's meaning
     (main.py:63-64 reads ``shape[-1]``); an item is the transformed slate ``(x [L, F], y [L], indices [L])`` -- on the device."""
 
-    def __init__(self, slates, slate_length=None):
+    def __init__(self, slates, slate_length=None, sampling="device"):
         self.slates = slates
         self.slate_length = int(slates.longest_query_length if slate_length is None else slate_length)
+        self.sampling = sampling_mode(sampling)          # how ``ds[i]`` samples a long slate (DeviceLoader has its own switch)
 
     @classmethod
-    def from_svm_file(cls, svm_file_path, slate_length=None, device="cuda", parser="device"):
-        return cls(DeviceSlates.from_svm_file(svm_file_path, device=device, parser=parser), slate_length)
+    def from_svm_file(cls, svm_file_path, slate_length=None, device="cuda", parser="device", sampling="device"):
+        return cls(DeviceSlates.from_svm_file(svm_file_path, device=device, parser=parser), slate_length, sampling)
 
     def __len__(self):
         return self.slates.n_slates
@@ -315,6 +424,13 @@ class DeviceLibSVMDataset(object):
         return self.slates.longest_query_length >= self.slate_length
 
     def __getitem__(self, idx):
+        if self.sampling == "reference":                 # FixLength draws from numpy's global generator (dataset_loading.py:70)
+            L, dev = self.slate_length, self.slates.device
+            y = self.slates.host_labels(L).get(int(idx))
+            picks = None if y is None else torch.from_numpy(reference_picks(y, L, np.random).astype(np.int32))[None, :]
+            xb, yb, ib = self.slates.batch_picked(torch.tensor([int(idx)], device=dev), L,
+                                                  torch.tensor([-1 if y is None else 0], dtype=torch.int32, device=dev), picks)
+            return xb[0], yb[0], ib[0]
         xb, yb, ib = self.slates.batch(torch.tensor([int(idx)], device=self.slates.device), self.slate_length,
                                        seed=int(np.random.randint(0, 2 ** 31 - 1)) if self.samples else 0)
         return xb[0], yb[0], ib[0]
@@ -330,17 +446,29 @@ class DeviceLoader(object):
       resulting permutation are the reference loader's: under main.py:36-38's seeds epoch e visits the same slates in the same
       batches in the same order.  ``burn()`` consumes the draws of one iteration without running it (``allrank_amd.fit`` skips the
       reference's extra passes over the loaders, train_utils.py:99,107, and keeps the generator in step this way).
-    * FixLength: the padding branch is exact.  The sampling branch (slates of >= L items, :61-79) is keyed by one seed per
-      iteration -- drawn from numpy's global generator, the generator the reference samples from (:70) -- and the slate id.
+    * FixLength: the padding branch is exact.  The sampling branch (slates of >= L items, :61-79) depends on ``sampling``:
+      - ``"device"`` (default): drawn on the device (``ltrx_fixlength_positions``), keyed by one seed per iteration -- taken from
+        numpy's global generator, the generator the reference samples from (:70) -- and the slate id: the reference's distribution,
+        not its items.  ``num_workers`` is ignored.
+      - ``"reference"``: the reference's own draws, made on the host batch by batch as each batch is requested (labels only; a few
+        KB of picks are uploaded per batch and ``ltrx_assemble_batch_picked`` assembles the batch in one launch): the same items,
+        ``indices`` and generator states as the reference's ``DataLoader(num_workers=W)``.  ``W == 0``: item by item, in batch order,
+        from numpy's global generator.  ``W >= 1``: batch k is made by worker k % W, whose numpy generator torch's worker loop
+        seeded with ``_generate_state(base_seed, worker)``; numpy's global generator is not touched.  A non-training role is
+        padded to its longest slate, so its longest slate(s) are "sampled" (permuted) too and consume draws in every pass.
+        ``burn()`` and ``id_batches()`` leave both global generators where a full pass of the reference's loader leaves them
+        (``W == 0``: the pass's numpy draws are made and discarded); ``id_batches()`` keeps the stored item order.
     * ``world`` > 1: this rank yields its contiguous block (``parallel.shard_slates``, the rule of DataParallel.scatter) of each
-      global batch as a ``ShardBatch``; nothing of the other ranks' blocks is assembled.  ``batch_size`` stays the GLOBAL size."""
+      global batch as a ``ShardBatch``; nothing of the other ranks' blocks is assembled.  ``batch_size`` stays the GLOBAL size.
+      Under ``"reference"`` every rank makes the draws of the whole global batch (the generator stream is shared)."""
 
-    def __init__(self, dataset, batch_size, shuffle=False, rank=0, world=1):
+    def __init__(self, dataset, batch_size, shuffle=False, rank=0, world=1, sampling="device", num_workers=0):
         from torch.utils.data import DataLoader
         self.dataset, self.batch_size, self.shuffle = dataset, int(batch_size), bool(shuffle)
         self.rank, self.world = int(rank), max(1, int(world))
         self.drop_last = False
-        self.num_workers = 0
+        self.sampling = sampling_mode(sampling)
+        self.num_workers = max(0, int(num_workers)) if self.sampling == "reference" else 0
         self._ids = DataLoader(_SlateIds(len(dataset)), batch_size=self.batch_size, shuffle=self.shuffle, num_workers=0)
         self.sampler = self._ids.sampler
 
@@ -349,8 +477,42 @@ class DeviceLoader(object):
     def __len__(self):
         return len(self._ids)
 
+    def _pass(self):
+        """start one pass: (slate ids of every global batch as host int64 tensors, the numpy generator that makes batch k's draws).
+        All of the pass's draws from torch's global generator (worker base seed, RandomSampler seed) happen here, as in ``iter`` of
+        the reference's loader."""
+        it = iter(self._ids)
+        chunks = [c.to(torch.int64) for c in it]
+        if self.num_workers == 0:
+            return chunks, lambda k: np.random
+        from torch.utils.data._utils.worker import _generate_state
+        workers = [np.random.RandomState(_generate_state(it._base_seed, w)) for w in range(self.num_workers)]
+        return chunks, lambda k: workers[k % self.num_workers]
+
+    def _draw(self, ids, rng, labels, keep=None):
+        """the reference's draws for one global batch, item by item in batch order; ``keep`` = (a, b): also return (pick_row i32[b-a],
+        picks i32[n, L]) of that block of rows"""
+        L = self.dataset.slate_length
+        rows, picks = [], []
+        for j, s in enumerate(ids.tolist()):
+            y = labels.get(s)
+            pick = reference_picks(y, L, rng) if y is not None else None
+            if keep is not None and keep[0] <= j < keep[1]:
+                rows.append(-1 if pick is None else len(picks))
+                if pick is not None:
+                    picks.append(pick)
+        if keep is None:
+            return None
+        return np.asarray(rows, dtype=np.int32), (np.stack(picks).astype(np.int32) if picks else np.zeros((0, L), dtype=np.int32))
+
     def burn(self):
-        """consume what ONE iteration over the reference's loader draws from torch's global generator, without assembling a batch"""
+        """consume what ONE iteration over the reference's loader draws from the global generators, without assembling a batch"""
+        if self.sampling == "reference" and self.num_workers == 0 and self.dataset.samples:
+            chunks, rng = self._pass()
+            labels = self.dataset.slates.host_labels(self.dataset.slate_length)
+            for k, c in enumerate(chunks):
+                self._draw(c, rng(k), labels)
+            return
         next(iter(self._ids), None)
 
     def batch_shape(self):
@@ -372,18 +534,58 @@ class DeviceLoader(object):
         order (the padding branch of FixLength)."""
         from .parallel import shard_slates
         ds, L = self.dataset, self.dataset.slate_length
-        chunks = [c.to(torch.int64) for c in self._ids]                # the epoch's draws from torch's global generator, as __iter__
-        if ds.samples:
-            np.random.randint(0, 2 ** 31 - 1)                          # ... and the sampling seed __iter__ draws from numpy's
+        if self.sampling == "reference":
+            chunks, rng = self._pass()
+            labels = ds.slates.host_labels(L) if (ds.samples and self.num_workers == 0) else None
+        else:
+            chunks, labels = [c.to(torch.int64) for c in self._ids], None   # the epoch's draws from torch's global generator, as __iter__
+            if ds.samples:
+                np.random.randint(0, 2 ** 31 - 1)                          # ... and the sampling seed __iter__ draws from numpy's
         weights = torch.arange(1, self.batch_size + 1, dtype=torch.int64)
-        for c in chunks:
+        for k, c in enumerate(chunks):
             n = int(c.numel())
             a, b = shard_slates(n, self.rank, self.world)
+            if labels:
+                self._draw(c, rng(k), labels)                              # made where __iter__ makes them, and discarded
             tag = int((c * weights[:n]).sum().item()) & 0x7FFFFFFFFFFF
             yield SlateIds(ds.slates, c[a:b], ds.slates.lengths_host[c[a:b]].clamp(max=L), n, a, tag)
 
+    def _upload_picks(self, rows, picks):
+        """(pick_row i32[B], picks i32[n, L] or None) on the device: one small copy per batch, from pinned memory on a GPU so that the
+        host never waits for the step in flight"""
+        dev = self.dataset.slates.device
+        nb = int(rows.size)
+        host = torch.empty(nb + int(picks.size), dtype=torch.int32, pin_memory=dev.type == "cuda")
+        host[:nb] = torch.from_numpy(rows)
+        host[nb:] = torch.from_numpy(picks.reshape(-1))
+        buf = host.to(dev, non_blocking=True)
+        return buf[:nb], (buf[nb:].view(picks.shape) if picks.size else None)
+
+    def _iter_reference(self):
+        from .parallel import shard_slates
+        ds, L = self.dataset, self.dataset.slate_length
+        chunks, rng = self._pass()
+        if not chunks:
+            return
+        labels = ds.slates.host_labels(L) if ds.samples else {}
+        order = torch.cat(chunks).to(ds.slates.device)                 # ONE small upload per epoch (8 B per slate)
+        start = 0
+        weights = torch.arange(1, self.batch_size + 1, dtype=torch.int64)
+        for k, c in enumerate(chunks):
+            n = int(c.numel())
+            a, b = shard_slates(n, self.rank, self.world)
+            rows, picks = self._draw(c, rng(k), labels, keep=(a, b))    # the whole global batch's draws; this rank's block kept
+            pick_row, picks = self._upload_picks(rows, picks)
+            xb, yb, ib = ds.slates.batch_picked(order[start + a:start + b], L, pick_row, picks)
+            tag = int((c * weights[:n]).sum().item()) & 0x7FFFFFFFFFFF
+            start += n
+            yield ShardBatch((xb, yb, ib), n, a, tag, ds.slates.lengths_host[c[a:b]].clamp(max=L))
+
     def __iter__(self):
         from .parallel import shard_slates
+        if self.sampling == "reference":
+            yield from self._iter_reference()
+            return
         ds, L = self.dataset, self.dataset.slate_length
         chunks = [c.to(torch.int64) for c in self._ids]                # host tensors; all of the epoch's generator draws happen here
         seed = int(np.random.randint(0, 2 ** 31 - 1)) if ds.samples else 0
@@ -408,7 +610,7 @@ def _local_path(input_path, role):
 
 def load_libsvm_role(input_path, role, device=None):
     """dataset_loading.py:168-182 (``{input_path}/{role}.txt`` -> dataset, no transform yet = padded to its longest slate): the
-    file's bytes go to the GPU once and are parsed there."""
+    file's bytes go to the GPU once and are parsed there.  ``ds[i]`` samples as ALLRANK_AMD_SAMPLING says."""
     from .launch import get_torch_device
     dev = torch.device(device) if device is not None else get_torch_device()
     path = _local_path(input_path, role)
@@ -416,7 +618,7 @@ def load_libsvm_role(input_path, role, device=None):
         raise NotImplementedError("allrank_amd.data: %s is a GCS path -- copy the files to local storage (the device-resident loader "
                                   "reads local files; the reference's GCS helper, utils/file_utils.py, is out of scope)" % path)
     log.info("will load %s data from %s", role, path)
-    ds = DeviceLibSVMDataset.from_svm_file(path, None, device=dev)
+    ds = DeviceLibSVMDataset.from_svm_file(path, None, device=dev, sampling=sampling_mode())
     log.info("%s DS shape: %s (resident on %s)", role, ds.shape, dev)
     return ds
 
@@ -453,9 +655,11 @@ def create_data_loaders(train_ds, val_ds, num_workers, batch_size):
     """dataset_loading.py:230-248: train loader shuffled, validation loader not, drop_last False, both with ``units x batch_size``
     slates per GLOBAL batch (":240-241: multiplying the batch size by the processing units count").  The processing units are the
     ranks of the process group when one is up (one process per GPU, ``allrank_amd.launch``), else the visible GPUs as in the
-    reference.  DeviceLibSVMDataset -> DeviceLoader (``num_workers`` is meaningless there: no host work per batch); any other
-    dataset -> the reference's torch DataLoader."""
+    reference.  DeviceLibSVMDataset -> DeviceLoader; any other dataset -> the reference's torch DataLoader.  The environment variable
+    ALLRANK_AMD_SAMPLING (``device``, the default, or ``reference``; main.py can pass nothing else) selects the DeviceLoader's sampling
+    mode; ``num_workers`` only matters under ``reference``, where it decides which generator stream the reference's draws come from."""
     from torch.utils.data import DataLoader
+    mode = sampling_mode()
     rank, world = processing_units()
     units = world if world > 1 else max(1, torch.cuda.device_count())
     total = units * int(batch_size)
@@ -463,7 +667,7 @@ def create_data_loaders(train_ds, val_ds, num_workers, batch_size):
     out = []
     for ds, shuffle in ((train_ds, True), (val_ds, False)):
         if isinstance(ds, DeviceLibSVMDataset):
-            out.append(DeviceLoader(ds, total, shuffle=shuffle, rank=rank, world=world))
+            out.append(DeviceLoader(ds, total, shuffle=shuffle, rank=rank, world=world, sampling=mode, num_workers=num_workers))
         else:
             out.append(DataLoader(ds, batch_size=total, num_workers=num_workers, shuffle=shuffle))
     return out[0], out[1]

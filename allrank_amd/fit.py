@@ -57,7 +57,8 @@ from .parallel import shard_slates
 
 log = logging.getLogger("allrank_amd.fit")
 
-last_run = {}          # what the most recent fit() used: {"engine": "fused" | "autograd", "compact": bool, "reason": str}
+last_run = {}          # what the most recent fit() used: {"engine": "fused" | "autograd", "compact": bool, "reason": str,
+#                        "sampling": the training DeviceLoader's mode ("device" | "reference"; None for any other loader), ...}
 
 
 class _EarlyStop(object):
@@ -433,7 +434,7 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
         trainer = Trainer(model, loss_func, optimizer, gradient_clipping_norm, world, None)
     last_run.clear()
     last_run.update(engine="fused" if fused else "autograd", compact=bool(trainer.compact) if fused else False, reason=reason,
-                    fcstep=getattr(trainer, "fcstep", False))
+                    fcstep=getattr(trainer, "fcstep", False), sampling=getattr(train_dl, "sampling", None))
     log.info("allrank_amd.fit: %s step%s", last_run["engine"], (" (" + reason + ")") if reason else "")
     vs_reason = _packed_blocker(loss_func, fused, reason) if val_scorer_mode == "packed" else ""
     scorers = {} if val_scorer_mode == "packed" and not vs_reason else None

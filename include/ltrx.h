@@ -518,11 +518,19 @@ int ltrx_fc_linear_listnet_step(const float* x, const float* y, int B, int L, in
  *       batch or batch row it arrives in (a rank assembling only its block of a global batch == the one-rank run);
  *       max_slate_len <= 12288.
  *   ltrx_assemble_batch: xb[B,L,F], yb[B,L] (-1 on padding), indices[B,L] (= positions) from the CSR arrays (ToTensor +
- *       collate, :19-29). */
+ *       collate, :19-29).
+ *   ltrx_assemble_batch_picked: the same outputs in ONE launch from positions chosen on the host (the reference's own
+ *       np.random.choice draws; no [B,L] positions tensor in HBM).  Row b with pick_row[b] >= 0 takes position
+ *       picks[pick_row[b]][l] for slot l; a row with pick_row[b] < 0 keeps its stored order, l < len ? l : -1 (the first L items of
+ *       a slate of >= L items).  A position outside [0, len), or a pick_row >= n_pick_rows, is padding (features 0, label -1,
+ *       index -1): nothing outside the slate is read.  picks may be NULL only with n_pick_rows == 0.  Slates of any length. */
 int ltrx_fixlength_positions(const int64_t* offsets, const float* y_items, const int64_t* slates, int B, int L, int max_slate_len,
                              uint64_t seed, int64_t* positions, ltrx_stream_t stream);
 int ltrx_assemble_batch(const float* x_items, const float* y_items, const int64_t* offsets, const int64_t* slates,
                         const int64_t* positions, int B, int L, int F, float* xb, float* yb, int64_t* indices, ltrx_stream_t stream);
+int ltrx_assemble_batch_picked(const float* x_items, const float* y_items, const int64_t* offsets, const int64_t* slates,
+                               const int32_t* pick_row, const int32_t* picks, int n_pick_rows, int B, int L, int F, float* xb, float* yb,
+                               int64_t* indices, ltrx_stream_t stream);
 
 /* libsvm / SVMlight text parsed on the device (the reference: sklearn's load_svmlight_file on the host, dataset_loading.py:130).
  * text = the file's bytes in device memory, line_start[n_lines] = byte offset of every line.  One thread per line.
