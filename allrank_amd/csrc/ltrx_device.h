@@ -151,14 +151,19 @@ struct DropSpec {
   uint32_t thresh;     // drop iff (hash >> 8) < thresh,  thresh = p * 2^24  (0 = dropout off)
   float inv_keep;
 };
-__device__ __forceinline__ float drop_keep_scale(const DropSpec& d, uint64_t idx) {
-  uint32_t x = (uint32_t)idx ^ ((uint32_t)(idx >> 32) * 0x9E3779B9u) ^ d.seed;
+// the generator itself: 32 hashed bits of element `idx` under `seed` (its top 24 bits are what the sites consume: the dropout
+// decision below, the uniform draw of the stochastic NeuralSort noise in ltrx_neuralsort_stoch.hip)
+__device__ __forceinline__ uint32_t counter_hash(uint32_t seed, uint64_t idx) {
+  uint32_t x = (uint32_t)idx ^ ((uint32_t)(idx >> 32) * 0x9E3779B9u) ^ seed;
   x ^= x >> 16;
   x *= 0x85EBCA6Bu;
   x ^= x >> 13;
   x *= 0xC2B2AE35u;
   x ^= x >> 16;
-  return ((x >> 8) >= d.thresh) ? d.inv_keep : 0.f;
+  return x;
+}
+__device__ __forceinline__ float drop_keep_scale(const DropSpec& d, uint64_t idx) {
+  return ((counter_hash(d.seed, idx) >> 8) >= d.thresh) ? d.inv_keep : 0.f;
 }
 
 }  // namespace ltrx

@@ -237,6 +237,10 @@ class FusedTrainer(object):
       ReLU+dropout, the residual sum in the epilogue of the projection that closes a sublayer, the attention probabilities)
       and REGENERATED in the backward
       -- no mask tensors, and a replayed hipGraph draws fresh masks because the step word lives in device memory.
+    * every loss of allrank_amd.losses with every argument, ``stochastic=True`` of neuralNDCG / neuralNDCG_transposed included: its
+      Gumbel noise is one more site of the same generator (FusedLoss; the last draw stays in ``self.loss.gumbel``).  Such a job
+      runs on the padded grid (``compact`` is dropped: the batch-wide minimum reads the scores of padded slots) and on one
+      rank (sharded: NotImplementedError -- a global minimum and tie count would take two more collectives per step).
     Supported model family: FCModel (optional input_norm = nn.LayerNorm, activation None / ReLU, or Sigmoid / Tanh without FC
     dropout) -> optional encoder with
     optional fixed / learned positional encoding (positional.py:15-77) -> OutputLayer(any d_output, activation None / Sigmoid /
@@ -319,6 +323,10 @@ class FusedTrainer(object):
         # ``force_dist`` asks for it on a one-rank group: the whole collective path, RCCL included, on the one GPU a build box has
         # (bench.py --force-dist, tests/test_gpu_rccl.py).  Needs an initialised process group.
         self.sharded = bool(world_size > 1 or force_dist)
+        stoch = loss_name in ("neuralNDCG", "neuralNDCG_transposed") and bool((loss_args or {}).get("stochastic"))
+        if stoch and self.sharded:
+            raise NotImplementedError("FusedTrainer: stochastic NeuralNDCG under slate sharding -- the batch-wide minimum of the scores and "
+                                      "its tie count (loss_utils.py:102) would take two more collectives per step")
         self.clip = float(gradient_clipping_norm) if gradient_clipping_norm else None
         seed = self._read_model(model, dropout, seed)
         # final norm + score head fused: an encoder, one output unit, a register-resident width (D = 256 NV <= 1024), and the deferred
@@ -341,6 +349,13 @@ class FusedTrainer(object):
                     "compact=%s / use_graph=%s do not apply to it; scores / labels of the last step alias the caller's tensors until the "
                     "next step()", compact, use_graph)
             compact = False
+        # stochastic NeuralNDCG takes its minimum over the padded slots' scores too (loss_utils.py:102): the packed step computes no
+        # score there (it leaves 0), so the step stays on the padded grid
+        if stoch and compact:
+            logging.getLogger("allrank_amd.engine").info(
+                "FusedTrainer: stochastic NeuralNDCG reads the scores of padded slots (batch-wide minimum): compact=%s does not apply "
+                "to it", compact)
+            compact = False
         # forward buffers (the trainer is its own buffer set).  Input rows are padded to a multiple of 256 floats where the first FC
         # layer can then run the large-tile GEMMs: the forward projection contracts over F rounded up to the kernel's 32-column step
         # against a row-padded copy of W_0 (refreshed with the weight images), the weight gradient reads the padded rows as tiles.
@@ -356,6 +371,8 @@ class FusedTrainer(object):
         if self.gemm != "hipblaslt":
             self._init_weight_images()
         self.loss = FusedLoss(loss_name, B, L, self.dev, **(loss_args or {}))
+        if self.loss.stochastic:                              # Gumbel noise: a site of the step's generator, re-keyed by drop_step
+            self.loss.set_noise_key(self._site(2000), self.drop_step)
         if (self.n_out > 1) != (loss_name == "ordinal") or (loss_name == "ordinal" and int(loss_args["n"]) != self.n_out):
             raise NotImplementedError("FusedTrainer: d_output > 1 goes with the ordinal loss of the same n (and only with it)")
         # ListMLE: the reference draws torch.randperm(L) on every call (listMLE.py:17).  shuffle_ties=True (default) does
@@ -666,7 +683,7 @@ class FusedTrainer(object):
         return dist.get_rank(group)
 
     def _site(self, k):
-        """seed of dropout site k (one per nn.Dropout instance of the model)"""
+        """seed of site k of the step's generator (one per nn.Dropout instance of the model; 2000: the stochastic loss's noise)"""
         x = (self._seed ^ ((k + 1) * 0x85EBCA6B)) & 0xFFFFFFFF
         x = ((x ^ (x >> 16)) * 0x7FEB352D) & 0xFFFFFFFF
         x = ((x ^ (x >> 15)) * 0x846CA68B) & 0xFFFFFFFF
@@ -1182,8 +1199,8 @@ class FusedTrainer(object):
                       "adam_step")
 
     def _full(self):
-        if self._any_dropout:
-            self.LB.check(self.lib.ltrx_bump_u32(self.LB.ptr(self.drop_step), self._st()), "bump_u32")   # fresh masks every step
+        if self._any_dropout or self.loss.stochastic:
+            self.LB.check(self.lib.ltrx_bump_u32(self.LB.ptr(self.drop_step), self._st()), "bump_u32")   # fresh masks / noise every step
         loss = self._body()
         self._wait_buckets()
         self._adam()

@@ -406,7 +406,13 @@ def binary_listNet(y_pred, y_true, eps=DEFAULT_EPS, padded_value_indicator=PADDE
 # no allocation and no autograd node in run() -> capturable in a hipGraph.
 # ----------------------------------------------------------------------------------------------------------------
 class FusedLoss(object):
-    """``run(scores[B,L], y[B,L], batch_divisor)`` -> (loss[1], dloss/dscores[B,L]) on persistent device buffers."""
+    """``run(scores[B,L], y[B,L], batch_divisor)`` -> (loss[1], dloss/dscores[B,L]) on persistent device buffers.
+
+    ``neuralNDCG`` / ``neuralNDCG_transposed`` with ``stochastic=True`` run here too: ltrx_neuralndcg_prepare on the B slates,
+    ltrx_neuralsort_perturb (batch-wide minimum, Gumbel draw, the n_samples * B perturbed pseudo slates with their labels, cut-offs and
+    ideal DCGs), ltrx_neuralndcg_fwd_bwd over the pseudo slates, ltrx_neuralsort_fold_grad back onto [B, L].  The noise is a pure
+    function of (``set_noise_key``'s seed, its device step word, element index) -- the engine's counter-based generator, not
+    torch's -- and the draw of the last ``run`` stays readable in ``self.gumbel`` [n_samples, B, L]."""
 
     def __init__(self, name, B, SL, device, **args):
         if name not in _LOSSES:
@@ -419,18 +425,69 @@ class FusedLoss(object):
         self.args = a = dict(a, **fixed)
         if name == "lambdaLoss":
             _check_lambdaloss(a)
-        if a.get("stochastic"):
-            raise NotImplementedError("stochastic NeuralSort draws fresh noise per step: use the autograd Trainer")
+        self.stochastic = bool(a.get("stochastic"))
         self.pad, self.eps = float(a["padded_value_indicator"]), float(a.get("eps", DEFAULT_EPS))
         self.bufs = _buffers(self.fam, B, SL, device, a, torch.zeros)
         if self.fam is _LISTMLE:
             self.bufs["perm"] = self.perm = torch.arange(SL, dtype=torch.int64, device=device)
         self.loss, self.ws = self.bufs["loss"], self.bufs["ws"]
         self.grad = torch.zeros((B, SL, int(a["n"])) if a.get("n") else (B, SL), dtype=torch.float32, device=device)
+        if self.stochastic:
+            self._init_stochastic(device)
+
+    def _init_stochastic(self, device):
+        """the persistent buffers of the stochastic form: everything per pseudo slate, the draw, and the S * B-slate workspace"""
+        a, B, SL = self.args, self.B, self.SL
+        S = self.S = int(a["n_samples"])
+        if S < 1:
+            raise ValueError("n_samples must be at least 1")
+
+        def new(*shape, dtype=torch.float32):
+            return torch.zeros(shape, dtype=dtype, device=device)
+        self.s_pert, self.y_ps, self.grad_ps = new(S * B, SL), new(S * B, SL), new(S * B, SL)
+        self.k_rows = new(S * B, dtype=torch.int32)
+        self.idcg_ps, self.cnt_ps, self.smin = new(S * B), new(1), new(2)
+        self.gumbel = new(S, B, SL)
+        self._gumbel_given = False
+        # the pseudo slates' Sinkhorn call: the transposed form pads under a private sentinel (its gains are the RAW labels)
+        self.args_ps = dict(a, padded_value_indicator=-1.0e30) if a["transposed"] else a
+        self.ws_ps = torch.empty(max(int(self.fam.ws_bytes(S * B, SL, a)), 64), dtype=torch.uint8, device=device)
+        self.ws_stoch = torch.empty(max(int(L.lib().ltrx_neuralsort_stoch_workspace_bytes(B, SL, S)), 64), dtype=torch.uint8, device=device)
+        self.set_noise_key(0, torch.zeros(1, dtype=torch.int32, device=device))
 
     def set_perm(self, perm):
         self.perm.copy_(perm.to(self.perm.device))
 
+    def set_gumbel(self, gumbel):
+        """tests: inject the Gumbel draw ([n_samples, B, L] or [n_samples, B, L, 1]) that ``run`` perturbs with instead of drawing;
+        None returns to the generator.  (A launch argument: a step captured before the call keeps what it was captured with.)"""
+        self._gumbel_given = gumbel is not None
+        if gumbel is not None:
+            self.gumbel.copy_(gumbel.to(device=self.gumbel.device, dtype=torch.float32).reshape(self.gumbel.shape))
+
+    def set_noise_key(self, seed, step_word):
+        """the generator's key: ``seed`` (u32, by value) and ``step_word`` (int32 / u32 [1] on the device, read at every launch -- a
+        replayed hipGraph draws fresh noise when the word has moved), folded as the dropout sites fold theirs"""
+        self.noise_seed, self.noise_step = int(seed) & 0xFFFFFFFF, step_word
+
+    def _run_stochastic(self, yp, yt):
+        a, B, SL, S, lib, P = self.args, self.B, self.SL, self.S, L.lib(), L.ptr
+        st = L.stream_of(yp)
+        _neural_prepare(yt, a, self.bufs["idcg"], self.bufs["cnt"], self.ws)
+        given = self._gumbel_given
+        L.check(lib.ltrx_neuralsort_perturb(P(yp), P(yt), P(self.bufs["idcg"]), P(self.bufs["cnt"]), B, SL, S, self.pad, float(a["beta"]),
+                                            1 if a["log_scores"] else 0, 1 if a["transposed"] else 0, self.noise_seed,
+                                            P(self.noise_step), P(self.gumbel) if given else None, P(self.s_pert), P(self.y_ps),
+                                            P(self.k_rows), P(self.idcg_ps), P(self.cnt_ps), P(self.smin),
+                                            None if given else P(self.gumbel), P(self.ws_stoch), st), "neuralsort_perturb")
+        _launch_neuralndcg(self.s_pert, self.y_ps, self.args_ps, float(S * B), self.loss, self.grad_ps, self.ws_ps, self.idcg_ps,
+                           self.cnt_ps, k_rows=None if a["transposed"] else self.k_rows, prepared=True)
+        L.check(lib.ltrx_neuralsort_fold_grad(P(self.grad_ps), P(yp), P(self.smin), B, SL, S, 1 if a["log_scores"] else 0, P(self.grad),
+                                              P(self.ws_stoch), st), "neuralsort_fold_grad")
+
     def run(self, yp, yt, batch_divisor=None):
-        self.fam.launch(yp, yt, self.args, float(batch_divisor if batch_divisor is not None else self.B), grad=self.grad, **self.bufs)
+        if self.stochastic:
+            self._run_stochastic(yp, yt)
+        else:
+            self.fam.launch(yp, yt, self.args, float(batch_divisor if batch_divisor is not None else self.B), grad=self.grad, **self.bufs)
         return self.loss, self.grad

@@ -127,6 +127,36 @@ int ltrx_neuralndcg_fwd_bwd(const float* y_pred, const float* y_true, const floa
                             const int32_t* k_rows, int transposed, int max_iter, float tol, float* loss_out, float* per_slate_out,
                             float* grad_out, int32_t* iters_out, int path, void* ws, ltrx_stream_t stream);
 
+/* Stochastic NeuralSort around the two calls above (loss_utils.py:84-112, neuralNDCG.py:35-47,69): n_samples Gumbel-perturbed
+ * copies of every slate run through ltrx_neuralndcg_fwd_bwd as ONE batch of n_samples * B pseudo slates, pseudo slate
+ * i = sample * B + b holding the scores of slate b.
+ *   ltrx_neuralsort_perturb (after ltrx_neuralndcg_prepare on the B slates): m = min over ALL B * L scores, padded slots included
+ *           (:102); s_pos = s + |m|, log(s_pos + 1e-10) with log_scores (:104-105); s_pert[i] = s_pos[b] + beta * g[sample, b].
+ *           smin_out[2] = (m, number of elements equal to m).  The reference sorts pseudo slate i under the padding mask of slate
+ *           i / n_samples (mask.repeat_interleave, :108) and reads it out with the labels of slate i % B = b; y_ps carries that:
+ *           plain: pad_value where slate i / n_samples pads, else the label of slate b where that is valid, else 0, and
+ *           k_rows[i] = valid items of slate b; transposed (k_rows is not written): the raw label of slate b wherever slate
+ *           i / n_samples is valid, LTRX_NEURALSORT_PAD (-1e30, the pad_value of the following ltrx_neuralndcg_fwd_bwd call) where
+ *           it pads.  idcg_ps[i] = idcg[b]; cnt_ps[0] = nonzero_count[0] * n_samples (neuralNDCG.py:69).
+ *           Noise: gumbel_in[n_samples,B,L] (optional) is used as given; without it g = -logf(-logf(U + 1e-10) + 1e-10)
+ *           (loss_utils.py:70-81) with U = (hash >> 8) * 2^-24, hash = the dropout sites' counter hash of element
+ *           (sample * B + b) * L + l under seed ^ (seed_step[0] * 0x9E3779B9) -- a replayed hipGraph draws fresh noise whenever
+ *           the device word seed_step[0] (optional) has moved.  gumbel_out[n_samples,B,L] (optional) receives the noise used.
+ *   ltrx_neuralsort_fold_grad (after ltrx_neuralndcg_fwd_bwd wrote grad_ps[n_samples*B,L]): gs[b,l] = w[b,l] sum_sample
+ *           grad_ps[sample*B+b,l], w = 1 / (s + |m| + 1e-10) with log_scores, else 1; grad_out = gs, and every element with
+ *           s == m also gets sign(m) * sum(gs) / smin[1] -- the path through |min(s)|, spread evenly over tied minima as
+ *           torch's min() backward does; sign(0) = 0.
+ * Both reductions (m with its tie count, sum(gs)) are two-stage and fixed-order: the same inputs and step word give the same
+ * bits on every call.  L > LTRX_MAX_SLATE_LEN is unsupported, as for ltrx_neuralndcg_*. */
+#define LTRX_NEURALSORT_PAD (-1.0e30f)
+size_t ltrx_neuralsort_stoch_workspace_bytes(int B, int L, int n_samples);
+int ltrx_neuralsort_perturb(const float* scores, const float* y_true, const float* idcg, const float* nonzero_count, int B, int L,
+                            int n_samples, float pad_value, float beta, int log_scores, int transposed, uint32_t seed,
+                            const uint32_t* seed_step, const float* gumbel_in, float* s_pert, float* y_ps, int32_t* k_rows,
+                            float* idcg_ps, float* cnt_ps, float* smin_out, float* gumbel_out, void* ws, ltrx_stream_t stream);
+int ltrx_neuralsort_fold_grad(const float* grad_ps, const float* scores, const float* smin, int B, int L, int n_samples,
+                              int log_scores, float* grad_out, void* ws, ltrx_stream_t stream);
+
 /* allrank/models/metrics.py:7-77   ndcg(y_pred, y_true, ats, gain=2^x-1, padding_indicator, filler_value)
  * ats[n_ats] is a HOST array.  ndcg_out[B,n_ats]; dcg_out[B,n_ats] optional; order_out[B,L] (int64, optional)
  * = stable descending argsort of the masked predictions (padded slots last, in original order). */
