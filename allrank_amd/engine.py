@@ -8,6 +8,7 @@ the device; call ``.item()`` when you want it), gradients live in one flat buffe
 ``world_size > 1`` the loss is normalised by the global batch and gradients are summed over RCCL.
 """
 import collections
+import contextlib
 import ctypes
 import logging
 import warnings
@@ -170,37 +171,62 @@ class _Stager(object):
 
 
 class _GraphLRU(object):
-    """The forward-graph rule: a key runs eagerly on its first two visits (warm-up outside capture: lazy module loads, kernel
-    attributes), is captured in a hipGraph on the third and replayed afterwards.  The captures form an LRU of ``max_graphs`` keys
-    (``graphs``: least recently used first); a new key beyond that evicts the oldest (``evictions`` counts them)."""
+    """The capture-and-replay rule of every hipGraph the engine records (training step, ``score()``, the scorer's row buckets): two
+    eager warm-up visits stay outside any capture (lazy module loads, kernel attributes, workspaces), then a key is captured --
+    a list of ``(hipGraph, host action | None)`` segments, recording only -- and replayed: each graph, then its action.  The captures
+    form an LRU of ``max_graphs`` keys (``graphs``: least recently used first; emptying it is how captures are dropped); a new key
+    beyond that first evicts the oldest (``evictions`` counts them, ``on_evict(key)`` hears of each)."""
 
-    def __init__(self, max_graphs, own_pool=False):
+    def __init__(self, max_graphs, capture=None, warm="key", on_evict=lambda key: None, new_pool=None):
+        # (nothing of torch.cuda is touched before the default ``capture`` or ``new_pool`` runs: a fake of either drives this on a CPU)
         self.graphs, self._visits = collections.OrderedDict(), collections.Counter()
-        self.max_graphs, self.evictions = int(max_graphs), 0
-        self._own_pool, self._pool = own_pool, None
+        self.max_graphs, self.evictions, self._on_evict = int(max_graphs), 0, on_evict
+        # capture(fn): records ``fn`` into ``self.pool`` and returns the segments; default: one torch.cuda.graph
+        self._capture = capture or self._record
+        # warm: what the two warm-up visits are counted over --
+        #   "key":   each key.  The forward users: a new row bucket can select kernels that were never launched, and a first launch
+        #            (module load, kernel attributes) must stay outside a capture.
+        #   "cache": the whole cache, once.  The training step: a new batch divisor changes only a by-value scalar of launches that
+        #            have all been made before, so every later key is captured on its first visit.
+        self._slot = {"key": lambda key: key, "cache": lambda key: None}[warm]
+        # new_pool(): the memory-pool handle the captures share (None: every capture gets a private pool of the default kind).  A
+        # pool whose graphs are all gone cannot be captured into again, so capture_now starts a fresh one whenever ``graphs`` is
+        # empty -- however it got empty: a caller's ``graphs.clear()`` (set_lr, bench.py), an eviction with max_graphs = 1.
+        self._new_pool, self.pool = new_pool, None
+
+    def _record(self, fn):
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, pool=self.pool):
+            fn()
+        return [(g, None)]
+
+    def capture_now(self, key, fn=None):
+        """record ``key`` unless it is live -- nothing executes; False (and nothing recorded) while its warm-up is not over"""
+        if key in self.graphs:
+            return True
+        if self._visits[self._slot(key)] < 2:
+            return False
+        while len(self.graphs) >= self.max_graphs:
+            self.evictions += 1
+            self._on_evict(self.graphs.popitem(last=False)[0])
+        if not self.graphs and self._new_pool is not None:
+            self.pool = self._new_pool()
+        self.graphs[key] = self._capture(fn)                  # (a capture that raises leaves no entry)
+        return True
 
     def run(self, key, fn):
         """run, capture and replay, or replay ``fn`` for ``key``; returns "eager", "capture" or "replay" """
-        g = self.graphs.get(key)
-        if g is not None:
-            self.graphs.move_to_end(key)
-            g.replay()
-            return "replay"
-        self._visits[key] += 1
-        if self._visits[key] <= 2:
+        mode = "replay" if key in self.graphs else "capture"
+        if not self.capture_now(key, fn):
+            self._visits[self._slot(key)] += 1
             fn()
             return "eager"
-        if len(self.graphs) >= self.max_graphs:
-            self.graphs.popitem(last=False)
-            self.evictions += 1
-        if self._own_pool and self._pool is None:
-            self._pool = torch.cuda.graph_pool_handle()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, pool=self._pool):
-            fn()
-        self.graphs[key] = g
-        g.replay()
-        return "capture"
+        self.graphs.move_to_end(key)
+        for g, after in self.graphs[key]:                     # (capture only records: the replay executes this visit)
+            g.replay()
+            if after is not None:
+                after()
+        return mode
 
 
 def pad_batch(xb, yb, idx, B):
@@ -386,14 +412,19 @@ class FusedTrainer(object):
         self.probe = None                                     # list collecting (start, end) events of the FFN1 GEMM (eager steps only)
         self.probe_wgrad = None                               # ... of the grouped weight-gradient launch (bench.py, eager steps only)
         # captured steps: {(batch divisor, collectives on?): [(hipGraph segment, collective to launch after it | None), ...]}
-        self._graphs = collections.OrderedDict()
+        # The batch divisor is a by-value launch argument of the loss kernels (include/ltrx.h: `batch_divisor`), i.e. a captured
+        # step keeps the divisor it was captured with.  Captured steps are therefore keyed by the divisor: the short last batch of
+        # an epoch (DataLoader drop_last=False, dataset_loading.py:245; it arrives topped up with padded slates and global_batch =
+        # its real slate count) gets its own capture.  The captures form an LRU of ``max_graphs`` (4) entries: a fifth distinct
+        # divisor evicts the least recently used one (and says so once) instead of silently running eagerly (VERDICT r3 item 7).
         self.max_graphs = 4
-        self._warned_evict = False
-        self.capture_fallback = None                          # repr of the capture error if a sharded run fell back to eager steps
+        self._step_graphs = _GraphLRU(self.max_graphs, capture=lambda fn: self._capture(), warm="cache", on_evict=self._warn_evicted,
+                                      new_pool=torch.cuda.graph_pool_handle)
+        self._graphs = self._step_graphs.graphs               # (live mapping: least recently used first)
+        self.capture_fallback = None                          # why the step is not captured: the capture error after which a sharded
+        #                                                       run fell back to eager steps, or ensure_captured()'s "not warmed up"
         self._seg_break = None                                # set while capturing: ends the current segment (see _capture)
-        self._graph_pool = None
         self._cap_stream = None
-        self._warm = 0
         self._wver = [p._version for p in self._order]
         self._images_stale = False
         self.y_cur = self.y_in                                # labels of the last step() (the caller's tensor in the fcstep path)
@@ -1228,7 +1259,6 @@ class FusedTrainer(object):
         if float(lr) != float(self.lr):
             self.lr = float(lr)
             self._graphs.clear()
-            self._graph_pool = None      # (a pool whose graphs are all gone cannot be captured into again: fresh handle)
 
     def _pack(self, xb, lengths):
         """compact mode: build idx / cu_seqlens for this batch and gather the valid rows of xb into x_in.  ``lengths`` (host
@@ -1310,70 +1340,59 @@ class FusedTrainer(object):
             # listMLE.py:17: a fresh random column order per call breaks ties among equal labels at random; the
             # permutation lives in a persistent device buffer, so the refresh is safe under hipGraph replay
             self.loss.perm.copy_(torch.randperm(self.L, device=self.dev, generator=self._perm_gen))
-        self._divisor = float(global_batch if global_batch is not None else self.B * self.world)
+        key = self._key(global_batch)
+        self._divisor = key[0]
         self._stage_batch(xb, yb, indices, lengths, "step")
-        if not self.use_graph:
-            return self._eager()
-        # The batch divisor is a by-value launch argument of the loss kernels (include/ltrx.h: `batch_divisor`), i.e. a captured
-        # step keeps the divisor it was captured with.  Captured steps are therefore keyed by the divisor: the short last batch of
-        # an epoch (DataLoader drop_last=False, dataset_loading.py:245; it arrives topped up with padded slates and global_batch =
-        # its real slate count) gets its own capture.  The captures form an LRU of ``max_graphs`` (4) entries: a fifth distinct
-        # divisor evicts the least recently used one (and says so once) instead of silently running eagerly (VERDICT r3 item 7).
-        key = (self._divisor, bool(self.comm_enabled))
-        segs = self._graphs.get(key)
-        if segs is None:
-            if self._warm < 2:
-                self._warm += 1                       # warm-up outside capture (lazy module loads, kernel attributes, workspaces)
-                return self._eager()
-            if len(self._graphs) >= self.max_graphs:
-                old_key = next(iter(self._graphs))
-                del self._graphs[old_key]
-                if not self._warned_evict:
-                    self._warned_evict = True
-                    warnings.warn("allrank_amd: more than %d distinct batch divisors in flight -- evicting the least recently used captured "
-                                  "step (divisor %g); every new divisor costs one re-capture" % (self.max_graphs, old_key[0]))
-            try:
-                segs = self._graphs[key] = self._capture()
-            except RuntimeError as exc:
-                # sharded only, and only for errors of the capture mechanism itself (a collective backend that cannot live next to a
-                # stream capture): the eager step is the same arithmetic (tests/dist_equiv_worker.py), only with launch overhead.  Any
-                # other error -- a failed LB.check, a shape error, out of memory -- is a bug in the captured path and is raised.
-                msg = str(exc)
-                if not self.sharded or not any(t in msg for t in ("capture", "Capture", "hipErrorStreamCapture", "cudaErrorStreamCapture")):
-                    raise
-                warnings.warn("allrank_amd: hipGraph capture of the sharded step failed (%r); running eagerly" % (exc,))
-                self.capture_fallback = repr(exc)     # queryable: tests/dist_equiv_worker.py asserts it stays None
-                self.use_graph = False
-                self._graphs.clear()
-                return self._eager()
+        if self.use_graph:
+            self._captured(key)                                   # (a failed capture of a sharded step turns use_graph off for good)
+        if self.use_graph:
+            self._step_graphs.run(key, self._eager)               # warm-up step, or replay
         else:
-            self._graphs.move_to_end(key)
-        for g, after in segs:                         # (capture only records: the replay executes this step)
-            g.replay()
-            if after is not None:
-                after()
-        return self._graph_loss
+            self._eager()
+        return self.loss.loss
+
+    def _key(self, global_batch=None):                            # (batch divisor, collectives on?); None: a full batch on every rank
+        return float(global_batch if global_batch is not None else self.B * self.world), bool(self.comm_enabled)
+
+    def _captured(self, key):
+        """capture the step for ``key`` now unless it is live or the warm-up is not over (True: it is live); what a capture error means"""
+        try:
+            return self._step_graphs.capture_now(key)
+        except RuntimeError as exc:
+            # sharded only, and only for errors of the capture mechanism itself (a collective backend that cannot live next to a
+            # stream capture): the eager step is the same arithmetic (tests/dist_equiv_worker.py), only with launch overhead.  Any
+            # other error -- a failed LB.check, a shape error, out of memory -- is a bug in the captured path and is raised.
+            msg = str(exc)
+            if not self.sharded or not any(t in msg for t in ("capture", "Capture", "hipErrorStreamCapture", "cudaErrorStreamCapture")):
+                raise
+            warnings.warn("allrank_amd: hipGraph capture of the sharded step failed (%r); running eagerly" % (exc,))
+            self.capture_fallback = repr(exc)                     # queryable: tests/dist_equiv_worker.py asserts it stays None
+            self.use_graph = False
+            self._graphs.clear()
+            return False
+
+    def _warn_evicted(self, key):
+        if self._step_graphs.evictions == 1:                      # (say so once)
+            warnings.warn("allrank_amd: more than %d distinct batch divisors in flight -- evicting the least recently used captured "
+                          "step (divisor %g); every new divisor costs one re-capture" % (self.max_graphs, key[0]))
 
     def ensure_captured(self, global_batch=None):
         """Capture the step for this batch divisor NOW -- recording only: nothing executes and no collective is issued -- and say
         whether that worked.  For callers that must agree ACROSS RANKS on captured-vs-eager before any rank runs a step in either form
-        (bench.py): each rank calls this after its eager warm-up steps, the ranks all-reduce the answers, and a rank whose
-        peers could not capture switches to eager with them (``use_graph = False``).  A failed capture is closed before returning
-        (``_capture``) and its error kept in ``capture_fallback``.  (``step()`` itself also survives a capture failure of ONE rank:
-        the eager step issues the same collectives in the same order as a captured one.)"""
+        (bench.py): each rank calls this after its two eager warm-up steps, the ranks all-reduce the answers, and a rank
+        whose peers could not capture switches to eager with them (``use_graph = False``).  It follows ``step()``'s rule.  Before two
+        warm-up steps have run it records nothing, returns False and says so in ``capture_fallback`` (``use_graph`` stays on).  After
+        them it captures through the same LRU: a full cache evicts its least recently used divisor.  A capture that fails is closed
+        (``_capture``) and means what it means in ``step()`` (``_captured``): eager steps for good and False, or the error raised.
+        (``step()`` also survives a capture failure of ONE rank: eager and captured steps issue the same collectives in one order.)"""
         if not self.use_graph or self.fcstep:
             return True
-        self._divisor = float(global_batch if global_batch is not None else self.B * self.world)
-        key = (self._divisor, bool(self.comm_enabled))
-        if key in self._graphs:
-            return True
-        try:
-            self._graphs[key] = self._capture()
-            return True
-        except RuntimeError as exc:
-            self.capture_fallback = repr(exc)
-            self._graphs.pop(key, None)
-            return False
+        key = self._key(global_batch)
+        self._divisor = key[0]
+        ok = self._captured(key)
+        if not ok and self.use_graph:
+            self.capture_fallback = "ensure_captured: not captured -- the two eager warm-up steps have not run yet"
+        return ok
 
     def _fc_step(self, xb, yb, global_batch):
         """the slate-resident step (ltrx_fc_listnet_step): reads the caller's batch in place -- x once -- and leaves scores in
@@ -1396,7 +1415,7 @@ class FusedTrainer(object):
             yb = yb.float().contiguous()
         LB.require_device(xb, yb)
         self.y_cur = yb
-        div = float(global_batch if global_batch is not None else self.B * self.world)
+        div = self._key(global_batch)[0]
         fused_adam = not self.sharded and not self.clip
         hid = P(self.fc_out[0]) if self.keep_fc_out else None
         if fused_adam:
@@ -1419,14 +1438,17 @@ class FusedTrainer(object):
         self._images_stale = True                             # (score()'s GEMM forward reads the weight images: refresh them first)
         return self.loss.loss
 
+    def _shard(self, deferred=None):                              # the step's shard context; ``deferred``: see sharding.shard_context
+        return sharding.shard_context(int(self._divisor), self.group, deferred=deferred) if self.sharded else contextlib.nullcontext()
+
     def _eager(self):
-        with sharding.shard_context(int(self._divisor), self.group) if self.sharded else _null():
-            return self._full()
+        with self._shard():
+            self._full()
 
     @property
     def graph(self):
         """the captured full-batch step (None before capture)"""
-        return self._graphs.get((float(self.B * self.world), bool(self.comm_enabled)))
+        return self._graphs.get(self._key())
 
     def _capture(self):
         """Record the step as a chain of hipGraph segments.  On one GPU that is a single graph.  Sharded (world > 1), every
@@ -1435,8 +1457,7 @@ class FusedTrainer(object):
         action to run between two replays: the compute of a step is ~75 launches of 10-300 us at 64 slates per GPU (launch
         latency matters exactly where 8-GPU runs sit), while the collectives stay ordinary torch.distributed calls on the
         process group's stream, whatever the backend (RCCL on a node, gloo in the one-GPU tests)."""
-        if self._graph_pool is None:
-            self._graph_pool = torch.cuda.graph_pool_handle()
+        if self._cap_stream is None:
             self._cap_stream = torch.cuda.Stream(device=self.dev)
         segs = []
         torch.cuda.synchronize(self.dev)
@@ -1445,19 +1466,19 @@ class FusedTrainer(object):
             # "thread_local": only this thread's calls are checked against the capture -- a process group's watchdog thread or a
             # data-loader thread touching the runtime must not invalidate it
             cur = [torch.cuda.CUDAGraph()]
-            cur[0].capture_begin(pool=self._graph_pool, capture_error_mode="thread_local")
+            cur[0].capture_begin(pool=self._step_graphs.pool, capture_error_mode="thread_local")
 
             def seg_break(after):
                 cur[0].capture_end()
                 segs.append((cur[0], after))
                 cur[0] = torch.cuda.CUDAGraph()
-                cur[0].capture_begin(pool=self._graph_pool, capture_error_mode="thread_local")
+                cur[0].capture_begin(pool=self._step_graphs.pool, capture_error_mode="thread_local")
 
             self._seg_break = seg_break
             ok = False
             try:
-                with sharding.shard_context(int(self._divisor), self.group, deferred=seg_break) if self.sharded else _null():
-                    self._graph_loss = self._full()
+                with self._shard(deferred=seg_break):
+                    self._full()
                 ok = True
             finally:
                 self._seg_break = None
@@ -1469,7 +1490,6 @@ class FusedTrainer(object):
             segs.append((cur[0], None))
         torch.cuda.current_stream(self.dev).wait_stream(self._cap_stream)
         return segs
-
 
     def score(self, xb, yb, indices=None, lengths=None):
         """``model.score(xb, yb == PADDED_Y_VALUE, indices)`` in eval mode (model.py:82-92) through the kernels of the training
@@ -1543,7 +1563,7 @@ class FusedScorer(object):
                 nb += v.untyped_storage().nbytes()
         self.nbytes = nb
         self.use_graph, self.max_graphs = bool(use_graph), int(max_graphs)
-        self._fwd_graphs = _GraphLRU(max_graphs, own_pool=True)
+        self._fwd_graphs = _GraphLRU(max_graphs, new_pool=torch.cuda.graph_pool_handle)
         self._graphs = self._fwd_graphs.graphs             # row bucket -> captured forward, least recently used first
         self.last_mode, self.evictions = None, 0           # "eager" / "capture" / "replay" of the last call; buckets evicted so far
 
@@ -1631,14 +1651,6 @@ class FusedScorer(object):
         else:
             self.last_mode = "eager"
             fwd()
-
-
-class _null(object):
-    def __enter__(self):
-        return None
-
-    def __exit__(self, *a):
-        return False
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -152,6 +152,85 @@ def test_captured_steps_form_an_lru_over_batch_divisors():
     assert (11.0, True) in tg._graphs and (12.0, True) in tg._graphs     # the most recent divisors are the live captures
 
 
+class _Twins(object):
+    """a capturing trainer and a ``use_graph=False`` twin on copies of one model, stepped in lockstep on one batch: every step must
+    give the same loss and the same weights bit for bit (captured, replayed and eager steps make the same launches)"""
+
+    def __init__(self):
+        import copy
+        from allrank_amd.engine import FusedTrainer
+        L, F, bs = 30, 20, 16
+        self.x, self.y, _ = (t.to(DEV) for t in _data(16, L, F, 9))
+        m_g = _model(F)
+        m_e = copy.deepcopy(m_g)
+        self.tg = FusedTrainer(m_g, "approxNDCGLoss", {}, bs, L, lr=1e-3, use_graph=True)
+        self.te = FusedTrainer(m_e, "approxNDCGLoss", {}, bs, L, lr=1e-3, use_graph=False)
+
+    def step(self, div=16):
+        lg = self.tg.step(self.x, self.y, None, global_batch=div)
+        le = self.te.step(self.x, self.y, None, global_batch=div)
+        assert torch.equal(lg, le) and torch.equal(self.tg.flat_p, self.te.flat_p), div
+
+
+def test_ensure_captured_waits_for_the_warm_up_steps():
+    """ensure_captured() follows step()'s rule: on a fresh trainer it records nothing (a first launch -- module load, kernel
+    attributes, workspace allocation -- must not fall inside a capture), says so and leaves use_graph on; after the two eager
+    warm-up steps it captures, and the steps that follow replay that capture."""
+    tw = _Twins()
+    tg = tw.tg
+    assert tg.ensure_captured(16) is False
+    assert len(tg._graphs) == 0 and tg.use_graph is True
+    assert tg.capture_fallback is not None and "warm-up" in tg.capture_fallback
+    tw.step()
+    tw.step()
+    assert len(tg._graphs) == 0
+    assert tg.ensure_captured(16) is True
+    assert (16.0, True) in tg._graphs and len(tg._graphs) == 1
+    segs = tg._graphs[(16.0, True)]
+    for _ in range(3):
+        tw.step()
+    assert tg._graphs[(16.0, True)] is segs and len(tg._graphs) == 1 and tg.graph is segs and tg.use_graph
+
+
+def test_ensure_captured_obeys_the_lru():
+    """a capture made by ensure_captured() goes through the LRU of step(): a full cache evicts its least recently used divisor"""
+    import warnings
+    tw = _Twins()
+    tg = tw.tg
+    with warnings.catch_warnings(record=True) as rec:
+        warnings.simplefilter("always")
+        for div in (16, 16, 16, 15, 14, 13):
+            tw.step(div)
+        assert list(tg._graphs) == [(16.0, True), (15.0, True), (14.0, True), (13.0, True)] and len(tg._graphs) == tg.max_graphs
+        assert tg.ensure_captured(12) is True
+    assert len(tg._graphs) == tg.max_graphs and (16.0, True) not in tg._graphs
+    assert list(tg._graphs) == [(15.0, True), (14.0, True), (13.0, True), (12.0, True)]
+    assert sum("evicting the least recently used" in str(w.message) for w in rec) == 1
+    segs = tg._graphs[(12.0, True)]
+    tw.step(12)                                                     # replays what ensure_captured recorded: no new entry
+    assert tg._graphs[(12.0, True)] is segs and len(tg._graphs) == tg.max_graphs and tg.capture_fallback is None
+
+
+def test_set_lr_drops_the_captures_and_the_next_step_recaptures():
+    """the learning rate is a by-value launch argument of the captured Adam kernel: a new rate drops every capture, the next step
+    re-captures at once (the warm-up is not repeated) and the updates are those of the eager twin at the new rate"""
+    tw = _Twins()
+    tg = tw.tg
+    for div in (16, 16, 16, 15):
+        tw.step(div)
+    assert len(tg._graphs) == 2
+    tg.set_lr(1e-3)                                                 # unchanged rate: the captures stay
+    assert len(tg._graphs) == 2
+    tg.set_lr(5e-4)
+    tw.te.set_lr(5e-4)
+    assert len(tg._graphs) == 0 and tg.graph is None
+    tw.step()
+    assert list(tg._graphs) == [(16.0, True)]                       # captured on the first step after the change
+    for div in (16, 15, 16):
+        tw.step(div)
+    assert list(tg._graphs) == [(15.0, True), (16.0, True)] and tg.use_graph and tg.capture_fallback is None
+
+
 @pytest.mark.parametrize("name,kw", [("Adam", dict(lr=2e-3, betas=(0.8, 0.95), eps=1e-6, weight_decay=0.01)),
                                      ("AdamW", dict(lr=2e-3, weight_decay=0.05)),
                                      ("SGD", dict(lr=0.05, momentum=0.9, nesterov=True, weight_decay=1e-3)),
