@@ -28,6 +28,8 @@ __device__ __forceinline__ float sigmoid_neg_fast(float x) {
 }
 }  // namespace
 
+// the seven work arrays of the kernel below (ltrx_device.h: LtrxSlateArrays)
+static LtrxSlateArrays approx_arrays{7, 0, ltrx_per_slate_floats};
 // GWS: the seven work arrays live in a global workspace (slates too long for LDS; ltrx_device.h)
 template <bool GWS>
 __global__ void __launch_bounds__(1024) ltrx_approxndcg_kernel(const float* __restrict__ y_pred,
@@ -130,10 +132,7 @@ __global__ void __launch_bounds__(1024) ltrx_approxndcg_kernel(const float* __re
   }
 }
 
-static size_t approx_per_floats(int B) { return ((size_t)(B > 0 ? B : 0) + 3) & ~(size_t)3; }
-extern "C" size_t ltrx_approxndcg_workspace_bytes(int B, int L) {
-  return (approx_per_floats(B) + ltrx_array_ws_floats(7, 0, B > 0 ? B : 0, L > 0 ? L : 0)) * sizeof(float);
-}
+extern "C" size_t ltrx_approxndcg_workspace_bytes(int B, int L) { return approx_arrays.workspace_bytes(B, L); }
 
 extern "C" int ltrx_approxndcg_fwd_bwd(const float* y_pred, const float* y_true, int B, int L, float eps,
                                        float pad_value, float alpha, float batch_divisor, float* loss_out,
@@ -142,22 +141,8 @@ extern "C" int ltrx_approxndcg_fwd_bwd(const float* y_pred, const float* y_true,
   if (L > LTRX_MAX_LONG_SLATE_LEN) return LTRX_EUNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   float* per = (float*)ws;
-  if (ltrx_arrays_in_lds(7, 0, L)) {
-    const size_t lds = 7 * (size_t)L * sizeof(float);
-    if (lds > 48 * 1024) {
-      static std::atomic<uint64_t> attr_done{0};
-      const int arc = ltrx_once_per_device(attr_done, []() {
-        return hipFuncSetAttribute((const void*)ltrx_approxndcg_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   LTRX_LDS_ARRAY_BUDGET_BYTES) == hipSuccess ? LTRX_OK : LTRX_EHIP;
-      });
-      if (arc != LTRX_OK) return arc;
-    }
-    hipLaunchKernelGGL(ltrx_approxndcg_kernel<false>, dim3(B), dim3(1024), lds, s, y_pred, y_true, L, eps, pad_value, alpha,
-                       1.0f / batch_divisor, per, per_slate_out, grad_out, (float*)nullptr, (size_t)0);
-  } else {
-    hipLaunchKernelGGL(ltrx_approxndcg_kernel<true>, dim3(B), dim3(1024), 0, s, y_pred, y_true, L, eps, pad_value, alpha,
-                       1.0f / batch_divisor, per, per_slate_out, grad_out, per + approx_per_floats(B), ltrx_array_ws_stride(7, 0, L));
-  }
-  LTRX_LAUNCH_CHECK();
+  const int rc = ltrx_launch_slate_arrays(approx_arrays, ltrx_approxndcg_kernel<false>, ltrx_approxndcg_kernel<true>, B, L, dim3(1024), per, s,
+                                          y_pred, y_true, L, eps, pad_value, alpha, 1.0f / batch_divisor, per, per_slate_out, grad_out);
+  if (rc != LTRX_OK) return rc;
   return ltrx_launch_finalize_sum(per, B, -1.0f / batch_divisor, loss_out, s);
 }

@@ -23,15 +23,6 @@ using namespace ltrx;
 
 namespace {
 
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
-  x ^= x >> 16;
-  x *= 0x85EBCA6Bu;
-  x ^= x >> 13;
-  x *= 0xC2B2AE35u;
-  x ^= x >> 16;
-  return x;
-}
-
 constexpr int FIX_MAX_LEN = 12288;        // items of one slate held in LDS (48 KB of keys)
 
 }  // namespace
@@ -84,8 +75,8 @@ __global__ void __launch_bounds__(256) ltrx_fixlength_positions_kernel(const int
   }
   const int argmax_pos = sh_arg;
   for (int attempt = 0; attempt < 64; ++attempt) {
-    const uint32_t sd = mix32(seed_lo ^ mix32(seed_hi + 0x9E3779B9u * (uint32_t)(s + 1) + 0x7F4A7C15u * (uint32_t)((uint64_t)s >> 32)) ^ (0x85EBCA6Bu * (uint32_t)attempt));
-    for (int i = threadIdx.x; i < len; i += blockDim.x) keys[i] = mix32(sd ^ (0xC2B2AE35u * (uint32_t)(i + 1)));
+    const uint32_t sd = fmix32(seed_lo ^ fmix32(seed_hi + 0x9E3779B9u * (uint32_t)(s + 1) + 0x7F4A7C15u * (uint32_t)((uint64_t)s >> 32)) ^ (0x85EBCA6Bu * (uint32_t)attempt));
+    for (int i = threadIdx.x; i < len; i += blockDim.x) keys[i] = fmix32(sd ^ (0xC2B2AE35u * (uint32_t)(i + 1)));
     __syncthreads();
     float ysel = 0.f;
     for (int i = threadIdx.x; i < len; i += blockDim.x) {

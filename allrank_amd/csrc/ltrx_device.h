@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <math.h>
 #include <atomic>
+#include <initializer_list>
 
 #include "../../include/ltrx.h"
 
@@ -27,6 +28,29 @@ static inline int ltrx_once_per_device(std::atomic<uint64_t>& done, F&& setup) {
   const int rc = setup();            // two threads racing here both set the same attribute: harmless
   if (rc == LTRX_OK) done.fetch_or(bit, std::memory_order_release);
   return rc;
+}
+
+// Dynamic LDS beyond the default allowance.  hipFuncAttributeMaxDynamicSharedMemorySize is the opt-in of this API for a launch that asks
+// for more dynamic LDS than a runtime grants by default.  What HIP requires on gfx950 was measured (ROCm 7.2, MI355X): nothing -- it reports
+// the CU's whole 160 KB as sharedMemPerBlock, launches with 48 KB + 4 B, 64 KB + 4 B, 100 KB and 159 KB of dynamic LDS run without the
+// attribute, and hip_runtime_api.h calls the attribute a hint that AMD devices may ignore.  So neither the "48 * 1024" nor the "default
+// 64 KB" that the launchers used to quote is a limit of this runtime.  The opt-in stays because it costs one call per kernel and device and
+// keeps the library independent of that default; its threshold is the smallest default behind this API, 48 KB (CUDA's), so no runtime sees
+// a larger request unannounced.  A site whose kernels always need more opts in unconditionally, a site whose need depends on the shape
+// only above the allowance; both go through this one function.  `done` is the site's per-device flag.
+#define LTRX_DEFAULT_DYNAMIC_LDS_BYTES (48 * 1024)
+struct LtrxDynLds {
+  const void* kernel;
+  size_t bytes;
+  template <typename K>
+  LtrxDynLds(K* k, size_t b) : kernel((const void*)k), bytes(b) {}
+};
+static inline int ltrx_allow_dynamic_lds(std::atomic<uint64_t>& done, std::initializer_list<LtrxDynLds> kernels) {
+  return ltrx_once_per_device(done, [&]() {
+    for (const LtrxDynLds& k : kernels)
+      if (hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.bytes) != hipSuccess) return LTRX_EHIP;
+    return LTRX_OK;
+  });
 }
 
 // cut-off ranks of a metric call, passed to the kernel by value (ltrx_ndcg_at, ltrx_mrr_at)
@@ -142,6 +166,27 @@ __device__ __forceinline__ void block_inclusive_scan(float* a, int n, float* red
 
 __device__ __forceinline__ float sigmoidf_acc(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+// the murmur3 32-bit finaliser: every counter-based draw of the library ends in it (counter_hash below, the attention dropout's row
+// seed in ltrx_mfma.h, the FixLength sampling keys in ltrx_data.hip)
+__device__ __forceinline__ uint32_t fmix32(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x85EBCA6Bu;
+  x ^= x >> 13;
+  x *= 0xC2B2AE35u;
+  x ^= x >> 16;
+  return x;
+}
+
+// The split-bf16 split of one float: x ~= hi + lo (+ lo2), hi = bf16(x), lo = bf16(x - hi), lo2 = bf16((x - hi) - lo): each further
+// term is what the previous one leaves of the rest.  Every operand image and every on-the-fly staging of the library is written with
+// these macros, so an image written anywhere is bit-identical to the split a GEMM applies while staging.  `hi` and `lo` are __bf16
+// lvalues: vector elements, or locals that the site stores afterwards.
+// (Macros, not a function: the terms of an inlined by-value function reach the optimiser in one fixed order relative to the vector
+//  inserts around them, the sites have two such orders, and kernels of ltrx_gemm.hip, ltrx_mha_res.hip and ltrx_fcstep.hip schedule
+//  differently when theirs changes; see profiles/NOTES.md.)
+#define LTRX_BF16_REST(rest, prev) ((__bf16)((rest) - (float)(prev)))
+#define LTRX_SPLIT_BF16(x, hi, lo) ((hi) = (__bf16)(x), (lo) = LTRX_BF16_REST(x, hi))
+
 // Counter-based dropout: the keep decision of element `idx` of a tensor is a pure function of (seed, idx), so forward and
 // backward kernels regenerate the same mask without storing it (murmur3 finaliser over the folded 64-bit index).
 // `seed` = per-site constant XOR a per-step word read from device memory (so a captured hipGraph draws a fresh mask at
@@ -154,13 +199,7 @@ struct DropSpec {
 // the generator itself: 32 hashed bits of element `idx` under `seed` (its top 24 bits are what the sites consume: the dropout
 // decision below, the uniform draw of the stochastic NeuralSort noise in ltrx_neuralsort_stoch.hip)
 __device__ __forceinline__ uint32_t counter_hash(uint32_t seed, uint64_t idx) {
-  uint32_t x = (uint32_t)idx ^ ((uint32_t)(idx >> 32) * 0x9E3779B9u) ^ seed;
-  x ^= x >> 16;
-  x *= 0x85EBCA6Bu;
-  x ^= x >> 13;
-  x *= 0xC2B2AE35u;
-  x ^= x >> 16;
-  return x;
+  return fmix32((uint32_t)idx ^ ((uint32_t)(idx >> 32) * 0x9E3779B9u) ^ seed);
 }
 __device__ __forceinline__ float drop_keep_scale(const DropSpec& d, uint64_t idx) {
   return ((counter_hash(d.seed, idx) >> 8) >= d.thresh) ? d.inv_keep : 0.f;
@@ -174,21 +213,16 @@ inline ltrx::DropSpec ltrx_make_drop(float p, uint32_t seed) {
   d.inv_keep = (p > 0.f) ? 1.0f / (1.0f - p) : 1.0f;
   return d;
 }
-namespace ltrx {
-}  // namespace ltrx
 
-// 4 floats -> the 16 bytes {hi0..hi3, lo0..lo3} (bf16) of a pre-split operand image: hi = bf16(x), lo = bf16(x - hi), the same
-// expressions the GEMM kernels apply while staging (ltrx_gemm.hip split4), so an image written anywhere is bit-identical to the
-// on-the-fly split
+// 4 floats -> the 16 bytes {hi0..hi3, lo0..lo3} (bf16) of a pre-split operand image, by the same macro (LTRX_SPLIT_BF16) the GEMM
+// kernels apply while staging, so an image written anywhere is bit-identical to the on-the-fly split
 typedef __bf16 ltrx_bf16x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 ltrx_split_image4(const float4 v) {
   const float x[4] = {v.x, v.y, v.z, v.w};
   ltrx_bf16x4_t hi, lo;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    const __bf16 h = (__bf16)x[e];
-    hi[e] = h;
-    lo[e] = (__bf16)(x[e] - (float)h);
+    LTRX_SPLIT_BF16(x[e], hi[e], lo[e]);
   }
   float4 o;
   *reinterpret_cast<ltrx_bf16x4_t*>(&o.x) = hi;
@@ -201,18 +235,46 @@ __device__ __forceinline__ float4 ltrx_split_image4(const float4 v) {
 // arrays of a slate stay in its CU's L1 / the XCD's L2, and __syncthreads() orders global accesses inside a workgroup exactly as it
 // orders LDS.  Slates up to LTRX_MAX_SLATE_LEN take the LDS form (the tuned path); up to LTRX_MAX_LONG_SLATE_LEN the global form --
 // the reference pads a validation set to its longest slate with no bound (allrank/data/dataset_loading.py:185-194).
+// One description per loss states its working set -- `narr` arrays of L floats plus `extra_floats`, and the per-slate results
+// (`per_floats(B)`, a multiple of 4) that lead the call's workspace -- and everything else derives from it: the exported
+// *_workspace_bytes, the LDS byte count, where the work arrays start in the workspace and their per-slate stride.  The description sits
+// directly above its kernel, whose carve spells the same counts out.
 #define LTRX_LDS_ARRAY_BUDGET_BYTES (160 * 1024 - 1024)
-static inline bool ltrx_arrays_in_lds(int narr, int extra_floats, int L) {
-  return ((size_t)narr * (size_t)L + (size_t)extra_floats) * sizeof(float) <= (size_t)LTRX_LDS_ARRAY_BUDGET_BYTES;
-}
-// bytes of the global work arrays (0 when they fit in LDS), rounded so that the per-slate block keeps 16-byte alignment
-static inline size_t ltrx_array_ws_floats(int narr, int extra_floats, int B, int L) {
-  if (ltrx_arrays_in_lds(narr, extra_floats, L)) return 0;
-  const size_t per = (((size_t)narr * (size_t)L + (size_t)extra_floats) + 3) & ~(size_t)3;
-  return per * (size_t)B;
-}
-static inline size_t ltrx_array_ws_stride(int narr, int extra_floats, int L) {
-  return (((size_t)narr * (size_t)L + (size_t)extra_floats) + 3) & ~(size_t)3;
+struct LtrxSlateArrays {
+  int narr, extra_floats;
+  size_t (*per_floats)(int B);
+  std::atomic<uint64_t> lds_allowed{0};        // ltrx_allow_dynamic_lds of the LDS-form kernel, per device
+
+  size_t floats(int L) const { return (size_t)narr * (size_t)L + (size_t)extra_floats; }
+  size_t lds_bytes(int L) const { return floats(L) * sizeof(float); }
+  bool in_lds(int L) const { return lds_bytes(L) <= (size_t)LTRX_LDS_ARRAY_BUDGET_BYTES; }
+  size_t ws_stride(int L) const { return (floats(L) + 3) & ~(size_t)3; }      // a slate's block keeps 16-byte alignment
+  size_t workspace_bytes(int B, int L) const {                                 // non-positive B, L count as 0
+    B = B > 0 ? B : 0;
+    L = L > 0 ? L : 0;
+    return (per_floats(B) + (in_lds(L) ? 0 : ws_stride(L) * (size_t)B)) * sizeof(float);
+  }
+};
+// per-slate results of a loss that keeps one float per slate
+static inline size_t ltrx_per_slate_floats(int B) { return ((size_t)B + 3) & ~(size_t)3; }
+
+// Launches one workgroup per slate: `lds_kernel` (GWS = false) with the arrays as dynamic LDS, or `ws_kernel` (GWS = true) with the
+// arrays in the workspace `ws` behind the per-slate results.  `args` are the kernel's parameters up to its last two, (gws, gws_stride).
+template <typename K, typename... Args>
+static inline int ltrx_launch_slate_arrays(LtrxSlateArrays& d, K* lds_kernel, K* ws_kernel, int B, int L, dim3 block, float* ws,
+                                           hipStream_t s, Args... args) {
+  if (d.in_lds(L)) {
+    const size_t lds = d.lds_bytes(L);
+    if (lds > LTRX_DEFAULT_DYNAMIC_LDS_BYTES) {
+      const int rc = ltrx_allow_dynamic_lds(d.lds_allowed, {{lds_kernel, LTRX_LDS_ARRAY_BUDGET_BYTES}});
+      if (rc != LTRX_OK) return rc;
+    }
+    hipLaunchKernelGGL(lds_kernel, dim3(B), block, lds, s, args..., (float*)nullptr, (size_t)0);
+  } else {
+    hipLaunchKernelGGL(ws_kernel, dim3(B), block, 0, s, args..., ws + d.per_floats(B), d.ws_stride(L));
+  }
+  LTRX_LAUNCH_CHECK();
+  return LTRX_OK;
 }
 
 // Final cross-slate reduction: out[0] = scale * sum_b per[b]  (fixed order -> deterministic).  One block.

@@ -31,14 +31,9 @@
 // LDS image of one plane (hi or lo): two panels [256 rows][64 cols] bf16 (128-byte rows; 16-byte chunk c of row r at position
 // c ^ s(r), s(r) = 2 ((r >> 1) & 3): conflict-free for the row-wise b128 reads of a 16x16x32 A fragment AND for the [8 rows][16 cols]
 // footprint of a half-wave's transposed read) and a tail panel [256][16] for columns 128..143 (32-byte rows, no swizzle needed).
-#include "ltrx_device.h"
+#include "ltrx_mfma.h"
 
 using namespace ltrx;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef bf16x4 __attribute__((address_space(3))) * lds_bf16x4_ptr;
 
 namespace {
 
@@ -89,16 +84,8 @@ __device__ __forceinline__ int plane_off(int row, int col8) {
 __device__ __forceinline__ void split8(const float (&x)[8], bf16x8& h, bf16x8& l) {
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
-    h[e] = (__bf16)x[e];
-    l[e] = (__bf16)(x[e] - (float)h[e]);
+    LTRX_SPLIT_BF16(x[e], h[e], l[e]);
   }
-}
-
-// barrier that orders LDS only: __syncthreads() also drains vmcnt(0), i.e. it would wait for the next slate's prefetch
-__device__ __forceinline__ void lds_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
 // sum over the 16 lanes of a DPP row (every lane of the row gets the total; fixed order)
@@ -127,7 +114,7 @@ __device__ __forceinline__ float listnet_rows(float s, float yy, bool in_range, 
     const float sw = wave_sum(e), syw = wave_sum(f);
     if (lane == 0) *reinterpret_cast<f32x4*>(&red[4 * wave]) = f32x4{mw, sw, myw, syw};
   }
-  lds_barrier();
+  lds_only_barrier();
   if (wave < 4) {
     f32x4 st[4];
 #pragma unroll
@@ -152,7 +139,7 @@ __device__ __forceinline__ float listnet_rows(float s, float yy, bool in_range, 
       red[17 + 2 * wave] = rw;
     }
   }
-  lds_barrier();
+  lds_only_barrier();
   float g = 0.f;
   if (wave < 4) {
     const float R = (red[17] + red[19]) + (red[21] + red[23]);
@@ -261,8 +248,7 @@ __global__ void __launch_bounds__(768) ltrx_fc_listnet_kernel(const FcArgs a) {
     const float xv[4] = {p.x, p.y, p.z, p.w};
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      h_[e] = (__bf16)xv[e];
-      l_[e] = (__bf16)(xv[e] - (float)h_[e]);
+      LTRX_SPLIT_BF16(xv[e], h_[e], l_[e]);
     }
     *reinterpret_cast<bf16x4*>(hi + o) = h_;
     *reinterpret_cast<bf16x4*>(lo + o) = l_;
@@ -288,8 +274,7 @@ __global__ void __launch_bounds__(768) ltrx_fc_listnet_kernel(const FcArgs a) {
     const float xv[4] = {p.x, p.y, p.z, p.w};
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      h_[e] = (__bf16)xv[e];
-      l_[e] = (__bf16)(xv[e] - (float)h_[e]);
+      LTRX_SPLIT_BF16(xv[e], h_[e], l_[e]);
     }
     const int o = plane_off(row, c4 >> 1) + (c4 & 1) * 8;
     *reinterpret_cast<bf16x4*>(hi + o) = h_;
@@ -361,7 +346,7 @@ __global__ void __launch_bounds__(768) ltrx_fc_listnet_kernel(const FcArgs a) {
       for (int q = tid_ + nthr * FC_NLD; q < total4_; q += nthr) stage4(q, x4[q]);
     }
     FC_STAMP(it_, 1);
-    lds_barrier();
+    lds_only_barrier();
     FC_STAMP(it_, 2);
 
     // ---- forward: h[t] = act(x[rows of tile t] W1[hrow]^T + b1)   (D layout: lane (n16, kg) holds rows 4 kg + i of the tile) ----
@@ -441,7 +426,7 @@ __global__ void __launch_bounds__(768) ltrx_fc_listnet_kernel(const FcArgs a) {
         }
     }
     FC_STAMP(it_, 3);
-    lds_barrier();
+    lds_only_barrier();
     FC_STAMP(it_, 4);
 
     // ---- scores + ListNet (listNet.py:8-30) by waves 0-3, one row per lane ----
@@ -462,7 +447,7 @@ __global__ void __launch_bounds__(768) ltrx_fc_listnet_kernel(const FcArgs a) {
       }
     }
     FC_STAMP(it_, 5);
-    lds_barrier();
+    lds_only_barrier();
     FC_STAMP(it_, 6);
 
     // ---- backward: dh = dscore (x) w_out (* relu'), d w_out += dscore h, d b1 += dh, dW1^T += x^T dh on the matrix cores ----
@@ -511,7 +496,7 @@ __global__ void __launch_bounds__(768) ltrx_fc_listnet_kernel(const FcArgs a) {
       }
     }
     FC_STAMP(it_, 7);
-    lds_barrier();                                                // the image is free for the next slate
+    lds_only_barrier();                                                // the image is free for the next slate
     FC_STAMP(it_, 8);
   }
 
@@ -726,7 +711,7 @@ __global__ void __launch_bounds__(768) ltrx_fc_linear_listnet_kernel(const FlArg
         if (r < L) part[r * FL_PSTRIDE + c4] = (xr[k][0] * v4[0] + xr[k][1] * v4[1]) + (xr[k][2] * v4[2] + xr[k][3] * v4[3]);
       }
     }
-    lds_barrier();
+    lds_only_barrier();
     float sc = 0.f, yy = a.pad;
     if (wave < 4) {
       const int r = tid;
@@ -742,7 +727,7 @@ __global__ void __launch_bounds__(768) ltrx_fc_linear_listnet_kernel(const FlArg
       if (a.dscores && tid < L) a.dscores[(size_t)b * L + tid] = g;
       dsum += g;
     }
-    lds_barrier();
+    lds_only_barrier();
     if (active) {
 #pragma unroll
       for (int k = 0; k < KMAX; ++k) {
@@ -753,7 +738,7 @@ __global__ void __launch_bounds__(768) ltrx_fc_linear_listnet_kernel(const FlArg
         }
       }
     }
-    lds_barrier();                                              // part / dbuf / ybuf are free for the next slate
+    lds_only_barrier();                                              // part / dbuf / ybuf are free for the next slate
   };
 
   for (int b = blockIdx.x; b < a.B; b += 2 * gridDim.x) {
@@ -926,13 +911,8 @@ extern "C" int ltrx_fc_listnet_step(const float* x, const float* y, int B, int L
   if ((((uintptr_t)x | (uintptr_t)params | (uintptr_t)grads | (uintptr_t)ws) & 15)) return LTRX_EINVAL;
   if (exp_avg && (!exp_avg_sq || !step_count)) return LTRX_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  const int rc = ltrx_once_per_device(g_fc_attr, []() -> int {
-    const void* ks[4] = {(const void*)ltrx_fc_listnet_kernel<false, false>, (const void*)ltrx_fc_listnet_kernel<true, false>,
-                         (const void*)ltrx_fc_listnet_kernel<false, true>, (const void*)ltrx_fc_listnet_kernel<true, true>};
-    for (int i = 0; i < 4; ++i)
-      if (hipFuncSetAttribute(ks[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)FC_SMEM) != hipSuccess) return LTRX_EHIP;
-    return LTRX_OK;
-  });
+  const int rc = ltrx_allow_dynamic_lds(g_fc_attr, {{ltrx_fc_listnet_kernel<false, false>, FC_SMEM}, {ltrx_fc_listnet_kernel<true, false>, FC_SMEM},
+                                                    {ltrx_fc_listnet_kernel<false, true>, FC_SMEM}, {ltrx_fc_listnet_kernel<true, true>, FC_SMEM}});
   if (rc != LTRX_OK) return rc;
   FcArgs a;
   a.x = x;
@@ -1007,12 +987,7 @@ extern "C" int ltrx_fc_linear_listnet_step(const float* x, const float* y, int B
   if ((((uintptr_t)x | (uintptr_t)params | (uintptr_t)grads | (uintptr_t)ws) & 15)) return LTRX_EINVAL;
   if (exp_avg && (!exp_avg_sq || !step_count)) return LTRX_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  const int rc = ltrx_once_per_device(g_fl_attr, []() -> int {
-    if (hipFuncSetAttribute((const void*)ltrx_fc_linear_listnet_kernel<11>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FL_SMEM) != hipSuccess)
-      return LTRX_EHIP;
-    return hipFuncSetAttribute((const void*)ltrx_fc_linear_listnet_kernel<FL_KMAX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FL_SMEM) ==
-                   hipSuccess ? LTRX_OK : LTRX_EHIP;
-  });
+  const int rc = ltrx_allow_dynamic_lds(g_fl_attr, {{ltrx_fc_linear_listnet_kernel<11>, FL_SMEM}, {ltrx_fc_linear_listnet_kernel<FL_KMAX>, FL_SMEM}});
   if (rc != LTRX_OK) return rc;
   FlArgs a;
   a.x = x;

@@ -31,31 +31,26 @@
 // LDS operand images are [row][k] bf16 with k contiguous, UNPADDED 64-byte rows and an XOR swizzle of the 16-byte chunks
 // (swz_off): every lane fetches its 8-element MFMA fragment with one ds_read_b128, conflict-free in both directions.
 // Workgroup ids are remapped so that the column tiles of one A row-panel run on the same XCD (shared L2).
-#include "ltrx_device.h"
+#include "ltrx_mfma.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+using ltrx::lds_only_barrier;
+using ltrx::rowmap;
 
 namespace {
 
 constexpr int BN = 128;   // output-tile columns (rows of B); the row count BM_ and the K-tile depth BK_ are template parameters
 
-__device__ __forceinline__ int rowmap(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-
-// split 4 floats into hi / lo (/ lo2) bf16 quads
+// split 4 floats into hi / lo (/ lo2) bf16 quads (LTRX_SPLIT_BF16 per element)
 template <int NTERMS>
 __device__ __forceinline__ void split4(const float4 v, bf16x4& hi, bf16x4& lo, bf16x4& lo2) {
   const float x[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    const __bf16 h = (__bf16)x[e];
-    const float r1 = x[e] - (float)h;
-    const __bf16 l = (__bf16)r1;
+    __bf16 h, l;
+    LTRX_SPLIT_BF16(x[e], h, l);
     hi[e] = h;
     lo[e] = l;
-    if (NTERMS == 3) lo2[e] = (__bf16)(r1 - (float)l);
+    if (NTERMS == 3) lo2[e] = LTRX_BF16_REST(x[e] - (float)h, l);
   }
 }
 
@@ -241,12 +236,6 @@ __global__ void __launch_bounds__(BM_ * 2) __attribute__((amdgpu_waves_per_eu(2,
 // the chip (a ragged last row tile is handled by clamped loads and guarded stores); everything else (and the strict
 // 3-term mode, whose LDS images do not fit twice) stays on the kernel above.
 // ------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void lds_only_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
 // BM = 256 (wave tile 128 x 64) or 128 (wave tile 64 x 64, 96 KB of LDS): the 128-row variant is for shapes whose 256-row
 // tiling would leave half of the CUs without a tile (M 15360 x N 512: 120 tiles of 256 x 256, 240 of 128 x 256)
 // NT = number of bf16 terms per operand: 2 = hi + lo (three products), 1 = hi only (ONE product: the plain-bf16
@@ -1004,17 +993,11 @@ extern "C" int ltrx_gemm_nt(const float* A, int lda, const float* B, int ldb, co
   if (v == 8) {              // 64-row tiles, two workgroups per CU
     if ((N % 256) || (K % 32) || strict || !vec_epi || act == 4 || act == 5) return LTRX_EUNSUPPORTED;
     static std::atomic<uint64_t> attr64_done{0};
-    const int arc = ltrx_once_per_device(attr64_done, []() {
-#define LTRX_NT64_ATTR(TAIL_, NT_, BIMG_)                                                                                  \
-  (hipFuncSetAttribute((const void*)ltrx_gemm_nt64_kernel<TAIL_, NT_, BIMG_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                       (int)(2 * sizeof(SmemNT<64, NT_>))) != hipSuccess)
-      if (LTRX_NT64_ATTR(false, 2, false) || LTRX_NT64_ATTR(false, 2, true) || LTRX_NT64_ATTR(true, 2, false) ||
-          LTRX_NT64_ATTR(true, 2, true) || LTRX_NT64_ATTR(false, 1, false) || LTRX_NT64_ATTR(false, 1, true) ||
-          LTRX_NT64_ATTR(true, 1, false) || LTRX_NT64_ATTR(true, 1, true))
-        return LTRX_EHIP;
+#define LTRX_NT64_ATTR(TAIL_, NT_) \
+  {ltrx_gemm_nt64_kernel<TAIL_, NT_, false>, 2 * sizeof(SmemNT<64, NT_>)}, {ltrx_gemm_nt64_kernel<TAIL_, NT_, true>, 2 * sizeof(SmemNT<64, NT_>)}
+    const int arc = ltrx_allow_dynamic_lds(attr64_done, {LTRX_NT64_ATTR(false, 2), LTRX_NT64_ATTR(true, 2), LTRX_NT64_ATTR(false, 1),
+                                                         LTRX_NT64_ATTR(true, 1)});
 #undef LTRX_NT64_ATTR
-      return LTRX_OK;
-    });
     if (arc != LTRX_OK) return arc;
     const int tiles_n = N / 256;
     const dim3 grid(((M + 63) / 64) * tiles_n);
@@ -1040,19 +1023,14 @@ extern "C" int ltrx_gemm_nt(const float* A, int lda, const float* B, int ldb, co
   if (v == 6 || v == 7) {
     if ((N % 256) || (K % 32) || strict || !vec_epi) return LTRX_EUNSUPPORTED;
     static std::atomic<uint64_t> attr_done{0};
-    const int arc = ltrx_once_per_device(attr_done, []() {
-#define LTRX_NT256_ATTR(TAIL_, BM_, NT_)                                                                                         \
-  (hipFuncSetAttribute((const void*)ltrx_gemm_nt256_kernel<TAIL_, BM_, NT_, false>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                       (int)(2 * sizeof(SmemNT<BM_, NT_>))) != hipSuccess ||                                                   \
-   hipFuncSetAttribute((const void*)ltrx_gemm_nt256_kernel<TAIL_, BM_, NT_, true>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                       (int)(2 * sizeof(SmemNT<BM_, NT_>))) != hipSuccess)
-      if (LTRX_NT256_ATTR(false, 256, 2) || LTRX_NT256_ATTR(true, 256, 2) || LTRX_NT256_ATTR(false, 128, 2) ||
-          LTRX_NT256_ATTR(true, 128, 2) || LTRX_NT256_ATTR(false, 256, 1) || LTRX_NT256_ATTR(true, 256, 1) ||
-          LTRX_NT256_ATTR(false, 128, 1) || LTRX_NT256_ATTR(true, 128, 1))
-        return LTRX_EHIP;
+#define LTRX_NT256_ATTR(TAIL_, BM_, NT_)                                                    \
+  {ltrx_gemm_nt256_kernel<TAIL_, BM_, NT_, false>, 2 * sizeof(SmemNT<BM_, NT_>)}, {         \
+    ltrx_gemm_nt256_kernel<TAIL_, BM_, NT_, true>, 2 * sizeof(SmemNT<BM_, NT_>)             \
+  }
+    const int arc = ltrx_allow_dynamic_lds(
+        attr_done, {LTRX_NT256_ATTR(false, 256, 2), LTRX_NT256_ATTR(true, 256, 2), LTRX_NT256_ATTR(false, 128, 2), LTRX_NT256_ATTR(true, 128, 2),
+                    LTRX_NT256_ATTR(false, 256, 1), LTRX_NT256_ATTR(true, 256, 1), LTRX_NT256_ATTR(false, 128, 1), LTRX_NT256_ATTR(true, 128, 1)});
 #undef LTRX_NT256_ATTR
-      return LTRX_OK;
-    });
     if (arc != LTRX_OK) return arc;
     const int tiles_n = N / 256;
     const int bm = (v == 6) ? 256 : 128;
@@ -1145,6 +1123,12 @@ extern "C" size_t ltrx_gemm_tn_workspace_bytes(int M, int NP, int KP) {
   return (sp * NP * KP + 2 * sp * NP) * sizeof(float);
 }
 
+// the large-tile kernel's two staging buffers exceed the default dynamic-LDS allowance (ltrx_gemm_tn and ltrx_gemm_tn_group launch it)
+static int tn256_allow_lds() {
+  static std::atomic<uint64_t> attr_done{0};
+  return ltrx_allow_dynamic_lds(attr_done, {{ltrx_gemm_tn256_kernel<2>, 2 * sizeof(SmemNT<256, 2>)}, {ltrx_gemm_tn256_kernel<1>, 2 * sizeof(SmemNT<256, 1>)}});
+}
+
 extern "C" int ltrx_gemm_tn(const float* A, int lda, const float* B, int ldb, float* C, float* bias_out, int M, int NP,
                             int KP, int strict, int tile, void* ws, ltrx_stream_t stream) {
   if (!A || !B || !C || !ws || M <= 0 || NP <= 0 || KP <= 0 || tile < 0) return LTRX_EINVAL;
@@ -1162,15 +1146,7 @@ extern "C" int ltrx_gemm_tn(const float* A, int lda, const float* B, int ldb, fl
     hipStream_t s = (hipStream_t)stream;
     int splits, mps;
     tn256_plan(M, NP, KP, &splits, &mps);
-    static std::atomic<uint64_t> attr_done{0};
-    const int arc = ltrx_once_per_device(attr_done, []() {
-      if (hipFuncSetAttribute((const void*)ltrx_gemm_tn256_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(2 * sizeof(SmemNT<256, 2>))) != hipSuccess ||
-          hipFuncSetAttribute((const void*)ltrx_gemm_tn256_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(2 * sizeof(SmemNT<256, 1>))) != hipSuccess)
-        return LTRX_EHIP;
-      return LTRX_OK;
-    });
+    const int arc = tn256_allow_lds();
     if (arc != LTRX_OK) return arc;
     float* bslabs = bias_out ? (float*)ws + (((size_t)splits * NP * kv + 3) & ~(size_t)3) : nullptr;
     TnGroup g = {};
@@ -1339,15 +1315,7 @@ extern "C" int ltrx_gemm_tn_group(int nprob, const float* const* A, const int* l
     return LTRX_OK;
   }
   hipStream_t s = (hipStream_t)stream;
-  static std::atomic<uint64_t> attr_done{0};
-  const int arc = ltrx_once_per_device(attr_done, []() {
-    if (hipFuncSetAttribute((const void*)ltrx_gemm_tn256_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(2 * sizeof(SmemNT<256, 2>))) != hipSuccess ||
-        hipFuncSetAttribute((const void*)ltrx_gemm_tn256_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(2 * sizeof(SmemNT<256, 1>))) != hipSuccess)
-      return LTRX_EHIP;
-    return LTRX_OK;
-  });
+  const int arc = tn256_allow_lds();
   if (arc != LTRX_OK) return arc;
   TnGroup g = {};
   g.nprob = nprob;

@@ -63,6 +63,10 @@ __device__ __forceinline__ void pair_terms(const PairCtx& c, float w, float sig,
 
 }  // namespace
 
+// the thirteen work arrays (+ the 2 extra entries of invD) of the kernel below (ltrx_device.h: LtrxSlateArrays); per-slate results:
+// loss [B], pair count [B], and the scale word of the finalize kernel
+static size_t lambda_per_floats(int B) { return ((size_t)(2 * B + 4) + 3) & ~(size_t)3; }
+static LtrxSlateArrays lambda_arrays{13, 2, lambda_per_floats};
 // 1024 threads per slate: thread (i, q) = (tid & 255 [+256 ...], tid >> 8) owns item i and a quarter of the partner range j;
 // the four partial sums per item are combined through LDS (16 waves per CU instead of 4 hide the exp/log latency).
 // GWS: the thirteen work arrays live in a global workspace (slates too long for LDS; ltrx_device.h)
@@ -231,10 +235,7 @@ __global__ void __launch_bounds__(256) ltrx_scale_by_device_scalar_kernel(float*
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) x[i] *= sc;
 }
 
-static size_t lambda_per_floats(int B) { return ((size_t)(2 * (B > 0 ? B : 0) + 4) + 3) & ~(size_t)3; }
-extern "C" size_t ltrx_lambdaloss_workspace_bytes(int B, int L) {
-  return (lambda_per_floats(B) + ltrx_array_ws_floats(13, 2, B > 0 ? B : 0, L > 0 ? L : 0)) * sizeof(float);
-}
+extern "C" size_t ltrx_lambdaloss_workspace_bytes(int B, int L) { return lambda_arrays.workspace_bytes(B, L); }
 
 extern "C" int ltrx_lambdaloss_fwd_bwd(const float* y_pred, const float* y_true, int B, int L, float eps,
                                        float pad_value, int scheme, int k, float sigma, float mu, int reduction,
@@ -251,21 +252,10 @@ extern "C" int ltrx_lambdaloss_fwd_bwd(const float* y_pred, const float* y_true,
   float* per_loss = (float*)ws;
   float* per_cnt = per_loss + B;
   float* scale = per_cnt + B;
-  if (ltrx_arrays_in_lds(13, 2, L)) {
-    const size_t lds = (size_t)(13 * L + 2) * sizeof(float);
-    static std::atomic<uint64_t> attr_done{0};   // long slates need more than the default 64 KB of dynamic LDS
-    const int arc = ltrx_once_per_device(attr_done, []() {
-      return hipFuncSetAttribute((const void*)ltrx_lambdaloss_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 LTRX_LDS_ARRAY_BUDGET_BYTES) == hipSuccess ? LTRX_OK : LTRX_EHIP;
-    });
-    if (arc != LTRX_OK) return arc;
-    hipLaunchKernelGGL(ltrx_lambdaloss_kernel<false>, dim3(B), dim3(1024), lds, s, y_pred, y_true, L, eps, pad_value, scheme, k, sigma, mu,
-                       logbase, per_loss, per_cnt, grad_out, order_out, (float*)nullptr, (size_t)0);
-  } else {
-    hipLaunchKernelGGL(ltrx_lambdaloss_kernel<true>, dim3(B), dim3(1024), 0, s, y_pred, y_true, L, eps, pad_value, scheme, k, sigma, mu,
-                       logbase, per_loss, per_cnt, grad_out, order_out, per_loss + lambda_per_floats(B), ltrx_array_ws_stride(13, 2, L));
-  }
-  LTRX_LAUNCH_CHECK();
+  const int rc = ltrx_launch_slate_arrays(lambda_arrays, ltrx_lambdaloss_kernel<false>, ltrx_lambdaloss_kernel<true>, B, L, dim3(1024), per_loss,
+                                          s, y_pred, y_true, L, eps, pad_value, scheme, k, sigma, mu, logbase, per_loss, per_cnt, grad_out,
+                                          order_out);
+  if (rc != LTRX_OK) return rc;
   hipLaunchKernelGGL(ltrx_lambdaloss_finalize_kernel, dim3(1), dim3(256), 0, s, per_loss, per_cnt, B, reduction,
                      ext_pair_count, loss_out, pair_count_out, scale);
   LTRX_LAUNCH_CHECK();

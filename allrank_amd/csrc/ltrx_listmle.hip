@@ -16,6 +16,8 @@
 
 using namespace ltrx;
 
+// the six work arrays of the kernel below (ltrx_device.h: LtrxSlateArrays)
+static LtrxSlateArrays listmle_arrays{6, 0, ltrx_per_slate_floats};
 // GWS: the six work arrays live in a global workspace (slates too long for LDS; ltrx_device.h)
 template <bool GWS>
 __global__ void __launch_bounds__(1024) ltrx_listmle_kernel(const float* __restrict__ y_pred,
@@ -115,10 +117,7 @@ __global__ void __launch_bounds__(1024) ltrx_listmle_kernel(const float* __restr
   }
 }
 
-static size_t listmle_per_floats(int B) { return ((size_t)(B > 0 ? B : 0) + 3) & ~(size_t)3; }
-extern "C" size_t ltrx_listmle_workspace_bytes(int B, int L) {
-  return (listmle_per_floats(B) + ltrx_array_ws_floats(6, 0, B > 0 ? B : 0, L > 0 ? L : 0)) * sizeof(float);
-}
+extern "C" size_t ltrx_listmle_workspace_bytes(int B, int L) { return listmle_arrays.workspace_bytes(B, L); }
 
 extern "C" int ltrx_listmle_fwd_bwd(const float* y_pred, const float* y_true, const int64_t* perm, int B, int L,
                                     float eps, float pad_value, float batch_divisor, float* loss_out,
@@ -129,22 +128,8 @@ extern "C" int ltrx_listmle_fwd_bwd(const float* y_pred, const float* y_true, co
   hipStream_t s = (hipStream_t)stream;
   float* per = (float*)ws;
   const dim3 block(L > 512 ? 1024 : 256);                /* long slates: 16 waves */
-  if (ltrx_arrays_in_lds(6, 0, L)) {
-    const size_t lds = 6 * (size_t)L * sizeof(float);
-    if (lds > 48 * 1024) {
-      static std::atomic<uint64_t> attr_done{0};
-      const int arc = ltrx_once_per_device(attr_done, []() {
-        return hipFuncSetAttribute((const void*)ltrx_listmle_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   LTRX_LDS_ARRAY_BUDGET_BYTES) == hipSuccess ? LTRX_OK : LTRX_EHIP;
-      });
-      if (arc != LTRX_OK) return arc;
-    }
-    hipLaunchKernelGGL(ltrx_listmle_kernel<false>, dim3(B), block, lds, s, y_pred, y_true, perm, L, eps, pad_value, 1.0f / batch_divisor,
-                       per, per_slate_out, grad_out, order_out, (float*)nullptr, (size_t)0);
-  } else {
-    hipLaunchKernelGGL(ltrx_listmle_kernel<true>, dim3(B), block, 0, s, y_pred, y_true, perm, L, eps, pad_value, 1.0f / batch_divisor, per,
-                       per_slate_out, grad_out, order_out, per + listmle_per_floats(B), ltrx_array_ws_stride(6, 0, L));
-  }
-  LTRX_LAUNCH_CHECK();
+  const int rc = ltrx_launch_slate_arrays(listmle_arrays, ltrx_listmle_kernel<false>, ltrx_listmle_kernel<true>, B, L, block, per, s, y_pred,
+                                          y_true, perm, L, eps, pad_value, 1.0f / batch_divisor, per, per_slate_out, grad_out, order_out);
+  if (rc != LTRX_OK) return rc;
   return ltrx_launch_finalize_sum(per, B, 1.0f / batch_divisor, loss_out, s);
 }

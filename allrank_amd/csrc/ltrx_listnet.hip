@@ -11,6 +11,9 @@
 
 using namespace ltrx;
 
+// the two work arrays of the kernel below (ltrx_device.h: LtrxSlateArrays).  Their workspace form cannot be reached today: at
+// LTRX_MAX_LONG_SLATE_LEN = 16384 they are 2 * 16384 * 4 B = 128 KB, inside the LDS budget; the rule is kept uniform all the same.
+static LtrxSlateArrays listnet_arrays{2, 0, ltrx_per_slate_floats};
 // GWS: the two work arrays live in a global workspace (slates too long for LDS; ltrx_device.h)
 template <bool GWS>
 __global__ void __launch_bounds__(256) ltrx_listnet_kernel(const float* __restrict__ y_pred,
@@ -78,10 +81,7 @@ __global__ void __launch_bounds__(256) ltrx_listnet_kernel(const float* __restri
   }
 }
 
-static size_t listnet_per_floats(int B) { return ((size_t)(B > 0 ? B : 0) + 3) & ~(size_t)3; }
-extern "C" size_t ltrx_listnet_workspace_bytes(int B, int L) {
-  return (listnet_per_floats(B) + ltrx_array_ws_floats(2, 0, B > 0 ? B : 0, L > 0 ? L : 0)) * sizeof(float);
-}
+extern "C" size_t ltrx_listnet_workspace_bytes(int B, int L) { return listnet_arrays.workspace_bytes(B, L); }
 
 extern "C" int ltrx_listnet_fwd_bwd(const float* y_pred, const float* y_true, int B, int L, float eps, float pad_value,
                                     float batch_divisor, float* loss_out, float* per_slate_out, float* grad_out,
@@ -90,22 +90,8 @@ extern "C" int ltrx_listnet_fwd_bwd(const float* y_pred, const float* y_true, in
   if (L > LTRX_MAX_LONG_SLATE_LEN) return LTRX_EUNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   float* per = (float*)ws;
-  if (ltrx_arrays_in_lds(2, 0, L)) {
-    const size_t lds = 2 * (size_t)L * sizeof(float);
-    if (lds > 48 * 1024) {                               // more than the default dynamic-LDS allowance: once per device
-      static std::atomic<uint64_t> attr_done{0};
-      const int arc = ltrx_once_per_device(attr_done, []() {
-        return hipFuncSetAttribute((const void*)ltrx_listnet_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   LTRX_LDS_ARRAY_BUDGET_BYTES) == hipSuccess ? LTRX_OK : LTRX_EHIP;
-      });
-      if (arc != LTRX_OK) return arc;
-    }
-    hipLaunchKernelGGL(ltrx_listnet_kernel<false>, dim3(B), dim3(256), lds, s, y_pred, y_true, L, eps, pad_value, 1.0f / batch_divisor,
-                       per, per_slate_out, grad_out, (float*)nullptr, (size_t)0);
-  } else {
-    hipLaunchKernelGGL(ltrx_listnet_kernel<true>, dim3(B), dim3(256), 0, s, y_pred, y_true, L, eps, pad_value, 1.0f / batch_divisor, per,
-                       per_slate_out, grad_out, per + listnet_per_floats(B), ltrx_array_ws_stride(2, 0, L));
-  }
-  LTRX_LAUNCH_CHECK();
+  const int rc = ltrx_launch_slate_arrays(listnet_arrays, ltrx_listnet_kernel<false>, ltrx_listnet_kernel<true>, B, L, dim3(256), per, s, y_pred,
+                                          y_true, L, eps, pad_value, 1.0f / batch_divisor, per, per_slate_out, grad_out);
+  if (rc != LTRX_OK) return rc;
   return ltrx_launch_finalize_sum(per, B, 1.0f / batch_divisor, loss_out, s);
 }

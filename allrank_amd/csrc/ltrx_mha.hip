@@ -28,15 +28,11 @@
 //             dV += P^T dO, dK += dS^T Q.  No atomics anywhere: every output element has one owner (deterministic).
 // Arithmetic intensity: 4 L d_k flop per (query, head) against 4 d_k-float rows read once per workgroup -> compute
 // (fp32 MFMA) bound; K/V re-reads by the 2 workgroups of a (slate, head) are served by L2.
-#include "ltrx_device.h"
+#include "ltrx_mfma.h"
 
 using namespace ltrx;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 namespace {
-
-__device__ __forceinline__ int rowmap(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
 template <int DKP>
 struct Tile {
@@ -178,25 +174,7 @@ __device__ __forceinline__ void store_rows(float* __restrict__ base, int row0, i
   }
 }
 
-// Dropout on the attention probabilities (transformer.py:154-155): counter-based, two-level -- a fully mixed 32-bit seed
-// per (slate*head, query) row and a short 2-multiply mix per key, so the per-element cost is ~8 VALU operations with 32-bit
-// arithmetic only.  The forward and both backward kernels regenerate the same mask from (seed, row, key).
-typedef DropSpec DropCfg;
-__device__ __forceinline__ uint32_t drop_row_seed(const DropCfg& d, uint32_t bh, int L, int qrow) {
-  uint32_t x = d.seed ^ ((bh * (uint32_t)L + (uint32_t)qrow) * 0x9E3779B9u);
-  x ^= x >> 16;
-  x *= 0x85EBCA6Bu;
-  x ^= x >> 13;
-  x *= 0xC2B2AE35u;
-  x ^= x >> 16;
-  return x;
-}
-__device__ __forceinline__ float drop_scale_rk(const DropCfg& d, uint32_t row_seed, int key) {
-  uint32_t x = (row_seed ^ (uint32_t)key) * 0x9E3779B1u;
-  x ^= x >> 16;
-  x *= 0x85EBCA6Bu;
-  return ((x >> 8) >= d.thresh) ? d.inv_keep : 0.f;
-}
+// (the dropout draw on the attention probabilities, drop_row_seed / drop_scale_rk: ltrx_mfma.h)
 
 // Softmax arithmetic runs in the log2 domain: one v_exp_f32 per probability (exp2 of scores pre-multiplied by
 // log2(e)/sqrt(d_k)) instead of the 14-instruction expf expansion, and key padding enters as an additive -inf bias, so
@@ -204,7 +182,6 @@ __device__ __forceinline__ float drop_scale_rk(const DropCfg& d, uint32_t row_se
 // P = exp2(s * log2e/sqrt(d_k) - lse * log2e) from the stored natural-log LSE (lse_out keeps its meaning).
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kLn2 = 0.6931471805599453f;
-__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
 template <int DKP>
 __device__ __forceinline__ void zero_acc(f32x16 (&o)[DKP / 32]) {

@@ -26,15 +26,9 @@
 // Softmax in the log2 domain, natural-log LSE saved, dropout on P regenerated from (seed, query row, key) -- identical
 // conventions to ltrx_mha.hip, so forward / backward kernels of the two paths are interchangeable.  Variable-length
 // (cu_seqlens) batches: slate b is rows cu[b] .. cu[b+1]-1; waves beyond the slate's length exit after the staging barrier.
-#include "ltrx_device.h"
+#include "ltrx_mfma.h"
 
 using namespace ltrx;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef bf16x4 __attribute__((address_space(3))) * lds_bf16x4_ptr;
 
 namespace {
 
@@ -47,24 +41,6 @@ constexpr size_t dq_smem(int nw) { return 2 * (size_t)PLANE + (size_t)nw * 32 * 
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kLn2 = 0.6931471805599453f;
 
-typedef DropSpec DropCfg;
-__device__ __forceinline__ uint32_t drop_row_seed(const DropCfg& d, uint32_t bh, int L, int qrow) {   // == ltrx_mha.hip
-  uint32_t x = d.seed ^ ((bh * (uint32_t)L + (uint32_t)qrow) * 0x9E3779B9u);
-  x ^= x >> 16;
-  x *= 0x85EBCA6Bu;
-  x ^= x >> 13;
-  x *= 0xC2B2AE35u;
-  x ^= x >> 16;
-  return x;
-}
-__device__ __forceinline__ float drop_scale_rk(const DropCfg& d, uint32_t row_seed, int key) {
-  uint32_t x = (row_seed ^ (uint32_t)key) * 0x9E3779B1u;
-  x ^= x >> 16;
-  x *= 0x85EBCA6Bu;
-  return ((x >> 8) >= d.thresh) ? d.inv_keep : 0.f;
-}
-__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-__device__ __forceinline__ int rowmap(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
 // byte offset of 16-byte chunk `chunk` (8 columns) of row `row` inside a plane
 __device__ __forceinline__ int img_off(int row, int chunk) {
@@ -96,8 +72,7 @@ __device__ __forceinline__ void tile_sstore(unsigned char* img, int tile, const 
   bf16x8 h, l;
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
-    h[e] = (__bf16)x[e];
-    l[e] = (__bf16)(x[e] - (float)h[e]);
+    LTRX_SPLIT_BF16(x[e], h[e], l[e]);
   }
   const int o = img_off(row, chunk);
   *reinterpret_cast<bf16x8*>(img + o) = h;
@@ -136,20 +111,12 @@ __device__ __forceinline__ void fixed_finish(bf16x8 (&fh)[4], bf16x8 (&fl)[4], c
     const float v[8] = {a.x * pre, a.y * pre, a.z * pre, a.w * pre, b.x * pre, b.y * pre, b.z * pre, b.w * pre};
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      fh[ks][e] = (__bf16)v[e];
-      fl[ks][e] = (__bf16)(v[e] - (float)fh[ks][e]);
+      LTRX_SPLIT_BF16(v[e], fh[ks][e], fl[ks][e]);
     }
   }
 }
 
 #define LTRX_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
-// barrier that orders LDS only: __syncthreads() also drains vmcnt(0), i.e. it would wait at every tile for the global loads of
-// the NEXT tile that were issued just before it (and for the touch_line requests)
-__device__ __forceinline__ void lds_only_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
 #ifdef LTRX_MHA_STAMP        // lab builds only (tools/lab/lib_variant.sh): cycle stamps of one workgroup of the forward kernel
 __device__ unsigned long long g_mha_stamps[8][40][8];       // (or of the dK/dV kernel with -DLTRX_MHA_STAMP_DKDV)
 #define STAMP_(kt, ph)                                                                 \
@@ -825,21 +792,12 @@ size_t ltrx_mha_res_bwd_ws_bytes(int B, int L, int h) {
   return (size_t)B * h * lk * lk * sizeof(float);
 }
 
-template <typename K>
-static int res_attr(K kernel, size_t bytes) {
-  return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess ? LTRX_OK : LTRX_EHIP;
-}
-
 int ltrx_mha_fwd_res_launch(const float* q, const float* k, const float* v, const uint8_t* kpm, int B, int L, int h, int dk, int rs,
                             float* o, int ors, float* lse, float p_drop, uint32_t seed, const uint32_t* seed_step, const int* cu,
                             const int* order, bool plain, hipStream_t s) {
   static std::atomic<uint64_t> attr_done{0};
-  const int arc = ltrx_once_per_device(attr_done, []() {
-    if (res_attr(ltrx_mha_fwd_res_kernel<false, false>, RES_SMEM) != LTRX_OK || res_attr(ltrx_mha_fwd_res_kernel<true, false>, RES_SMEM) != LTRX_OK ||
-        res_attr(ltrx_mha_fwd_res_kernel<false, true>, RES_SMEM) != LTRX_OK || res_attr(ltrx_mha_fwd_res_kernel<true, true>, RES_SMEM) != LTRX_OK)
-      return LTRX_EHIP;
-    return LTRX_OK;
-  });
+  const int arc = ltrx_allow_dynamic_lds(attr_done, {{ltrx_mha_fwd_res_kernel<false, false>, RES_SMEM}, {ltrx_mha_fwd_res_kernel<true, false>, RES_SMEM},
+                                                     {ltrx_mha_fwd_res_kernel<false, true>, RES_SMEM}, {ltrx_mha_fwd_res_kernel<true, true>, RES_SMEM}});
   if (arc != LTRX_OK) return arc;
   const DropCfg drop = ltrx_make_drop(p_drop, seed);
   const float scale = 1.0f / sqrtf((float)dk);
@@ -862,16 +820,11 @@ int ltrx_mha_bwd_res_launch(const float* q, const float* k, const float* v, cons
                             void* ws, float p_drop, uint32_t seed, const uint32_t* seed_step, const int* cu, const int* order,
                             bool plain, hipStream_t s) {
   static std::atomic<uint64_t> attr_done{0};
-  const int arc = ltrx_once_per_device(attr_done, []() {
-    if (res_attr(ltrx_mha_bwd_dq_res_kernel<false, 4, 6, false>, dq_smem(4)) != LTRX_OK || res_attr(ltrx_mha_bwd_dq_res_kernel<true, 4, 6, false>, dq_smem(4)) != LTRX_OK ||
-        res_attr(ltrx_mha_bwd_dq_res_kernel<false, 8, 4, true>, dq_smem(8)) != LTRX_OK || res_attr(ltrx_mha_bwd_dq_res_kernel<true, 8, 4, true>, dq_smem(8)) != LTRX_OK ||
-        res_attr(ltrx_mha_bwd_dkdv_res_kernel<false, false>, RES_SMEM) != LTRX_OK ||
-        res_attr(ltrx_mha_bwd_dkdv_res_kernel<true, false>, RES_SMEM) != LTRX_OK ||
-        res_attr(ltrx_mha_bwd_dkdv_res_kernel<false, true>, RES_SMEM) != LTRX_OK ||
-        res_attr(ltrx_mha_bwd_dkdv_res_kernel<true, true>, RES_SMEM) != LTRX_OK)
-      return LTRX_EHIP;
-    return LTRX_OK;
-  });
+  const int arc = ltrx_allow_dynamic_lds(
+      attr_done, {{ltrx_mha_bwd_dq_res_kernel<false, 4, 6, false>, dq_smem(4)}, {ltrx_mha_bwd_dq_res_kernel<true, 4, 6, false>, dq_smem(4)},
+                  {ltrx_mha_bwd_dq_res_kernel<false, 8, 4, true>, dq_smem(8)}, {ltrx_mha_bwd_dq_res_kernel<true, 8, 4, true>, dq_smem(8)},
+                  {ltrx_mha_bwd_dkdv_res_kernel<false, false>, RES_SMEM}, {ltrx_mha_bwd_dkdv_res_kernel<true, false>, RES_SMEM},
+                  {ltrx_mha_bwd_dkdv_res_kernel<false, true>, RES_SMEM}, {ltrx_mha_bwd_dkdv_res_kernel<true, true>, RES_SMEM}});
   if (arc != LTRX_OK) return arc;
   const DropCfg drop = ltrx_make_drop(p_drop, seed);
   const float scale = 1.0f / sqrtf((float)dk);

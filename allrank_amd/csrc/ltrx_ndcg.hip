@@ -87,12 +87,9 @@ static int ndcg_launch(const float* y_pred, const float* y_true, const float* ga
   (void)ws;
   if (!y_pred || !y_true || !ats || !ndcg_out || B <= 0 || L <= 0 || n_ats <= 0) return LTRX_EINVAL;
   if (n_ats > LTRX_MAX_ATS || L > LTRX_MAX_METRIC_SLATE_LEN) return LTRX_EUNSUPPORTED;
-  if (L > 4096) {                                   // more than the default 64 KB of dynamic LDS
+  if (4 * (size_t)L * sizeof(float) > LTRX_DEFAULT_DYNAMIC_LDS_BYTES) {
     static std::atomic<uint64_t> attr_done{0};
-    const int arc = ltrx_once_per_device(attr_done, []() {
-      return hipFuncSetAttribute((const void*)ltrx_ndcg_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)(4 * LTRX_MAX_METRIC_SLATE_LEN * sizeof(float))) == hipSuccess ? LTRX_OK : LTRX_EHIP;
-    });
+    const int arc = ltrx_allow_dynamic_lds(attr_done, {{ltrx_ndcg_kernel, 4 * LTRX_MAX_METRIC_SLATE_LEN * sizeof(float)}});
     if (arc != LTRX_OK) return arc;
   }
   LtrxAts a;

@@ -91,6 +91,43 @@ def test_workspace_queries_and_argument_validation_run_without_a_gpu(libpath):
     assert lib.ltrx_mha_fwd(None, None, None, None, 1, 1, 1, 64, 64, None, 64, None, 0.0, 0, None, None, None, 1, None) == -1
 
 
+def test_long_slate_loss_workspace_bytes_follow_one_formula(libpath):
+    """the four losses that move their per-slate work arrays from LDS to the call's workspace: `per` result floats, then -- only when
+    the narr * L + extra work floats of a slate exceed the 159 KB LDS budget -- B blocks of them, each rounded up to 4 floats.
+    Both sides of every loss's LDS / workspace boundary; listNet has none up to LTRX_MAX_LONG_SLATE_LEN.  Non-positive B, L count as 0."""
+    from allrank_amd import _lib
+    lib = _lib.lib()
+
+    def round4(n):
+        return (n + 3) // 4 * 4
+
+    def want(narr, extra, per, B, L):
+        B, L = max(B, 0), max(L, 0)
+        work = narr * L + extra
+        return 4 * (per(B) + (0 if 4 * work <= 162816 else B * round4(work)))
+
+    def one(B):
+        return round4(B)
+
+    def lam(B):
+        return round4(2 * B + 4)
+
+    losses = [("listnet", 2, 0, one, [16384]), ("listmle", 6, 0, one, [6784, 6785]), ("approxndcg", 7, 0, one, [5814, 5815]),
+              ("lambdaloss", 13, 2, lam, [3130, 3131])]
+    assert _lib.MAX_LONG_SLATE_LEN == 16384
+    for name, narr, extra, per, edges in losses:
+        fn = getattr(lib, "ltrx_%s_workspace_bytes" % name)
+        for B in (1, 3, 64, 0, -5):
+            for L in [1, 240, 2048] + edges + [0, -7]:
+                assert fn(B, L) == want(narr, extra, per, B, L), (name, B, L)
+        if len(edges) == 2:                      # the boundary is where the table of the formula says it is
+            assert fn(3, edges[0]) == 4 * per(3) and fn(3, edges[1]) == 4 * (per(3) + 3 * round4(narr * edges[1] + extra)), name
+        else:
+            assert fn(3, edges[0]) == 4 * per(3), name
+        assert fn(-5, 7000) == fn(0, 7000) == 4 * per(0) and fn(3, -7) == fn(3, 0) == 4 * per(3), name
+    assert lib.ltrx_listnet_workspace_bytes(0, 0) == 0 and lib.ltrx_lambdaloss_workspace_bytes(0, 0) == 16
+
+
 def test_wgrad_workspace_covers_every_smaller_row_count(libpath):
     """a variable-length batch calls ltrx_gemm_tn with a different row count every step against a
     workspace sized once for B*L rows; the split plan is not monotone in the row count, so the size query must be an
