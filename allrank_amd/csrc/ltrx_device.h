@@ -277,6 +277,39 @@ static inline int ltrx_launch_slate_arrays(LtrxSlateArrays& d, K* lds_kernel, K*
   return LTRX_OK;
 }
 
+// The two layouts of a listwise loss / metric call (ltrx.h, "Ragged layout"), resolved once per workgroup -- the counterpart of
+// which_slate() in ltrx_mha_res.hip.  One kernel body serves both through the template flag RAGGED:
+//   padded: slate b = blockIdx.x owns rows b*L .. b*L+L-1, `len` = L, and a slot is padding where its label equals `pad`;
+//   ragged: slate b = slate_order[blockIdx.x] (or blockIdx.x) owns rows cu[b] .. cu[b+1]-1, every one of them valid; L is max_len, which
+//           only sizes the carve of the work arrays.  A slate longer than max_len is cut to its first max_len items, a negative
+//           extent counts as empty and an order entry outside [0, B) is clamped: whatever the tables hold, a workgroup stays inside
+//           its carve and the rows its cu entries name.
+// The padded instantiation sees len == L and ltrx_is_pad's label compare, i.e. the loop bounds and tests it had before the flag.
+struct LtrxSlate {
+  int b, len;
+  size_t row0;
+};
+template <bool RAGGED>
+__device__ __forceinline__ LtrxSlate ltrx_slate(int L, const int32_t* __restrict__ cu, const int32_t* __restrict__ order) {
+  LtrxSlate s;
+  if (RAGGED) {
+    const int b = order ? order[blockIdx.x] : (int)blockIdx.x;
+    s.b = min(max(b, 0), (int)gridDim.x - 1);
+    const int lo = cu[s.b];
+    s.row0 = (size_t)lo;
+    s.len = min(max(cu[s.b + 1] - lo, 0), L);
+  } else {
+    s.b = blockIdx.x;
+    s.row0 = (size_t)blockIdx.x * L;
+    s.len = L;
+  }
+  return s;
+}
+template <bool RAGGED>
+__device__ __forceinline__ bool ltrx_is_pad(float y, float pad) {
+  return !RAGGED && y == pad;
+}
+
 // Final cross-slate reduction: out[0] = scale * sum_b per[b]  (fixed order -> deterministic).  One block.
 // (host launcher lives in ltrx_common.hip; kernels are never launched across translation units)
 int ltrx_launch_finalize_sum(const float* per, int B, float scale, float* out, hipStream_t s);

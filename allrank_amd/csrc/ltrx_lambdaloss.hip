@@ -70,13 +70,16 @@ static LtrxSlateArrays lambda_arrays{13, 2, lambda_per_floats};
 // 1024 threads per slate: thread (i, q) = (tid & 255 [+256 ...], tid >> 8) owns item i and a quarter of the partner range j;
 // the four partial sums per item are combined through LDS (16 waves per CU instead of 4 hide the exp/log latency).
 // GWS: the thirteen work arrays live in a global workspace (slates too long for LDS; ltrx_device.h)
-template <bool GWS>
+// RAGGED: the cu_seqlens layout (ltrx_device.h: ltrx_slate) -- L is then max_len and sizes the carve only; the pair loops, the partner
+// split and invD run to the slate's own length n, the pad tests fold away, and order_out holds indices inside the slate
+template <bool GWS, bool RAGGED>
 __global__ void __launch_bounds__(1024) ltrx_lambdaloss_kernel(const float* __restrict__ y_pred,
                                                               const float* __restrict__ y_true, int L, float eps,
                                                               float pad, int scheme, int k, float sigma, float mu,
                                                               int logbase, float* __restrict__ per_loss,
                                                               float* __restrict__ per_cnt, float* __restrict__ grad,
-                                                              int64_t* __restrict__ order_out, float* gws, size_t gws_stride) {
+                                                              int64_t* __restrict__ order_out, const int32_t* __restrict__ cu,
+                                                              const int32_t* __restrict__ order, float* gws, size_t gws_stride) {
   extern __shared__ float lds[];
   float* base = GWS ? gws + (size_t)blockIdx.x * gws_stride : lds;
   float* ss = base;                    // [L] scores
@@ -88,31 +91,33 @@ __global__ void __launch_bounds__(1024) ltrx_lambdaloss_kernel(const float* __re
   int* parti = (int*)(base + 9 * L + 2);   // [4][L] int partials (score-rank and label-rank counts packed: rs | ry << 16)
   __shared__ float red[LTRX_MAX_WAVES];
   __shared__ int redi[LTRX_MAX_WAVES];
-  const int b = blockIdx.x;
-  const float* sp = y_pred + (size_t)b * L;
-  const float* yp = y_true + (size_t)b * L;
+  const LtrxSlate sl = ltrx_slate<RAGGED>(L, cu, order);
+  const int b = sl.b;
+  const int n = RAGGED ? sl.len : L;     // items of this slate that the loops visit
+  const float* sp = y_pred + sl.row0;
+  const float* yp = y_true + sl.row0;
   int nv = 0;
-  for (int i = threadIdx.x; i < L; i += blockDim.x) {
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
     ss[i] = sp[i];
     const float y = yp[i];
     ys[i] = y;
-    nv += (y != pad);
+    nv += !ltrx_is_pad<RAGGED>(y, pad);
   }
-  for (int p = threadIdx.x; p < L + 2; p += blockDim.x) invD[p] = (p == 0) ? 0.f : 1.0f / log2f(1.0f + (float)p);
+  for (int p = threadIdx.x; p < n + 2; p += blockDim.x) invD[p] = (p == 0) ? 0.f : 1.0f / log2f(1.0f + (float)p);
   nv = block_sum_i(nv, redi);         // barriers publish ss/ys/invD
-  const int kk = (k <= 0 || k > L) ? L : k;
+  const int kk = (k <= 0 || k > n) ? n : k;
 
   const int q = threadIdx.x >> 8, i0 = threadIdx.x & 255;
-  const int lq = (L + 3) >> 2;
-  const int j0 = q * lq, j1 = min(L, j0 + lq);
+  const int lq = (n + 3) >> 2;
+  const int j0 = q * lq, j1 = min(n, j0 + lq);
   // ---- ranks by score, ideal DCG@k by label rank ----
-  for (int i = i0; i < L; i += 256) {
+  for (int i = i0; i < n; i += 256) {
     const float yi = ys[i], si = ss[i];
     int rs = 0, ry = 0;
-    if (yi != pad)
+    if (!ltrx_is_pad<RAGGED>(yi, pad))
       for (int j = j0; j < j1; ++j) {
         const float yj = ys[j];
-        if (yj == pad) continue;
+        if (ltrx_is_pad<RAGGED>(yj, pad)) continue;
         const float sj = ss[j];
         rs += (sj > si) || (sj == si && j < i);
         ry += (yj > yi) || (yj == yi && j < i);
@@ -122,9 +127,9 @@ __global__ void __launch_bounds__(1024) ltrx_lambdaloss_kernel(const float* __re
   __syncthreads();
   float dsum = 0.f;
   if (q == 0)
-    for (int i = i0; i < L; i += 256) {
+    for (int i = i0; i < n; i += 256) {
       const float yi = ys[i];
-      if (yi == pad) {
+      if (ltrx_is_pad<RAGGED>(yi, pad)) {
         rk[i] = L;
         continue;
       }
@@ -135,16 +140,16 @@ __global__ void __launch_bounds__(1024) ltrx_lambdaloss_kernel(const float* __re
       if (ry < kk) dsum += (exp2f(fmaxf(yi, 0.f)) - 1.0f) * invD[ry + 1];     // lambdaLoss.py:54
     }
   const float maxdcg = fmaxf(block_sum(dsum, red), eps);
-  for (int i = threadIdx.x; i < L; i += blockDim.x) Gs[i] = (ys[i] == pad) ? 0.f : (exp2f(fmaxf(ys[i], 0.f)) - 1.0f) / maxdcg;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) Gs[i] = ltrx_is_pad<RAGGED>(ys[i], pad) ? 0.f : (exp2f(fmaxf(ys[i], 0.f)) - 1.0f) / maxdcg;
   __syncthreads();
   if (order_out) {   // stable descending argsort of the masked predictions: valid by rank, padded after, in index order
-    int64_t* op = order_out + (size_t)b * L;
-    for (int i = threadIdx.x; i < L; i += blockDim.x) {
-      if (ys[i] != pad) {
+    int64_t* op = order_out + sl.row0;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+      if (!ltrx_is_pad<RAGGED>(ys[i], pad)) {
         op[rk[i]] = i;
       } else {
         int before = 0;
-        for (int j = 0; j < i; ++j) before += (ys[j] == pad);
+        for (int j = 0; j < i; ++j) before += ltrx_is_pad<RAGGED>(ys[j], pad);
         op[nv + before] = i;
       }
     }
@@ -161,17 +166,17 @@ __global__ void __launch_bounds__(1024) ltrx_lambdaloss_kernel(const float* __re
   const bool all_pairs = (scheme == LTRX_SCHEME_NDCGLOSS1);
 
   float lsum = 0.f, csum = 0.f;
-  float* gp = grad ? grad + (size_t)b * L : nullptr;
-  for (int i = i0; i < L; i += 256) {
+  float* gp = grad ? grad + sl.row0 : nullptr;
+  for (int i = i0; i < n; i += 256) {
     const float yi = ys[i];
     const int ri = rk[i];
     float gacc = 0.f;
-    if (yi != pad && ri < kk) {
+    if (!ltrx_is_pad<RAGGED>(yi, pad) && ri < kk) {
       const float si = ss[i], Gi = Gs[i], yci = fmaxf(yi, 0.f);
       for (int j = j0; j < j1; ++j) {
         const float yj = ys[j];
         const int rj = rk[j];
-        if (yj == pad || rj >= kk) continue;
+        if (ltrx_is_pad<RAGGED>(yj, pad) || rj >= kk) continue;
         const bool fwd = all_pairs || (yi > yj);          // pair (i, j): i is the "first" element
         const bool bwd = (j != i) && (all_pairs || (yj > yi));   // pair (j, i): i is the "second" element
         if (!(fwd || bwd)) continue;
@@ -196,7 +201,7 @@ __global__ void __launch_bounds__(1024) ltrx_lambdaloss_kernel(const float* __re
   }
   __syncthreads();
   if (gp && q == 0)
-    for (int i = i0; i < L; i += 256) gp[i] = (part[i] + part[L + i]) + (part[2 * L + i] + part[3 * L + i]);
+    for (int i = i0; i < n; i += 256) gp[i] = (part[i] + part[L + i]) + (part[2 * L + i] + part[3 * L + i]);
   lsum = block_sum(lsum, red);
   csum = block_sum(csum, red);
   if (threadIdx.x == 0) {
@@ -229,19 +234,22 @@ __global__ void __launch_bounds__(256) ltrx_lambdaloss_finalize_kernel(const flo
   }
 }
 
+// x[0..n) *= scale[0]; n_dev (optional, device): the element count is min(n, n_dev[0]) -- the ragged layout's row count cu[B]
 __global__ void __launch_bounds__(256) ltrx_scale_by_device_scalar_kernel(float* __restrict__ x, size_t n,
-                                                                          const float* __restrict__ scale) {
+                                                                          const float* __restrict__ scale,
+                                                                          const int32_t* __restrict__ n_dev) {
   const float sc = scale[0];
+  if (n_dev) n = min(n, (size_t)max(n_dev[0], 0));
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) x[i] *= sc;
 }
 
 extern "C" size_t ltrx_lambdaloss_workspace_bytes(int B, int L) { return lambda_arrays.workspace_bytes(B, L); }
 
-extern "C" int ltrx_lambdaloss_fwd_bwd(const float* y_pred, const float* y_true, int B, int L, float eps,
-                                       float pad_value, int scheme, int k, float sigma, float mu, int reduction,
-                                       int logbase, const float* ext_pair_count, float* loss_out,
-                                       float* pair_count_out, float* grad_out, int64_t* order_out, void* ws,
-                                       ltrx_stream_t stream) {
+// one host path for both layouts: cu == NULL is the padded call
+static int lambdaloss_launch(const float* y_pred, const float* y_true, const int32_t* cu, const int32_t* order, int B, int L, float eps,
+                             float pad_value, int scheme, int k, float sigma, float mu, int reduction, int logbase,
+                             const float* ext_pair_count, float* loss_out, float* pair_count_out, float* grad_out, int64_t* order_out,
+                             void* ws, ltrx_stream_t stream) {
   if (!y_pred || !y_true || !loss_out || !ws || B <= 0 || L <= 0) return LTRX_EINVAL;
   if (scheme < 0 || scheme > LTRX_SCHEME_RANKNET_GTDIFF_POWED) return LTRX_EINVAL;
   if (reduction != LTRX_REDUCE_SUM && reduction != LTRX_REDUCE_MEAN) return LTRX_EINVAL;
@@ -252,19 +260,40 @@ extern "C" int ltrx_lambdaloss_fwd_bwd(const float* y_pred, const float* y_true,
   float* per_loss = (float*)ws;
   float* per_cnt = per_loss + B;
   float* scale = per_cnt + B;
-  const int rc = ltrx_launch_slate_arrays(lambda_arrays, ltrx_lambdaloss_kernel<false>, ltrx_lambdaloss_kernel<true>, B, L, dim3(1024), per_loss,
-                                          s, y_pred, y_true, L, eps, pad_value, scheme, k, sigma, mu, logbase, per_loss, per_cnt, grad_out,
-                                          order_out);
+  const int rc = cu ? ltrx_launch_slate_arrays(lambda_arrays, ltrx_lambdaloss_kernel<false, true>, ltrx_lambdaloss_kernel<true, true>, B, L,
+                                               dim3(1024), per_loss, s, y_pred, y_true, L, eps, pad_value, scheme, k, sigma, mu, logbase,
+                                               per_loss, per_cnt, grad_out, order_out, cu, order)
+                    : ltrx_launch_slate_arrays(lambda_arrays, ltrx_lambdaloss_kernel<false, false>, ltrx_lambdaloss_kernel<true, false>, B, L,
+                                               dim3(1024), per_loss, s, y_pred, y_true, L, eps, pad_value, scheme, k, sigma, mu, logbase,
+                                               per_loss, per_cnt, grad_out, order_out, cu, order);
   if (rc != LTRX_OK) return rc;
   hipLaunchKernelGGL(ltrx_lambdaloss_finalize_kernel, dim3(1), dim3(256), 0, s, per_loss, per_cnt, B, reduction,
                      ext_pair_count, loss_out, pair_count_out, scale);
   LTRX_LAUNCH_CHECK();
   if (grad_out && reduction == LTRX_REDUCE_MEAN) {
-    const size_t n = (size_t)B * L;
+    const size_t n = (size_t)B * L;          // ragged: an upper bound of the row count, which the kernel reads from cu[B]
     int blocks = (int)((n + 255) / 256);
     if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(ltrx_scale_by_device_scalar_kernel, dim3(blocks), dim3(256), 0, s, grad_out, n, scale);
+    hipLaunchKernelGGL(ltrx_scale_by_device_scalar_kernel, dim3(blocks), dim3(256), 0, s, grad_out, n, scale, cu ? cu + B : nullptr);
     LTRX_LAUNCH_CHECK();
   }
   return LTRX_OK;
+}
+
+extern "C" int ltrx_lambdaloss_fwd_bwd(const float* y_pred, const float* y_true, int B, int L, float eps,
+                                       float pad_value, int scheme, int k, float sigma, float mu, int reduction,
+                                       int logbase, const float* ext_pair_count, float* loss_out,
+                                       float* pair_count_out, float* grad_out, int64_t* order_out, void* ws,
+                                       ltrx_stream_t stream) {
+  return lambdaloss_launch(y_pred, y_true, nullptr, nullptr, B, L, eps, pad_value, scheme, k, sigma, mu, reduction, logbase, ext_pair_count,
+                           loss_out, pair_count_out, grad_out, order_out, ws, stream);
+}
+
+extern "C" int ltrx_lambdaloss_fwd_bwd_cu(const float* y_pred, const float* y_true, const int32_t* cu_seqlens, const int32_t* slate_order,
+                                          int B, int max_len, float eps, int scheme, int k, float sigma, float mu, int reduction,
+                                          int logbase, const float* ext_pair_count, float* loss_out, float* pair_count_out,
+                                          float* grad_out, int64_t* order_out, void* ws, ltrx_stream_t stream) {
+  if (!cu_seqlens) return LTRX_EINVAL;
+  return lambdaloss_launch(y_pred, y_true, cu_seqlens, slate_order, B, max_len, eps, 0.f, scheme, k, sigma, mu, reduction, logbase,
+                           ext_pair_count, loss_out, pair_count_out, grad_out, order_out, ws, stream);
 }

@@ -312,29 +312,42 @@ extern "C" int ltrx_binary_listnet_fwd_bwd(const float* y_pred, const float* y_t
 // -inf, padded labels 0); (value, index) = first maximum of that sequence; 1/(index+1) if index < at else 0.  The
 // reference zeroes the WHOLE result when the batch sum of the maxima is 0 (metrics.py:108-109: a 0-dim mask) -- kept.
 // ---------------------------------------------------------------------------------------------------------------
+// RAGGED: the cu_seqlens layout (ltrx_device.h: ltrx_slate) -- L is then max_len (the carve), the loops run to the slate's length n;
+// an empty slate gives (0, 0), what an all-padded one gives
+template <bool RAGGED>
 __global__ void __launch_bounds__(256) ltrx_mrr_slate_kernel(const float* __restrict__ y_pred, const float* __restrict__ y_true,
                                                              int L, float pad, float* __restrict__ best_val,
-                                                             int* __restrict__ best_idx) {
+                                                             int* __restrict__ best_idx, const int32_t* __restrict__ cu,
+                                                             const int32_t* __restrict__ order) {
   extern __shared__ float lds[];
   float* ss = lds;
   float* ys = lds + L;
   __shared__ float red[LTRX_MAX_WAVES];
-  const int b = blockIdx.x;
+  const LtrxSlate sl = ltrx_slate<RAGGED>(L, cu, order);
+  const int b = sl.b;
+  const int n = RAGGED ? sl.len : L;
+  if (RAGGED && n == 0) {                         // (uniform: before any barrier)
+    if (threadIdx.x == 0) {
+      best_val[b] = 0.f;
+      best_idx[b] = 0;
+    }
+    return;
+  }
   float ymax = -INFINITY;
-  for (int i = threadIdx.x; i < L; i += blockDim.x) {
-    const float y = y_true[(size_t)b * L + i];
-    const bool valid = (y != pad);
-    ss[i] = valid ? y_pred[(size_t)b * L + i] : -INFINITY;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const float y = y_true[sl.row0 + i];
+    const bool valid = !ltrx_is_pad<RAGGED>(y, pad);
+    ss[i] = valid ? y_pred[sl.row0 + i] : -INFINITY;
     ys[i] = valid ? y : 0.f;
     ymax = fmaxf(ymax, ys[i]);
   }
   ymax = block_max(ymax, red);
-  int best = L;                                   // smallest rank among the items that carry the maximum label
-  for (int i = threadIdx.x; i < L; i += blockDim.x) {
+  int best = n;                                   // smallest rank among the items that carry the maximum label
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
     if (ys[i] != ymax) continue;
     const float si = ss[i];
     int r = 0;
-    for (int j = 0; j < L; ++j) {
+    for (int j = 0; j < n; ++j) {
       const float sj = ss[j];
       r += (sj > si) || (sj == si && j < i);
     }
@@ -369,8 +382,9 @@ extern "C" size_t ltrx_mrr_workspace_bytes(int B, int L, int n_ats) {
   return (size_t)(B > 0 ? B : 0) * 8 + 64;
 }
 
-extern "C" int ltrx_mrr_at(const float* y_pred, const float* y_true, int B, int L, const int* ats, int n_ats, float pad_value,
-                           float* mrr_out, void* ws, ltrx_stream_t stream) {
+// one host path for both layouts: cu == NULL is the padded call, L the ragged call's max_len
+static int mrr_launch(const float* y_pred, const float* y_true, const int32_t* cu, const int32_t* order, int B, int L, const int* ats,
+                      int n_ats, float pad_value, float* mrr_out, void* ws, ltrx_stream_t stream) {
   if (!y_pred || !y_true || !ats || !mrr_out || !ws || B <= 0 || L <= 0 || n_ats <= 0) return LTRX_EINVAL;
   if (n_ats > LTRX_MAX_ATS || L > LTRX_MAX_METRIC_SLATE_LEN) return LTRX_EUNSUPPORTED;   // 8 B of LDS per item: 64 KB at the limit
   hipStream_t s = (hipStream_t)stream;
@@ -379,10 +393,25 @@ extern "C" int ltrx_mrr_at(const float* y_pred, const float* y_true, int B, int 
   LtrxAts dats;
   dats.n = n_ats;
   for (int i = 0; i < n_ats; ++i) dats.at[i] = ats[i];
-  hipLaunchKernelGGL(ltrx_mrr_slate_kernel, dim3(B), dim3(256), 2 * (size_t)L * sizeof(float), s, y_pred, y_true, L, pad_value,
-                     bv, bi);
+  if (cu)
+    hipLaunchKernelGGL(ltrx_mrr_slate_kernel<true>, dim3(B), dim3(256), 2 * (size_t)L * sizeof(float), s, y_pred, y_true, L, pad_value,
+                       bv, bi, cu, order);
+  else
+    hipLaunchKernelGGL(ltrx_mrr_slate_kernel<false>, dim3(B), dim3(256), 2 * (size_t)L * sizeof(float), s, y_pred, y_true, L, pad_value,
+                       bv, bi, cu, order);
   LTRX_LAUNCH_CHECK();
   hipLaunchKernelGGL(ltrx_mrr_finalize_kernel, dim3(1), dim3(256), 0, s, bv, bi, B, dats, mrr_out);
   LTRX_LAUNCH_CHECK();
   return LTRX_OK;
+}
+
+extern "C" int ltrx_mrr_at(const float* y_pred, const float* y_true, int B, int L, const int* ats, int n_ats, float pad_value,
+                           float* mrr_out, void* ws, ltrx_stream_t stream) {
+  return mrr_launch(y_pred, y_true, nullptr, nullptr, B, L, ats, n_ats, pad_value, mrr_out, ws, stream);
+}
+
+extern "C" int ltrx_mrr_at_cu(const float* y_pred, const float* y_true, const int32_t* cu_seqlens, const int32_t* slate_order, int B,
+                              int max_len, const int* ats, int n_ats, float* mrr_out, void* ws, ltrx_stream_t stream) {
+  if (!cu_seqlens) return LTRX_EINVAL;
+  return mrr_launch(y_pred, y_true, cu_seqlens, slate_order, B, max_len, ats, n_ats, 0.f, mrr_out, ws, stream);
 }

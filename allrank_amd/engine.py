@@ -1540,7 +1540,9 @@ class FusedScorer(object):
         (``_Stager``): no host sync.  ``run`` without host lengths counts the valid items on the device -- one sync, as compact
         training does.
     Results (``scores_raw`` [B, L] or [B, L, d_output], ``scores`` [B, L], labels ``y`` [B, L] of ``run_resident``) stay valid until
-    the next call."""
+    the next call.  ``packed()`` gives the same batch in the ragged layout of allrank_amd.ragged -- the packed scores the forward
+    wrote (before the scatter), the packed labels, ``cu``, ``order`` and the batch's host ``max_len`` -- for a loss and metrics that
+    run on the valid items only."""
 
     def __init__(self, trainer, B, L, use_graph=True, max_graphs=8):
         from . import _lib as LB
@@ -1556,6 +1558,8 @@ class FusedScorer(object):
         self.ids = self._stager.ids
         self.rows, self.n_valid = 32, 0
         self.y = torch.full((B, L), float(PADDED_Y_VALUE), dtype=torch.float32, device=t.dev)
+        self.y_c = torch.zeros(self.cap, dtype=torch.float32, device=t.dev)     # the labels of the packed rows (``packed()``)
+        self.max_len, self._y_c_fresh = 0, False           # longest slate of the last batch (host); y_c holds that batch's labels
         seen, nb = set(), 0
         for v in list(vars(self).values()) + [v for st in self.layers for v in st.values()]:
             if torch.is_tensor(v) and v.is_cuda and v.untyped_storage().data_ptr() not in seen:
@@ -1576,6 +1580,7 @@ class FusedScorer(object):
             raise ValueError("FusedScorer: %d slates in a batch of a %d-slate scorer" % (n, self.B))
         if n and int(lens.max()) > self.L:
             raise ValueError("FusedScorer: a slate of %d items in a scorer for slate length %d" % (int(lens.max()), self.L))
+        self.max_len = max(int(lens.max()), 0) if n else 0
         return self._stager.upload(lens.clamp(min=0), None if ids is None else torch.as_tensor(ids, dtype=torch.int64).cpu())
 
     def _set_rows(self, n):
@@ -1628,7 +1633,7 @@ class FusedScorer(object):
             self.cu[0] = 0
             torch.cumsum(full, 0, dtype=torch.int32, out=self.cu[1:])
             self.order.copy_(torch.argsort(full, descending=True, stable=True))
-            n = int(self.cu[B])                            # (host sync: the row count picks the bucket)
+            n, self.max_len = (int(v) for v in torch.stack([self.cu[B], full.max()]).tolist())     # (host sync: the row count picks the bucket)
         self._set_rows(n)
         self.y[:n_sl].copy_(yb)
         self.y[n_sl:].fill_(float(PADDED_Y_VALUE))
@@ -1643,7 +1648,22 @@ class FusedScorer(object):
         self._run()
         return self.scores_raw
 
+    def packed(self):
+        """The last batch in the ragged layout (include/ltrx.h): (scores [n], labels [n], cu_seqlens [B+1], launch order [B], host
+        max_len).  The scores are the rows the forward wrote before scattering them (d_output == 1), the labels are packed from
+        ``self.y`` on the first call after a run; both stay valid until the next run."""
+        if self.t.n_out != 1:
+            raise NotImplementedError("FusedScorer.packed: d_output > 1 (the ordinal loss reads the padded grid)")
+        if not self._y_c_fresh:
+            LB, P = self.LB, self.LB.ptr
+            LB.check(self.t.lib.ltrx_gather_rows_cu(P(self.y), 1, P(self.cu), self.B, self.L, 1, self.rows, P(self.y_c), 1, None,
+                                                    self.t._st()), "gather_rows_cu(labels)")
+            self._y_c_fresh = True
+        n = self.n_valid
+        return self.scores_c[:n], self.y_c[:n], self.cu, self.order, self.max_len
+
     def _run(self):
+        self._y_c_fresh = False
         fwd = lambda: self.t._forward(False, self)
         if self.use_graph:
             self.last_mode = self._fwd_graphs.run(self.rows, fwd)

@@ -19,7 +19,9 @@ What changes (all outside the arithmetic of a step):
   * no ``loss.item()`` per step: the running loss is accumulated on the device, one host sync per epoch (train_utils.py:29);
   * the validation pass runs through ``FusedTrainer.score`` (the forward half of the explicit step, dropout off, its own hipGraph)
     instead of the nn.Module forward; with ``val_scorer="packed"`` (or ALLRANK_AMD_VAL_SCORER=packed) every validation batch,
-    whatever its slate length, runs the packed, captured forward-only scorer (engine.FusedScorer) on its valid items only;
+    whatever its slate length, runs the packed, captured forward-only scorer (engine.FusedScorer) on its valid items only; with
+    ``val_scorer="ragged"`` the loss and the metrics of those batches run on the valid items too (allrank_amd.ragged: the cu_seqlens
+    layout of the loss and metric kernels) wherever they have a ragged form, and on the padded grid as under "packed" otherwise;
   * train metrics come from the scores of the training forward itself instead of a second full pass over ``train_dl`` in train()
     mode (train_utils.py:99; same mode, same data).  ``train_metrics="reference"`` (or the environment variable
     ALLRANK_AMD_TRAIN_METRICS=reference -- main.py passes only config.training's keys) runs the reference's second pass instead: one
@@ -51,6 +53,7 @@ import torch
 
 from . import losses as E
 from . import metrics as EM
+from . import ragged as RG
 from .data import ShardBatch
 from .engine import FusedTrainer, Trainer, PADDED_Y_VALUE, pad_batch as _pad_batch
 from .parallel import shard_slates
@@ -275,7 +278,17 @@ def _val_scorer(scorers, trainer, n, L):
     return s
 
 
-def _evaluate(model, loss_func, dl, device, metrics, trainer=None, world=1, rank=0, scorers=None):
+def _ragged_plan(loss_func, trainer, metrics):
+    """what fit(val_scorer="ragged") evaluates on the packed rows: {"loss": the ragged form of ``loss_func`` or None, "metrics": the
+    metric names with a ragged form}.  A model with d_output > 1 (ordinal) keeps everything on the padded grid: its loss reads
+    [B, L, d_output] scores."""
+    if getattr(trainer, "n_out", 1) != 1:
+        return {"loss": None, "metrics": ()}
+    return {"loss": RG.form_of(loss_func) if loss_func is not None else None,
+            "metrics": tuple(name for name in metrics if RG.form_of(getattr(EM, name, None)) is not None)}
+
+
+def _evaluate(model, loss_func, dl, device, metrics, trainer=None, world=1, rank=0, scorers=None, ragged=None):
     """validation pass of train_utils.py:101-107: mean loss (weighted by batch size) and metric means, no autograd.  With a
     FusedTrainer the scores come from its forward-only pass (``FusedTrainer.score``: the kernels of the training step, dropout
     off, hipGraph replay) instead of the nn.Module forward (fp32 library GEMMs).
@@ -283,6 +296,9 @@ def _evaluate(model, loss_func, dl, device, metrics, trainer=None, world=1, rank
     (kept in the dict across epochs) -- straight from the resident set when the loader is a packable DeviceLoader
     (``id_batches``), else from the padded batch; slates above LTRX_MAX_METRIC_SLATE_LEN take the nn.Module path and
     ``last_run["val_scorer_reason"]`` says so.
+    ``ragged`` (a ``_ragged_plan``, fit(val_scorer="ragged")): for the batches a scorer ran, the loss and the metrics the plan names
+    are computed from ``FusedScorer.packed()`` -- packed scores and labels, cu_seqlens, launch order, the batch's own longest slate --
+    instead of the grid padded to the set's longest slate; same values (the ragged contract, include/ltrx.h), same accumulation.
     Sharded (``world`` > 1, round 5): every rank scores its contiguous block of each validation batch -- the same partition as the
     training step -- under ``shard_context(global batch)``, so its loss is its share of the reference's loss on the whole batch
     (global divisors / normalisers); shares, slate counts and per-slate metric sums are all-reduced once at the end, and
@@ -297,11 +313,13 @@ def _evaluate(model, loss_func, dl, device, metrics, trainer=None, world=1, rank
                 and loader.slate_length <= LB.MAX_METRIC_SLATE_LEN)
     with torch.no_grad():
         for batch in (loader.id_batches() if resident else pf):
+            pk = None                                                 # the scorer whose packed batch the ragged plan may read
             if resident:                                              # packed straight from the resident set: no padded features
                 n, n_glob = len(batch.ids), batch.global_slates
                 scorer = _val_scorer(scorers, trainer, -(-loader.batch_size // world), loader.slate_length)
                 scorer.run_resident(batch.slates, batch.ids, batch.lengths)
                 sc, out, yl, yb = scorer.scores[:n], scorer.scores_raw[:max(n, 1)], scorer.y[:max(n, 1)], scorer.y
+                pk = scorer
             else:
                 xb, yb, idx, n_glob, pre = _my_block(batch, loader, rank, world)
                 n = int(xb.shape[0])
@@ -310,6 +328,7 @@ def _evaluate(model, loss_func, dl, device, metrics, trainer=None, world=1, rank
                     lens = getattr(batch, "lengths", None) if (pre is not None or world == 1) else None
                     scorer.run(xb, yb, idx, lengths=lens if lens is not None and int(lens.numel()) == n else None)
                     sc, out, yl = scorer.scores[:n], scorer.scores_raw[:max(n, 1)], scorer.y[:max(n, 1)]
+                    pk = scorer
                 elif trainer is not None and scorers is None and n <= trainer.B and tuple(xb.shape[1:2]) == (trainer.L,):
                     xs, ys, ids = _pad_batch(xb, yb, idx, trainer.B)
                     sc = trainer.score(xs, ys, ids, lengths=_host_lengths(batch, trainer, n, pre, world))[:n]
@@ -326,18 +345,32 @@ def _evaluate(model, loss_func, dl, device, metrics, trainer=None, world=1, rank
                     out = model(xb, mask, idx)
                     sc = (out if out.dim() == 2 else model.score(xb, mask, idx))[:n]
                     yl = yb
+            rag_loss, rag_metrics, call = None, (), lambda: loss_func(out, yl)
+            if ragged is not None and pk is not None:
+                rag_loss, rag_metrics = ragged["loss"], ragged["metrics"]
+                if rag_loss is not None or (rag_metrics and n > 0):
+                    s_p, y_p, cu, order, max_len = pk.packed()
+                    # the batch's slates (one empty slate for an empty shard, as the padded path's one padded slate); the launch order
+                    # covers the scorer's B slates, so a short batch goes without it
+                    lay = lambda k: dict(cu_seqlens=cu[:k + 1], max_len=max(max_len, 1), slate_order=order if k == pk.B else None)
+                    call = lambda: rag_loss(s_p, y_p, **lay(max(n, 1)))
+            elif ragged is not None:
+                last_run["val_eval"] = {"loss": "padded", "metrics": "padded"}      # a batch no scorer could take: the module path
             if loss_func is None:                                     # (metrics only: the reference's compute_metrics pass)
                 share = tot.new_zeros(())
             elif world > 1:
                 with sharding.shard_context(n_glob):
-                    share = loss_func(out, yl).detach().float()
+                    share = (call() if rag_loss is not None else loss_func(out, yl)).detach().float()
             else:
-                share = loss_func(out, yl).detach().float()
+                share = (call() if rag_loss is not None else loss_func(out, yl)).detach().float()
             tot += share.reshape(()) * n_glob
             num += n
             if n > 0:
                 for name, ats in metrics.items():
-                    v = getattr(EM, name)(sc, yb[:n], ats=ats).sum(0)
+                    if name in rag_metrics:
+                        v = getattr(RG, name)(s_p, y_p, ats=ats, **lay(n)).sum(0)
+                    else:
+                        v = getattr(EM, name)(sc, yb[:n], ats=ats).sum(0)
                     acc[name] = v if acc[name] is None else acc[name] + v
     sums = [acc[name].float() if acc[name] is not None else torch.zeros(len(metrics[name]), device=device) for name in metrics]
     stats = torch.cat([tot.reshape(1), torch.tensor([float(num)], device=device)] + sums)
@@ -386,8 +419,11 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
     train_utils.py:99; check_finite: None = ``config.detect_anomaly`` or LTRX_CHECK_FINITE=1, see the module docstring; val_scorer:
     "module" (default) = the validation batches of another slate length than the training step's run the nn.Module forward,
     "packed" = every validation batch runs the packed, captured forward-only scorer of the fused step (engine.FusedScorer; the
-    environment variable ALLRANK_AMD_VAL_SCORER=packed does the same under main.py), ``last_run["val_scorer"]`` says which one ran
-    and ``last_run["val_scorer_reason"]`` why the packed one could not)."""
+    environment variable ALLRANK_AMD_VAL_SCORER=packed does the same under main.py), "ragged" = "packed", and the loss and the
+    ndcg / dcg / mrr metrics of those batches run on the packed rows as well (allrank_amd.ragged) -- the loss when
+    ``ragged.form_of(loss_func)`` exists, anything else on the padded grid exactly as under "packed";
+    ``last_run["val_scorer"]`` says which one ran, ``last_run["val_scorer_reason"]`` why the packed one could not, and
+    ``last_run["val_eval"]`` = {"loss": "ragged" | "padded", "metrics": "ragged" | "padded"} what the "ragged" scorer evaluated on)."""
     import torch.distributed as dist
     device = torch.device(device)
     world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
@@ -408,8 +444,8 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
     if train_metrics_mode not in ("fused", "reference"):
         raise ValueError("train_metrics must be 'fused' or 'reference', got %r" % (train_metrics_mode,))
     val_scorer_mode = (val_scorer or os.environ.get("ALLRANK_AMD_VAL_SCORER") or "module").lower()
-    if val_scorer_mode not in ("module", "packed"):
-        raise ValueError("val_scorer must be 'module' or 'packed', got %r" % (val_scorer_mode,))
+    if val_scorer_mode not in ("module", "packed", "ragged"):
+        raise ValueError("val_scorer must be 'module', 'packed' or 'ragged', got %r" % (val_scorer_mode,))
     if check_finite is None:
         check_finite = bool(getattr(config, "detect_anomaly", False)) or os.environ.get("LTRX_CHECK_FINITE", "0") not in ("", "0")
     writer = _tensorboard(tensorboard_output_path) if tensorboard_output_path else None
@@ -436,9 +472,13 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
     last_run.update(engine="fused" if fused else "autograd", compact=bool(trainer.compact) if fused else False, reason=reason,
                     fcstep=getattr(trainer, "fcstep", False), sampling=getattr(train_dl, "sampling", None))
     log.info("allrank_amd.fit: %s step%s", last_run["engine"], (" (" + reason + ")") if reason else "")
-    vs_reason = _packed_blocker(loss_func, fused, reason) if val_scorer_mode == "packed" else ""
-    scorers = {} if val_scorer_mode == "packed" and not vs_reason else None
-    last_run.update(val_scorer="packed" if scorers is not None else "module", val_scorer_reason=vs_reason)
+    vs_reason = _packed_blocker(loss_func, fused, reason) if val_scorer_mode in ("packed", "ragged") else ""
+    scorers = {} if val_scorer_mode in ("packed", "ragged") and not vs_reason else None
+    last_run.update(val_scorer=val_scorer_mode if scorers is not None else "module", val_scorer_reason=vs_reason)
+    rag_plan = _ragged_plan(loss_func, trainer, metrics) if val_scorer_mode == "ragged" and scorers is not None else None
+    if rag_plan is not None:
+        last_run["val_eval"] = {"loss": "ragged" if rag_plan["loss"] is not None else "padded",
+                                "metrics": "ragged" if rag_plan["metrics"] else "padded"}
     if vs_reason:
         log.info("allrank_amd.fit: validation through the nn.Module forward (%s)", vs_reason)
 
@@ -507,7 +547,8 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
 
         model.eval()
         t_val = time.perf_counter()
-        val_loss, val_metrics = _evaluate(model, loss_func, valid_pf, device, metrics, trainer if fused else None, world, rank, scorers)
+        val_loss, val_metrics = _evaluate(model, loss_func, valid_pf, device, metrics, trainer if fused else None, world, rank, scorers,
+                                          rag_plan)
         _burn(valid_dl, len(metrics))                              # train_utils.py:107 iterates valid_dl once more per metric name
         last_run["epoch_log"].append({"train_s": t_train, "val_s": time.perf_counter() - t_val, "slates": int(stats[1]),
                                       "slots": int(slots), "val_loss": val_loss})

@@ -41,9 +41,12 @@ class _FusedLoss(torch.autograd.Function):
         return grad * g, None, None
 
 
-def _prep(y_pred, y_true, n=None):
-    """shape and device checks; (float32 contiguous scores, labels, whether a gradient is wanted).  ``n``: ordinal's [B, L, n] scores"""
-    if n is None and (y_pred.dim() != 2 or y_pred.shape != y_true.shape):
+def _prep(y_pred, y_true, n=None, ragged=False):
+    """shape and device checks; (float32 contiguous scores, labels, whether a gradient is wanted).  ``n``: ordinal's [B, L, n] scores;
+    ``ragged``: the [n] tensors of the cu_seqlens layout (allrank_amd.ragged)"""
+    if ragged and (y_pred.dim() != 1 or y_pred.shape != y_true.shape):
+        raise ValueError("y_pred and y_true must both be [n], the valid items of the batch's slates one after the other")
+    if n is None and not ragged and (y_pred.dim() != 2 or y_pred.shape != y_true.shape):
         raise ValueError("y_pred and y_true must both be [batch_size, slate_length]")
     if n is not None and (y_pred.dim() != 3 or y_pred.shape[:2] != y_true.shape or y_pred.shape[2] != n):
         raise ValueError("y_pred must be [batch_size, slate_length, n] and y_true [batch_size, slate_length]")
@@ -72,10 +75,11 @@ def _buffers(fam, B, SL, device, a, new):
     return bufs
 
 
-def _call(fam, y_pred, y_true, a, n=None, **given):
-    """a plugin call: fresh buffers (plus the ``given`` ones), the family's launcher, the autograd node"""
-    yp, yt, need_grad = _prep(y_pred, y_true, n)
-    B, SL = yt.shape
+def _call(fam, y_pred, y_true, a, n=None, shape=None, **given):
+    """a plugin call: fresh buffers (plus the ``given`` ones), the family's launcher, the autograd node.  ``shape``: (slates, max_len)
+    of a call in the cu_seqlens layout (allrank_amd.ragged), whose tensors are [n] and do not carry it"""
+    yp, yt, need_grad = _prep(y_pred, y_true, n, ragged=shape is not None)
+    B, SL = shape if shape is not None else yt.shape
     bufs = dict(_buffers(fam, B, SL, yp.device, a, torch.empty), **given)
     grad = torch.empty_like(yp) if need_grad else None
     fam.launch(yp, yt, a, sharding.batch_divisor(B), grad=grad, **bufs)

@@ -209,6 +209,43 @@ int ltrx_mrr_at(const float* y_pred, const float* y_true, int B, int L, const in
                 float* mrr_out, void* ws, ltrx_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Ragged layout of the listwise losses and metrics (*_cu): a batch evaluated on its valid items only, as ltrx_mha_fwd takes it.
+ *   - y_pred[n], y_true[n], grad_out[n] (and order_out[n]) hold only valid items; slate b is rows cu_seqlens[b] .. cu_seqlens[b+1]-1,
+ *     cu_seqlens = i32[B+1] in device memory, n = cu_seqlens[B].  Every packed row is valid: there is no pad_value, and no label
+ *     is compared with one.
+ *   - slate_order (i32[B] in device memory, or NULL): the launch order of the slates -- longest first balances the CUs; results
+ *     do not depend on it.
+ *   - max_len (host): an upper bound of every slate's length in the call.  It sizes the work arrays (LDS, or the workspace beyond
+ *     the CU's 160 KB), the workspace is the padded namesake's *_workspace_bytes(B, max_len), and the limits apply to it:
+ *     LTRX_MAX_LONG_SLATE_LEN for the losses, LTRX_MAX_METRIC_SLATE_LEN for the metrics, LTRX_EUNSUPPORTED beyond.  A slate longer
+ *     than max_len is the caller's error; it is evaluated as its first max_len items, so no access leaves the call's buffers.
+ *   - a slate of length 0 is legal and gives what the padded call gives for a fully padded slate: loss contribution 0 (listNet,
+ *     approxNDCG, lambdaLoss: no pair), ndcg = filler_value, dcg = 0, and for mrr the first maximum (label 0 at rank 0), i.e. the
+ *     reciprocal rank 1 that metrics.py:100-107 gives a slate without relevant items, subject to the batch-wide rule below.
+ *   - contract: each call returns what its padded namesake returns on the [B, L] grid that holds every slate's items first and
+ *     pad_value after them, for any L >= max_len (same kernel bodies, loops bounded by the slate's length instead of L).
+ *     per_slate_out[B], ndcg_out / dcg_out / mrr_out[B, n_ats] are indexed by slate; order_out[n] (int64) holds, at each sorted
+ *     position of a slate's rows, the item's index INSIDE its slate.  Other arguments as in the padded call.
+ * ------------------------------------------------------------------------------------------- */
+int ltrx_listnet_fwd_bwd_cu(const float* y_pred, const float* y_true, const int32_t* cu_seqlens, const int32_t* slate_order, int B,
+                            int max_len, float eps, float batch_divisor, float* loss_out, float* per_slate_out, float* grad_out,
+                            void* ws, ltrx_stream_t stream);
+int ltrx_approxndcg_fwd_bwd_cu(const float* y_pred, const float* y_true, const int32_t* cu_seqlens, const int32_t* slate_order, int B,
+                               int max_len, float eps, float alpha, float batch_divisor, float* loss_out, float* per_slate_out,
+                               float* grad_out, void* ws, ltrx_stream_t stream);
+int ltrx_lambdaloss_fwd_bwd_cu(const float* y_pred, const float* y_true, const int32_t* cu_seqlens, const int32_t* slate_order, int B,
+                               int max_len, float eps, int scheme, int k, float sigma, float mu, int reduction, int logbase,
+                               const float* ext_pair_count, float* loss_out, float* pair_count_out, float* grad_out,
+                               int64_t* order_out, void* ws, ltrx_stream_t stream);
+/* default gain 2^y - 1 (a caller-supplied gain_function has no ragged form); ats[i] above a slate's length counts as its length */
+int ltrx_ndcg_at_cu(const float* y_pred, const float* y_true, const int32_t* cu_seqlens, const int32_t* slate_order, int B,
+                    int max_len, const int* ats, int n_ats, float filler_value, float* ndcg_out, float* dcg_out, int64_t* order_out,
+                    void* ws, ltrx_stream_t stream);
+/* the batch-wide rule of metrics.py:108-109 (sum of the slates' maximum labels == 0 -> all zeros) is kept; ws: ltrx_mrr_workspace_bytes */
+int ltrx_mrr_at_cu(const float* y_pred, const float* y_true, const int32_t* cu_seqlens, const int32_t* slate_order, int B, int max_len,
+                   const int* ats, int n_ats, float* mrr_out, void* ws, ltrx_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Scoring model kernels (allrank/models/transformer.py).
  * ------------------------------------------------------------------------------------------- */
 

@@ -1,8 +1,10 @@
 """One validation pass at the reference's validation shape, three ways: the nn.Module forward over the padded batches (what
 ``fit`` runs for validation slates longer than the training slates), and the packed scorer (engine.FusedScorer) eager and
-captured -- plus one ``fit()`` epoch of a WEB30K-fold-sized job with each scorer.
+captured -- plus ``ragged``: the captured scorer with the loss and the metrics on the packed rows as well
+(fit(val_scorer="ragged"), allrank_amd.ragged) -- and one ``fit()`` epoch of a WEB30K-fold-sized job with each scorer.
 
-    python tools/val_timing.py [--models c3,nn96] [--batches 64,256] [--reps 3] [--epoch] [--only PATH] [--json OUT]
+    python tools/val_timing.py [--models c3,nn96] [--batches 64,256] [--reps 3] [--paths module,captured,ragged] [--epoch]
+                               [--only PATH] [--json OUT]
 
 Set: a WEB30K-vali-shaped set of 6,306 slates, lengths round(lognormal(ln 100, 0.6)) clipped to [1, 1251] (bench.py's
 ``_web30k_lengths``), 136 features on the 4-decimal grid of [0, 1), labels ~ Cat(.52, .32, .13, .02, .01), resident in HBM and read
@@ -78,6 +80,8 @@ def one_pass(path, model, ft, loader, scorers, loss, metrics):
     if path == "module":
         model.eval()
         vl, vm = EF._evaluate(model, loss, loader, DEV, metrics)
+    elif path == "ragged":
+        vl, vm = EF._evaluate(model, loss, loader, DEV, metrics, ft, 1, 0, scorers[path], EF._ragged_plan(loss, ft, metrics))
     else:
         vl, vm = EF._evaluate(model, loss, loader, DEV, metrics, ft, 1, 0, scorers[path])
     torch.cuda.synchronize()
@@ -89,7 +93,7 @@ def time_pass(args, slates, lens):
     from allrank_amd.engine import FusedTrainer
     rows = []
     loss, metrics = partial(E.approxNDCGLoss), {"ndcg": [5, 10]}
-    paths = [args.only] if args.only else ["module", "eager", "captured"]
+    paths = [args.only] if args.only else args.paths.split(",")
     for name in args.models.split(","):
         spec = MODELS[name]
         for B in [int(b) for b in args.batches.split(",")]:
@@ -97,7 +101,8 @@ def time_pass(args, slates, lens):
             ft = FusedTrainer(model, "approxNDCGLoss", {}, B, 240, lr=1e-3, use_graph=True)
             loader = ED.DeviceLoader(ED.DeviceLibSVMDataset(slates), B, shuffle=False)
             Lv = loader.slate_length
-            scorers = {"eager": {Lv: ft.scorer(B, Lv, use_graph=False)}, "captured": {Lv: ft.scorer(B, Lv)}}
+            cap = {Lv: ft.scorer(B, Lv)}
+            scorers = {"eager": {Lv: ft.scorer(B, Lv, use_graph=False)}, "captured": cap, "ragged": cap}
             res = {p: [] for p in paths}
             out = {}
             reps = 1 if args.only else args.reps + 1                       # (first round: warm-up, graph captures)
@@ -153,7 +158,8 @@ def main():
     ap.add_argument("--models", default="c3,nn96")
     ap.add_argument("--batches", default="64,256")
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--only", choices=["module", "eager", "captured"])
+    ap.add_argument("--paths", default="module,eager,captured,ragged", help="the interleaved paths of the pass timing, in order")
+    ap.add_argument("--only", choices=["module", "eager", "captured", "ragged"])
     ap.add_argument("--epoch", action="store_true")
     ap.add_argument("--scorers", default="module,packed", help="validation scorers of the --epoch runs, in order")
     ap.add_argument("--no-pass", action="store_true", help="skip the validation-pass timing (with --epoch)")
