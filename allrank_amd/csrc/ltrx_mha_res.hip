@@ -3,7 +3,8 @@
 //
 // Why another attention path: the exact-fp32 kernels of ltrx_mha.hip run on v_mfma_f32_32x32x2_f32, 1/16 of the bf16 MFMA
 // rate -- 29 % of the training step at config (3).  Here every contraction is three v_mfma_f32_32x32x16_bf16 products
-// X Y ~= Xhi Yhi + Xhi Ylo + Xlo Yhi (x = hi + lo, both bf16; fp32 accumulate; error <= 3 * 2^-18 per product, the same
+// X Y ~= Xhi Yhi + Xhi Ylo + Xlo Yhi (x = hi + lo, both bf16; fp32 accumulate; error typically 3 * 2^-18 per product and bounded
+// by 3 * 2^-16 (1 + 2^-7) -- include/ltrx.h; contractions over one or two keys do come close to the bound --, the same
 // arithmetic as the dense projections of ltrx_gemm.hip): 5.3x fewer matrix-pipe cycles.  What made the earlier split-bf16
 // attempt (round 1, ltrx_mha_bf16.hip: no faster than fp32) slow was not the MFMAs but everything around them: every
 // 128-query workgroup re-staged and re-split every 32-key tile of K and V behind two barriers, with a strided transposition
