@@ -227,7 +227,8 @@ __global__ void __launch_bounds__(BM_ * 2) __attribute__((amdgpu_waves_per_eu(2,
 //   * per MFMA the 256 x 256 tile needs half the global-load and LDS-write traffic and 3/4 of the LDS fragment reads;
 //   * __syncthreads() drains vmcnt(0), i.e. it exposes the latency of the prefetch issued just before it on every K-step;
 //     the barrier here orders LDS only (release/acquire fences on the "local" address space + s_barrier), so the global
-//     loads of tile t+2 stay in flight across it;
+//     loads of tile t+2 stay in flight across it -- the prologue's barrier included (the loads of K-tile 1 land behind the MFMAs of
+//     tile 0); after the last K-tile there is no barrier at all, the epilogue touches no LDS;
 //   * the steady-state loop is branch-free, which lets the scheduler interleave the split/ds_write VALU work of tile t+1
 //     with the MFMAs of tile t;
 //   * the output tile is streamed with nontemporal stores: C (0.5 GB for the FFN) no longer evicts the operand panels
@@ -250,12 +251,48 @@ struct SmemNT {
 // (bf16) in place of the 4 floats, same addressing (ltrx_split_image; the weights and their transposes, refreshed once per optimizer
 // step).  The staging of B is then a plain copy: half of the kernel's split work (VALU, and the power it draws) is gone, the bits
 // that reach LDS -- and the results -- are identical.
-template <bool TAIL, int BM, int NT, bool BIMG>
+//
+// EPI: the epilogue as a compile-time kind.  The dropout-free epilogues the default training step launches are straight-line code --
+// no test of act / bias / drop per row quad, one basic block from the last K-step's MFMAs to the last store -- and issue their loads
+// EARLY: both bias vectors and the mask word ahead of the last K-step's MFMAs (the staging registers are dead there), the residual tile
+// rolled two accumulator blocks ahead of its use, its first two blocks also ahead of those MFMAs.  EPI_GENERIC is the runtime-tested
+// epilogue (acts 1 / 2, every dropout form, the ragged last row tile, the one-product mode, B read as fp32): same arithmetic per
+// element in the same order, so a launch's bits do not depend on which kind the host picked (nt_epilogue_kind).
+// In <false, 256, 2, true> the code after the last MFMA went from ~6000 static instructions, 308 conditional branches and 66 vmcnt
+// waits to 200-720 instructions, no branch and 0-14 counted waits (the epilogue's first blocks are scheduled between the last
+// K-step's MFMAs).  Measured on the MI355X, 256 slates x 240: 8.48 -> 8.39 ms per step; FFN-1 forward 394 -> 376 us, the QKV
+// launches 282 -> 274 and 307 -> 287 us, FFN-2 dgrad 381 -> 372 us; the residual launches keep their ~25 us over their
+// residual-free twins -- that is the HBM time of the 126 MB they read, not latency (profiles/NOTES.md, "Straight-line epilogues").
+enum : int {
+  EPI_GENERIC = 0,
+  EPI_PLAIN,        // act 0, no bias: C = acc                      (the input-gradient launches)
+  EPI_BIAS,         // act 0: C = acc + bias                        (Q / K / V)
+  EPI_RELU_BITS,    // act 4: C = relu(acc + bias), one-bit mask written   (FFN-1 forward)
+  EPI_MASK_READ,    // act 5, no bias: C = bit ? acc * inv_keep : 0        (FFN-2 input gradient)
+  EPI_RESIDUAL,     // act 3: C = acc + bias + aux                  (out-projection and FFN-2 forward)
+  EPI_KINDS
+};
+
+// 4x4 transpose inside a lane quad (two DPP butterflies: quad_perm [1,0,3,2] then [2,3,0,1]): registers a0..a3 of the four lanes
+// (4 rows of ONE column each) become 4 consecutive columns of one row per lane (row q of the quad); b0 / b1 = bits 0 / 1 of q
+__device__ __forceinline__ f32x4 quad_transpose(float a0, float a1, float a2, float a3, bool b0, bool b1) {
+  // stage 1: exchange across lane bit 0
+  const float r_lo = LTRX_DPP_F(0.f, b0 ? a0 : a1, 0xB1, 0xF, true);
+  const float r_hi = LTRX_DPP_F(0.f, b0 ? a2 : a3, 0xB1, 0xF, true);
+  const float c0 = b0 ? r_lo : a0, c1 = b0 ? a1 : r_lo, c2 = b0 ? r_hi : a2, c3 = b0 ? a3 : r_hi;
+  // stage 2: exchange across lane bit 1
+  const float r_a = LTRX_DPP_F(0.f, b1 ? c0 : c2, 0x4E, 0xF, true);
+  const float r_b = LTRX_DPP_F(0.f, b1 ? c1 : c3, 0x4E, 0xF, true);
+  return f32x4{b1 ? r_a : c0, b1 ? r_b : c1, b1 ? c2 : r_a, b1 ? c3 : r_b};
+}
+
+template <bool TAIL, int BM, int NT, bool BIMG, int EPI>
 __device__ __forceinline__ void nt256_body(const float* __restrict__ A, int lda, const float* __restrict__ B,
                                            int ldb, float* __restrict__ C, int ldc, int M, int N, int K,
                                            const float* __restrict__ bias, int act,
                                            const float* __restrict__ aux, int ldaux, int tiles_n,
                                            ltrx::DropSpec drop, const uint32_t* __restrict__ drop_step) {
+  static_assert(EPI == EPI_GENERIC || (!TAIL && NT == 2), "the straight-line epilogues have no row guard and are built for the parity arithmetic");
   constexpr int BK_ = 32;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   typedef SmemNT<BM, NT> SmemT;
@@ -342,7 +379,7 @@ __device__ __forceinline__ void nt256_body(const float* __restrict__ A, int lda,
   gload(0);
   sstore(s[0]);
   if (nk > 1) gload(BK_);
-  __syncthreads();
+  lds_only_barrier();                         // orders LDS only: the loads of K-tile 1 stay in flight behind the MFMAs of tile 0
   int kt = 0;
   for (; kt + 2 < nk; ++kt) {                 // steady state, branch-free: MFMAs of tile kt | stage tile kt+1 | prefetch kt+2
     mma(s[kt & 1]);
@@ -350,27 +387,94 @@ __device__ __forceinline__ void nt256_body(const float* __restrict__ A, int lda,
     gload((kt + 2) * BK_);
     lds_only_barrier();
   }
-  for (; kt < nk; ++kt) {
+  if (kt + 1 < nk) {                          // the second-to-last K-tile (nk >= 2): nothing left to prefetch
     mma(s[kt & 1]);
-    if (kt + 1 < nk) sstore(s[(kt + 1) & 1]);
-    __syncthreads();
+    sstore(s[(kt + 1) & 1]);
+    lds_only_barrier();
+    ++kt;
   }
 
-  ltrx::DropSpec dsp = drop;
-  if (drop_step) dsp.seed ^= drop_step[0] * 0x9E3779B9u;
   // Epilogue with 16-byte stores.  An accumulator block keeps one COLUMN per lane (16 rows down the registers); a 4x4
-  // transpose inside each lane quad (two DPP butterflies: quad_perm [1,0,3,2] then [2,3,0,1]) turns registers 4g..4g+3 of
-  // the four lanes of a quad into 4 consecutive columns of ONE row per lane, so the tile leaves the CU as 32 dwordx4 stores
-  // per lane instead of 128 dword stores -- the vector-memory issue path is what bounds this kernel, and the saved
-  // activation of the ReLU backward (act 2) and the bias are read as float4 the same way.
+  // transpose inside each lane quad (quad_transpose) turns registers 4g..4g+3 of the four lanes of a quad into 4 consecutive
+  // columns of ONE row per lane, so the tile leaves the CU as 32 dwordx4 stores per lane instead of 128 dword stores -- the
+  // vector-memory issue path is what bounds this kernel, and the saved activation of the ReLU backward (act 2), the residual
+  // (act 3) and the bias are read as float4 the same way.
   const int q = lane & 3;
   const bool b0 = q & 1, b1 = q & 2;
   const int cq = l31 & ~3;
   // act 4 / 5: the ReLU(+dropout) mask as ONE BIT per element instead of the saved fp32 activation.  The lane that produces an
   // element in the forward launch (act 4) is the lane that needs its mask in the input-gradient launch (act 5: same M, N, tiling),
   // so the 128 bits of a lane's 32 row-quads travel as one private 16-byte word per (tile, thread): 1/32 of the bytes act 2 reads.
-  unsigned int mbits[4] = {0u, 0u, 0u, 0u};
   uint4* const mask_words = reinterpret_cast<uint4*>(const_cast<float*>(aux)) + (size_t)id * 512 + threadIdx.x;
+
+  if constexpr (EPI != EPI_GENERIC) {
+    // Straight-line epilogue (see EPI above).  Element arithmetic = the generic epilogue's expressions in its order: + bias (+ 0
+    // without one), ReLU, * inv_keep under the mask, + residual.
+    constexpr bool HAS_BIAS = EPI == EPI_BIAS || EPI == EPI_RELU_BITS || EPI == EPI_RESIDUAL;
+    constexpr int NBLK = 2 * RI;               // 32 x 32 accumulator blocks of a lane, in epilogue order: block b = (j, i) = (b / RI, b % RI)
+    // Addresses as (wave-uniform 64-bit base, in scalar registers) + (one 32-bit byte offset per lane and matrix): a row quad's
+    // address then costs scalar arithmetic only, and two VGPRs hold every address of the tile.
+    const int wru = __builtin_amdgcn_readfirstlane(wr), wcu = __builtin_amdgcn_readfirstlane(wc);
+    const int rowu = m0 + wru * (BM / 2), colu = n0 + wcu * 64;           // the wave's first row / column
+    const char* const aux_u = reinterpret_cast<const char*>(aux + (size_t)rowu * ldaux + colu);
+    char* const c_u = reinterpret_cast<char*>(C + (size_t)rowu * ldc + colu);
+    const uint32_t aux_lane = 4u * (uint32_t)((4 * half + q) * ldaux + cq), c_lane = 4u * (uint32_t)((4 * half + q) * ldc + cq);
+    f32x4 bv[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+    f32x4 ax[EPI == EPI_RESIDUAL ? NBLK : 1][4];
+    unsigned int mbits[4] = {0u, 0u, 0u, 0u};
+    auto aux_load = [&](int b) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+        ax[b][g] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(
+            aux_u + 4 * ((size_t)((b % RI) * 32 + 8 * g) * ldaux + (b / RI) * 32) + aux_lane));
+    };
+    // issued ahead of the last K-step's MFMAs, whose ~1.5 us cover the round trips
+    if constexpr (HAS_BIAS) {
+      bv[0] = *reinterpret_cast<const f32x4*>(bias + colu + cq);
+      bv[1] = *reinterpret_cast<const f32x4*>(bias + colu + cq + 32);
+    }
+    if constexpr (EPI == EPI_MASK_READ) {
+      const uint4 w = *mask_words;
+      mbits[0] = w.x; mbits[1] = w.y; mbits[2] = w.z; mbits[3] = w.w;
+    }
+    if constexpr (EPI == EPI_RESIDUAL) {
+      aux_load(0);
+      aux_load(1);
+    }
+    mma(s[kt & 1]);                           // the last K-tile; the epilogue touches no LDS, so no barrier follows
+#pragma unroll
+    for (int b = 0; b < NBLK; ++b) {
+      const int j = b / RI, i = b % RI;
+      if constexpr (EPI == EPI_RESIDUAL)
+        if (b + 2 < NBLK) aux_load(b + 2);
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        f32x4 v = quad_transpose(acc[i][j][4 * g + 0], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3], b0, b1);
+        v.x += bv[j].x; v.y += bv[j].y; v.z += bv[j].z; v.w += bv[j].w;
+        if constexpr (EPI == EPI_RELU_BITS) {
+          v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+          mbits[(b * 4 + g) >> 3] |= ((v.x > 0.f ? 1u : 0u) | (v.y > 0.f ? 2u : 0u) | (v.z > 0.f ? 4u : 0u) | (v.w > 0.f ? 8u : 0u))
+                                     << (((b * 4 + g) & 7) * 4);
+        }
+        if constexpr (EPI == EPI_MASK_READ) {
+          const unsigned int nb_ = mbits[(b * 4 + g) >> 3] >> (((b * 4 + g) & 7) * 4);
+          v.x = (nb_ & 1u) ? v.x * drop.inv_keep : 0.f;
+          v.y = (nb_ & 2u) ? v.y * drop.inv_keep : 0.f;
+          v.z = (nb_ & 4u) ? v.z * drop.inv_keep : 0.f;
+          v.w = (nb_ & 8u) ? v.w * drop.inv_keep : 0.f;
+        }
+        if constexpr (EPI == EPI_RESIDUAL) {
+          v.x += ax[b][g].x; v.y += ax[b][g].y; v.z += ax[b][g].z; v.w += ax[b][g].w;
+        }
+        __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(c_u + 4 * ((size_t)(i * 32 + 8 * g) * ldc + j * 32) + c_lane));
+      }
+    }
+    if constexpr (EPI == EPI_RELU_BITS) *mask_words = make_uint4(mbits[0], mbits[1], mbits[2], mbits[3]);
+  } else {
+  mma(s[kt & 1]);                             // the last K-tile; the epilogue touches no LDS, so no barrier follows
+  ltrx::DropSpec dsp = drop;
+  if (drop_step) dsp.seed ^= drop_step[0] * 0x9E3779B9u;
+  unsigned int mbits[4] = {0u, 0u, 0u, 0u};
   if (act == 5) {
     const uint4 w = *mask_words;
     mbits[0] = w.x; mbits[1] = w.y; mbits[2] = w.z; mbits[3] = w.w;
@@ -393,15 +497,7 @@ __device__ __forceinline__ void nt256_body(const float* __restrict__ A, int lda,
       }
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        const float a0 = acc[i][j][4 * g + 0], a1 = acc[i][j][4 * g + 1], a2 = acc[i][j][4 * g + 2], a3 = acc[i][j][4 * g + 3];
-        // stage 1: exchange across lane bit 0
-        const float r_lo = LTRX_DPP_F(0.f, b0 ? a0 : a1, 0xB1, 0xF, true);
-        const float r_hi = LTRX_DPP_F(0.f, b0 ? a2 : a3, 0xB1, 0xF, true);
-        const float c0 = b0 ? r_lo : a0, c1 = b0 ? a1 : r_lo, c2 = b0 ? r_hi : a2, c3 = b0 ? a3 : r_hi;
-        // stage 2: exchange across lane bit 1
-        const float r_a = LTRX_DPP_F(0.f, b1 ? c0 : c2, 0x4E, 0xF, true);
-        const float r_b = LTRX_DPP_F(0.f, b1 ? c1 : c3, 0x4E, 0xF, true);
-        f32x4 v = {b1 ? r_a : c0, b1 ? r_b : c1, b1 ? c2 : r_a, b1 ? c3 : r_b};   // row q, columns col..col+3
+        f32x4 v = quad_transpose(acc[i][j][4 * g + 0], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3], b0, b1);   // row q, columns col..col+3
         const int row = m0 + wr * (BM / 2) + i * 32 + 8 * g + 4 * half + q;
         if (TAIL && row >= M) continue;
         v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
@@ -437,25 +533,26 @@ __device__ __forceinline__ void nt256_body(const float* __restrict__ A, int lda,
     }
   }
   if (act == 4) *mask_words = make_uint4(mbits[0], mbits[1], mbits[2], mbits[3]);
+  }
 }
 
-template <bool TAIL, int BM, int NT, bool BIMG>
+template <bool TAIL, int BM, int NT, bool BIMG, int EPI>
 __global__ void __launch_bounds__(512) ltrx_gemm_nt256_kernel(const float* __restrict__ A, int lda, const float* __restrict__ B,
                                                               int ldb, float* __restrict__ C, int ldc, int M, int N, int K,
                                                               const float* __restrict__ bias, int act,
                                                               const float* __restrict__ aux, int ldaux, int tiles_n,
                                                               ltrx::DropSpec drop, const uint32_t* __restrict__ drop_step) {
-  nt256_body<TAIL, BM, NT, BIMG>(A, lda, B, ldb, C, ldc, M, N, K, bias, act, aux, ldaux, tiles_n, drop, drop_step);
+  nt256_body<TAIL, BM, NT, BIMG, EPI>(A, lda, B, ldb, C, ldc, M, N, K, bias, act, aux, ldaux, tiles_n, drop, drop_step);
 }
 // 64-row tiles, TWO workgroups per CU (2 x 80 KB of LDS, 128 registers per lane): for the shapes whose 128-row tiling is a single,
 // not even full round of workgroups (N = 512 projections at 64 slates per GPU: 240 tiles) -- twice the workgroups, four waves per
 // SIMD to hide the staging latency that two waves leave exposed
-template <bool TAIL, int NT, bool BIMG>
+template <bool TAIL, int NT, bool BIMG, int EPI>
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4)))
 ltrx_gemm_nt64_kernel(const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb, float* __restrict__ C, int ldc, int M,
                       int N, int K, const float* __restrict__ bias, int act, const float* __restrict__ aux, int ldaux, int tiles_n,
                       ltrx::DropSpec drop, const uint32_t* __restrict__ drop_step) {
-  nt256_body<TAIL, 64, NT, BIMG>(A, lda, B, ldb, C, ldc, M, N, K, bias, act, aux, ldaux, tiles_n, drop, drop_step);
+  nt256_body<TAIL, 64, NT, BIMG, EPI>(A, lda, B, ldb, C, ldc, M, N, K, bias, act, aux, ldaux, tiles_n, drop, drop_step);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -926,6 +1023,81 @@ static void launch_nt(const float* A, int lda, const float* B, int ldb, float* C
                      ldc, M, N, K, bias, act, aux, ldaux, tiles_n, drop, drop_step);
 }
 
+// ---- the 256-column kernel's launcher: one function per tile height, one table of its instantiations ----
+struct NtLargeArgs {
+  const float* A; int lda; const float* B; int ldb; float* C; int ldc; int M, N, K;
+  const float* bias; int act; const float* aux; int ldaux; ltrx::DropSpec drop; const uint32_t* drop_step;
+};
+typedef void (*NtLargeFn)(const float*, int, const float*, int, float*, int, int, int, int, const float*, int, const float*, int, int,
+                          ltrx::DropSpec, const uint32_t*);
+
+// The epilogue kind of a launch, from (act, bias, dropout): the straight-line kinds are the dropout-free epilogues of the default
+// training step, in its form of the launch (exact row tiles, three products, B as a pre-split image).  With drop.thresh == 0 the
+// generic epilogue never reads drop_step, so the kind does not depend on it.  Everything else is EPI_GENERIC -- same bits either way.
+static int nt_epilogue_kind(int act, bool has_bias, const ltrx::DropSpec& drop, bool tail, bool plain, bool bimg) {
+  if (drop.thresh != 0u || tail || plain || !bimg) return EPI_GENERIC;
+  switch (act) {
+    case 0: return has_bias ? EPI_BIAS : EPI_PLAIN;
+    case 3: return has_bias ? EPI_RESIDUAL : EPI_GENERIC;
+    case 4: return has_bias ? EPI_RELU_BITS : EPI_GENERIC;
+    case 5: return has_bias ? EPI_GENERIC : EPI_MASK_READ;
+    default: return EPI_GENERIC;
+  }
+}
+
+template <int BM, bool TAIL, int NT, bool BIMG, int EPI>
+static NtLargeFn nt_large_fn() {
+  if constexpr (BM == 64) return ltrx_gemm_nt64_kernel<TAIL, NT, BIMG, EPI>;
+  else return ltrx_gemm_nt256_kernel<TAIL, BM, NT, BIMG, EPI>;
+}
+// nullptr: no such instantiation (the mask kinds exist for the 256-row tile only -- the mask is kept in its (tile, thread) order)
+template <int BM>
+static NtLargeFn nt_large_kernel(bool tail, int nt, bool bimg, int epi) {
+  switch (epi) {
+    case EPI_GENERIC:
+#define LTRX_NT_GENERIC(TAIL_) \
+  (nt == 2 ? (bimg ? nt_large_fn<BM, TAIL_, 2, true, EPI_GENERIC>() : nt_large_fn<BM, TAIL_, 2, false, EPI_GENERIC>()) \
+           : (bimg ? nt_large_fn<BM, TAIL_, 1, true, EPI_GENERIC>() : nt_large_fn<BM, TAIL_, 1, false, EPI_GENERIC>()))
+      return tail ? LTRX_NT_GENERIC(true) : LTRX_NT_GENERIC(false);
+#undef LTRX_NT_GENERIC
+    case EPI_PLAIN: return nt_large_fn<BM, false, 2, true, EPI_PLAIN>();
+    case EPI_BIAS: return nt_large_fn<BM, false, 2, true, EPI_BIAS>();
+    case EPI_RESIDUAL: return nt_large_fn<BM, false, 2, true, EPI_RESIDUAL>();
+    case EPI_RELU_BITS:
+      if constexpr (BM == 256) return nt_large_fn<BM, false, 2, true, EPI_RELU_BITS>();
+      return nullptr;
+    case EPI_MASK_READ:
+      if constexpr (BM == 256) return nt_large_fn<BM, false, 2, true, EPI_MASK_READ>();
+      return nullptr;
+  }
+  return nullptr;
+}
+
+template <int BM>
+static int launch_nt_large(const NtLargeArgs& a, bool plain, bool bimg, hipStream_t s) {
+  static std::atomic<uint64_t> attr_done{0};
+  const int arc = ltrx_once_per_device(attr_done, [&]() {
+    for (int epi = 0; epi < EPI_KINDS; ++epi)
+      for (int c = 0; c < (epi == EPI_GENERIC ? 8 : 1); ++c) {
+        const int nt = epi == EPI_GENERIC ? 1 + (c & 1) : 2;
+        const NtLargeFn f = nt_large_kernel<BM>(epi == EPI_GENERIC && (c & 4), nt, epi != EPI_GENERIC || (c & 2), epi);
+        const size_t bytes = 2 * (nt == 2 ? sizeof(SmemNT<BM, 2>) : sizeof(SmemNT<BM, 1>));
+        if (f && hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return LTRX_EHIP;
+      }
+    return LTRX_OK;
+  });
+  if (arc != LTRX_OK) return arc;
+  const bool tail = (a.M % BM) != 0;
+  const int nt = plain ? 1 : 2, tiles_n = a.N / 256;
+  const NtLargeFn f = nt_large_kernel<BM>(tail, nt, bimg, nt_epilogue_kind(a.act, a.bias != nullptr, a.drop, tail, plain, bimg));
+  if (!f) return LTRX_EUNSUPPORTED;
+  const size_t lds = 2 * (nt == 2 ? sizeof(SmemNT<BM, 2>) : sizeof(SmemNT<BM, 1>));
+  hipLaunchKernelGGL(f, dim3(((a.M + BM - 1) / BM) * tiles_n), dim3(512), lds, s, a.A, a.lda, a.B, a.ldb, a.C, a.ldc, a.M, a.N, a.K, a.bias,
+                     a.act, a.aux, a.ldaux, tiles_n, a.drop, a.drop_step);
+  LTRX_LAUNCH_CHECK();
+  return LTRX_OK;
+}
+
 // bytes of the one-bit ReLU mask of an [M, N] activation (acts 4 / 5 of ltrx_gemm_nt), 0 where that form does not apply: the mask is
 // kept in the 256 x 256 tile kernel's (tile, thread) order, so both launches must take that kernel whatever their K, dropout and
 // epilogue -- N a multiple of 256, K a multiple of the kernel's 32-column step (K of the launch asked about: the forward and the
@@ -990,74 +1162,14 @@ extern "C" int ltrx_gemm_nt(const float* A, int lda, const float* B, int ldb, co
   // (the mask's (tile, thread) order is the 256-row kernel's: refuse rather than run any other tiling if the predicate above and this
   //  dispatch ever disagree)
   if ((act == 4 || act == 5) && v != 6) return LTRX_EUNSUPPORTED;
-  if (v == 8) {              // 64-row tiles, two workgroups per CU
-    if ((N % 256) || (K % 32) || strict || !vec_epi || act == 4 || act == 5) return LTRX_EUNSUPPORTED;
-    static std::atomic<uint64_t> attr64_done{0};
-#define LTRX_NT64_ATTR(TAIL_, NT_) \
-  {ltrx_gemm_nt64_kernel<TAIL_, NT_, false>, 2 * sizeof(SmemNT<64, NT_>)}, {ltrx_gemm_nt64_kernel<TAIL_, NT_, true>, 2 * sizeof(SmemNT<64, NT_>)}
-    const int arc = ltrx_allow_dynamic_lds(attr64_done, {LTRX_NT64_ATTR(false, 2), LTRX_NT64_ATTR(true, 2), LTRX_NT64_ATTR(false, 1),
-                                                         LTRX_NT64_ATTR(true, 1)});
-#undef LTRX_NT64_ATTR
-    if (arc != LTRX_OK) return arc;
-    const int tiles_n = N / 256;
-    const dim3 grid(((M + 63) / 64) * tiles_n);
-    const bool bimg = B_image != nullptr && (((uintptr_t)B_image) & 15) == 0;
-    const float* Bk = bimg ? reinterpret_cast<const float*>(B_image) : B;
-#define LTRX_NT64_(TAIL_, NT_, BIMG_)                                                                                       \
-  hipLaunchKernelGGL((ltrx_gemm_nt64_kernel<TAIL_, NT_, BIMG_>), grid, dim3(512), 2 * sizeof(SmemNT<64, NT_>), s, A, lda, Bk, ldb, C, \
-                     ldc, M, N, K, bias, act, aux, ldaux, tiles_n, drop, drop_step)
-#define LTRX_NT64(TAIL_)                                                                                                    \
-  do {                                                                                                                      \
-    if (plain) {                                                                                                            \
-      if (bimg) LTRX_NT64_(TAIL_, 1, true); else LTRX_NT64_(TAIL_, 1, false);                                               \
-    } else {                                                                                                                \
-      if (bimg) LTRX_NT64_(TAIL_, 2, true); else LTRX_NT64_(TAIL_, 2, false);                                               \
-    }                                                                                                                       \
-  } while (0)
-    if (M % 64) LTRX_NT64(true); else LTRX_NT64(false);
-#undef LTRX_NT64_
-#undef LTRX_NT64
-    LTRX_LAUNCH_CHECK();
-    return LTRX_OK;
-  }
-  if (v == 6 || v == 7) {
-    if ((N % 256) || (K % 32) || strict || !vec_epi) return LTRX_EUNSUPPORTED;
-    static std::atomic<uint64_t> attr_done{0};
-#define LTRX_NT256_ATTR(TAIL_, BM_, NT_)                                                    \
-  {ltrx_gemm_nt256_kernel<TAIL_, BM_, NT_, false>, 2 * sizeof(SmemNT<BM_, NT_>)}, {         \
-    ltrx_gemm_nt256_kernel<TAIL_, BM_, NT_, true>, 2 * sizeof(SmemNT<BM_, NT_>)             \
-  }
-    const int arc = ltrx_allow_dynamic_lds(
-        attr_done, {LTRX_NT256_ATTR(false, 256, 2), LTRX_NT256_ATTR(true, 256, 2), LTRX_NT256_ATTR(false, 128, 2), LTRX_NT256_ATTR(true, 128, 2),
-                    LTRX_NT256_ATTR(false, 256, 1), LTRX_NT256_ATTR(true, 256, 1), LTRX_NT256_ATTR(false, 128, 1), LTRX_NT256_ATTR(true, 128, 1)});
-#undef LTRX_NT256_ATTR
-    if (arc != LTRX_OK) return arc;
-    const int tiles_n = N / 256;
-    const int bm = (v == 6) ? 256 : 128;
-    const dim3 grid(((M + bm - 1) / bm) * tiles_n);
+  if (v == 6 || v == 7 || v == 8) {          // the 256-column kernel: 256- / 128-row tiles, or 64-row tiles with two workgroups per CU
+    if ((N % 256) || (K % 32) || strict || !vec_epi || (v == 8 && (act == 4 || act == 5))) return LTRX_EUNSUPPORTED;
     // the pre-split image of B (same addressing as B, 16-byte aligned) replaces the fp32 operand in this kernel family only
     const bool bimg = B_image != nullptr && (((uintptr_t)B_image) & 15) == 0;
-    const float* Bk = bimg ? reinterpret_cast<const float*>(B_image) : B;
-#define LTRX_NT256_(TAIL_, BM_, NT_, BIMG_)                                                                                  \
-  hipLaunchKernelGGL((ltrx_gemm_nt256_kernel<TAIL_, BM_, NT_, BIMG_>), grid, dim3(512), 2 * sizeof(SmemNT<BM_, NT_>), s, A, lda, Bk, \
-                     ldb, C, ldc, M, N, K, bias, act, aux, ldaux, tiles_n, drop, drop_step)
-#define LTRX_NT256(TAIL_, BM_)                                                                                               \
-  do {                                                                                                                       \
-    if (plain) {                                                                                                             \
-      if (bimg) LTRX_NT256_(TAIL_, BM_, 1, true); else LTRX_NT256_(TAIL_, BM_, 1, false);                                    \
-    } else {                                                                                                                 \
-      if (bimg) LTRX_NT256_(TAIL_, BM_, 2, true); else LTRX_NT256_(TAIL_, BM_, 2, false);                                    \
-    }                                                                                                                        \
-  } while (0)
-    if (v == 6) {
-      if (M % 256) LTRX_NT256(true, 256); else LTRX_NT256(false, 256);
-    } else {
-      if (M % 128) LTRX_NT256(true, 128); else LTRX_NT256(false, 128);
-    }
-#undef LTRX_NT256_
-#undef LTRX_NT256
-    LTRX_LAUNCH_CHECK();
-    return LTRX_OK;
+    const NtLargeArgs a = {A, lda, bimg ? reinterpret_cast<const float*>(B_image) : B, ldb, C, ldc, M, N, K, bias, act, aux, ldaux, drop, drop_step};
+    if (v == 6) return launch_nt_large<256>(a, plain, bimg, s);
+    if (v == 7) return launch_nt_large<128>(a, plain, bimg, s);
+    return launch_nt_large<64>(a, plain, bimg, s);
   }
   if (strict) {
     launch_nt<3, 128, 32>(A, lda, B, ldb, C, ldc, M, N, K, bias, act, aux, ldaux, drop, drop_step, s);
