@@ -32,6 +32,7 @@
 // (swz_off): every lane fetches its 8-element MFMA fragment with one ds_read_b128, conflict-free in both directions.
 // Workgroup ids are remapped so that the column tiles of one A row-panel run on the same XCD (shared L2).
 #include "ltrx_mfma.h"
+#include "ltrx_rowreg.h"
 
 using ltrx::lds_only_barrier;
 using ltrx::rowmap;
@@ -692,12 +693,32 @@ struct TnGroup {
   unsigned char map_split[256];
 };
 
-template <int NT>
-__global__ void __launch_bounds__(512) ltrx_gemm_tn256_kernel(const TnGroup grp, int M, int m_per_split) {
+// A grouped launch with a SIDE JOB (ltrx_gemm_tn_group_ln): a one-dimensional grid of gemm_wgs + side workgroups, one per CU; ids
+// below gemm_wgs take their (tile, split) from the map and run the GEMM path as it stands, the `side` ids above run the first-sublayer
+// LayerNorm backward of the same encoder layer (ltrx::rowreg_ln_bwd_side) on CUs the plan would leave without a workgroup.
+struct TnGroupLn {
+  TnGroup g;
+  ltrx::LnBwdJob ln;
+  int gemm_wgs, side;
+};
+__device__ __forceinline__ const TnGroup& tn_group_of(const TnGroup& a) { return a; }
+__device__ __forceinline__ const TnGroup& tn_group_of(const TnGroupLn& a) { return a.g; }
+
+// SNV = 0: no side job (every launch of ltrx_gemm_tn and ltrx_gemm_tn_group).  SNV = 1..4: the side path for rows of 256 * SNV floats.
+template <int NT, int SNV = 0>
+__global__ void __launch_bounds__(512) ltrx_gemm_tn256_kernel(const std::conditional_t<SNV == 0, TnGroup, TnGroupLn> arg, int M,
+                                                              int m_per_split) {
   constexpr int BK_ = 32;
   constexpr int L1 = NT - 1;
   typedef SmemNT<256, NT> SmemT;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  if constexpr (SNV > 0) {
+    if ((int)blockIdx.x >= arg.gemm_wgs) {                               // (workgroup-uniform)
+      ltrx::rowreg_ln_bwd_side<SNV>(arg.ln, (int)blockIdx.x - arg.gemm_wgs, arg.side, reinterpret_cast<float*>(smem_raw));
+      return;
+    }
+  }
+  const TnGroup& grp = tn_group_of(arg);
   SmemT* s = reinterpret_cast<SmemT*>(smem_raw);
   // Workgroup -> (split, tile) in split-major order through the XCD remap: all tiles of one m-slab run on ONE XCD, so the dY
   // slab (shared by the tiles of a tile row) and the X slab (shared by the tiles of a tile column) are fetched from HBM once
@@ -706,7 +727,7 @@ __global__ void __launch_bounds__(512) ltrx_gemm_tn256_kernel(const TnGroup grp,
   // kernel is bound by its staging path, not by HBM), the freed bandwidth is what the overlapped all-reduce needs.
   const int n_tiles = gridDim.x;
   int gtile, split;
-  if (grp.nprob > 1) {
+  if (SNV > 0 || grp.nprob > 1) {                                       // (a launch with a side job always carries the map)
     const int w = blockIdx.x + n_tiles * blockIdx.y;
     gtile = grp.map_tile[w];
     split = grp.map_split[w];
@@ -1238,7 +1259,9 @@ extern "C" size_t ltrx_gemm_tn_workspace_bytes(int M, int NP, int KP) {
 // the large-tile kernel's two staging buffers exceed the default dynamic-LDS allowance (ltrx_gemm_tn and ltrx_gemm_tn_group launch it)
 static int tn256_allow_lds() {
   static std::atomic<uint64_t> attr_done{0};
-  return ltrx_allow_dynamic_lds(attr_done, {{ltrx_gemm_tn256_kernel<2>, 2 * sizeof(SmemNT<256, 2>)}, {ltrx_gemm_tn256_kernel<1>, 2 * sizeof(SmemNT<256, 1>)}});
+  return ltrx_allow_dynamic_lds(attr_done, {{ltrx_gemm_tn256_kernel<2>, 2 * sizeof(SmemNT<256, 2>)}, {ltrx_gemm_tn256_kernel<1>, 2 * sizeof(SmemNT<256, 1>)},
+                                           {ltrx_gemm_tn256_kernel<2, 1>, 2 * sizeof(SmemNT<256, 2>)}, {ltrx_gemm_tn256_kernel<2, 2>, 2 * sizeof(SmemNT<256, 2>)},
+                                           {ltrx_gemm_tn256_kernel<2, 3>, 2 * sizeof(SmemNT<256, 2>)}, {ltrx_gemm_tn256_kernel<2, 4>, 2 * sizeof(SmemNT<256, 2>)}});
 }
 
 extern "C" int ltrx_gemm_tn(const float* A, int lda, const float* B, int ldb, float* C, float* bias_out, int M, int NP,
@@ -1400,36 +1423,75 @@ extern "C" size_t ltrx_gemm_tn_group_workspace_bytes(int nprob, int M, const int
   return grouped > single ? grouped : single;
 }
 
-extern "C" int ltrx_gemm_tn_group(int nprob, const float* const* A, const int* lda, const float* const* B, const int* ldb, float* const* C,
-                                  float* const* bias_out, int M, const int* NP, const int* KP, int strict, void* ws, size_t ws_bytes,
-                                  const float** slabs_out, const float** bias_slabs_out, int* splits_out, ltrx_stream_t stream) {
-  const bool defer = slabs_out && bias_slabs_out && splits_out;   // the caller sums the slabs (ltrx_reduce_group)
-  if ((slabs_out || bias_slabs_out || splits_out) && !defer) return LTRX_EINVAL;
-  if (defer) *splits_out = 0;
-  if (nprob < 1 || nprob > LTRX_TN_GROUP || !A || !lda || !B || !ldb || !C || !bias_out || !NP || !KP || !ws || M <= 0) return LTRX_EINVAL;
-  for (int p = 0; p < nprob; ++p)
-    if (!A[p] || !B[p] || !C[p] || NP[p] <= 0 || KP[p] <= 0) return LTRX_EINVAL;
-  const bool plain = strict == 2;
-  int total = 0, splits = 1, mps = M;
-  bool grouped = tn_group_ok(nprob, M, NP, KP, lda, ldb, strict);
+// ---- the side job of a grouped launch (TnGroupLn): host plan ----
+// Two measured figures decide whether the LayerNorm backward rides in the launch (profiles/NOTES.md, "LayerNorm backward in the
+// weight-gradient launch's idle CUs"; tables in profiles/ln_in_wgrad_kernel_stats.md):
+//   R = 49 000 bytes per microsecond streamed by ONE side workgroup (8 waves, two rows in flight each): 503 MB of dy, x, residual
+//       gradient and dx at 61440 x 512 in 642 us on 16 side workgroups, 1221 us on 8 (51 500 each), next to a one-tile GEMM part;
+//   2.5 us per K-step (32 rows) of a three-product GEMM workgroup: the grouped launch without a side job runs 1030 us at 384 K-steps
+//       per workgroup (256 slates) and 246 us at 96 (64 slates), i.e. 2.68 and 2.56; earlier traces had 922-972 us (2.40-2.53).
+// T, the duration of the GEMM part, is K-steps per workgroup x that figure.  The side job is taken only when
+// bytes / (side x R) <= 0.8 T: the margin keeps it off the critical path on a slower device (the bench layer: 642 <= 768 us).
+#ifndef LTRX_TN_SIDE_BYTES_PER_US
+#define LTRX_TN_SIDE_BYTES_PER_US 49000.0
+#endif
+#ifndef LTRX_TN_KSTEP_US
+#define LTRX_TN_KSTEP_US 2.5
+#endif
+struct TnSidePlan {
+  bool grouped;                       // the grouped kernel runs (else: one ltrx_gemm_tn per problem)
+  int total, splits, mps;             // tn_group_plan
+  int gemm_wgs, side;                 // workgroups of the GEMM path; side workgroups (0: no side job)
+  LnBwdShape sh;                      // the stand-alone LayerNorm backward launch whose blocks the side workgroups play
+};
+// side_wgs 0: the rule above; > 0: that many side workgroups (tests), clamped to the CUs the GEMM path leaves free
+static TnSidePlan tn_group_side_plan(int nprob, int M, const int* NP, const int* KP, const int* lda, const int* ldb, int strict,
+                                     size_t ws_bytes, int rows, int D, bool vec, bool has_dres, int side_wgs) {
+  TnSidePlan pl = {};
+  pl.mps = M;
+  pl.splits = 1;
+  pl.sh = ltrx_ln_bwd_shape(rows, D);
+  pl.grouped = tn_group_ok(nprob, M, NP, KP, lda, ldb, strict);
+  if (!pl.grouped) return pl;
+  tn_group_plan(nprob, M, NP, KP, &pl.total, &pl.splits, &pl.mps);
   size_t need = 0;
-  if (grouped) {
-    tn_group_plan(nprob, M, NP, KP, &total, &splits, &mps);
-    for (int p = 0; p < nprob; ++p) need += ((size_t)splits * NP[p] * KP[p] + (size_t)splits * NP[p] + 4) * sizeof(float);
-    if (need > ws_bytes) grouped = false;
+  for (int p = 0; p < nprob; ++p) need += ((size_t)pl.splits * NP[p] * KP[p] + (size_t)pl.splits * NP[p] + 4) * sizeof(float);
+  if (need > ws_bytes) {
+    pl.grouped = false;
+    return pl;
   }
-  if (!grouped) {                                     // shapes outside the large-tile kernel: one call per problem
-    for (int p = 0; p < nprob; ++p) {
-      if (ltrx_gemm_tn_workspace_bytes(M, NP[p], KP[p]) > ws_bytes) return LTRX_EINVAL;
-      const int rc = ltrx_gemm_tn(A[p], lda[p], B[p], ldb[p], C[p], bias_out[p], M, NP[p], KP[p], strict, 0, ws, stream);
-      if (rc != LTRX_OK) return rc;
-    }
-    return LTRX_OK;
+  pl.gemm_wgs = pl.total * pl.splits;
+  const int free_cus = 256 - pl.gemm_wgs;
+  // (the side path exists in the three-product kernel only; its spill rows must fit the kernel's LDS)
+  if (free_cus <= 0 || strict != 0 || !vec || rows <= 0 || (pl.sh.wpb != 4 && pl.sh.wpb != 16) ||
+      ltrx::rowreg_ln_side_lds_floats(D, pl.sh.wpb) * sizeof(float) > 2 * sizeof(SmemNT<256, 2>))
+    return pl;
+  if (side_wgs > 0) {
+    pl.side = side_wgs < free_cus ? side_wgs : free_cus;
+    return pl;
   }
-  hipStream_t s = (hipStream_t)stream;
+  const double bytes = (double)rows * D * sizeof(float) * (has_dres ? 4.0 : 3.0);
+  const double t_gemm = (double)(pl.mps / 32) * LTRX_TN_KSTEP_US;
+  if (bytes / ((double)free_cus * LTRX_TN_SIDE_BYTES_PER_US) <= 0.8 * t_gemm) pl.side = free_cus;
+  return pl;
+}
+
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + nb && b0 < a0 + na;
+}
+
+// ltrx_gemm_tn_group, and with `ln` the same launch carrying the LayerNorm backward as its side job (pl.side > 0)
+static int tn_group_run(int nprob, const float* const* A, const int* lda, const float* const* B, const int* ldb, float* const* C,
+                        float* const* bias_out, int M, const int* NP, const int* KP, int strict, void* ws, const float** slabs_out,
+                        const float** bias_slabs_out, int* splits_out, const TnSidePlan& pl, const ltrx::LnBwdJob* ln, int ln_D, hipStream_t s) {
+  const bool defer = slabs_out != nullptr;
+  const bool plain = strict == 2;
+  const int total = pl.total, splits = pl.splits, mps = pl.mps;
   const int arc = tn256_allow_lds();
   if (arc != LTRX_OK) return arc;
-  TnGroup g = {};
+  TnGroupLn gl = {};
+  TnGroup& g = gl.g;
   g.nprob = nprob;
   float* w = (float*)ws;
   int t0 = 0;
@@ -1451,10 +1513,19 @@ extern "C" int ltrx_gemm_tn_group(int nprob, const float* const* A, const int* l
   }
   g.tile_start[nprob] = t0;
   tn_group_map(g, total, splits);
-  if (plain)
+  if (ln && pl.side > 0) {
+    gl.ln = *ln;
+    gl.gemm_wgs = pl.gemm_wgs;
+    gl.side = pl.side;
+    ltrx_rowreg_dispatch(ln_D, [&](auto nv) {
+      hipLaunchKernelGGL((ltrx_gemm_tn256_kernel<2, decltype(nv)::value>), dim3(pl.gemm_wgs + pl.side), dim3(512), 2 * sizeof(SmemNT<256, 2>),
+                         s, gl, M, mps);
+    });
+  } else if (plain) {
     hipLaunchKernelGGL(ltrx_gemm_tn256_kernel<1>, dim3(total, splits), dim3(512), 2 * sizeof(SmemNT<256, 1>), s, g, M, mps);
-  else
+  } else {
     hipLaunchKernelGGL(ltrx_gemm_tn256_kernel<2>, dim3(total, splits), dim3(512), 2 * sizeof(SmemNT<256, 2>), s, g, M, mps);
+  }
   LTRX_LAUNCH_CHECK();
   if (defer) {
     for (int p = 0; p < nprob; ++p) {
@@ -1468,6 +1539,76 @@ extern "C" int ltrx_gemm_tn_group(int nprob, const float* const* A, const int* l
     launch_slab_reduce(g.slabs[p], splits, (size_t)NP[p] * KP[p], C[p], g.bias_slabs[p], splits, (size_t)NP[p], bias_out[p], s);
     LTRX_LAUNCH_CHECK();
   }
+  return LTRX_OK;
+}
+
+static int tn_group_check(int nprob, const float* const* A, const int* lda, const float* const* B, const int* ldb, float* const* C,
+                          float* const* bias_out, int M, const int* NP, const int* KP, void* ws, const float** slabs_out,
+                          const float** bias_slabs_out, int* splits_out) {
+  const bool defer = slabs_out && bias_slabs_out && splits_out;   // the caller sums the slabs (ltrx_reduce_group)
+  if ((slabs_out || bias_slabs_out || splits_out) && !defer) return LTRX_EINVAL;
+  if (defer) *splits_out = 0;
+  if (nprob < 1 || nprob > LTRX_TN_GROUP || !A || !lda || !B || !ldb || !C || !bias_out || !NP || !KP || !ws || M <= 0) return LTRX_EINVAL;
+  for (int p = 0; p < nprob; ++p)
+    if (!A[p] || !B[p] || !C[p] || NP[p] <= 0 || KP[p] <= 0) return LTRX_EINVAL;
+  return LTRX_OK;
+}
+
+extern "C" int ltrx_gemm_tn_group(int nprob, const float* const* A, const int* lda, const float* const* B, const int* ldb, float* const* C,
+                                  float* const* bias_out, int M, const int* NP, const int* KP, int strict, void* ws, size_t ws_bytes,
+                                  const float** slabs_out, const float** bias_slabs_out, int* splits_out, ltrx_stream_t stream) {
+  const int crc = tn_group_check(nprob, A, lda, B, ldb, C, bias_out, M, NP, KP, ws, slabs_out, bias_slabs_out, splits_out);
+  if (crc != LTRX_OK) return crc;
+  const TnSidePlan pl = tn_group_side_plan(nprob, M, NP, KP, lda, ldb, strict, ws_bytes, 0, 0, false, false, 0);
+  if (!pl.grouped) {                                  // shapes outside the large-tile kernel: one call per problem
+    for (int p = 0; p < nprob; ++p) {
+      if (ltrx_gemm_tn_workspace_bytes(M, NP[p], KP[p]) > ws_bytes) return LTRX_EINVAL;
+      const int rc = ltrx_gemm_tn(A[p], lda[p], B[p], ldb[p], C[p], bias_out[p], M, NP[p], KP[p], strict, 0, ws, stream);
+      if (rc != LTRX_OK) return rc;
+    }
+    return LTRX_OK;
+  }
+  return tn_group_run(nprob, A, lda, B, ldb, C, bias_out, M, NP, KP, strict, ws, slabs_out, bias_slabs_out, splits_out, pl, nullptr,
+                      0, (hipStream_t)stream);
+}
+
+// ltrx_gemm_tn_group followed by ltrx_layernorm_bwd_partial, with the LayerNorm backward run by the workgroups of the grouped launch
+// that would otherwise leave their CUs idle whenever tn_group_side_plan takes it; else the two launches one after the other.  Same
+// bits either way.  dx_out / ln_ws must not overlap an operand of the group: the side workgroups write while the others read.
+extern "C" int ltrx_gemm_tn_group_ln(int nprob, const float* const* A, const int* lda, const float* const* B, const int* ldb,
+                                     float* const* C, float* const* bias_out, int M, const int* NP, const int* KP, int strict, void* ws,
+                                     size_t ws_bytes, const float** slabs_out, const float** bias_slabs_out, int* splits_out,
+                                     const float* dy, const float* xsum, const float* a, const float* mean, const float* rstd,
+                                     const float* dres_in, int rows, int D, float eps, float* dx_out, void* ln_ws, int* partial_rows_out,
+                                     int side_wgs, int* side_taken_out, ltrx_stream_t stream) {
+  if (!side_taken_out || !partial_rows_out || side_wgs < 0) return LTRX_EINVAL;
+  *side_taken_out = 0;
+  const int crc = tn_group_check(nprob, A, lda, B, ldb, C, bias_out, M, NP, KP, ws, slabs_out, bias_slabs_out, splits_out);
+  if (crc != LTRX_OK) return crc;
+  if (!dy || !xsum || !a || !mean || !rstd || !dx_out || !ln_ws || rows <= 0 || D < 2) return LTRX_EINVAL;   // (ln_bwd_main's)
+  const bool vec = ln_vec_ok(D, dy, xsum, dx_out) && ln_vec_ok(D, a, dres_in, ln_ws);
+  const TnSidePlan pl = tn_group_side_plan(nprob, M, NP, KP, lda, ldb, strict, ws_bytes, rows, D, vec, dres_in != nullptr, side_wgs);
+  // (the partial rows' extent: the workspace the LayerNorm call asks for)
+  const size_t dx_bytes = (size_t)rows * D * sizeof(float), lnws_bytes = ltrx_layernorm_bwd_workspace_bytes(rows, D);
+  for (int p = 0; p < nprob; ++p) {
+    if (lda[p] < NP[p] || ldb[p] < KP[p]) continue;   // (refused below by the GEMM call itself)
+    const size_t na = ((size_t)(M - 1) * lda[p] + NP[p]) * sizeof(float), nb = ((size_t)(M - 1) * ldb[p] + KP[p]) * sizeof(float);
+    if (ranges_overlap(dx_out, dx_bytes, A[p], na) || ranges_overlap(dx_out, dx_bytes, B[p], nb) ||
+        ranges_overlap(ln_ws, lnws_bytes, A[p], na) || ranges_overlap(ln_ws, lnws_bytes, B[p], nb))
+      return LTRX_EINVAL;
+  }
+  if (!pl.grouped || pl.side == 0) {
+    const int rc = ltrx_gemm_tn_group(nprob, A, lda, B, ldb, C, bias_out, M, NP, KP, strict, ws, ws_bytes, slabs_out, bias_slabs_out,
+                                      splits_out, stream);
+    if (rc != LTRX_OK) return rc;
+    return ltrx_layernorm_bwd_partial(dy, xsum, a, mean, rstd, dres_in, rows, D, eps, dx_out, ln_ws, partial_rows_out, stream);
+  }
+  ltrx::LnBwdJob job = {dy, xsum, a, mean, rstd, dres_in, dx_out, (float*)ln_ws, rows, pl.sh.grid, pl.sh.wpb, eps};
+  const int rc = tn_group_run(nprob, A, lda, B, ldb, C, bias_out, M, NP, KP, strict, ws, slabs_out, bias_slabs_out, splits_out, pl, &job,
+                              D, (hipStream_t)stream);
+  if (rc != LTRX_OK) return rc;
+  *partial_rows_out = pl.sh.grid;
+  *side_taken_out = pl.side;
   return LTRX_OK;
 }
 
@@ -1492,4 +1633,24 @@ extern "C" int ltrx_debug_tn_group_map(int nprob, int M, const int* NP, const in
     split_out[w] = g.map_split[w];
   }
   return total * splits;
+}
+
+// test hook (no GPU needed): the side-job plan of ltrx_gemm_tn_group_ln for these shapes (pointers taken as 16-byte aligned, the
+// workspace as sufficient, three-product arithmetic).  Returns the number of side workgroups (0: not taken); *gemm_wgs_out = workgroups
+// of the GEMM path (0 on the per-problem path), *vblocks_out = virtual blocks of the LayerNorm backward (ln_bwd_shape's grid),
+// owner_out[vb] (at least 320 ints) = id of the workgroup that plays virtual block vb, -1 where none does.
+extern "C" int ltrx_debug_tn_group_side_plan(int nprob, int M, const int* NP, const int* KP, int rows, int D, int has_dres, int side_wgs,
+                                             int* gemm_wgs_out, int* vblocks_out, int* owner_out) {
+  if (nprob < 1 || nprob > LTRX_TN_GROUP || !NP || !KP || M <= 0 || rows <= 0 || D <= 0 || side_wgs < 0 || !gemm_wgs_out || !vblocks_out ||
+      !owner_out)
+    return 0;
+  const TnSidePlan pl = tn_group_side_plan(nprob, M, NP, KP, nullptr, nullptr, 0, ~(size_t)0, rows, D, ln_vec_ok(D, nullptr, nullptr, nullptr),
+                                           has_dres != 0, side_wgs);
+  *gemm_wgs_out = pl.grouped ? pl.gemm_wgs : 0;
+  *vblocks_out = pl.sh.grid;
+  for (int vb = 0; vb < 320; ++vb) owner_out[vb] = -1;
+  if (!pl.grouped) return 0;
+  for (int sw = 0; sw < pl.side; ++sw)                 // the kernel's walk (rowreg_ln_bwd_side)
+    for (int vb = sw; vb < pl.sh.grid; vb += pl.side) owner_out[vb] = pl.gemm_wgs + sw;
+  return pl.side;
 }

@@ -366,10 +366,12 @@ static int ln_bwd_grid(int rows) {
 #endif
 static bool ln_bwd_wide(int rows, int D) { return D <= 512 && rows >= LTRX_LN_BWD_WIDE_ROWS; }
 // launch shape of the register-resident backward kernels (plain and norm + head): grid and waves per workgroup
-struct LnBwdShape { int grid, wpb; };
+// (LnBwdShape: ltrx_rowreg.h)
 static LnBwdShape ln_bwd_shape(int rows, int D) {
   return ln_bwd_wide(rows, D) ? LnBwdShape{LTRX_LN_BWD_G16, 16} : LnBwdShape{ln_bwd_grid(rows), 4};
 }
+// ... for the side job of the grouped weight-gradient launch (csrc/ltrx_gemm.hip), which plays the blocks of this launch
+LnBwdShape ltrx_ln_bwd_shape(int rows, int D) { return ln_bwd_shape(rows, D); }
 // f(NV, WPB as integral constants) for that shape; the wide arm exists at NV 1 and 2 only (D <= 512)
 template <typename F>
 static void ln_bwd_dispatch(const LnBwdShape& sh, int D, F&& f) {
@@ -384,9 +386,7 @@ static int ln_fwd_vec_grid(int rows) {
   int g = (rows + 7) / 8;
   return g > 1024 ? 1024 : (g < 1 ? 1 : g);
 }
-static bool ln_vec_ok(int D, const void* p0, const void* p1, const void* p2) {
-  return D % 256 == 0 && D <= 1024 && (((uintptr_t)p0 | (uintptr_t)p1 | (uintptr_t)p2) & 15) == 0;
-}
+// (ln_vec_ok: ltrx_rowreg.h)
 
 extern "C" int ltrx_layernorm_fwd(const float* x, const float* res, const float* a, const float* b, int rows, int D,
                                   float eps, float* xsum_out, float* y_out, float* mean_out, float* rstd_out,

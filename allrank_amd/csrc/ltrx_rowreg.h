@@ -66,20 +66,31 @@ __device__ __forceinline__ float4 rowreg_bwd_dx(const float4 g, const float4 xc,
   o.w = r * (g.w - gm) - tc * xc.w;
   return o;
 }
-// The workgroup's (da, db) partials: wave w spills its da / db to lds[WPB][2][D], then prow[c], c < 2 D (the workgroup's row of the
-// partials) is their sum in wave order.  A macro for the reason above; the kernel's NV, WPB, lane and w, the rest are lvalues.
-#define LTRX_ROWREG_LN_COMBINE(NV, WPB, lds, lane, w, da, db, prow)                                  \
+// The workgroup's (da, db) partials in two halves, so that a kernel whose waves stand in for another launch shape's (rowreg_ln_bwd_side
+// below) states the same stores and the same sum.  Spill: wave w writes its da / db to lds[WPB][2][D].  Sum, after a workgroup barrier:
+// prow[c], c < 2 D (the workgroup's row of the partials) is the sum of the WPB spilled rows in wave order, one thread per column --
+// which thread takes which column does not enter the result.  Macros for the reason above; WPB may be a run-time value.
+#define LTRX_ROWREG_LN_SPILL(NV, lds, lane, w, da, db)                                               \
   do {                                                                                             \
     _Pragma("unroll") for (int t = 0; t < NV; ++t) {                                               \
       reinterpret_cast<float4*>(lds + (size_t)w * 2 * (256 * NV))[lane + 64 * t] = da[t];          \
       reinterpret_cast<float4*>(lds + (size_t)w * 2 * (256 * NV) + 256 * NV)[lane + 64 * t] = db[t]; \
     }                                                                                              \
-    __syncthreads();                                                                               \
+  } while (0)
+#define LTRX_ROWREG_LN_SUM(NV, WPB, lds, prow)                                                       \
+  do {                                                                                             \
     for (int c = threadIdx.x; c < 2 * (256 * NV); c += blockDim.x) {                               \
       float sacc = 0.f;                                                                            \
       for (int ww = 0; ww < WPB; ++ww) sacc += lds[(size_t)ww * 2 * (256 * NV) + c];               \
       (prow)[c] = sacc;                                                                            \
     }                                                                                              \
+  } while (0)
+// a launch whose workgroup IS the block of WPB waves: the kernel's NV, WPB, lane and w, the rest are lvalues
+#define LTRX_ROWREG_LN_COMBINE(NV, WPB, lds, lane, w, da, db, prow)                                  \
+  do {                                                                                             \
+    LTRX_ROWREG_LN_SPILL(NV, lds, lane, w, da, db);                                                \
+    __syncthreads();                                                                               \
+    LTRX_ROWREG_LN_SUM(NV, WPB, lds, prow);                                                        \
   } while (0)
 // The score head's (dw, db) partials of a four-wave workgroup: acc / dbacc to lds[4][D + 4], prow[c], c <= D, their pairwise sum -- at
 // NV = 3, the one width ltrx_score_head_bwd gives to its scalar kernel, that kernel's wave-by-wave sum.
@@ -96,9 +107,125 @@ __device__ __forceinline__ float4 rowreg_bwd_dx(const float4 g, const float4 xc,
     }                                                                                                           \
   } while (0)
 
+// ---- the plain LayerNorm backward (ltrx_layernorm_bwd_vec_kernel<NV, WPB> on `grid` workgroups) as a SIDE JOB of another launch ----
+// The grouped weight-gradient launch (ltrx_gemm_tn256_kernel, csrc/ltrx_gemm.hip) keeps one 8-wave workgroup per CU and leaves
+// 256 - tiles x splits CUs without one; those run this instead.  Bit for bit what the stand-alone kernel writes: side workgroup s of
+// `side` plays the virtual blocks s, s + side, ... of that launch, its 8 waves standing in for a block's wpb waves (wpb 16: two passes
+// of 8; wpb 4: two blocks at once).  A virtual wave walks the rows of the real one (row = vb * wpb + vw; row += grid * wpb) and
+// accumulates da / db in that order; the block's partial row is LTRX_ROWREG_LN_SUM over the spilled rows as in the kernel; a virtual
+// block without rows writes its zero row.  Few CUs carry the stream, so a wave keeps two rows in flight: the loads of the next row are
+// issued before the arithmetic of the current one (only WHEN a load is issued differs from the kernel, no expression does).
+struct LnBwdJob {
+  const float *dy, *xsum, *a, *mean, *rstd, *dres;
+  float *dx, *partial;
+  int rows, grid, wpb;               // the stand-alone launch shape (ln_bwd_shape): wpb is 4 or 16
+  float eps;
+};
+// lds: side_lds_floats(NV, wpb) floats; s: this workgroup's index among the `side` side workgroups; blockDim.x = 512
+__host__ __device__ constexpr int rowreg_ln_side_par(int wpb) { return wpb < 8 ? 8 / wpb : 1; }       // virtual blocks played at once
+__host__ __device__ constexpr size_t rowreg_ln_side_lds_floats(int D, int wpb) { return (size_t)rowreg_ln_side_par(wpb) * wpb * 2 * D; }
+template <int NV>
+__device__ __forceinline__ void rowreg_ln_bwd_side(const LnBwdJob& j, int s, int side, float* __restrict__ lds) {
+  constexpr int D = 256 * NV;
+  const float* __restrict__ dy = j.dy;
+  const float* __restrict__ xsum = j.xsum;
+  const float* __restrict__ dres = j.dres;
+  const float* __restrict__ mean_in = j.mean;
+  const float* __restrict__ rstd_in = j.rstd;
+  float* __restrict__ dx = j.dx;
+  const int rows = j.rows, grid = j.grid, wpb = j.wpb;
+  const float eps = j.eps;
+  const int lane = lane_id(), w = wave_id();
+  const int par = rowreg_ln_side_par(wpb), passes = wpb > 8 ? wpb / 8 : 1;
+  const int vslot = wpb < 8 ? w / wpb : 0;                  // which of the blocks played at once this wave belongs to
+  float* slot = lds + (size_t)vslot * wpb * 2 * D;
+  const int row_step = grid * wpb;
+  float4 av[NV];
+#pragma unroll
+  for (int t = 0; t < NV; ++t) av[t] = reinterpret_cast<const float4*>(j.a)[lane + 64 * t];
+  for (int k0 = 0; s + k0 * side < grid; k0 += par) {       // (workgroup-uniform)
+    const int vb = s + (k0 + vslot) * side;
+    for (int ps = 0; ps < passes; ++ps) {
+      const int vw = wpb < 8 ? w % wpb : w + 8 * ps;
+      float4 da[NV], db[NV];
+#pragma unroll
+      for (int t = 0; t < NV; ++t) {
+        da[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+        db[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+      // two row buffers, addressed by compile-time constants only (registers)
+      float4 g[2][NV], xs[2][NV], dr[2][NV];
+      float mean[2], r[2];
+      auto load = [&](auto bc, int row) {
+        constexpr int b = decltype(bc)::value;
+        mean[b] = mean_in[row];
+        r[b] = rstd_in[row];
+#pragma unroll
+        for (int t = 0; t < NV; ++t) {
+          g[b][t] = reinterpret_cast<const float4*>(dy + (size_t)row * D)[lane + 64 * t];
+          xs[b][t] = reinterpret_cast<const float4*>(xsum + (size_t)row * D)[lane + 64 * t];
+          if (dres) dr[b][t] = reinterpret_cast<const float4*>(dres + (size_t)row * D)[lane + 64 * t];
+        }
+        __builtin_amdgcn_sched_barrier(0);                    // the loads stay ahead of the other row's arithmetic
+      };
+      auto work = [&](auto bc, int row) {
+        constexpr int b = decltype(bc)::value;
+        float gsum = 0.f, dot = 0.f;
+#pragma unroll
+        for (int t = 0; t < NV; ++t) {
+          xs[b][t].x -= mean[b]; xs[b][t].y -= mean[b]; xs[b][t].z -= mean[b]; xs[b][t].w -= mean[b];
+          LTRX_ROWREG_BWD_ACC(g[b][t], xs[b][t], av[t], r[b], da[t], db[t], gsum, dot);
+        }
+        float gm, tc;
+        rowreg_bwd_coef<NV>(gsum, dot, r[b], eps, gm, tc);
+#pragma unroll
+        for (int t = 0; t < NV; ++t) {
+          float4 o = rowreg_bwd_dx(g[b][t], xs[b][t], r[b], gm, tc);
+          if (dres) {
+            const float4 d = dr[b][t];
+            o.x += d.x; o.y += d.y; o.z += d.z; o.w += d.w;
+          }
+          reinterpret_cast<float4*>(dx + (size_t)row * D)[lane + 64 * t] = o;
+        }
+      };
+      const std::integral_constant<int, 0> b0{};
+      const std::integral_constant<int, 1> b1{};
+      int row = vb < grid ? vb * wpb + vw : rows;
+      if (row < rows) load(b0, row);
+      while (row < rows) {
+        int nx = row + row_step;
+        if (nx < rows) load(b1, nx);
+        work(b0, row);
+        row = nx;
+        if (row >= rows) break;
+        nx = row + row_step;
+        if (nx < rows) load(b0, nx);
+        work(b1, row);
+        row = nx;
+      }
+      LTRX_ROWREG_LN_SPILL(NV, slot, lane, vw, da, db);
+    }
+    __syncthreads();
+    for (int q = 0; q < par; ++q) {
+      const int vbq = s + (k0 + q) * side;
+      if (vbq < grid) LTRX_ROWREG_LN_SUM(NV, wpb, (lds + (size_t)q * wpb * 2 * D), j.partial + (size_t)vbq * 2 * D);
+    }
+    __syncthreads();                                          // the spill rows are reused by the next blocks
+  }
+}
+
 }  // namespace ltrx
 
-// Host side: f(std::integral_constant<int, NV>) for the NV of a width D = 256 * NV <= 1024 (1, 2, 3 -> themselves, else 4)
+// Host side: launch shape of the register-resident LayerNorm backward kernels (plain, norm + head, and the side job above): the grid
+// and the waves per workgroup, decided in csrc/ltrx_layernorm.hip (ln_bwd_shape)
+struct LnBwdShape { int grid, wpb; };
+LnBwdShape ltrx_ln_bwd_shape(int rows, int D);
+// the register-resident row layout holds D and these pointers
+static inline bool ln_vec_ok(int D, const void* p0, const void* p1, const void* p2) {
+  return D % 256 == 0 && D <= 1024 && (((uintptr_t)p0 | (uintptr_t)p1 | (uintptr_t)p2) & 15) == 0;
+}
+
+// f(std::integral_constant<int, NV>) for the NV of a width D = 256 * NV <= 1024 (1, 2, 3 -> themselves, else 4)
 template <typename F>
 static inline void ltrx_rowreg_dispatch(int D, F&& f) {
   switch (D / 256) {

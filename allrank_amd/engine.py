@@ -278,7 +278,7 @@ class FusedTrainer(object):
                  optimizer="Adam", weight_decay=0.0, momentum=0.0, nesterov=False,
                  use_graph=True, gemm="split_bf16", dropout=True, seed=None, gradient_clipping_norm=None, compact=False,
                  weight_images=True, fc_step=True, group_wgrad=True, relu_bits=True, pad_input=True, force_dist=False,
-                 _norm_head=True):
+                 _norm_head=True, ln_in_wgrad=True):
         """gemm: "split_bf16" -- libltrx fp32-accurate GEMMs on the bf16 MFMA (3 products), "split_bf16_strict" (6
         products), "hipblaslt" (torch.mm/addmm, exact-fp32 library GEMMs), or "bf16" -- the THROUGHPUT mode: one bf16
         product per contraction in the dense projections AND in attention (fp32 storage, accumulation, LayerNorm, softmax,
@@ -316,7 +316,11 @@ class FusedTrainer(object):
         force_dist=True: see ``self.sharded`` below.
         _norm_head=True: the encoder's final norm and the d_output == 1 score head run as one kernel each way (ltrx_norm_head_fwd /
         ltrx_norm_head_bwd_partial / ltrx_norm_head_wgrad: the normalised rows and their gradient never reach HBM) where ``self.norm_head`` says so; False keeps
-        ltrx_layernorm_* + ltrx_score_head_* (A/B runs, tests: the same bits everywhere)."""
+        ltrx_layernorm_* + ltrx_score_head_* (A/B runs, tests: the same bits everywhere).
+        ln_in_wgrad=True (with group_wgrad): the first-sublayer LayerNorm backward of an encoder layer runs INSIDE the layer's grouped
+        weight-gradient launch, on the CUs that launch leaves without a workgroup (ltrx_gemm_tn_group_ln: 48 tiles x 5 splits = 240 of 256),
+        instead of as a launch of its own behind it; the residual-stream gradient then rotates over three buffers, because that
+        LayerNorm backward may no longer write into the buffer the weight gradient is reading.  Same bits; False = the two launches."""
         from . import _lib as LB
         from .losses import FusedLoss
         self.LB = LB
@@ -326,6 +330,8 @@ class FusedTrainer(object):
         self.gemm = gemm
         self.weight_images = bool(weight_images)
         self.group_wgrad = bool(group_wgrad) and gemm != "split_bf16_strict"     # (the strict arithmetic has no large-tile kernel)
+        self.ln_in_wgrad = bool(ln_in_wgrad) and self.group_wgrad and gemm != "hipblaslt"
+        self.ln_side_log = []                 # side workgroups the most recent ltrx_gemm_tn_group_ln calls used (0: the two-launch path)
         self._wg_pending = []
         self.wgrad_group_log = []             # (problems, grouped kernel ran?) of the most recent _wgrad_flush calls
         self._wg_probe = (ctypes.c_ubyte * 65536)()
@@ -620,6 +626,8 @@ class FusedTrainer(object):
             self.zb = torch.zeros(no, **f32)
         self.d_a = torch.zeros((M, d), **f32)                 # gradient w.r.t. the residual stream (ping)
         self.d_b = torch.zeros((M, d), **f32)                 # (pong)
+        if self.N and self.ln_in_wgrad:                       # a third one: see the layer loop of _step_body
+            self.d_c = torch.zeros((M, d), **f32)
         maxn = max([3 * d, self.dff if self.N else 0] + self.fc_sizes[1:])
         self.ws_col = torch.empty(max(self.lib.ltrx_colsum_workspace_bytes(M, maxn), 64), dtype=torch.uint8, device=dev)
         self.ws_head = torch.empty(max(self.lib.ltrx_score_head_bwd_workspace_bytes(M, d), 64), dtype=torch.uint8, device=dev)
@@ -931,11 +939,17 @@ class FusedTrainer(object):
                                             x.shape[1], self._prec, 9 if padded else 0, P(self.ws_tn), self._st()),
                       "gemm_tn(wgrad)")
 
-    def _wgrad_flush(self, defer_reduce=False):
+    def _wgrad_flush(self, defer_reduce=False, ln=None):
         """the queued weight gradients of a layer as ONE ltrx_gemm_tn_group launch; their partial slabs are summed by the call
         (one launch per projection) or, with ``defer_reduce``, by the layer's _reduce_flush (the workspace must stay untouched
-        until then)"""
+        until then).  ``ln``: the arguments of a _ln_bwd call that is due right after the launch and writes none of its operands --
+        the call then covers both (ltrx_gemm_tn_group_ln: the LayerNorm backward in the launch's idle CUs where the library takes it)."""
         q = self._wg_pending
+        buf = self._ln_partial_slot() if (ln is not None and q) else None
+        if ln is not None and buf is None:                        # nothing queued, or no deferred reduction: the plain pair
+            self._wgrad_flush(defer_reduce)
+            self._ln_bwd(*ln)
+            return
         if not q:
             return
         n = len(q)
@@ -962,8 +976,19 @@ class FusedTrainer(object):
         if self.probe_wgrad is not None:
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
-        self.LB.check(self.lib.ltrx_gemm_tn_group(n, A, lda, Bm, ldb, C, bo, self.rows, NP, KP, self._prec, self.LB.ptr(self.ws_tn),
-                                                  self.ws_tn.numel(), *outs, self._st()), "gemm_tn_group(wgrad)")
+        if ln is None:
+            self.LB.check(self.lib.ltrx_gemm_tn_group(n, A, lda, Bm, ldb, C, bo, self.rows, NP, KP, self._prec, self.LB.ptr(self.ws_tn),
+                                                      self.ws_tn.numel(), *outs, self._st()), "gemm_tn_group(wgrad)")
+        else:
+            P = self.LB.ptr
+            dy, xsum, a, mean, rstd, dres, dx, da, db = ln
+            rows_out, side = ctypes.c_int(0), ctypes.c_int(0)
+            self.LB.check(self.lib.ltrx_gemm_tn_group_ln(n, A, lda, Bm, ldb, C, bo, self.rows, NP, KP, self._prec, P(self.ws_tn),
+                                                         self.ws_tn.numel(), *outs, P(dy), P(xsum), P(a), P(mean), P(rstd), P(dres),
+                                                         self.rows, self.d, float(self.ln_eps), P(dx), P(buf), ctypes.byref(rows_out),
+                                                         0, ctypes.byref(side), self._st()), "gemm_tn_group_ln(wgrad + layernorm_bwd)")
+            self.ln_side_log.append(side.value)
+            del self.ln_side_log[:-16]
         if self.probe_wgrad is not None:
             ev1.record()
             self.probe_wgrad.append((ev0, ev1, n, bool(took)))
@@ -973,6 +998,8 @@ class FusedTrainer(object):
                 self._red_pending.append((so[i], sp.value, nw, nw, t[2].data_ptr()))
                 if bso[i]:
                     self._red_pending.append((bso[i], sp.value, t[0].shape[1], t[0].shape[1], t[3].data_ptr()))
+        if ln is not None:                                        # (after the slabs: the queue position _ln_bwd's entries had)
+            self._ln_partials_queue(buf, rows_out.value, da, db)
         q.clear()
 
     def _reduce_flush(self):
@@ -1097,6 +1124,7 @@ class FusedTrainer(object):
         loss, dsc = self.loss.run(self.scores_raw, self.y_in, self._divisor)
         # ---------------- backward ----------------
         ga, gb = self.d_a, self.d_b
+        spare = self.d_c if (self.N and self.ln_in_wgrad) else None
         if self.compact:                                          # d loss / d scores of the packed rows (alignment rows: 0)
             self.LB.check(lib.ltrx_gather_rows(P(dsc), no, P(self.idx), self.n_valid, M, no, P(self.dsc_c), no, self._st()),
                           "gather_rows")
@@ -1136,7 +1164,9 @@ class FusedTrainer(object):
                 n0, n1 = lay.sublayer[0].norm, lay.sublayer[1].norm
                 ff = lay.feed_forward
                 d_r, dq = self.d_r, self.dqkv
-                mid, outb = other, ds                              # where the two LayerNorm backwards of the layer write: ping-pong over (ga, gb)
+                # where the two LayerNorm backwards of the layer write: ping-pong over (ga, gb); with ln_in_wgrad the second one runs
+                # WHILE the weight gradients read ds (the FFN-2 dY operand), so it writes a third buffer and the three rotate
+                mid, outb, d_top = other, (ds if spare is None else spare), ds
                 # FFN branch
                 db = self._branch_grad(ds, st["p_s1"], st["s_s1"])
                 # (the four weight gradients of the layer are queued and run as one grouped launch before the first kernel that
@@ -1165,9 +1195,14 @@ class FusedTrainer(object):
                     dq[self.n_valid:M].zero_()
                 self._lin_wgrad(dq, st["xn0"], st["gwqkv"], st["gbqkv"], defer=True)
                 self._lin_dgrad(dq, st["wqkv"], st.get("wqkvT"), self.tmp_d)
-                self._wgrad_flush(defer_reduce=True)
-                self._ln_bwd(self.tmp_d, st["xin"], W(n0.a_2), st["mean0"], st["rstd0"], ds, outb, G(n0.a_2), G(n0.b_2))
-                ds, other = outb, mid                              # ds = d loss / d (layer input)
+                ln0 = (self.tmp_d, st["xin"], W(n0.a_2), st["mean0"], st["rstd0"], ds, outb, G(n0.a_2), G(n0.b_2))
+                if spare is None:
+                    self._wgrad_flush(defer_reduce=True)
+                    self._ln_bwd(*ln0)
+                    ds, other = outb, mid                          # ds = d loss / d (layer input)
+                else:
+                    self._wgrad_flush(defer_reduce=True, ln=ln0)
+                    ds, other, spare = outb, mid, d_top            # (the layer's incoming gradient is free in the next layer)
                 self._reduce_flush()                               # the layer's parameter gradients are final from here
                 self._bucket_done(self.N - 1 - i)
         else:

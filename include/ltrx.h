@@ -517,6 +517,25 @@ int ltrx_gemm_tn_group(int nprob, const float* const* A, const int* lda, const f
  * (problem, split) group on one XCD where they fit); tile_out / split_out: 256 bytes each; returns the workgroup count, 0 when the shapes
  * take the per-problem path. */
 int ltrx_debug_tn_group_map(int nprob, int M, const int* NP, const int* KP, unsigned char* tile_out, unsigned char* split_out);
+/* ltrx_gemm_tn_group followed by ltrx_layernorm_bwd_partial(dy .. partial_rows_out) in ONE call, every output with the bits that pair
+ * gives it.  The grouped launch keeps one workgroup per CU and plans tiles x splits <= 256 of them; when CUs are left over (the four
+ * projections of an encoder layer: 48 tiles x 5 splits = 240) and D is a register-resident row width (D % 256 == 0, D <= 1024, aligned
+ * pointers), the LayerNorm backward runs as 256 - tiles x splits extra workgroups of the SAME launch instead of a launch of its own
+ * behind it.  side_wgs: 0 = the library decides (taken only when its measured streaming rate puts the side job well inside the GEMM
+ * part's duration); > 0 = that many side workgroups, clamped to the free CUs (tests).  *side_taken_out = the side workgroups used, 0
+ * when the call ran the grouped GEMM (or its per-problem fall-back) and then the LayerNorm kernel: the caller handles one case.
+ * LTRX_EINVAL, and nothing launched, when dx_out or ln_ws overlaps an A[p] or B[p]: side workgroups write while the others read. */
+int ltrx_gemm_tn_group_ln(int nprob, const float* const* A, const int* lda, const float* const* B, const int* ldb, float* const* C,
+                          float* const* bias_out, int M, const int* NP, const int* KP, int strict, void* ws, size_t ws_bytes,
+                          const float** slabs_out, const float** bias_slabs_out, int* splits_out, const float* dy, const float* xsum,
+                          const float* a, const float* mean, const float* rstd, const float* dres_in, int rows, int D, float eps,
+                          float* dx_out, void* ln_ws, int* partial_rows_out, int side_wgs, int* side_taken_out, ltrx_stream_t stream);
+/* test hook, no GPU needed: the side-job plan of ltrx_gemm_tn_group_ln (aligned pointers, sufficient workspace, strict 0).  Returns the
+ * side workgroup count (0: not taken); *gemm_wgs_out: workgroups of the GEMM path (0: per-problem path); *vblocks_out: workgroups of
+ * the stand-alone LayerNorm backward launch, whose work the side workgroups divide; owner_out[vb], 320 ints: the id of the workgroup
+ * that takes block vb of that launch, -1 where none does. */
+int ltrx_debug_tn_group_side_plan(int nprob, int M, const int* NP, const int* KP, int rows, int D, int has_dres, int side_wgs,
+                                  int* gemm_wgs_out, int* vblocks_out, int* owner_out);
 #define LTRX_REDUCE_GROUP_MAX 16
 int ltrx_reduce_group(int n, const float* const* src, const int* splits, const size_t* row_stride, const size_t* cols, float* const* dst,
                       ltrx_stream_t stream);
