@@ -14,12 +14,14 @@ import numpy as np
 import pytest
 import torch
 
+from tests.test_gpu_norm_head import _wide_rows
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 EPS = 1e-6
 EINVAL = -1
 GUARD = 1024                               # floats of sentinel before and after dx and the partial rows
-WIDE_ROWS = 16 * 4 * 256                   # LTRX_LN_BWD_WIDE_ROWS (csrc/ltrx_rowreg.h)
+WIDE_ROWS = _wide_rows()                   # LTRX_LN_BWD_WIDE_ROWS, read from csrc/ltrx_layernorm.hip
 GEMM_ROWS = 2048                           # the smallest row count of the grouped kernel (tn256_ok)
 ONE = [(256, 256)]
 FOUR = [(256, 256), (512, 256), (256, 256), (256, 256)]
