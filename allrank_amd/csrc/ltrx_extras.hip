@@ -17,11 +17,11 @@ using namespace ltrx;
 __global__ void __launch_bounds__(256) ltrx_layernorm_torch_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                                        const float* __restrict__ b, int rows, int D, float eps,
                                                                        float* __restrict__ y, float* __restrict__ mean_out,
-                                                                       float* __restrict__ rstd_out) {
+                                                                       float* __restrict__ rstd_out, int ldx, int ldy) {
   const int lane = lane_id();
   const int wpb = blockDim.x >> 6;
   for (int row = blockIdx.x * wpb + wave_id(); row < rows; row += gridDim.x * wpb) {
-    const float* xr = x + (size_t)row * D;
+    const float* xr = x + (size_t)row * ldx;
     float sum = 0.f;
     for (int c = lane; c < D; c += 64) sum += xr[c];
     const float mean = wave_sum(sum) / (float)D;
@@ -31,7 +31,7 @@ __global__ void __launch_bounds__(256) ltrx_layernorm_torch_fwd_kernel(const flo
       sq += d * d;
     }
     const float r = 1.0f / sqrtf(wave_sum(sq) / (float)D + eps);
-    float* yr = y + (size_t)row * D;
+    float* yr = y + (size_t)row * ldy;               // (columns D .. ldy of a row are not touched)
     for (int c = lane; c < D; c += 64) yr[c] = (xr[c] - mean) * r * w[c] + b[c];
     if (lane == 0) {
       mean_out[row] = mean;
@@ -46,7 +46,20 @@ extern "C" int ltrx_layernorm_torch_fwd(const float* x, const float* w, const fl
   int g = (rows + 3) / 4;
   if (g > 2048) g = 2048;
   hipLaunchKernelGGL(ltrx_layernorm_torch_fwd_kernel, dim3(g), dim3(256), 0, (hipStream_t)stream, x, w, b, rows, D, eps, y, mean_out,
-                     rstd_out);
+                     rstd_out, D, D);
+  LTRX_LAUNCH_CHECK();
+  return LTRX_OK;
+}
+
+// the same rows with row strides: x[row * ldx + c] -> y[row * ldy + c], c < D (the engine normalises dense input rows into the padded
+// operand rows of the first projection when the feature count is no multiple of 4)
+extern "C" int ltrx_layernorm_torch_fwd_strided(const float* x, int ldx, const float* w, const float* b, int rows, int D, float eps,
+                                                float* y, int ldy, float* mean_out, float* rstd_out, ltrx_stream_t stream) {
+  if (!x || !w || !b || !y || !mean_out || !rstd_out || rows <= 0 || D <= 0 || ldx < D || ldy < D) return LTRX_EINVAL;
+  int g = (rows + 3) / 4;
+  if (g > 2048) g = 2048;
+  hipLaunchKernelGGL(ltrx_layernorm_torch_fwd_kernel, dim3(g), dim3(256), 0, (hipStream_t)stream, x, w, b, rows, D, eps, y, mean_out,
+                     rstd_out, ldx, ldy);
   LTRX_LAUNCH_CHECK();
   return LTRX_OK;
 }

@@ -512,6 +512,8 @@ static int mha_check(int B, int L, int h, int dk, int rs, int ors) {
   return LTRX_OK;
 }
 
+extern "C" int ltrx_mha_head_width_supported(int d_k) { return mha_check(1, 1, 1, d_k, d_k, d_k) == LTRX_OK ? 1 : 0; }
+
 #define LTRX_DKP_DISPATCH(dk, CALL) \
   do {                              \
     if ((dk) <= 32) { CALL(32); }   \

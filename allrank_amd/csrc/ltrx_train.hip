@@ -480,12 +480,25 @@ __global__ void __launch_bounds__(256) ltrx_weight_images_kernel(const float* __
   if ((int)blockIdx.x >= total_tiles + flat_blocks) {
     // row-padded copy of one matrix (the first FC weight [rows][cols] -> [rows][ld], so that its K extent is a multiple of the
     // GEMM's 32-column step): fp32 copy and image; the padding columns keep the zeros they were allocated with
-    const int c4 = pad.cols >> 2, l4 = pad.ld >> 2;
+    // (cols % 4 != 0: the source rows are no longer 16-byte aligned -- scalar loads, and the last group of a row carries the row's tail
+    //  followed by zeros, i.e. it rewrites pad columns with the zeros they hold)
+    const int c4 = (pad.cols + 3) >> 2, l4 = pad.ld >> 2;
+    const bool vec = (pad.cols & 3) == 0;
     const size_t tot = (size_t)pad.rows * c4, nb = gridDim.x - total_tiles - flat_blocks;
     for (size_t i = (size_t)(blockIdx.x - total_tiles - flat_blocks) * blockDim.x + threadIdx.x; i < tot; i += nb * blockDim.x) {
       const size_t r = i / c4;
       const int c = (int)(i - r * c4);
-      const float4 v = reinterpret_cast<const float4*>(pad.src)[i];
+      float4 v;
+      if (vec) {
+        v = reinterpret_cast<const float4*>(pad.src)[i];
+      } else {
+        const float* sr = pad.src + r * pad.cols;
+        const int c0 = 4 * c;
+        v.x = sr[c0];                                            // (c0 < cols: c < ceil(cols / 4))
+        v.y = c0 + 1 < pad.cols ? sr[c0 + 1] : 0.f;
+        v.z = c0 + 2 < pad.cols ? sr[c0 + 2] : 0.f;
+        v.w = c0 + 3 < pad.cols ? sr[c0 + 3] : 0.f;
+      }
       reinterpret_cast<float4*>(pad.dst)[r * l4 + c] = v;
       reinterpret_cast<float4*>(pad.dst_image)[r * l4 + c] = ltrx_split_image4(v);
     }
@@ -528,7 +541,7 @@ extern "C" int ltrx_weight_images(const float* src_base, size_t nflat, void* src
                                   int pad_rows, int pad_cols, int pad_ld, float* pad_dst, void* pad_dst_image, ltrx_stream_t stream) {
   LtrxPadJob pad = {pad_src, pad_dst, pad_dst_image, pad_rows, pad_cols, pad_ld};
   if (pad_src) {
-    if (!pad_dst || !pad_dst_image || pad_rows <= 0 || pad_cols <= 0 || pad_ld < pad_cols || (pad_cols & 3) || (pad_ld & 3) ||
+    if (!pad_dst || !pad_dst_image || pad_rows <= 0 || pad_cols <= 0 || pad_ld < (pad_cols + 3) / 4 * 4 || (pad_ld & 3) ||
         (((uintptr_t)pad_src | (uintptr_t)pad_dst | (uintptr_t)pad_dst_image) & 15))
       return LTRX_EINVAL;
   }
@@ -538,7 +551,7 @@ extern "C" int ltrx_weight_images(const float* src_base, size_t nflat, void* src
   if (n == 0) total_tiles = 0;
   size_t blocks = (nflat / 4 + 255) / 256;
   if (blocks > 2048) blocks = 2048;
-  size_t pblocks = pad_src ? ((size_t)pad_rows * (pad_cols / 4) + 255) / 256 : 0;
+  size_t pblocks = pad_src ? ((size_t)pad_rows * ((pad_cols + 3) / 4) + 255) / 256 : 0;
   if (pblocks > 256) pblocks = 256;
   if (blocks == 0 && total_tiles == 0 && pblocks == 0) return LTRX_OK;
   hipLaunchKernelGGL(ltrx_weight_images_kernel, dim3((unsigned)(total_tiles + blocks + pblocks)), dim3(256), 0, (hipStream_t)stream,

@@ -10,6 +10,7 @@ the device; call ``.item()`` when you want it), gradients live in one flat buffe
 import collections
 import contextlib
 import ctypes
+import gc
 import logging
 import warnings
 
@@ -59,6 +60,24 @@ class Trainer(object):
 # ------------------------------------------------------------------------------------------------------------------
 # shared by FusedTrainer and FusedScorer: the forward-buffer plan, the batch stager, the forward-graph cache
 # ------------------------------------------------------------------------------------------------------------------
+def input_row_plan(F, H, M, gemm, has_input_norm, pad_input):
+    """How the rows the first FC projection reads are laid out: ``(stride, K, large)`` for ``F`` input features, a first FC width
+    ``H``, ``M`` rows per step, the trainer's ``gemm`` mode, an ``input_norm`` or none, and its ``pad_input`` option.
+      stride: floats per row of the operand buffer (the features are its first F columns, the rest stays zero);
+      K:      columns the projection contracts over -- the ``[:, :K]`` view of the buffer against W_0 zero-padded to [H, K];
+      large:  rows of 256 floats and K a multiple of the GEMM's 32-column step, so that the first layer runs the large-tile forward and
+              weight-gradient kernels (a large batch into a 256-multiple width, no input_norm, the bf16-MFMA arithmetic).
+    ``stride == K == F`` is the dense form: no padded buffer, W_0 itself.  F % 4 != 0 -- a feature count the data set dictates
+    (46, 45, 137) -- never has it: ltrx_gemm_nt takes K and row strides in multiples of 4 floats, so stride and K are at least F
+    rounded up to 4.  Pure: no GPU, no library."""
+    large = bool(pad_input and not has_input_norm and gemm in ("split_bf16", "bf16") and F % 256 != 0 and F <= 1024
+                 and H % 256 == 0 and M >= 2048)
+    if large:
+        return (F + 255) // 256 * 256, (F + 31) // 32 * 32, True
+    F4 = (F + 3) // 4 * 4
+    return F4, F4, False
+
+
 def _alloc_forward(owner, t, rows, B, L, saved, compact):
     """Create on ``owner`` the buffer set that ``FusedTrainer._forward`` of trainer ``t`` runs over (``B`` slates of ``L`` items, up to
     ``rows`` rows), every buffer zero-initialised.  The only place that makes forward buffers, and the list of what ``_forward`` reads
@@ -66,8 +85,12 @@ def _alloc_forward(owner, t, rows, B, L, saved, compact):
       B, L, compact (rows = the packed valid items, else the padded grid); rows (of THIS pass: kept current by the owner, not here)
       mask [B, L] u8 key padding (None in the scorer's form: packed rows are all valid keys)
       cu [B+1], order [B] (views of the owner's ``_stager`` tensor), idx [rows] packed row -> grid slot: compact only, else None
-      x_in [rows, F] -- with t._x_pad a view of x_in_buf (rows padded to 256 floats; the pad columns are never written again and
-      must stay zero) next to x_in_k (F rounded up to 32 columns); x_norm, mean_in, rstd_in (input_norm only); fc_out[i]
+      x_in [rows, F]; x_norm [rows, F], mean_in, rstd_in (input_norm only); fc_out[i].  With t._x_pad (``input_row_plan``: the
+      large-tile form, or F % 4 != 0) the rows the first projection reads -- x_in, or x_norm under input_norm (x_in is then dense:
+      no GEMM reads it) -- are the ``[:, :F]`` view of a buffer with rows of t._x_stride floats (x_in_buf / x_norm_buf), and x_in_k
+      is its ``[:, :t._x_k]`` view, the GEMM operand.  INVARIANT: the columns from F on are zero at allocation and nothing writes
+      them again -- every staging kernel, the strided input LayerNorm included, writes F columns per row -- so the K - F surplus
+      columns of the contraction multiply zeros, whatever the pad columns of w0_pad hold (zeros too)
       idx_rows (i64 rank of every row, -1 = none) and x_pe: positional encoding only
       layers[i]: wqkv, bqkv, mod, p_*, s_* (the trainer's parameter views and dropout sites; its own dicts also hold gwqkv / gbqkv
       and later rbits / wqkvT), xsum0 (the residual stream entering layer i > 0), xn0, mean0, rstd0, qkv, o, lse, x1, xn1, mean1,
@@ -96,12 +119,18 @@ def _alloc_forward(owner, t, rows, B, L, saved, compact):
     owner.cu, owner.order = (owner._stager.cu, owner._stager.order) if compact else (None, None)
     owner.idx = torch.full((rows,), 0 if saved else -1, dtype=torch.int32, device=dev) if compact else None
     if t._x_pad:
-        owner.x_in_buf = z(rows, (F0 + 255) // 256 * 256)
-        owner.x_in, owner.x_in_k = owner.x_in_buf[:, :F0], owner.x_in_buf[:, :(F0 + 31) // 32 * 32]
+        op = z(rows, t._x_stride)                             # the first projection's operand rows
+        owner.x_in_k = op[:, :t._x_k]
+        if t.in_norm is None:
+            owner.x_in_buf, owner.x_in = op, op[:, :F0]
+        else:
+            owner.x_in, owner.x_norm_buf, owner.x_norm = z(rows, F0), op, op[:, :F0]
     else:
         owner.x_in = z(rows, F0)
+        if t.in_norm is not None:
+            owner.x_norm = z(rows, F0)
     if t.in_norm is not None:
-        owner.x_norm, owner.mean_in, owner.rstd_in = z(rows, F0), z(rows), z(rows)
+        owner.mean_in, owner.rstd_in = z(rows), z(rows)
     owner.fc_out = [z(rows, s) for s in t.fc_sizes[1:]]
     if t.pos is not None:
         owner.idx_rows = torch.full((rows,), -1, dtype=torch.int64, device=dev)
@@ -170,6 +199,22 @@ class _Stager(object):
         return n
 
 
+@contextlib.contextmanager
+def _collector_at_rest():
+    """Python's cyclic collector stays out of a hipGraph recording.  A trainer or scorer that has been dropped is cyclic garbage (its
+    graph cache refers back to it), and collecting it destroys its hipGraphs and returns their memory pool: runtime calls that a
+    thread must not make while it records.  So what is dead is collected first, as torch.cuda.graph does on entry, and the collector
+    rests until the recording is closed."""
+    gc.collect()
+    was_on = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_on:
+            gc.enable()
+
+
 class _GraphLRU(object):
     """The capture-and-replay rule of every hipGraph the engine records (training step, ``score()``, the scorer's row buckets): two
     eager warm-up visits stay outside any capture (lazy module loads, kernel attributes, workspaces), then a key is captured --
@@ -196,7 +241,7 @@ class _GraphLRU(object):
 
     def _record(self, fn):
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, pool=self.pool):
+        with _collector_at_rest(), torch.cuda.graph(g, pool=self.pool):
             fn()
         return [(g, None)]
 
@@ -272,6 +317,9 @@ class FusedTrainer(object):
     optional fixed / learned positional encoding (positional.py:15-77) -> OutputLayer(any d_output, activation None / Sigmoid /
     Tanh; d_output > 1 feeds the ``ordinal`` loss, ``scores`` is then the sum over the output units, model.py:119-128).
     Other FC / output activations raise NotImplementedError (use ``Trainer``).
+    The input feature count is free: where it is no multiple of 4 (46, 45, 137) the first projection reads rows padded to the next one
+    against a zero-padded copy of W_0 (``input_row_plan``).  The widths the model chooses -- FC widths, d_ff, the head width
+    d_model / h -- must be multiples of 4 (head width <= 128): anything else raises NotImplementedError here, naming the width.
     """
 
     def __init__(self, model, loss_name, loss_args, B, L, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, world_size=1, group=None,
@@ -306,7 +354,8 @@ class FusedTrainer(object):
         relu_bits=True: the feed-forward ReLU(+dropout) mask travels from the forward GEMM to the input-gradient GEMM as one bit per
         element (ltrx_gemm_nt acts 4 / 5) instead of being re-read from the saved fp32 activation; same results bit for bit.
         pad_input=True: the static input buffer keeps the features in rows padded to 256 floats so that the first FC layer (F = 136 is
-        no multiple of the GEMM's 32-column step) runs the large-tile forward and weight-gradient kernels; False = dense rows (A/B).
+        no multiple of the GEMM's 32-column step) runs the large-tile forward and weight-gradient kernels; False = dense rows (A/B) -- or,
+        for a feature count that is no multiple of 4, rows padded to the next one, which the GEMM entries need (``input_row_plan``).
         (Round 6: the two opt-in NEGATIVE RESULTS of round 5 -- ``overlap_wgrad`` (fork / join of the weight-gradient launches on a
         second stream: 1-2 % slower, profiles/r05_wgrad_overlap_ab.md) and ``act_images`` (activations as pre-split operand images:
         VALU -6 ... -28 % in the consumers, cycles unchanged, step -1 %, profiles/r05_act_images_ab.md) -- no longer live in this class;
@@ -365,7 +414,6 @@ class FusedTrainer(object):
         # reduction of the LayerNorm partials (_reduce_flush), whose sums the two-kernel path's (a_2, b_2) gradients have there
         self.norm_head = bool(_norm_head and self.N > 0 and self.n_out == 1 and self.d % 256 == 0 and self.d <= 1024
                               and self.group_wgrad and gemm != "hipblaslt")
-        offs = self._layout_parameters(dropout)
         # slate-resident FC + ListNet step (csrc/ltrx_fcstep.hip): eligibility.  It reads the padded batch in place and masks padded
         # items itself, so a request for variable-length execution is moot for such a job (and would only route it to the slower
         # GEMM launch sequence): compact is dropped.
@@ -374,6 +422,9 @@ class FusedTrainer(object):
             and self.p_fc == 0.0 and self.n_out == 1 and self.out_act == 0 and loss_name == "listNet"
             and gemm == "split_bf16" and optimizer in ("Adam", "AdamW")
             and self.lib.ltrx_fc_listnet_supported(L, self.fc_sizes[0], self.fc_sizes[1]))
+        if not fc_ok:                                         # (before the module's parameters are re-pointed: a refusal leaves it untouched)
+            self._check_widths()
+        offs = self._layout_parameters(dropout)
         if fc_ok:
             if compact or not use_graph:
                 logging.getLogger("allrank_amd.engine").info(
@@ -391,9 +442,11 @@ class FusedTrainer(object):
         # forward buffers (the trainer is its own buffer set).  Input rows are padded to a multiple of 256 floats where the first FC
         # layer can then run the large-tile GEMMs: the forward projection contracts over F rounded up to the kernel's 32-column step
         # against a row-padded copy of W_0 (refreshed with the weight images), the weight gradient reads the padded rows as tiles.
+        # A feature count that is no multiple of 4 (MQ2007 / MQ2008: 46, OHSUMED: 45) takes the same route whatever the batch: the
+        # GEMMs address rows and K in multiples of 4 floats, so the rows are padded to the next one (input_row_plan).
         F0 = self.fc_sizes[0]
-        self._x_pad = bool(pad_input and self.in_norm is None and gemm in ("split_bf16", "bf16") and F0 % 4 == 0 and F0 % 256 != 0
-                           and F0 <= 1024 and self.fc_sizes[1] % 256 == 0 and self.M >= 2048)
+        self._x_stride, self._x_k, self._x_large = input_row_plan(F0, self.fc_sizes[1], self.M, gemm, self.in_norm is not None, pad_input)
+        self._x_pad = (self._x_stride, self._x_k) != (F0, F0)
         _alloc_forward(self, self, self.M, B, L, saved=True, compact=bool(compact))
         self.rows = B * L                                                     # rows the row-wise kernels run over
         self.n_valid = B * L
@@ -498,6 +551,24 @@ class FusedTrainer(object):
             self.dff = l0.feed_forward.w_1.out_features
             self.ln_eps = enc.norm.eps
         return seed
+
+    def _check_widths(self):
+        """What the GEMM launch sequence cannot run is refused HERE, with the width named, so that a caller with another engine to turn
+        to (fit(): the autograd Trainer) takes it before the first batch instead of dying in it.  The input feature count is free
+        (input_row_plan); every width the model itself chooses is a row length of an activation the GEMMs, the LayerNorms and the
+        attention kernels address in 16-byte pieces: a multiple of 4, and a head width ltrx_mha_fwd takes."""
+        for i, s in enumerate(self.fc_sizes[1:]):
+            if s % 4:
+                raise NotImplementedError("FusedTrainer: FC layer %d is %d wide -- the fused step takes hidden widths that are multiples "
+                                          "of 4 (the input feature count is free)" % (i, s))
+        if self.N:
+            if self.dff % 4:
+                raise NotImplementedError("FusedTrainer: feed-forward width d_ff = %d is no multiple of 4" % self.dff)
+            if self.d % self.h or not self.lib.ltrx_mha_head_width_supported(self.d // self.h):
+                raise NotImplementedError("FusedTrainer: head width d_model / h = %d / %d -- the attention kernels take head widths that "
+                                          "are multiples of 4 up to 128" % (self.d, self.h))
+        if self.in_norm is not None and self.fc_sizes[0] < 2:
+            raise NotImplementedError("FusedTrainer: input_norm over %d feature (ltrx_layernorm_bwd needs at least 2 columns)" % self.fc_sizes[0])
 
     def _layout_parameters(self, dropout):
         """the flat parameter / gradient / moment buffers (16-byte aligned segments; q,k,v weights and biases adjacent) with the module's
@@ -660,7 +731,7 @@ class FusedTrainer(object):
         step by ONE batched transpose launch) and the pre-split images of the weights and of the copies"""
         fc, enc, d, dev = self.model.input_layer, self.enc, self.d, self.dev
         f32 = dict(dtype=torch.float32, device=dev)
-        if self._x_pad:                                           # the row-padded copy of W_0 the padded input rows multiply
+        if self._x_pad:                                           # the zero-padded copy [H, K] of W_0 the padded input rows multiply
             self.w0_pad = torch.zeros((self.fc_sizes[1], self.x_in_k.shape[1]), **f32)
             self.w0_pad_i = torch.zeros_like(self.w0_pad)
         tw = [l.weight for l in (fc.layers if self.in_norm is not None else fc.layers[1:])]
@@ -934,7 +1005,7 @@ class FusedTrainer(object):
             return
         P = self.LB.ptr
         # (tile 9: x is the padded input buffer -- its rows are readable up to the 256-column tile, see include/ltrx.h)
-        padded = self._x_pad and x.data_ptr() == self.x_in_buf.data_ptr() and x.stride(0) == self.x_in_buf.stride(0)
+        padded = self._x_large and x.data_ptr() == self.x_in_buf.data_ptr() and x.stride(0) == self.x_in_buf.stride(0)
         self.LB.check(self.lib.ltrx_gemm_tn(P(dy), dy.stride(0), P(x), x.stride(0), P(gw), P(gb), self.rows, dy.shape[1],
                                             x.shape[1], self._prec, 9 if padded else 0, P(self.ws_tn), self._st()),
                       "gemm_tn(wgrad)")
@@ -1029,15 +1100,21 @@ class FusedTrainer(object):
         fc = self.model.input_layer
         dp = (lambda p: p) if train else (lambda p: 0.0)          # dropout rate of a site in this pass
         h = bs.x_in
-        if self.in_norm is not None:                              # FCModel.input_norm (model.py:39)
+        if self.in_norm is not None and self._x_pad:              # ... into the first F columns of the padded operand rows
+            self.LB.check(lib.ltrx_layernorm_torch_fwd_strided(P(h), h.stride(0), P(W(self.in_norm.weight)), P(W(self.in_norm.bias)), M,
+                                                               self.fc_sizes[0], float(self.in_norm.eps), P(bs.x_norm),
+                                                               bs.x_norm.stride(0), P(bs.mean_in), P(bs.rstd_in), self._st()),
+                          "layernorm_torch_fwd_strided")
+            h = bs.x_norm
+        elif self.in_norm is not None:                            # FCModel.input_norm (model.py:39)
             self.LB.check(lib.ltrx_layernorm_torch_fwd(P(h), P(W(self.in_norm.weight)), P(W(self.in_norm.bias)), M, self.fc_sizes[0],
                                                        float(self.in_norm.eps), P(bs.x_norm), P(bs.mean_in), P(bs.rstd_in),
                                                        self._st()), "layernorm_torch_fwd")
             h = bs.x_norm
         for i, lyr in enumerate(fc.layers):
             w_i = W(lyr.weight)
-            if i == 0 and self._x_pad:                             # F rounded up to the GEMM's K step: padded rows x padded W_0
-                h, w_i = bs.x_in_k, self.w0_pad
+            if i == 0 and self._x_pad and self.gemm != "hipblaslt":     # F rounded up to the GEMM's K step: padded rows x padded W_0
+                h, w_i = bs.x_in_k, self.w0_pad                    # (hipblaslt: torch.addmm over the [:, :F] view and W_0 itself)
             if self.fc_act >= 3:                                   # Sigmoid / Tanh: GEMM + bias, then the activation in place
                 self._lin_fwd(h, w_i, W(lyr.bias), bs.fc_out[i], rows=M)
                 self.LB.check(lib.ltrx_out_act_fwd(P(bs.fc_out[i]), M * bs.fc_out[i].shape[1], self.fc_act - 2, P(bs.fc_out[i]),
@@ -1491,7 +1568,12 @@ class FusedTrainer(object):
         batch-global loss normaliser (sharding.allreduce_sum_) -- ends the segment being recorded and is kept as the host
         action to run between two replays: the compute of a step is ~75 launches of 10-300 us at 64 slates per GPU (launch
         latency matters exactly where 8-GPU runs sit), while the collectives stay ordinary torch.distributed calls on the
-        process group's stream, whatever the backend (RCCL on a node, gloo in the one-GPU tests)."""
+        process group's stream, whatever the backend (RCCL on a node, gloo in the one-GPU tests).
+        The cyclic collector rests meanwhile (``_collector_at_rest``)."""
+        with _collector_at_rest():
+            return self._record_step()
+
+    def _record_step(self):
         if self._cap_stream is None:
             self._cap_stream = torch.cuda.Stream(device=self.dev)
         segs = []

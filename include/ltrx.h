@@ -322,6 +322,8 @@ int ltrx_mha_fwd(const float* q, const float* k, const float* v, const uint8_t* 
  * dQ = dS K kernel through HBM (deterministic, no atomics).  Size it with ltrx_mha_bwd_workspace_bytes for the SAME (d_k, mode)
  * the call will use. */
 size_t ltrx_mha_bwd_workspace_bytes(int B, int L, int h, int d_k, int mode);
+/* 1 when ltrx_mha_fwd / ltrx_mha_bwd take heads of d_k columns (d_k % 4 == 0, d_k <= 128), else 0: they return LTRX_EUNSUPPORTED.  Host only. */
+int ltrx_mha_head_width_supported(int d_k);
 int ltrx_mha_bwd(const float* q, const float* k, const float* v, const uint8_t* key_pad_mask, const float* o,
                  const float* dout, const float* lse, int B, int L, int h, int d_k, int row_stride, int o_row_stride,
                  float* dq, float* dk, float* dv, int d_row_stride, float p_drop, uint32_t seed,
@@ -470,7 +472,10 @@ int ltrx_weight_images(const float* src_base, size_t nflat, void* src_image, flo
                        float* pad_dst, void* pad_dst_image, ltrx_stream_t stream);
 /*   pad_src (optional, NULL = none): one more matrix [pad_rows][pad_cols] copied to pad_dst[pad_rows][pad_ld] (fp32) and
  *   pad_dst_image (its image) in the same launch -- the engine keeps the first FC weight [H, F] with rows of ld = F rounded up to 32
- *   so that the input projection runs the large-tile GEMM (padding columns: whatever the buffers hold, zeros in the engine). */
+ *   so that the input projection runs the large-tile GEMM (padding columns: whatever the buffers hold, zeros in the engine).
+ *   pad_ld % 4 == 0 and pad_ld >= pad_cols rounded up to 4; the three pointers 16-byte aligned.  pad_cols % 4 != 0 (a feature count
+ *   the data set dictates: 46, 137, ...) is read with scalar loads, and the columns from pad_cols up to the next multiple of 4 are
+ *   then WRITTEN, with zeros (fp32 copy and image); the columns beyond stay untouched as above. */
 /* A batch into the step's static input buffers in one launch: x (nx floats = rows of F) into rows of ld_dst >= F floats of x_dst
  * (padding columns untouched; nx may be 0), y_dst = y (ny floats),
  * mask_dst[i] = (y[i] == pad_value) -- the padding mask the reference derives per batch (allrank/training/train_utils.py:19,
@@ -544,6 +549,9 @@ int ltrx_reduce_group(int n, const float* const* src, const int* splits, const s
  *   ltrx_layernorm_torch_fwd: FCModel.input_norm = nn.LayerNorm(n_features) (model.py:27,39): biased variance, eps inside the
  *       sqrt; saves mean and rstd.  Its parameter gradients come from ltrx_layernorm_bwd called with these statistics (D >= 2
  *       there: ltrx_layernorm_bwd refuses D == 1, which this forward accepts).
+ *   ltrx_layernorm_torch_fwd_strided: the same rows (same bits) read with row stride ldx >= D and written with row stride ldy >= D;
+ *       columns D .. ldy of y are not touched.  The engine normalises dense input rows into the padded operand rows of the first
+ *       projection when the feature count is no multiple of 4.  A stride below D: LTRX_EINVAL, nothing launched.
  *   ltrx_posenc_fwd: positional encoding (positional.py:15-77, transformer.py:51-52): y = scale * x + table[row(m)],
  *       row = padding_idx for masked items and ranks outside [0, padding_idx), else indices[m]; mask may be NULL.
  *   ltrx_posenc_table_bwd: gradient of a LEARNED table: dtable[r] = sum of dx[m] over the rows m with row(m) == r; the padding
@@ -551,6 +559,8 @@ int ltrx_reduce_group(int n, const float* const* src, const int* splits, const s
  *   ltrx_out_act_fwd / _bwd: OutputLayer activation (model.py:106-117), kind 1 = Sigmoid, 2 = Tanh; bwd: dz = dy * act'(y). */
 int ltrx_layernorm_torch_fwd(const float* x, const float* w, const float* b, int rows, int D, float eps, float* y, float* mean_out,
                              float* rstd_out, ltrx_stream_t stream);
+int ltrx_layernorm_torch_fwd_strided(const float* x, int ldx, const float* w, const float* b, int rows, int D, float eps, float* y, int ldy,
+                                     float* mean_out, float* rstd_out, ltrx_stream_t stream);
 int ltrx_posenc_fwd(const float* x, const float* table, const int64_t* indices, const uint8_t* mask, int M, int D, int padding_idx,
                     float scale, float* y, ltrx_stream_t stream);
 int ltrx_posenc_table_bwd(const float* dx, const int64_t* indices, const uint8_t* mask, int M, int D, int padding_idx, float* dtable,
