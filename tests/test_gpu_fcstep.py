@@ -8,6 +8,7 @@ Adam update against an fp64 replica driven by the engine's gradients (3e-7); on 
 of the same trainer (FusedTrainer(fc_step=False)).  Shapes cover ragged / one-item / fully padded slates, slate lengths and feature
 counts at and off the tile boundaries (L = 16 ... 256, F = 20 ... 144, H = 16 ... 96 including H % 16 != 0), several slates per
 workgroup (B > 256), and both activations.
+The entrywise, stagewise contract of the two kernels through the C ABI is tests/test_gpu_fcstep_contract.py (tests/fcstep_ref.py).
 """
 import copy
 
