@@ -33,6 +33,7 @@
 // Workgroup ids are remapped so that the column tiles of one A row-panel run on the same XCD (shared L2).
 #include "ltrx_mfma.h"
 #include "ltrx_rowreg.h"
+#include <limits.h>
 
 using ltrx::lds_only_barrier;
 using ltrx::rowmap;
@@ -1028,35 +1029,33 @@ extern "C" int ltrx_split_image(const float* src, void* dst, size_t n, ltrx_stre
 // ------------------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------------------
-// `tile` argument of ltrx_gemm_nt / ltrx_gemm_tn (a per-call tuning argument, no process state): 0 = auto; 1 = 128x128x32
-// (4 waves); 2 = 128x128x64; 3 = 256x128x32 (8 waves); 4 = 256x128x64; 6 = 256x256x32 large-tile kernel (auto picks it for
-// exact multiples with >= 360 tiles); 7 = its 128x256x32 form; 8 = its 64x256x32 form with two workgroups per CU (small batches)
+// `tile` argument of ltrx_gemm_nt / ltrx_gemm_tn (a per-call tuning argument, no process state).  ltrx_gemm_nt, and the code a plan
+// segment carries: 0 = auto; 1 = 128x128x32 (4 waves), 2 = 128x128x64, 3 = 256x128x32 (8 waves), 4 = 256x128x64 (six- and one-product
+// precision: 128x128x32 whatever the code); the 256-column (large-tile) kernel: 6 = 256x256x32, 7 = its 128x256x32 form, 8 = its 64x256x32
+// form with two workgroups per CU (small batches); else as 1.  ltrx_gemm_tn: 0 = auto, 1 = never the 256x256 kernel, 9 = see tn_plan.
 // (a PERSISTENT form of the 256x256x32 kernel -- one workgroup per CU walking its tiles, next tile's first K-steps prefetched
 //  behind the epilogue -- was built and measured in round 3: bit-identical results, 0 ... -13 % in speed; tools/lab/gemm_persist.inc,
 //  profiles/r03_gemm_persist_ab.md)
 
-template <int NTERMS, int BM_, int BK_>
-static void launch_nt(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int K,
-                      const float* bias, int act, const float* aux, int ldaux, ltrx::DropSpec drop, const uint32_t* drop_step,
-                      hipStream_t s) {
-  const int tiles_m = (M + BM_ - 1) / BM_, tiles_n = (N + BN - 1) / BN;
-  hipLaunchKernelGGL((ltrx_gemm_nt_kernel<NTERMS, BM_, BK_>), dim3(tiles_m * tiles_n), dim3(BM_ * 2), 0, s, A, lda, B, ldb, C,
-                     ldc, M, N, K, bias, act, aux, ldaux, tiles_n, drop, drop_step);
-}
-
-// ---- the 256-column kernel's launcher: one function per tile height, one table of its instantiations ----
-struct NtLargeArgs {
+// one launch of ltrx_gemm_nt (the rows and pointers of one plan segment); every NT kernel has the one signature and launch statement
+struct NtArgs {
   const float* A; int lda; const float* B; int ldb; float* C; int ldc; int M, N, K;
   const float* bias; int act; const float* aux; int ldaux; ltrx::DropSpec drop; const uint32_t* drop_step;
 };
-typedef void (*NtLargeFn)(const float*, int, const float*, int, float*, int, int, int, int, const float*, int, const float*, int, int,
-                          ltrx::DropSpec, const uint32_t*);
+typedef void (*NtFn)(const float*, int, const float*, int, float*, int, int, int, int, const float*, int, const float*, int, int,
+                     ltrx::DropSpec, const uint32_t*);
+static int nt_launch(NtFn f, int tiles_m, int tiles_n, int threads, size_t lds, const NtArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(f, dim3(tiles_m * tiles_n), dim3(threads), lds, s, a.A, a.lda, a.B, a.ldb, a.C, a.ldc, a.M, a.N, a.K, a.bias, a.act,
+                     a.aux, a.ldaux, tiles_n, a.drop, a.drop_step);
+  LTRX_LAUNCH_CHECK();
+  return LTRX_OK;
+}
 
 // The epilogue kind of a launch, from (act, bias, dropout): the straight-line kinds are the dropout-free epilogues of the default
 // training step, in its form of the launch (exact row tiles, three products, B as a pre-split image).  With drop.thresh == 0 the
 // generic epilogue never reads drop_step, so the kind does not depend on it.  Everything else is EPI_GENERIC -- same bits either way.
-static int nt_epilogue_kind(int act, bool has_bias, const ltrx::DropSpec& drop, bool tail, bool plain, bool bimg) {
-  if (drop.thresh != 0u || tail || plain || !bimg) return EPI_GENERIC;
+static int nt_epilogue_kind(int act, bool has_bias, bool drop_on, bool tail, bool plain, bool bimg) {
+  if (drop_on || tail || plain || !bimg) return EPI_GENERIC;
   switch (act) {
     case 0: return has_bias ? EPI_BIAS : EPI_PLAIN;
     case 3: return has_bias ? EPI_RESIDUAL : EPI_GENERIC;
@@ -1066,14 +1065,83 @@ static int nt_epilogue_kind(int act, bool has_bias, const ltrx::DropSpec& drop, 
   }
 }
 
+// ---- the launch plan of ltrx_gemm_nt: every decision of a call, made once on the host before anything is launched ----
+struct NtSeg {
+  int m0, rows;                       // the rows of A / C / aux this launch covers
+  int tile, nterms;                   // tile code 1-4, 6, 7, 8 (the `tile` table above); bf16 terms per operand (1, 2, 3)
+  int tail, bimg, epi;                // 256-column kernel only: a partial last row tile; B read from its image; epilogue kind
+};
+struct NtPlan { int rc, nseg; NtSeg seg[2]; };       // LTRX_OK and 1 segment (2 in the row-split window), or the refusal and none
+
+// the automatic tile where the 256-column kernel applies: one workgroup per CU, a grid that fills 3/4 .. 1 round, or at least ~1.4
+// rounds (measured, tools/gemm_variants.py: 240 tiles 53 vs 77 us, 360 tiles parity, 120 tiles parity, 480 tiles 102 vs 132 us)
+static int nt_auto_tile(int rows, int N) {
+  const size_t nn = (size_t)(N / 256), t = (size_t)((rows + 255) / 256) * nn, t128 = (size_t)((rows + 127) / 128) * nn;
+  if (t >= 360 || (t >= 168 && t <= 256)) return 6;
+  if (t >= 136 && t < 168 && t128 > 256) return 6;    // one partial round still beats two rounds of smaller tiles
+  if (t128 >= 176 && t128 <= 256) return 7;          // 128-row tiles when they make exactly one well-filled round
+  // small batches (32 slates x 240 per GPU: 120 tiles of 128 rows): 64-row tiles, two workgroups per CU -- 55 vs 77 (128-row) vs
+  // 108 us (small-tile kernel) at M 7680 x N 512 x K 2048 (tools/gemm_nt64_ab.py); same bits as every other tile
+  const size_t t64 = (size_t)((rows + 63) / 64) * nn;
+  if (t128 < 176 && t64 >= 176 && t64 <= 512) return 8;
+  return 1;
+}
+
+// bytes of the one-bit ReLU mask of an [M, N] activation (acts 4 / 5 of ltrx_gemm_nt), 0 where that form does not apply: the mask is
+// kept in the 256 x 256 tile kernel's (tile, thread) order, so both launches must take that kernel whatever their K, dropout and
+// epilogue -- N % 256 == 0, K % 32 == 0 (K of the launch asked about: forward and input-gradient launch of one mask may differ -- ask for
+// both) and a tile count with this property: wherever the function is non-zero, nt_plan for act 4 and for act 5, dropout off or on, is ONE
+// segment on the 256-row tile (tests/test_gemm_plan_cpu.py; asserted by ltrx_gemm_nt).  Callers use acts 1 / 2 where it returns 0.
+extern "C" size_t ltrx_gemm_nt_relu_bits_bytes(int M, int N, int K) {
+  if (M <= 0 || N <= 0 || K <= 0 || (N % 256) || (K % 32)) return 0;
+  const size_t t = (size_t)((M + 255) / 256) * (N / 256);
+  if (!(t >= 380 || (t >= 168 && t <= 256))) return 0;
+  return t * 512 * 16;
+}
+
+// Pure (no HIP call, no pointer): the caller has checked the pointers and M, N, K > 0, act 0..5, tile >= 0, and states vec_epi (16-byte
+// accesses to C, bias and aux) and bimg_ok (a usable image of B).  prec: 0 = three products, 1 = six (strict), 2 = one (plain bf16).
+static NtPlan nt_plan(int M, int N, int K, int lda, int ldb, int ldc, int act, bool has_bias, bool drop_on, int prec, int tile,
+                      bool vec_epi, bool bimg_ok) {
+  NtPlan pl = {LTRX_EUNSUPPORTED, 0, {}};
+  const bool plain = prec == 2, strict = prec != 0 && !plain;
+  // the one-bit mask lives in the large-tile kernel's own (tile, thread) order: only where it runs
+  if ((act == 4 || act == 5) && (tile != 0 || strict || !vec_epi || ltrx_gemm_nt_relu_bits_bytes(M, N, K) == 0)) return pl;
+  if ((K & 3) || (lda & 3) || (ldb & 3) || lda < K || ldb < K || ldc < N) return pl;
+  const bool large_ok = !strict && (N % 256) == 0 && (K % 32) == 0 && vec_epi;
+  if (tile >= 6 && tile <= 8 && !large_ok) return pl;
+  auto segment = [&](int m0, int rows, int v) {
+    const bool large = v >= 6 && v <= 8, tail = large && rows % (v == 6 ? 256 : (v == 7 ? 128 : 64)) != 0;
+    const int nterms = strict ? 3 : (plain ? 1 : 2);
+    pl.seg[pl.nseg++] = {m0, rows, (large || (nterms == 2 && v >= 2 && v <= 4)) ? v : 1, nterms, tail, large && bimg_ok,
+                         large ? nt_epilogue_kind(act, has_bias, drop_on, tail, plain, bimg_ok) : EPI_GENERIC};
+  };
+  const int nn = N / 256, tiles_m = (M + 255) / 256;
+  if (tile != 0 || !large_ok) {
+    segment(0, M, tile);
+  } else if (const size_t t = (size_t)tiles_m * nn; t > 256 && t < 380 && (!drop_on || act == 2) && nn <= 256) {
+    // between one and ~1.5 rounds of 256-row tiles: a second round for a handful of tiles costs as much as the first
+    // (M 33000 x N 512: 95 us against 54 us for M 30720).  One exact round of large tiles first, the remaining rows as
+    // their own (smaller) problem with its own automatic tile: 5-25 % faster over that range (tools/gemm_split_probe.py).
+    // Only without dropout generated in the epilogue -- its hash is indexed by the row of THIS launch.
+    const int m1 = (256 / nn) * 256;
+    segment(0, m1, nt_auto_tile(m1, N));
+    segment(m1, M - m1, nt_auto_tile(M - m1, N));
+  } else {
+    segment(0, M, nt_auto_tile(M, N));
+  }
+  pl.rc = LTRX_OK;
+  return pl;
+}
+
 template <int BM, bool TAIL, int NT, bool BIMG, int EPI>
-static NtLargeFn nt_large_fn() {
+static NtFn nt_large_fn() {
   if constexpr (BM == 64) return ltrx_gemm_nt64_kernel<TAIL, NT, BIMG, EPI>;
   else return ltrx_gemm_nt256_kernel<TAIL, BM, NT, BIMG, EPI>;
 }
 // nullptr: no such instantiation (the mask kinds exist for the 256-row tile only -- the mask is kept in its (tile, thread) order)
 template <int BM>
-static NtLargeFn nt_large_kernel(bool tail, int nt, bool bimg, int epi) {
+static NtFn nt_large_kernel(bool tail, int nt, bool bimg, int epi) {
   switch (epi) {
     case EPI_GENERIC:
 #define LTRX_NT_GENERIC(TAIL_) \
@@ -1095,40 +1163,34 @@ static NtLargeFn nt_large_kernel(bool tail, int nt, bool bimg, int epi) {
 }
 
 template <int BM>
-static int launch_nt_large(const NtLargeArgs& a, bool plain, bool bimg, hipStream_t s) {
+static int launch_nt_large(const NtArgs& a, const NtSeg& sg, hipStream_t s) {
   static std::atomic<uint64_t> attr_done{0};
   const int arc = ltrx_once_per_device(attr_done, [&]() {
     for (int epi = 0; epi < EPI_KINDS; ++epi)
       for (int c = 0; c < (epi == EPI_GENERIC ? 8 : 1); ++c) {
         const int nt = epi == EPI_GENERIC ? 1 + (c & 1) : 2;
-        const NtLargeFn f = nt_large_kernel<BM>(epi == EPI_GENERIC && (c & 4), nt, epi != EPI_GENERIC || (c & 2), epi);
+        const NtFn f = nt_large_kernel<BM>(epi == EPI_GENERIC && (c & 4), nt, epi != EPI_GENERIC || (c & 2), epi);
         const size_t bytes = 2 * (nt == 2 ? sizeof(SmemNT<BM, 2>) : sizeof(SmemNT<BM, 1>));
         if (f && hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return LTRX_EHIP;
       }
     return LTRX_OK;
   });
   if (arc != LTRX_OK) return arc;
-  const bool tail = (a.M % BM) != 0;
-  const int nt = plain ? 1 : 2, tiles_n = a.N / 256;
-  const NtLargeFn f = nt_large_kernel<BM>(tail, nt, bimg, nt_epilogue_kind(a.act, a.bias != nullptr, a.drop, tail, plain, bimg));
+  const NtFn f = nt_large_kernel<BM>(sg.tail != 0, sg.nterms, sg.bimg != 0, sg.epi);
   if (!f) return LTRX_EUNSUPPORTED;
-  const size_t lds = 2 * (nt == 2 ? sizeof(SmemNT<BM, 2>) : sizeof(SmemNT<BM, 1>));
-  hipLaunchKernelGGL(f, dim3(((a.M + BM - 1) / BM) * tiles_n), dim3(512), lds, s, a.A, a.lda, a.B, a.ldb, a.C, a.ldc, a.M, a.N, a.K, a.bias,
-                     a.act, a.aux, a.ldaux, tiles_n, a.drop, a.drop_step);
-  LTRX_LAUNCH_CHECK();
-  return LTRX_OK;
+  const size_t lds = 2 * (sg.nterms == 2 ? sizeof(SmemNT<BM, 2>) : sizeof(SmemNT<BM, 1>));
+  return nt_launch(f, (a.M + BM - 1) / BM, a.N / 256, 512, lds, a, s);
 }
 
-// bytes of the one-bit ReLU mask of an [M, N] activation (acts 4 / 5 of ltrx_gemm_nt), 0 where that form does not apply: the mask is
-// kept in the 256 x 256 tile kernel's (tile, thread) order, so both launches must take that kernel whatever their K, dropout and
-// epilogue -- N a multiple of 256, K a multiple of the kernel's 32-column step (K of the launch asked about: the forward and the
-// input-gradient launch of one mask may contract over different widths -- ask for both) and a tile count the dispatch below sends
-// there unconditionally.  One predicate mirrors the dispatch: callers fall back to acts 1 / 2 where it returns 0.
-extern "C" size_t ltrx_gemm_nt_relu_bits_bytes(int M, int N, int K) {
-  if (M <= 0 || N <= 0 || K <= 0 || (N % 256) || (K % 32)) return 0;
-  const size_t t = (size_t)((M + 255) / 256) * (N / 256);
-  if (!(t >= 380 || (t >= 168 && t <= 256))) return 0;
-  return t * 512 * 16;
+static int launch_nt_small(const NtArgs& a, const NtSeg& sg, hipStream_t s) {
+  const int bm = sg.tile >= 3 ? 256 : 128;            // (codes 3, 4: 256-row tiles, 8 waves; only with two terms, see nt_plan)
+  const NtFn f = sg.nterms == 3   ? ltrx_gemm_nt_kernel<3, 128, 32>
+                 : sg.nterms == 1 ? ltrx_gemm_nt_kernel<1, 128, 32>
+                 : sg.tile == 2   ? ltrx_gemm_nt_kernel<2, 128, 64>
+                 : sg.tile == 3   ? ltrx_gemm_nt_kernel<2, 256, 32>
+                 : sg.tile == 4   ? ltrx_gemm_nt_kernel<2, 256, 64>
+                                  : ltrx_gemm_nt_kernel<2, 128, 32>;
+  return nt_launch(f, (a.M + bm - 1) / bm, (a.N + BN - 1) / BN, 2 * bm, 0, a, s);
 }
 
 extern "C" int ltrx_gemm_nt(const float* A, int lda, const float* B, int ldb, const void* B_image, float* C, int ldc, int M, int N, int K,
@@ -1138,73 +1200,27 @@ extern "C" int ltrx_gemm_nt(const float* A, int lda, const float* B, int ldb, co
   if (!(drop_p >= 0.f) || drop_p >= 1.f) return LTRX_EINVAL;
   const ltrx::DropSpec drop = ltrx_make_drop(drop_p, drop_seed);
   if ((act == 2 || act == 3) && (!aux || ldaux < N)) return LTRX_EINVAL;
-  if (act == 4 || act == 5) {        // the one-bit mask lives in the large-tile kernel's own (tile, thread) order: only where it runs
-    if (!aux || ((uintptr_t)aux & 15) || tile != 0 || strict == 1 || ltrx_gemm_nt_relu_bits_bytes(M, N, K) == 0) return LTRX_EUNSUPPORTED;
-    ldaux = 0;
-  }
-  if ((K & 3) || (lda & 3) || (ldb & 3) || lda < K || ldb < K || ldc < N) return LTRX_EUNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
-  int v = tile;
-  // large-tile kernel: exact multiples only, and enough tiles to cover the 256 CUs at least ~1.4 times
+  const bool mask = act == 4 || act == 5;             // the one-bit mask: a 16-byte aligned buffer of its own, no row stride
+  if (mask && (!aux || ((uintptr_t)aux & 15))) return LTRX_EUNSUPPORTED;
+  if (mask) ldaux = 0;
+  // the alignment facts of the plan: 16-byte epilogue accesses; the pre-split image of B (same addressing as B, 16-byte aligned)
   const bool vec_epi = (ldc & 3) == 0 && ((uintptr_t)C & 15) == 0 && (!bias || ((uintptr_t)bias & 15) == 0) &&
-                       (!aux || ((ldaux & 3) == 0 && ((uintptr_t)aux & 15) == 0));      // 16-byte epilogue accesses
-  if ((act == 4 || act == 5) && (!vec_epi || (K % 32))) return LTRX_EUNSUPPORTED;
-  const bool plain = strict == 2;                     // precision code: 0 = three products, 1 = six (strict), 2 = one (plain bf16)
-  if (strict == 2) strict = 0;
-  if (v == 0 && !strict && (N % 256) == 0 && (K % 32) == 0 && vec_epi) {
-    // one workgroup per CU: a grid that fills 3/4 .. 1 round, or at least ~1.4 rounds (measured, tools/gemm_variants.py:
-    // 240 tiles 53 vs 77 us, 360 tiles parity, 120 tiles parity, 480 tiles 102 vs 132 us)
-    const size_t t = (size_t)((M + 255) / 256) * (N / 256);
-    if (t > 256 && t < 380 && (drop.thresh == 0u || act == 2) && N / 256 <= 256) {
-      // between one and ~1.5 rounds of 256-row tiles: a second round for a handful of tiles costs as much as the first
-      // (M 33000 x N 512: 95 us against 54 us for M 30720).  One exact round of large tiles first, the remaining rows as
-      // their own (smaller) problem: 5-25 % faster over that range (tools/gemm_split_probe.py).  Only without dropout
-      // generated in the epilogue -- its hash is indexed by the row of THIS launch.
-      const int m1 = (256 / (N / 256)) * 256;
-      const int prec = plain ? 2 : strict;
-      int rc = ltrx_gemm_nt(A, lda, B, ldb, B_image, C, ldc, m1, N, K, bias, act, aux, ldaux, drop_p, drop_seed, drop_step, prec, 0,
-                            stream);
-      if (rc != LTRX_OK) return rc;
-      return ltrx_gemm_nt(A + (size_t)m1 * lda, lda, B, ldb, B_image, C + (size_t)m1 * ldc, ldc, M - m1, N, K, bias, act,
-                          aux ? aux + (size_t)m1 * ldaux : nullptr, ldaux, drop_p, drop_seed, drop_step, prec, 0, stream);
-    }
-    if (t >= 360 || (t >= 168 && t <= 256)) v = 6;
-    else if (t >= 136 && t < 168 && (size_t)((M + 127) / 128) * (N / 256) > 256) v = 6;   // one partial round still beats two rounds of smaller tiles
-    else {                                           // 128-row tiles when they make exactly one well-filled round
-      const size_t t128 = (size_t)((M + 127) / 128) * (N / 256);
-      if (t128 >= 176 && t128 <= 256) v = 7;
-      else if (t128 < 176) {                         // small batches (32 slates x 240 per GPU: 120 tiles of 128 rows): 64-row tiles, two
-        const size_t t64 = (size_t)((M + 63) / 64) * (N / 256);   // workgroups per CU -- 55 vs 77 (128-row) vs 108 us (small-tile kernel)
-        if (t64 >= 176 && t64 <= 512) v = 8;         // at M 7680 x N 512 x K 2048 (tools/gemm_nt64_ab.py); same bits as every other tile
-      }
-    }
+                       (!aux || ((ldaux & 3) == 0 && ((uintptr_t)aux & 15) == 0));
+  const bool bimg = B_image != nullptr && (((uintptr_t)B_image) & 15) == 0;
+  const NtPlan pl = nt_plan(M, N, K, lda, ldb, ldc, act, bias != nullptr, drop.thresh != 0u, strict, tile, vec_epi, bimg);
+  if (pl.rc != LTRX_OK) return pl.rc;
+  // (the mask's (tile, thread) order is the 256-row kernel's: refuse any other tiling if the predicate and the plan ever disagree)
+  if (mask && !(pl.nseg == 1 && pl.seg[0].tile == 6)) return LTRX_EUNSUPPORTED;
+  for (int i = 0; i < pl.nseg; ++i) {
+    const NtSeg& sg = pl.seg[i];
+    const NtArgs a = {A + (size_t)sg.m0 * lda, lda, sg.bimg ? reinterpret_cast<const float*>(B_image) : B, ldb, C + (size_t)sg.m0 * ldc, ldc,
+                      sg.rows, N, K, bias, act, aux ? aux + (size_t)sg.m0 * ldaux : nullptr, ldaux, drop, drop_step};
+    const int rc = sg.tile == 6   ? launch_nt_large<256>(a, sg, (hipStream_t)stream)
+                   : sg.tile == 7 ? launch_nt_large<128>(a, sg, (hipStream_t)stream)
+                   : sg.tile == 8 ? launch_nt_large<64>(a, sg, (hipStream_t)stream)
+                                  : launch_nt_small(a, sg, (hipStream_t)stream);
+    if (rc != LTRX_OK) return rc;
   }
-  if (v == 0) v = 1;
-  // (the mask's (tile, thread) order is the 256-row kernel's: refuse rather than run any other tiling if the predicate above and this
-  //  dispatch ever disagree)
-  if ((act == 4 || act == 5) && v != 6) return LTRX_EUNSUPPORTED;
-  if (v == 6 || v == 7 || v == 8) {          // the 256-column kernel: 256- / 128-row tiles, or 64-row tiles with two workgroups per CU
-    if ((N % 256) || (K % 32) || strict || !vec_epi || (v == 8 && (act == 4 || act == 5))) return LTRX_EUNSUPPORTED;
-    // the pre-split image of B (same addressing as B, 16-byte aligned) replaces the fp32 operand in this kernel family only
-    const bool bimg = B_image != nullptr && (((uintptr_t)B_image) & 15) == 0;
-    const NtLargeArgs a = {A, lda, bimg ? reinterpret_cast<const float*>(B_image) : B, ldb, C, ldc, M, N, K, bias, act, aux, ldaux, drop, drop_step};
-    if (v == 6) return launch_nt_large<256>(a, plain, bimg, s);
-    if (v == 7) return launch_nt_large<128>(a, plain, bimg, s);
-    return launch_nt_large<64>(a, plain, bimg, s);
-  }
-  if (strict) {
-    launch_nt<3, 128, 32>(A, lda, B, ldb, C, ldc, M, N, K, bias, act, aux, ldaux, drop, drop_step, s);
-  } else if (plain) {
-    launch_nt<1, 128, 32>(A, lda, B, ldb, C, ldc, M, N, K, bias, act, aux, ldaux, drop, drop_step, s);
-  } else {
-    switch (v) {
-      case 2: launch_nt<2, 128, 64>(A, lda, B, ldb, C, ldc, M, N, K, bias, act, aux, ldaux, drop, drop_step, s); break;
-      case 3: launch_nt<2, 256, 32>(A, lda, B, ldb, C, ldc, M, N, K, bias, act, aux, ldaux, drop, drop_step, s); break;
-      case 4: launch_nt<2, 256, 64>(A, lda, B, ldb, C, ldc, M, N, K, bias, act, aux, ldaux, drop, drop_step, s); break;
-      default: launch_nt<2, 128, 32>(A, lda, B, ldb, C, ldc, M, N, K, bias, act, aux, ldaux, drop, drop_step, s); break;
-    }
-  }
-  LTRX_LAUNCH_CHECK();
   return LTRX_OK;
 }
 
@@ -1218,42 +1234,97 @@ static int tn_splits(int M, int tiles) {
 
 // large-tile wgrad kernel: exact multiples only
 static bool tn256_ok(int M, int NP, int KP) { return (NP % 256) == 0 && (KP % 256) == 0 && (M % 32) == 0 && M >= 2048; }
-static void tn256_plan(int M, int NP, int KP, int* splits, int* mps) {
-  const int tiles = (NP / 256) * (KP / 256);
-  int sp = 256 / tiles;                               // one workgroup per CU and ONE round: never more than 256 workgroups
-  if (sp > M / 128) sp = M / 128;                     // at least 4 K-steps per split
-  if (sp < 1) sp = 1;
-  int m = ((M + sp - 1) / sp + 31) / 32 * 32;
-  *mps = m;
-  *splits = (M + m - 1) / m;
+static int tn256_tiles(int NP, int KP) { return (NP / 256) * (KP / 256); }
+// THE row-split rule of the large-tile kernel, single problem or group: one workgroup per CU and ONE round (never more than 256
+// workgroups over all `tiles`), at least 4 K-steps (128 rows) per split, at least one split
+static int tn256_max_splits(int tiles, int M) {
+  int sp = tiles > 0 ? 256 / tiles : 1;
+  if (sp > M / 128) sp = M / 128;
+  return sp < 1 ? 1 : sp;
+}
+// ... and the split it becomes: rows per split in whole 32-row K-steps, then only as many splits as have rows
+static void tn256_split(int tiles, int M, int* splits, int* mps) {
+  const int sp = tn256_max_splits(tiles, M);
+  *mps = ((M + sp - 1) / sp + 31) / 32 * 32;
+  *splits = (M + *mps - 1) / *mps;
+}
+// THE slab layout of a grouped launch: problem (NP, kv) at `s` splits takes s weight slabs [NP, kv] (w floats), then s bias rows [NP]
+// (bias floats) padded to 4 floats (bias_pad): the pointer walk, the exact need and the sizing bound read it
+struct TnSlab { size_t w, bias, bias_pad; };
+static TnSlab tn_slab_floats(int s, int NP, int kv) {
+  const size_t b = (size_t)s * NP;
+  return {b * kv, b, (b + 3) & ~(size_t)3};
 }
 
-// splits the dispatch below will use for (M, NP, KP) (exported for the sizing test: the workspace must cover every row count
-// <= the M it was sized for, because variable-length batches call ltrx_gemm_tn with a different M every step)
+// ---- the launch plan of ltrx_gemm_tn (pure: no HIP call, no pointer) ----
+struct TnPlan {
+  bool large;                         // the 256 x 256 tile kernel (else the 128 x 128 one)
+  int kv;                             // columns of B that exist (the large tile computes kv rounded up to 256 of them)
+  int tiles, splits, mps;             // grid (tiles, splits); rows per split
+  size_t bias_off;                    // float offset of the bias slabs in the workspace ...
+  int bias_rows;                      // ... and their row count (the 128 x 128 kernel writes two per split)
+};
+static TnPlan tn_plan(int M, int NP, int KP, int lda, int ldb, int precision, int tile) {
+  TnPlan pl = {};
+  pl.kv = KP;
+  // the large tile also serves a B whose column count is not a multiple of 256 when its ROW STRIDE covers the last tile (the
+  // engine pads the input features to 256 floats per row): the surplus columns are computed from the padding and dropped
+  // (opt-in, tile = 9: the kernel reads B[m][KP .. KPr) -- the caller states that every row, the last one included, is readable there)
+  const int KPr = (KP + 255) / 256 * 256;
+  if (tile == 9 && (KPr == KP || ldb < KPr)) tile = 0;
+  pl.large = (precision == 0 || precision == 2) && tile != 1 && (KPr == KP || tile == 9) && tn256_ok(M, NP, KPr) && ldb >= KPr &&
+             (lda & 3) == 0 && (ldb & 3) == 0;
+  if (pl.large) {
+    pl.tiles = tn256_tiles(NP, KPr);
+    tn256_split(pl.tiles, M, &pl.splits, &pl.mps);
+    pl.bias_off = ((size_t)pl.splits * NP * KP + 3) & ~(size_t)3;
+    pl.bias_rows = pl.splits;
+  } else {
+    pl.tiles = ((NP + 127) / 128) * ((KP + BN - 1) / BN);
+    pl.splits = tn_splits(M, pl.tiles);
+    pl.mps = ((M + pl.splits - 1) / pl.splits + 31) / 32 * 32;
+    pl.bias_off = (size_t)pl.splits * NP * KP;
+    pl.bias_rows = 2 * pl.splits;
+  }
+  return pl;
+}
+
+// splits ltrx_gemm_tn will use for (M, NP, KP), dense operands, tile 0 (exported for the sizing test: the workspace must cover every
+// row count <= the M it was sized for, because variable-length batches call ltrx_gemm_tn with a different M every step)
 extern "C" int ltrx_gemm_tn_splits(int M, int NP, int KP) {
   if (M <= 0 || NP <= 0 || KP <= 0) return 0;
-  if (tn256_ok(M, NP, KP)) {
-    int s2, mps;
-    tn256_plan(M, NP, KP, &s2, &mps);
-    return s2;
-  }
-  return tn_splits(M, ((NP + 127) / 128) * ((KP + BN - 1) / BN));
+  return tn_plan(M, NP, KP, NP, KP, 0, 0).splits;
 }
 
 // Upper bound over ALL row counts m <= M (not only M itself): the small-tile plan is monotone in m (tn_splits), the
-// large-tile plan never uses more than min(256 / tiles256, m / 128) splits but is not monotone (m is rounded to 32-row
+// large-tile plan never uses more than tn256_max_splits but is not monotone (m is rounded to 32-row
 // slabs and the kernel switches on at m >= 2048, m % 32 == 0), so its bound is taken whenever the shape could select it.
 extern "C" size_t ltrx_gemm_tn_workspace_bytes(int M, int NP, int KP) {
   if (M <= 0 || NP <= 0 || KP <= 0) return 0;
   const int tiles = ((NP + 127) / 128) * ((KP + BN - 1) / BN);
   size_t sp = (size_t)tn_splits(M, tiles);
   if ((NP % 256) == 0 && M >= 2048) {                 // (KP % 256 != 0: the large tile over a padded B, when ldb allows it)
-    int s2 = 256 / ((NP / 256) * ((KP + 255) / 256));
-    if (s2 > M / 128) s2 = M / 128;
-    if (s2 < 1) s2 = 1;
-    if ((size_t)s2 > sp) sp = (size_t)s2;
+    const size_t s2 = (size_t)tn256_max_splits(tn256_tiles(NP, (KP + 255) / 256 * 256), M);
+    if (s2 > sp) sp = s2;
   }
   return (sp * NP * KP + 2 * sp * NP) * sizeof(float);
+}
+
+// problem p of a large-tile launch, set in the order p = 0, 1, ...: the one place that fills the kernel's table (kv: B's real columns)
+static void tn_group_set(TnGroup& g, int p, const float* A, int lda, const float* B, int ldb, int NP, int kv, float* slabs,
+                         float* bias_slabs) {
+  g.A[p] = A;
+  g.B[p] = B;
+  g.lda[p] = lda;
+  g.ldb[p] = ldb;
+  g.NP[p] = NP;
+  g.kv[p] = kv;
+  g.KP[p] = (kv + 255) / 256 * 256;
+  g.tiles_k[p] = g.KP[p] / 256;
+  g.tile_start[p + 1] = g.tile_start[p] + tn256_tiles(NP, g.KP[p]);      // (tile_start[0] = 0: the table starts zeroed)
+  g.slabs[p] = slabs;
+  g.bias_slabs[p] = bias_slabs;
+  g.nprob = p + 1;
 }
 
 // the large-tile kernel's two staging buffers exceed the default dynamic-LDS allowance (ltrx_gemm_tn and ltrx_gemm_tn_group launch it)
@@ -1263,90 +1334,46 @@ static int tn256_allow_lds() {
                                            {ltrx_gemm_tn256_kernel<2, 1>, 2 * sizeof(SmemNT<256, 2>)}, {ltrx_gemm_tn256_kernel<2, 2>, 2 * sizeof(SmemNT<256, 2>)},
                                            {ltrx_gemm_tn256_kernel<2, 3>, 2 * sizeof(SmemNT<256, 2>)}, {ltrx_gemm_tn256_kernel<2, 4>, 2 * sizeof(SmemNT<256, 2>)}});
 }
+static void tn256_launch(bool plain, dim3 grid, const TnGroup& g, int M, int mps, hipStream_t s) {
+  const auto k = plain ? ltrx_gemm_tn256_kernel<1> : ltrx_gemm_tn256_kernel<2>;
+  hipLaunchKernelGGL(k, grid, dim3(512), 2 * (plain ? sizeof(SmemNT<256, 1>) : sizeof(SmemNT<256, 2>)), s, g, M, mps);
+}
 
 extern "C" int ltrx_gemm_tn(const float* A, int lda, const float* B, int ldb, float* C, float* bias_out, int M, int NP,
                             int KP, int strict, int tile, void* ws, ltrx_stream_t stream) {
   if (!A || !B || !C || !ws || M <= 0 || NP <= 0 || KP <= 0 || tile < 0) return LTRX_EINVAL;
   if (lda < NP || ldb < KP) return LTRX_EUNSUPPORTED;
   const bool plain = strict == 2;                     // precision code as in ltrx_gemm_nt
-  if (strict == 2) strict = 0;
-  // the large tile also serves a B whose column count is not a multiple of 256 when its ROW STRIDE covers the last tile (the
-  // engine pads the input features to 256 floats per row): the surplus columns are computed from the padding and dropped
-  // (opt-in, tile = 9: the kernel reads B[m][KP .. KPr) -- the caller states that every row, the last one included, is readable there)
-  const int KPr = (KP + 255) / 256 * 256;
-  if (tile == 9 && (KPr == KP || ldb < KPr)) tile = 0;
-  if (!strict && tile != 1 && (KPr == KP || tile == 9) && tn256_ok(M, NP, KPr) && ldb >= KPr && (lda & 3) == 0 && (ldb & 3) == 0) {
-    const int kv = KP;
-    KP = KPr;
-    hipStream_t s = (hipStream_t)stream;
-    int splits, mps;
-    tn256_plan(M, NP, KP, &splits, &mps);
+  const TnPlan pl = tn_plan(M, NP, KP, lda, ldb, strict, tile);
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(pl.tiles, pl.splits);
+  float* bslabs = bias_out ? (float*)ws + pl.bias_off : nullptr;
+  if (pl.large) {
     const int arc = tn256_allow_lds();
     if (arc != LTRX_OK) return arc;
-    float* bslabs = bias_out ? (float*)ws + (((size_t)splits * NP * kv + 3) & ~(size_t)3) : nullptr;
     TnGroup g = {};
-    g.kv[0] = kv;
-    g.A[0] = A;
-    g.B[0] = B;
-    g.slabs[0] = (float*)ws;
-    g.bias_slabs[0] = bslabs;
-    g.lda[0] = lda;
-    g.ldb[0] = ldb;
-    g.NP[0] = NP;
-    g.KP[0] = KP;
-    g.tiles_k[0] = KP / 256;
-    g.tile_start[0] = 0;
-    g.tile_start[1] = (NP / 256) * (KP / 256);
-    g.nprob = 1;
-    if (plain)
-      hipLaunchKernelGGL(ltrx_gemm_tn256_kernel<1>, dim3((NP / 256) * (KP / 256), splits), dim3(512), 2 * sizeof(SmemNT<256, 1>), s, g, M, mps);
-    else
-      hipLaunchKernelGGL(ltrx_gemm_tn256_kernel<2>, dim3((NP / 256) * (KP / 256), splits), dim3(512), 2 * sizeof(SmemNT<256, 2>), s, g, M, mps);
-    LTRX_LAUNCH_CHECK();
-    launch_slab_reduce((const float*)ws, splits, (size_t)NP * kv, C, bslabs, splits, (size_t)NP, bias_out, s);
-    LTRX_LAUNCH_CHECK();
-    return LTRX_OK;
+    tn_group_set(g, 0, A, lda, B, ldb, NP, KP, (float*)ws, bslabs);
+    tn256_launch(plain, grid, g, M, pl.mps, s);
+  } else {
+    const auto k = plain ? ltrx_gemm_tn_kernel<1> : (strict ? ltrx_gemm_tn_kernel<3> : ltrx_gemm_tn_kernel<2>);
+    hipLaunchKernelGGL(k, grid, dim3(256), 0, s, A, lda, B, ldb, (float*)ws, bslabs, M, NP, KP, (KP + BN - 1) / BN, pl.mps);
   }
-  const int tiles_n = (NP + 127) / 128, tiles_k = (KP + BN - 1) / BN;
-  const int tiles = tiles_n * tiles_k;
-  const int splits = tn_splits(M, tiles);
-  int mps = (M + splits - 1) / splits;
-  mps = (mps + 31) / 32 * 32;
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 grid(tiles, splits);
-  float* bslabs = bias_out ? (float*)ws + (size_t)splits * NP * KP : nullptr;
-  if (strict)
-    hipLaunchKernelGGL(ltrx_gemm_tn_kernel<3>, grid, dim3(256), 0, s, A, lda, B, ldb, (float*)ws, bslabs, M, NP, KP, tiles_k, mps);
-  else if (plain)
-    hipLaunchKernelGGL(ltrx_gemm_tn_kernel<1>, grid, dim3(256), 0, s, A, lda, B, ldb, (float*)ws, bslabs, M, NP, KP, tiles_k, mps);
-  else
-    hipLaunchKernelGGL(ltrx_gemm_tn_kernel<2>, grid, dim3(256), 0, s, A, lda, B, ldb, (float*)ws, bslabs, M, NP, KP, tiles_k, mps);
   LTRX_LAUNCH_CHECK();
-  launch_slab_reduce((const float*)ws, splits, (size_t)NP * KP, C, bslabs, 2 * splits, (size_t)NP, bias_out, s);
+  launch_slab_reduce((const float*)ws, pl.splits, (size_t)NP * KP, C, bslabs, pl.bias_rows, (size_t)NP, bias_out, s);
   LTRX_LAUNCH_CHECK();
   return LTRX_OK;
 }
 
 // ---- grouped weight gradients (see TnGroup) ----
-static void tn_group_plan(int nprob, int M, const int* NP, const int* KP, int* total_tiles, int* splits, int* mps) {
-  int t = 0;
-  for (int p = 0; p < nprob; ++p) t += (NP[p] / 256) * (KP[p] / 256);
-  int sp = t > 0 ? 256 / t : 1;                       // one workgroup per CU and ONE round
-  if (sp > M / 128) sp = M / 128;                     // at least 4 K-steps per split
-  if (sp < 1) sp = 1;
-  const int m = ((M + sp - 1) / sp + 31) / 32 * 32;
-  *total_tiles = t;
-  *mps = m;
-  *splits = (M + m - 1) / m;
-}
-static bool tn_group_ok(int nprob, int M, const int* NP, const int* KP, const int* lda, const int* ldb, int strict) {
-  if (nprob < 1 || nprob > LTRX_TN_GROUP || strict == 1) return false;
+// tiles of the group when the grouped kernel can run it (every problem on the large tile, one round of at most 256 tiles), else 0
+static int tn_group_tiles(int nprob, int M, const int* NP, const int* KP, const int* lda, const int* ldb, int strict) {
+  if (nprob < 1 || nprob > LTRX_TN_GROUP || strict == 1) return 0;
   int t = 0;
   for (int p = 0; p < nprob; ++p) {
-    if (!tn256_ok(M, NP[p], KP[p]) || (lda && ((lda[p] & 3) || lda[p] < NP[p])) || (ldb && ((ldb[p] & 3) || ldb[p] < KP[p]))) return false;
-    t += (NP[p] / 256) * (KP[p] / 256);
+    if (!tn256_ok(M, NP[p], KP[p]) || (lda && ((lda[p] & 3) || lda[p] < NP[p])) || (ldb && ((ldb[p] & 3) || ldb[p] < KP[p]))) return 0;
+    t += tn256_tiles(NP[p], KP[p]);
   }
-  return t <= 256;
+  return t <= 256 ? t : 0;
 }
 
 // (problem, split) groups -> XCDs: fills g.map_tile / g.map_split for the total * splits (<= 256) workgroups of a grouped launch
@@ -1354,7 +1381,7 @@ static void tn_group_map(TnGroup& g, int total, int splits) {
   const int nprob = g.nprob;
   // (problem, split) groups, largest first, into the 8 XCDs (first fit, capacity = an even share of the grid; a group that fits
   // nowhere whole is cut); XCD x owns the workgroup ids x, x + 8, x + 16, ...
-  const int nwg = total * splits;                        // <= 256 (tn_group_plan)
+  const int nwg = total * splits;                        // <= 256 (tn256_split)
   const int cap = (nwg + 7) / 8;
   int fill[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int order[LTRX_TN_GROUP];
@@ -1403,9 +1430,8 @@ static void tn_group_map(TnGroup& g, int total, int splits) {
   }
   }
 
-// bytes for ltrx_gemm_tn_group: an upper bound over every row count m <= M (variable-length batches): per problem at most
-// min(256 / total_tiles, m / 128) + 1 slabs of NP x KP (+ NP for the bias), and never less than the single-problem calls need (the
-// group call falls back to them when a shape does not qualify)
+// bytes for ltrx_gemm_tn_group: an upper bound over every row count m <= M (variable-length batches): per problem one split more than
+// tn256_max_splits allows at any m, and never less than the single-problem calls need (the fall-back of shapes that do not qualify)
 extern "C" size_t ltrx_gemm_tn_group_workspace_bytes(int nprob, int M, const int* NP, const int* KP) {
   if (nprob < 1 || nprob > LTRX_TN_GROUP || M <= 0 || !NP || !KP) return 0;
   size_t single = 0;
@@ -1415,11 +1441,12 @@ extern "C" size_t ltrx_gemm_tn_group_workspace_bytes(int nprob, int M, const int
     if (b > single) single = b;
     t += ((NP[p] + 255) / 256) * ((KP[p] + 255) / 256);
   }
-  size_t sp = t > 0 ? (size_t)(256 / t) : 1;
-  if (sp < 1) sp = 1;
-  sp += 1;
+  const int sp = tn256_max_splits(t, INT_MAX) + 1;   // (no row clamp: the bound callers size by has never depended on M)
   size_t grouped = 0;
-  for (int p = 0; p < nprob; ++p) grouped += (sp * NP[p] * KP[p] + sp * NP[p] + 4) * sizeof(float);
+  for (int p = 0; p < nprob; ++p) {
+    const TnSlab sl = tn_slab_floats(sp, NP[p], KP[p]);
+    grouped += (sl.w + sl.bias + 4) * sizeof(float);  // (+ 4 floats where the layout pads by at most 3: the values callers size by)
+  }
   return grouped > single ? grouped : single;
 }
 
@@ -1440,7 +1467,8 @@ extern "C" size_t ltrx_gemm_tn_group_workspace_bytes(int nprob, int M, const int
 #endif
 struct TnSidePlan {
   bool grouped;                       // the grouped kernel runs (else: one ltrx_gemm_tn per problem)
-  int total, splits, mps;             // tn_group_plan
+  int total, splits, mps;             // tiles of the group, row splits, rows per split (tn256_split)
+  size_t need;                        // bytes of workspace the grouped launch writes (tn_slab_floats), exactly
   int gemm_wgs, side;                 // workgroups of the GEMM path; side workgroups (0: no side job)
   LnBwdShape sh;                      // the stand-alone LayerNorm backward launch whose blocks the side workgroups play
 };
@@ -1448,15 +1476,16 @@ struct TnSidePlan {
 static TnSidePlan tn_group_side_plan(int nprob, int M, const int* NP, const int* KP, const int* lda, const int* ldb, int strict,
                                      size_t ws_bytes, int rows, int D, bool vec, bool has_dres, int side_wgs) {
   TnSidePlan pl = {};
-  pl.mps = M;
-  pl.splits = 1;
   pl.sh = ltrx_ln_bwd_shape(rows, D);
-  pl.grouped = tn_group_ok(nprob, M, NP, KP, lda, ldb, strict);
+  pl.total = tn_group_tiles(nprob, M, NP, KP, lda, ldb, strict);
+  pl.grouped = pl.total > 0;
   if (!pl.grouped) return pl;
-  tn_group_plan(nprob, M, NP, KP, &pl.total, &pl.splits, &pl.mps);
-  size_t need = 0;
-  for (int p = 0; p < nprob; ++p) need += ((size_t)pl.splits * NP[p] * KP[p] + (size_t)pl.splits * NP[p] + 4) * sizeof(float);
-  if (need > ws_bytes) {
+  tn256_split(pl.total, M, &pl.splits, &pl.mps);
+  for (int p = 0; p < nprob; ++p) {
+    const TnSlab sl = tn_slab_floats(pl.splits, NP[p], KP[p]);
+    pl.need += (sl.w + sl.bias_pad) * sizeof(float);
+  }
+  if (pl.need > ws_bytes) {
     pl.grouped = false;
     return pl;
   }
@@ -1485,33 +1514,17 @@ static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
 static int tn_group_run(int nprob, const float* const* A, const int* lda, const float* const* B, const int* ldb, float* const* C,
                         float* const* bias_out, int M, const int* NP, const int* KP, int strict, void* ws, const float** slabs_out,
                         const float** bias_slabs_out, int* splits_out, const TnSidePlan& pl, const ltrx::LnBwdJob* ln, int ln_D, hipStream_t s) {
-  const bool defer = slabs_out != nullptr;
-  const bool plain = strict == 2;
   const int total = pl.total, splits = pl.splits, mps = pl.mps;
   const int arc = tn256_allow_lds();
   if (arc != LTRX_OK) return arc;
   TnGroupLn gl = {};
   TnGroup& g = gl.g;
-  g.nprob = nprob;
   float* w = (float*)ws;
-  int t0 = 0;
   for (int p = 0; p < nprob; ++p) {
-    g.A[p] = A[p];
-    g.B[p] = B[p];
-    g.lda[p] = lda[p];
-    g.ldb[p] = ldb[p];
-    g.NP[p] = NP[p];
-    g.KP[p] = KP[p];
-    g.kv[p] = KP[p];
-    g.tiles_k[p] = KP[p] / 256;
-    g.tile_start[p] = t0;
-    t0 += (NP[p] / 256) * (KP[p] / 256);
-    g.slabs[p] = w;
-    w += (size_t)splits * NP[p] * KP[p];
-    g.bias_slabs[p] = bias_out[p] ? w : nullptr;
-    w += ((size_t)splits * NP[p] + 3) & ~(size_t)3;
+    const TnSlab sl = tn_slab_floats(splits, NP[p], KP[p]);
+    tn_group_set(g, p, A[p], lda[p], B[p], ldb[p], NP[p], KP[p], w, bias_out[p] ? w + sl.w : nullptr);
+    w += sl.w + sl.bias_pad;
   }
-  g.tile_start[nprob] = t0;
   tn_group_map(g, total, splits);
   if (ln && pl.side > 0) {
     gl.ln = *ln;
@@ -1521,13 +1534,11 @@ static int tn_group_run(int nprob, const float* const* A, const int* lda, const 
       hipLaunchKernelGGL((ltrx_gemm_tn256_kernel<2, decltype(nv)::value>), dim3(pl.gemm_wgs + pl.side), dim3(512), 2 * sizeof(SmemNT<256, 2>),
                          s, gl, M, mps);
     });
-  } else if (plain) {
-    hipLaunchKernelGGL(ltrx_gemm_tn256_kernel<1>, dim3(total, splits), dim3(512), 2 * sizeof(SmemNT<256, 1>), s, g, M, mps);
   } else {
-    hipLaunchKernelGGL(ltrx_gemm_tn256_kernel<2>, dim3(total, splits), dim3(512), 2 * sizeof(SmemNT<256, 2>), s, g, M, mps);
+    tn256_launch(strict == 2, dim3(total, splits), g, M, mps, s);
   }
   LTRX_LAUNCH_CHECK();
-  if (defer) {
+  if (slabs_out) {                                    // the reduction is left to the caller (tn_group_check: all three or none)
     for (int p = 0; p < nprob; ++p) {
       slabs_out[p] = g.slabs[p];
       bias_slabs_out[p] = g.bias_slabs[p];
@@ -1612,33 +1623,21 @@ extern "C" int ltrx_gemm_tn_group_ln(int nprob, const float* const* A, const int
   return LTRX_OK;
 }
 
-// test hook (no GPU needed): the workgroup -> (tile, split) table ltrx_gemm_tn_group would launch with for these shapes; returns the
-// workgroup count (0 when the shapes take the per-problem path)
+// ---- test hooks (no GPU needed; documented in include/ltrx.h): what the plans above decide, by the code the calls run ----
 extern "C" int ltrx_debug_tn_group_map(int nprob, int M, const int* NP, const int* KP, unsigned char* tile_out, unsigned char* split_out) {
   if (nprob < 1 || nprob > LTRX_TN_GROUP || !NP || !KP || !tile_out || !split_out || M <= 0) return 0;
-  if (!tn_group_ok(nprob, M, NP, KP, nullptr, nullptr, 0)) return 0;
-  int total = 0, splits = 1, mps = M;
-  tn_group_plan(nprob, M, NP, KP, &total, &splits, &mps);
+  const TnSidePlan pl = tn_group_side_plan(nprob, M, NP, KP, nullptr, nullptr, 0, ~(size_t)0, 0, 0, false, false, 0);
+  if (!pl.grouped) return 0;
   TnGroup g = {};
-  g.nprob = nprob;
-  int t0 = 0;
-  for (int p = 0; p < nprob; ++p) {
-    g.tile_start[p] = t0;
-    t0 += (NP[p] / 256) * (KP[p] / 256);
-  }
-  g.tile_start[nprob] = t0;
-  tn_group_map(g, total, splits);
-  for (int w = 0; w < total * splits; ++w) {
+  for (int p = 0; p < nprob; ++p) tn_group_set(g, p, nullptr, 0, nullptr, 0, NP[p], KP[p], nullptr, nullptr);
+  tn_group_map(g, pl.total, pl.splits);
+  for (int w = 0; w < pl.gemm_wgs; ++w) {
     tile_out[w] = g.map_tile[w];
     split_out[w] = g.map_split[w];
   }
-  return total * splits;
+  return pl.gemm_wgs;
 }
 
-// test hook (no GPU needed): the side-job plan of ltrx_gemm_tn_group_ln for these shapes (pointers taken as 16-byte aligned, the
-// workspace as sufficient, three-product arithmetic).  Returns the number of side workgroups (0: not taken); *gemm_wgs_out = workgroups
-// of the GEMM path (0 on the per-problem path), *vblocks_out = virtual blocks of the LayerNorm backward (ln_bwd_shape's grid),
-// owner_out[vb] (at least 320 ints) = id of the workgroup that plays virtual block vb, -1 where none does.
 extern "C" int ltrx_debug_tn_group_side_plan(int nprob, int M, const int* NP, const int* KP, int rows, int D, int has_dres, int side_wgs,
                                              int* gemm_wgs_out, int* vblocks_out, int* owner_out) {
   if (nprob < 1 || nprob > LTRX_TN_GROUP || !NP || !KP || M <= 0 || rows <= 0 || D <= 0 || side_wgs < 0 || !gemm_wgs_out || !vblocks_out ||
@@ -1653,4 +1652,41 @@ extern "C" int ltrx_debug_tn_group_side_plan(int nprob, int M, const int* NP, co
   for (int sw = 0; sw < pl.side; ++sw)                 // the kernel's walk (rowreg_ln_bwd_side)
     for (int vb = sw; vb < pl.sh.grid; vb += pl.side) owner_out[vb] = pl.gemm_wgs + sw;
   return pl.side;
+}
+
+// (the three plans themselves)
+extern "C" int ltrx_debug_gemm_nt_plan(int M, int N, int K, int lda, int ldb, int ldc, int act, int has_bias, int drop_on, int strict,
+                                       int tile, int vec_epi, int b_image, int* out) {
+  if (!out) return 0;
+  NtPlan pl = {LTRX_EINVAL, 0, {}};
+  if (M > 0 && N > 0 && K > 0 && act >= 0 && act <= 5 && tile >= 0)
+    pl = nt_plan(M, N, K, lda, ldb, ldc, act, has_bias != 0, drop_on != 0, strict, tile, vec_epi != 0, b_image != 0);
+  out[0] = pl.rc;
+  for (int i = 0; i < pl.nseg; ++i) {
+    const NtSeg& sg = pl.seg[i];
+    const int v[7] = {sg.m0, sg.rows, sg.tile, sg.nterms, sg.tail, sg.bimg, sg.epi};
+    for (int j = 0; j < 7; ++j) out[7 * i + j] = v[j];
+  }
+  return pl.nseg;
+}
+
+extern "C" int ltrx_debug_gemm_tn_plan(int M, int NP, int KP, int lda, int ldb, int strict, int tile, int* splits_out, int* rows_per_split_out,
+                                       int* kv_out) {
+  if (M <= 0 || NP <= 0 || KP <= 0 || tile < 0 || lda < NP || ldb < KP || !splits_out || !rows_per_split_out || !kv_out) return -1;
+  const TnPlan pl = tn_plan(M, NP, KP, lda, ldb, strict, tile);
+  *splits_out = pl.splits;
+  *rows_per_split_out = pl.mps;
+  *kv_out = pl.kv;
+  return pl.large ? 1 : 0;
+}
+
+extern "C" int ltrx_debug_tn_group_plan(int nprob, int M, const int* NP, const int* KP, const int* lda, const int* ldb, int strict,
+                                        size_t ws_bytes, int* splits_out, size_t* need_bytes_out) {
+  if (splits_out) *splits_out = 0;
+  if (need_bytes_out) *need_bytes_out = 0;
+  if (nprob < 1 || nprob > LTRX_TN_GROUP || !NP || !KP || M <= 0 || !splits_out || !need_bytes_out) return 0;
+  const TnSidePlan pl = tn_group_side_plan(nprob, M, NP, KP, lda, ldb, strict, ws_bytes, 0, 0, false, false, 0);   // as ltrx_gemm_tn_group
+  *need_bytes_out = pl.need;
+  if (pl.grouped) *splits_out = pl.splits;
+  return pl.grouped ? 1 : 0;
 }

@@ -383,7 +383,6 @@ class FusedTrainer(object):
         self.ln_side_log = []                 # side workgroups the most recent ltrx_gemm_tn_group_ln calls used (0: the two-launch path)
         self._wg_pending = []
         self.wgrad_group_log = []             # (problems, grouped kernel ran?) of the most recent _wgrad_flush calls
-        self._wg_probe = (ctypes.c_ubyte * 65536)()
         self._red_pending = []                # (src ptr, partial rows, row stride, columns, dst ptr) entries of the next _reduce_flush
         self._ln_slot = 0
         self._prec = {"split_bf16_strict": 1, "bf16": 2}.get(gemm, 0)        # precision code of ltrx_gemm_nt / ltrx_gemm_tn
@@ -1039,9 +1038,10 @@ class FusedTrainer(object):
         else:
             outs = (None, None, None)
         # did the grouped kernel take this composition, or did the call fall back to one launch per problem (shapes outside the
-        # large-tile kernel / not enough workspace)?  Same host-side predicate the library applies; tests assert it
-        took = (self.lib.ltrx_debug_tn_group_map(n, self.rows, NP, KP, self._wg_probe, self._wg_probe) > 0
-                and self.lib.ltrx_gemm_tn_group_workspace_bytes(n, self.rows, NP, KP) <= self.ws_tn.numel())
+        # large-tile kernel / not enough workspace)?  The host-side predicate the library applies, asked of the library with the
+        # arguments of the call below; tests assert it
+        took = self.lib.ltrx_debug_tn_group_plan(n, self.rows, NP, KP, lda, ldb, self._prec, self.ws_tn.numel(),
+                                                 ctypes.byref(ctypes.c_int(0)), ctypes.byref(ctypes.c_size_t(0)))
         self.wgrad_group_log.append((n, bool(took)))
         del self.wgrad_group_log[:-16]
         if self.probe_wgrad is not None:

@@ -483,12 +483,28 @@ int ltrx_weight_images(const float* src_base, size_t nflat, void* src_image, flo
 int ltrx_ingest_batch(const float* x, const float* y, size_t nx, size_t ny, int F, int ld_dst, float pad_value, float* x_dst,
                       float* y_dst, unsigned char* mask_dst, ltrx_stream_t stream);
 /* `tile` (both GEMMs) is a per-call tuning argument: 0 = automatic choice per shape (what every product call passes);
- * ltrx_gemm_nt: 1 128x128x32, 2 128x128x64, 3 256x128x32, 4 256x128x64, 6 256x256x32, 7 128x256x32 (the large-tile forms
- * need N % 256 == 0, K % 32 == 0); ltrx_gemm_tn: 1 = the 128x128 kernel even where the 256x256 one applies; 9 = the caller states that
- * every row of B (the last one included) is READABLE up to column KP rounded up to 256 (ldb >= that): the 256x256 kernel then also
- * serves a KP that is no multiple of 256 -- it reads the padding, drops its products, C stays dense [NP, KP] (the engine's input
- * buffer keeps F = 136 features in rows of 256 floats).  8 (ltrx_gemm_nt) = 64x256x32 tiles, two workgroups per CU.  Results do not
- * depend on the tile beyond fp32 summation order. */
+ * ltrx_gemm_nt: the 128-column kernel 1 128x128x32, 2 128x128x64, 3 256x128x32, 4 256x128x64 (precision codes 1 and 2 have the
+ * 128x128x32 form only: every code runs it); the 256-column (large-tile) kernel 6 256x256x32, 7 128x256x32, 8 64x256x32 with two
+ * workgroups per CU (these need N % 256 == 0, K % 32 == 0, 16-byte aligned C / bias / aux and a precision code other than 1:
+ * LTRX_EUNSUPPORTED otherwise); any other code runs as 1.  ltrx_gemm_tn: 1 = the 128x128 kernel even where the 256x256 one applies;
+ * 9 = the caller states that every row of B (the last one included) is READABLE up to column KP rounded up to 256 (ldb >= that): the
+ * 256x256 kernel then also serves a KP that is no multiple of 256 -- it reads the padding, drops its products, C stays dense [NP, KP]
+ * (the engine's input buffer keeps F = 136 features in rows of 256 floats).  Results do not depend on the tile beyond fp32 summation
+ * order. */
+/* test hook, no GPU needed: the launch plan of an ltrx_gemm_nt call with these shapes, leading dimensions, act, bias / dropout present
+ * (0 / 1), precision code (`strict`) and `tile`, given the two alignment facts the call derives from its pointers -- vec_epi: C, bias
+ * and aux allow 16-byte accesses; b_image: a 16-byte aligned B_image was passed.  Returns the number of launches (1, or 2 in the
+ * row-split window of the automatic choice) and writes 7 ints per launch to out (14 ints): first row, rows, tile code (1-4, 6, 7, 8 as
+ * above), bf16 terms per operand (1, 2, 3), and for the large-tile kernel: partial last row tile (0 / 1), B read from its image
+ * (0 / 1), epilogue kind (0 generic, 1 plain, 2 bias, 3 ReLU + one-bit mask, 4 mask read, 5 residual).  Returns 0 where the call is
+ * refused, and then out[0] = its return code. */
+int ltrx_debug_gemm_nt_plan(int M, int N, int K, int lda, int ldb, int ldc, int act, int has_bias, int drop_on, int strict, int tile,
+                            int vec_epi, int b_image, int* out);
+/* test hook, no GPU needed: the launch plan of an ltrx_gemm_tn call.  Returns 1 when it runs the 256x256 kernel, 0 for the 128x128
+ * one, -1 for arguments the call refuses; *splits_out = row splits, *rows_per_split_out = rows of each, *kv_out = columns of B that
+ * exist (KP; the 256x256 kernel over padded rows, tile 9, computes KP rounded up to 256 of them). */
+int ltrx_debug_gemm_tn_plan(int M, int NP, int KP, int lda, int ldb, int strict, int tile, int* splits_out, int* rows_per_split_out,
+                            int* kv_out);
 /* workspace for ltrx_gemm_tn sized for M rows: sufficient for EVERY call with the same NP, KP and any row count <= M
  * (variable-length batches re-use one workspace); ltrx_gemm_tn_splits = the split count a call with exactly M rows uses
  * (each split owns an [NP,KP] slab + 2 bias rows of the workspace). */
@@ -522,6 +538,13 @@ int ltrx_gemm_tn_group(int nprob, const float* const* A, const int* lda, const f
  * (problem, split) group on one XCD where they fit); tile_out / split_out: 256 bytes each; returns the workgroup count, 0 when the shapes
  * take the per-problem path. */
 int ltrx_debug_tn_group_map(int nprob, int M, const int* NP, const int* KP, unsigned char* tile_out, unsigned char* split_out);
+/* test hook, no GPU needed: the decision of an ltrx_gemm_tn_group / ltrx_gemm_tn_group_ln call with these shapes, leading dimensions
+ * (lda / ldb may be NULL: dense), precision code and ws_bytes -- the library's own predicate, not a copy of it.  Returns 1 when the
+ * call runs the grouped kernel, 0 when it falls back to one ltrx_gemm_tn per problem (a shape outside the 256x256 kernel, more than
+ * 256 tiles, or ws_bytes below the need).  *splits_out = row splits of the grouped launch (0 on the per-problem path);
+ * *need_bytes_out = workspace bytes the grouped launch writes at that split count, exactly (0 where the shapes alone rule it out). */
+int ltrx_debug_tn_group_plan(int nprob, int M, const int* NP, const int* KP, const int* lda, const int* ldb, int strict, size_t ws_bytes,
+                             int* splits_out, size_t* need_bytes_out);
 /* ltrx_gemm_tn_group followed by ltrx_layernorm_bwd_partial(dy .. partial_rows_out) in ONE call, every output with the bits that pair
  * gives it.  The grouped launch keeps one workgroup per CU and plans tiles x splits <= 256 of them; when CUs are left over (the four
  * projections of an encoder layer: 48 tiles x 5 splits = 240) and D is a register-resident row width (D % 256 == 0, D <= 1024, aligned

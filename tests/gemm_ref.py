@@ -107,6 +107,71 @@ def bar_tn_bias(A, M):
     return (M + 2) * U32 * np.abs(np.asarray(A, np.float64)).sum(0)
 
 
+EUNSUPPORTED = -2
+EPI_GENERIC, EPI_PLAIN, EPI_BIAS, EPI_RELU_BITS, EPI_MASK_READ, EPI_RESIDUAL = range(6)
+
+
+def relu_bits_bytes_ref(M, N, K):
+    if M <= 0 or N <= 0 or K <= 0 or N % 256 or K % 32:
+        return 0
+    t = -(-M // 256) * (N // 256)
+    return t * 512 * 16 if (t >= 380 or 168 <= t <= 256) else 0
+
+
+def nt_plan_ref(M, N, K, lda, ldb, ldc, act, has_bias, drop_on, prec, tile, vec_epi, bimg):
+    """The dispatch of ltrx_gemm_nt as commit 5efdcb8 made it while launching, transcribed rule by rule from that source (it planned
+    nowhere, and split rows by calling itself): the launches of a call whose pointers are valid, given its two alignment facts.
+    Returns (rc, [(first row, rows, tile code, bf16 terms, tail, B image, epilogue kind), ...]); tile code 1-4 = the 128-column
+    kernel actually run (precisions 1 and 2 have its 128x128x32 form only), 6 / 7 / 8 = the 256-column kernel."""
+    if act in (4, 5) and (tile != 0 or prec == 1 or relu_bits_bytes_ref(M, N, K) == 0):
+        return EUNSUPPORTED, []
+    if (K & 3) or (lda & 3) or (ldb & 3) or lda < K or ldb < K or ldc < N:
+        return EUNSUPPORTED, []
+    if act in (4, 5) and (not vec_epi or K % 32):
+        return EUNSUPPORTED, []
+    plain, strict = prec == 2, prec == 1
+    v = tile
+    if v == 0 and not strict and N % 256 == 0 and K % 32 == 0 and vec_epi:
+        nn = N // 256
+        t = -(-M // 256) * nn
+        if 256 < t < 380 and (not drop_on or act == 2) and nn <= 256:
+            m1 = (256 // nn) * 256
+            rc, first = nt_plan_ref(m1, N, K, lda, ldb, ldc, act, has_bias, drop_on, prec, 0, vec_epi, bimg)
+            if rc:
+                return rc, []
+            rc, second = nt_plan_ref(M - m1, N, K, lda, ldb, ldc, act, has_bias, drop_on, prec, 0, vec_epi, bimg)
+            return rc, [] if rc else first + [(m1 + s[0],) + s[1:] for s in second]
+        t128 = -(-M // 128) * nn
+        if t >= 360 or 168 <= t <= 256:
+            v = 6
+        elif 136 <= t < 168 and t128 > 256:
+            v = 6
+        elif 176 <= t128 <= 256:
+            v = 7
+        elif t128 < 176 and 176 <= -(-M // 64) * nn <= 512:
+            v = 8
+    if v == 0:
+        v = 1
+    if act in (4, 5) and v != 6:
+        return EUNSUPPORTED, []
+    if v in (6, 7, 8):
+        if N % 256 or K % 32 or strict or not vec_epi or (v == 8 and act in (4, 5)):
+            return EUNSUPPORTED, []
+        tail = M % {6: 256, 7: 128, 8: 64}[v] != 0
+        epi = EPI_GENERIC
+        if not (drop_on or tail or plain or not bimg):
+            epi = {0: EPI_BIAS if has_bias else EPI_PLAIN, 3: EPI_RESIDUAL if has_bias else EPI_GENERIC,
+                   4: EPI_RELU_BITS if has_bias else EPI_GENERIC, 5: EPI_GENERIC if has_bias else EPI_MASK_READ}.get(act, EPI_GENERIC)
+        if epi in (EPI_RELU_BITS, EPI_MASK_READ) and v != 6:           # (no such instantiation)
+            return EUNSUPPORTED, []
+        return 0, [(0, M, v, 1 if plain else 2, int(tail), int(bool(bimg)), epi)]
+    if strict:
+        return 0, [(0, M, 1, 3, 0, 0, EPI_GENERIC)]
+    if plain:
+        return 0, [(0, M, 1, 1, 0, 0, EPI_GENERIC)]
+    return 0, [(0, M, v if v in (2, 3, 4) else 1, 2, 0, 0, EPI_GENERIC)]
+
+
 def scaled_operands(rng, M, N, K, scaled=True, zero_rows=True):
     """A [M, K], B [N, K], N(0, 1); ``scaled``: rows of A and rows of B times 2^[-40, 40], columns of A times 2^[-6, 6] (features
     that are not normalised); one all-zero row in each (when it has more than one row)"""

@@ -225,11 +225,16 @@ def test_forced_large_tiles_every_epilogue(tile):
 
 
 def _auto(case, seed, M, N, K, forced, epilogues, rows_split=None):
-    """an automatic arm reached with a small M and a wide N: the contract, and bit-equality with the forced tile it must have taken"""
+    """an automatic arm reached with a small M and a wide N: the contract, bit-equality with the forced tile it must have taken, and
+    the library's own plan of the call (ltrx_debug_gemm_nt_plan) naming that tile, in the split case over exactly these row ranges"""
     rng = np.random.default_rng(seed)
     nt = NT(case, rng, M, N, K, K + 4, K + 8)
+    plan = (ctypes.c_int * 14)()
     for (act, p) in epilogues:
         got = nt.run(case, act, 0, 0, N + 4, p, bias=(act != 2))
+        # (the windows of this file start 16 bytes into their buffers and have leading dimensions % 4 == 0: aligned; no B image)
+        nseg = _libs()[1].ltrx_debug_gemm_nt_plan(M, N, K, K + 4, K + 8, N + 4, act, int(act != 2), int(p > 0), 0, 0, 1, 0, plan)
+        assert [tuple(plan[7 * i:7 * i + 3]) for i in range(nseg)] == (rows_split or [(0, M, forced)]), (case, act, p, list(plan))
         if rows_split is None:
             rc, c = nt.call(act, 0, forced, N + 4, p, bias=(act != 2))
             assert rc == 0 and np.array_equal(c.fetch(case).view(np.uint32), got.view(np.uint32)), (case, act, p)
