@@ -17,7 +17,7 @@ import warnings
 import torch
 from torch.nn.utils import clip_grad_norm_
 
-from . import parallel, sharding
+from . import kernels as KN, parallel, sharding
 
 PADDED_Y_VALUE = -1
 
@@ -94,8 +94,8 @@ def _alloc_forward(owner, t, rows, B, L, saved, compact):
       idx_rows (i64 rank of every row, -1 = none) and x_pe: positional encoding only
       layers[i]: wqkv, bqkv, mod, p_*, s_* (the trainer's parameter views and dropout sites; its own dicts also hold gwqkv / gbqkv
       and later rbits / wqkvT), xsum0 (the residual stream entering layer i > 0), xn0, mean0, rstd0, qkv, o, lse, x1, xn1, mean1,
-      rstd1, r;  xsum_f, xf, mean_f, rstd_f (the final norm; xf is None where t.norm_head holds: the fused final norm + score head
-      keeps the normalised rows in registers);  scores_c (compact only), scores_raw [B, L(, n_out)], scores [B, L]
+      rstd1, r, and q, k, v (the column views of qkv that the attention launches read);  xsum_f, xf, mean_f, rstd_f (the final norm; xf
+      is None where t.norm_head holds: the fused final norm + score head keeps the normalised rows in registers);  scores_c (compact only), scores_raw [B, L(, n_out)], scores [B, L]
     ``saved=True``, the trainer's form: the backward reads the activations, so every layer has its own.  ``saved=False``, the scorer's:
     ONE activation set serves every layer -- the residual stream ping-pongs between two buffers (a layer's input is dead once its
     out-projection has added it: xsum0 of layer i = ping[i % 2], xsum_f = ping[N % 2], x_pe = ping[0], which layer 0 reads while
@@ -110,7 +110,9 @@ def _alloc_forward(owner, t, rows, B, L, saved, compact):
         return z(rows, d), z(rows), z(rows)
 
     def acts(ln0, ln1):
-        return dict(xn0=ln0[0], mean0=ln0[1], rstd0=ln0[2], xn1=ln1[0], mean1=ln1[1], rstd1=ln1[2], qkv=z(rows, 3 * d), o=z(rows, d),
+        qkv = z(rows, 3 * d)
+        q, k, v = KN.thirds(qkv)
+        return dict(xn0=ln0[0], mean0=ln0[1], rstd0=ln0[2], xn1=ln1[0], mean1=ln1[1], rstd1=ln1[2], qkv=qkv, q=q, k=k, v=v, o=z(rows, d),
                     lse=z(B, t.h, L), x1=z(rows, d), r=z(rows, t.dff))
 
     owner.B, owner.L, owner.compact = B, L, compact
@@ -671,7 +673,7 @@ class FusedTrainer(object):
         if self.in_norm is not None:
             F_ = self.fc_sizes[0]
             self.d_in = torch.zeros((M, F_), **f32)
-            self.ws_ln_in = torch.empty(max(self.lib.ltrx_layernorm_bwd_workspace_bytes(M, F_), 64), dtype=torch.uint8, device=dev)
+            self.ws_ln_in = KN.layernorm_bwd_workspace(self.lib, M, F_, self.d_in)
         if relu_bits and self.N and self.dff % 256 == 0 and d % 32 == 0 and gemm not in ("hipblaslt", "split_bf16_strict"):
             # one bit per feed-forward activation (written by the forward GEMM, read by the input-gradient GEMM instead of r)
             for st in self.layers:
@@ -679,13 +681,14 @@ class FusedTrainer(object):
         if self.N:
             self.d_r = torch.zeros((M, self.dff), **f32)
             self.dqkv = torch.zeros((M, 3 * d), **f32)
+            self.dq, self.dk, self.dv = KN.thirds(self.dqkv)    # (the views the attention backward writes through)
             self.d_o = torch.zeros((M, d), **f32)
             self.tmp_d = torch.zeros((M, d), **f32)
             self.d_br = torch.zeros((M, d), **f32)            # gradient of a dropped residual branch (ds * keep)
-            self.ws_ln = torch.empty(max(self.lib.ltrx_layernorm_bwd_workspace_bytes(M, d), 64), dtype=torch.uint8, device=dev)
+            self.ws_ln = KN.layernorm_bwd_workspace(self.lib, M, d, self.d_o)
             # deferred parameter-gradient partials of up to three LayerNorm backwards per encoder layer (_reduce_flush)
             self.ws_ln_g = [self.ws_ln] + [torch.empty_like(self.ws_ln) for _ in range(2)]
-            self.ws_mha = torch.empty(max(self.lib.ltrx_mha_bwd_workspace_bytes(B, L, self.h, self.d // self.h, self._mha_mode), 64), dtype=torch.uint8, device=dev)
+            self.ws_mha = KN.mha_bwd_workspace(self.lib, B, L, self.h, d // self.h, self._mha_mode, self.d_o)
         no = self.n_out
         if compact:
             self.dsc_c = torch.zeros(M if no == 1 else (M, no), **f32)
@@ -700,7 +703,7 @@ class FusedTrainer(object):
             self.d_c = torch.zeros((M, d), **f32)
         maxn = max([3 * d, self.dff if self.N else 0] + self.fc_sizes[1:])
         self.ws_col = torch.empty(max(self.lib.ltrx_colsum_workspace_bytes(M, maxn), 64), dtype=torch.uint8, device=dev)
-        self.ws_head = torch.empty(max(self.lib.ltrx_score_head_bwd_workspace_bytes(M, d), 64), dtype=torch.uint8, device=dev)
+        self.ws_head = KN.score_head_bwd_workspace(self.lib, M, d, self.d_a)
         self.fc_dgrad = [torch.zeros((M, s), **f32) for s in self.fc_sizes[1:-1]]
         if self.gemm != "hipblaslt":
             nb = 0
@@ -800,10 +803,8 @@ class FusedTrainer(object):
 
     def _ln_fwd(self, x, res, a, b, xsum, y, mean, rstd, p=0.0, seed=0, rows=None):
         """y = LN(x + drop_p(res)); xsum = x + drop_p(res)   (over ``rows`` rows, default the step's)"""
-        P = self.LB.ptr
-        self.LB.check(self.lib.ltrx_layernorm_fwd(P(x), P(res), P(a), P(b), self.rows if rows is None else rows, self.d,
-                                                  float(self.ln_eps), P(xsum), P(y), P(mean), P(rstd), float(p), seed, P(self.drop_step),
-                                                  self._st()), "layernorm_fwd")
+        KN.layernorm_fwd(self.lib, self._st(), x, res, a, b, self.rows if rows is None else rows, self.ln_eps, xsum, y, mean, rstd, p, seed,
+                         self.drop_step)
 
     def _drop_apply(self, src, dst, p, seed):
         """dst = src * keep-mask/(1-p) of the site (the backward of a dropped branch)"""
@@ -831,18 +832,12 @@ class FusedTrainer(object):
         self._red_pending.append((buf.data_ptr() + 4 * self.d, nrows, 2 * self.d, self.d, db.data_ptr()))
 
     def _ln_bwd(self, dy, xsum, a, mean, rstd, dres, dx, da, db):
-        P = self.LB.ptr
         buf = self._ln_partial_slot()
         if buf is not None:                                       # dx now, the parameter gradients with the layer's reductions
-            rows_out = ctypes.c_int(0)
-            self.LB.check(self.lib.ltrx_layernorm_bwd_partial(P(dy), P(xsum), P(a), P(mean), P(rstd), P(dres), self.rows, self.d,
-                                                              float(self.ln_eps), P(dx), P(buf), ctypes.byref(rows_out), self._st()),
-                          "layernorm_bwd_partial")
-            self._ln_partials_queue(buf, rows_out.value, da, db)
+            nrows = KN.layernorm_bwd_partial(self.lib, self._st(), dy, xsum, a, mean, rstd, dres, self.rows, self.ln_eps, dx, buf)
+            self._ln_partials_queue(buf, nrows, da, db)
             return
-        self.LB.check(self.lib.ltrx_layernorm_bwd(P(dy), P(xsum), P(a), P(mean), P(rstd), P(dres), self.rows, self.d,
-                                                  float(self.ln_eps), P(dx), P(da), P(db), P(self.ws_ln), self._st()),
-                      "layernorm_bwd")
+        KN.layernorm_bwd(self.lib, self._st(), dy, xsum, a, mean, rstd, dres, self.rows, self.ln_eps, dx, da, db, self.ws_ln)
 
     def _colsum(self, a, out):
         P = self.LB.ptr
@@ -873,12 +868,12 @@ class FusedTrainer(object):
             return
         if self._x_pad:
             self.w0_pad[:, :w0.shape[1]].copy_(w0)
-            self.LB.check(self.lib.ltrx_split_image(P(self.w0_pad), P(self.w0_pad_i), self.w0_pad.numel(), self._st()), "split_image(W0 padded)")
+            KN.split_image(self.lib, self._st(), self.w0_pad, self.w0_pad_i, "split_image(W0 padded)")
         if self._tn:
             self.LB.check(self.lib.ltrx_transpose_batch(P(self.flat_p), P(self.flat_t), P(self._tdesc), P(self._tstart), self._tn,
                                                         self._ttiles, self._st()), "transpose_batch")
-            self.LB.check(self.lib.ltrx_split_image(P(self.flat_t), P(self.flat_ti), self.flat_t.numel(), self._st()), "split_image(W^T)")
-        self.LB.check(self.lib.ltrx_split_image(P(self.flat_p), P(self.flat_pi), self.nflat, self._st()), "split_image(W)")
+            KN.split_image(self.lib, self._st(), self.flat_t, self.flat_ti, "split_image(W^T)")
+        KN.split_image(self.lib, self._st(), self.flat_p, self.flat_pi, "split_image(W)")
 
     def _sync_weights(self):
         """The forward / input-gradient GEMMs read the pre-split images and transposed copies of the weights, which the step
@@ -943,13 +938,10 @@ class FusedTrainer(object):
         need = self.lib.ltrx_gemm_nt_relu_bits_bytes(self.rows, self.dff, self.d)
         return buf if 0 < need <= buf.numel() else None
 
-    def _gemm_nt(self, a, b, out, M, bias, act, aux, ldaux, p, seed, what):
-        """the one ltrx_gemm_nt call of the step: out[:M] = epi_act(a b^T + bias), dropout (p, site ``seed``) in the epilogue;
-        ``aux`` / ``ldaux`` as the act code reads them (include/ltrx.h); ``b``'s split image is passed along where one exists"""
-        P = self.LB.ptr
-        self.LB.check(self.lib.ltrx_gemm_nt(P(a), a.stride(0), P(b), b.stride(0), self._img(b), P(out), out.stride(0), M, b.shape[0],
-                                            a.shape[1], P(bias), act, P(aux), ldaux, float(p), seed, P(self.drop_step), self._prec, 0,
-                                            self._st()), what)
+    def _gemm_nt(self, a, b, out, M, bias, act, aux, p, seed, what):
+        """the ltrx_gemm_nt launch of the step: out[:M] = epi_act(a b^T + bias), dropout (p, site ``seed``) in the epilogue; ``aux`` as
+        the act code reads it (include/ltrx.h); ``b``'s split image is passed along where one exists"""
+        KN.gemm_nt(self.lib, self._st(), a, b, out, M, bias, act, aux, p, seed, self.drop_step, self._prec, 0, self._img(b), what)
 
     def _lin_fwd(self, x, w, b, out, act=0, p=0.0, seed=0, res=None, bits=None, rows=None):
         """out = drop_p(act(x w^T + b)) [+ res]   (nn.Linear forward, act 1 = ReLU; dropout in the epilogue; ``res`` = the
@@ -968,11 +960,11 @@ class FusedTrainer(object):
                 out[:n].add_(res[:n])
             return
         if bits is not None and act == 1:                         # ReLU + its one-bit mask for the backward (act 4)
-            self._gemm_nt(x, w, out, M, b, 4, bits, 0, p, seed, "gemm_nt(fwd, relu bits)")
+            self._gemm_nt(x, w, out, M, b, 4, bits, p, seed, "gemm_nt(fwd, relu bits)")
         elif res is not None:
-            self._gemm_nt(x, w, out, M, b, 3, res, res.stride(0), p, seed, "gemm_nt(fwd)")
+            self._gemm_nt(x, w, out, M, b, 3, res, p, seed, "gemm_nt(fwd)")
         else:
-            self._gemm_nt(x, w, out, M, b, act, None, 0, p, seed, "gemm_nt(fwd)")
+            self._gemm_nt(x, w, out, M, b, act, None, p, seed, "gemm_nt(fwd)")
 
     def _lin_dgrad(self, dy, w, wT, out, relu_of=None, p=0.0, seed=0, bits=None):
         """out = dy w   (input gradient of nn.Linear); wT = w^T contiguous.  With ``relu_of`` (the saved post-ReLU,
@@ -986,11 +978,11 @@ class FusedTrainer(object):
                 self._drop_apply(out, out, p, seed)
             return
         if relu_of is None:
-            self._gemm_nt(dy, wT, out, self.rows, None, 0, None, 0, p, seed, "gemm_nt(dgrad)")
+            self._gemm_nt(dy, wT, out, self.rows, None, 0, None, p, seed, "gemm_nt(dgrad)")
         elif bits is not None:                                    # the mask written by the forward launch (act 5): 1/32 of the bytes
-            self._gemm_nt(dy, wT, out, self.rows, None, 5, bits, 0, p, seed, "gemm_nt(dgrad, relu bits)")
+            self._gemm_nt(dy, wT, out, self.rows, None, 5, bits, p, seed, "gemm_nt(dgrad, relu bits)")
         else:
-            self._gemm_nt(dy, wT, out, self.rows, None, 2, relu_of, relu_of.stride(0), p, seed, "gemm_nt(dgrad)")
+            self._gemm_nt(dy, wT, out, self.rows, None, 2, relu_of, p, seed, "gemm_nt(dgrad)")
 
     def _lin_wgrad(self, dy, x, gw, gb, defer=False):
         """gw = dy^T x, gb = column sums of dy   (weight and bias gradients of nn.Linear).  ``defer``: an encoder-layer projection
@@ -1002,12 +994,9 @@ class FusedTrainer(object):
         if defer and self.group_wgrad:
             self._wg_pending.append((dy, x, gw, gb))
             return
-        P = self.LB.ptr
         # (tile 9: x is the padded input buffer -- its rows are readable up to the 256-column tile, see include/ltrx.h)
         padded = self._x_large and x.data_ptr() == self.x_in_buf.data_ptr() and x.stride(0) == self.x_in_buf.stride(0)
-        self.LB.check(self.lib.ltrx_gemm_tn(P(dy), dy.stride(0), P(x), x.stride(0), P(gw), P(gb), self.rows, dy.shape[1],
-                                            x.shape[1], self._prec, 9 if padded else 0, P(self.ws_tn), self._st()),
-                      "gemm_tn(wgrad)")
+        KN.gemm_tn(self.lib, self._st(), dy, x, gw, gb, self.rows, self._prec, 9 if padded else 0, self.ws_tn, "gemm_tn(wgrad)")
 
     def _wgrad_flush(self, defer_reduce=False, ln=None):
         """the queued weight gradients of a layer as ONE ltrx_gemm_tn_group launch; their partial slabs are summed by the call
@@ -1117,8 +1106,7 @@ class FusedTrainer(object):
                 h, w_i = bs.x_in_k, self.w0_pad                    # (hipblaslt: torch.addmm over the [:, :F] view and W_0 itself)
             if self.fc_act >= 3:                                   # Sigmoid / Tanh: GEMM + bias, then the activation in place
                 self._lin_fwd(h, w_i, W(lyr.bias), bs.fc_out[i], rows=M)
-                self.LB.check(lib.ltrx_out_act_fwd(P(bs.fc_out[i]), M * bs.fc_out[i].shape[1], self.fc_act - 2, P(bs.fc_out[i]),
-                                                   self._st()), "fc_act_fwd")
+                KN.out_act_fwd(lib, self._st(), bs.fc_out[i], M * bs.fc_out[i].shape[1], self.fc_act - 2, bs.fc_out[i], "fc_act_fwd")
             else:
                 self._lin_fwd(h, w_i, W(lyr.bias), bs.fc_out[i], self.fc_act, dp(self.p_fc), self._site(1000 + i), rows=M)
             h = bs.fc_out[i]
@@ -1133,10 +1121,8 @@ class FusedTrainer(object):
             self._ln_fwd(x, None, W(n0.a_2), W(n0.b_2), None, st["xn0"], st["mean0"], st["rstd0"], rows=M)
             st["xin"] = x
             self._lin_fwd(st["xn0"], st["wqkv"], st["bqkv"], st["qkv"], rows=M)
-            qkv = st["qkv"]
-            self.LB.check(lib.ltrx_mha_fwd(P(qkv), qkv.data_ptr() + 4 * d, qkv.data_ptr() + 8 * d, P(kpm), B, L, self.h,
-                                           d // self.h, 3 * d, P(st["o"]), d, P(st["lse"]), dp(st["p_att"]), st["s_att"],
-                                           P(self.drop_step), P(bs.cu), P(bs.order), self._mha_mode, self._st()), "mha_fwd")
+            KN.mha_fwd(lib, self._st(), st["q"], st["k"], st["v"], kpm, B, L, self.h, st["o"], st["lse"], dp(st["p_att"]), st["s_att"],
+                       self.drop_step, bs.cu, bs.order, self._mha_mode)
             lo = lay.self_attn.linears[3]
             # x1 = x + dropout(attention branch): the residual sum is the out-projection's epilogue (act 3)
             self._lin_fwd(st["o"], W(lo.weight), W(lo.bias), st["x1"], 0, dp(st["p_s0"]), st["s_s0"], res=x, rows=M)
@@ -1168,12 +1154,11 @@ class FusedTrainer(object):
                                                  float(self.ln_eps), P(sc_rows), P(bs.mean_f), P(bs.rstd_f), None, self._st()),
                           "norm_head_fwd")
         elif no == 1:
-            self.LB.check(lib.ltrx_score_head_fwd(P(feat), P(W(out.w_1.weight)), P(W(out.w_1.bias)), M, d, P(sc_rows), self._st()),
-                          "score_head_fwd")
+            KN.score_head_fwd(lib, self._st(), feat, W(out.w_1.weight), W(out.w_1.bias), M, sc_rows)
         else:                                                     # Linear(d, d_output) as a GEMM (model.py:117)
             self._lin_fwd(feat, W(out.w_1.weight), W(out.w_1.bias), sc_rows.view(-1, no), rows=M)
         if self.out_act:                                          # OutputLayer activation (model.py:117), in place
-            self.LB.check(lib.ltrx_out_act_fwd(P(sc_rows), M * no, self.out_act, P(sc_rows), self._st()), "out_act_fwd")
+            KN.out_act_fwd(lib, self._st(), sc_rows, M * no, self.out_act, sc_rows)
         if bs is not self:                                        # scorer: packed scores -> padded grid, padding 0, count from cu[B]
             self.LB.check(lib.ltrx_scatter_rows_cu(P(sc_rows), no, P(bs.cu), B, L, no, M, P(bs.scores_raw), no, self._st()),
                           "scatter_rows_cu")
@@ -1207,7 +1192,7 @@ class FusedTrainer(object):
                           "gather_rows")
             dsc = self.dsc_c
         if self.out_act:                                          # d loss / d pre-activation = d loss / d score * act'(score)
-            self.LB.check(lib.ltrx_out_act_bwd(P(dsc), P(sc_rows), M * no, self.out_act, P(dsc), self._st()), "out_act_bwd")
+            KN.out_act_bwd(lib, self._st(), dsc, sc_rows, M * no, self.out_act, dsc)
         if self.norm_head:
             # backward of the fused pair.  The head's own gradients first, in ltrx_score_head_bwd's row order (their bits), from the
             # recomputed LN(x); then d_xf = dsc w is formed in registers and dx lands where _ln_bwd put it, the (a_2, b_2) partials
@@ -1223,8 +1208,7 @@ class FusedTrainer(object):
                                                          self._st()), "norm_head_bwd_partial")
             self._ln_partials_queue(buf, rows_out.value, G(nf.a_2), G(nf.b_2))
         elif no == 1:
-            self.LB.check(lib.ltrx_score_head_bwd(P(dsc), P(feat), P(W(out.w_1.weight)), M, d, P(ga), P(G(out.w_1.weight)),
-                                                  P(G(out.w_1.bias)), P(self.ws_head), self._st()), "score_head_bwd")
+            KN.score_head_bwd(lib, self._st(), dsc, feat, W(out.w_1.weight), M, ga, G(out.w_1.weight), G(out.w_1.bias), self.ws_head)
         else:                                                     # the d_output-wide head: weight / bias / input gradients as GEMMs
             self.dz_pad[:M, :no].copy_(dsc.reshape(-1, no)[:M])
             self._lin_wgrad(self.dz_pad[:, :no], feat, G(out.w_1.weight), G(out.w_1.bias))
@@ -1240,7 +1224,7 @@ class FusedTrainer(object):
                 lay = st["mod"]
                 n0, n1 = lay.sublayer[0].norm, lay.sublayer[1].norm
                 ff = lay.feed_forward
-                d_r, dq = self.d_r, self.dqkv
+                d_r, dqkv = self.d_r, self.dqkv
                 # where the two LayerNorm backwards of the layer write: ping-pong over (ga, gb); with ln_in_wgrad the second one runs
                 # WHILE the weight gradients read ds (the FFN-2 dY operand), so it writes a third buffer and the three rotate
                 mid, outb, d_top = other, (ds if spare is None else spare), ds
@@ -1262,16 +1246,12 @@ class FusedTrainer(object):
                 db = self._branch_grad(ds, st["p_s0"], st["s_s0"])
                 self._lin_wgrad(db, st["o"], G(lo.weight), G(lo.bias), defer=True)
                 self._lin_dgrad(db, W(lo.weight), self._wT.get(id(lo.weight)), self.d_o)
-                qkv = st["qkv"]
-                self.LB.check(lib.ltrx_mha_bwd(P(qkv), qkv.data_ptr() + 4 * d, qkv.data_ptr() + 8 * d, P(kpm), P(st["o"]),
-                                               P(self.d_o), P(st["lse"]), B, L, self.h, d // self.h, 3 * d, d, P(dq),
-                                               dq.data_ptr() + 4 * d, dq.data_ptr() + 8 * d, 3 * d, st["p_att"], st["s_att"],
-                                               P(self.drop_step), P(self.cu), P(self.order), self._mha_mode, P(self.ws_mha), self._st()),
-                              "mha_bwd")
+                KN.mha_bwd(lib, self._st(), st["q"], st["k"], st["v"], kpm, st["o"], self.d_o, st["lse"], B, L, self.h, self.dq, self.dk,
+                           self.dv, st["p_att"], st["s_att"], self.drop_step, self.cu, self.order, self._mha_mode, self.ws_mha)
                 if self.compact and M > self.n_valid:              # alignment rows belong to no slate: no gradient
-                    dq[self.n_valid:M].zero_()
-                self._lin_wgrad(dq, st["xn0"], st["gwqkv"], st["gbqkv"], defer=True)
-                self._lin_dgrad(dq, st["wqkv"], st.get("wqkvT"), self.tmp_d)
+                    dqkv[self.n_valid:M].zero_()
+                self._lin_wgrad(dqkv, st["xn0"], st["gwqkv"], st["gbqkv"], defer=True)
+                self._lin_dgrad(dqkv, st["wqkv"], st.get("wqkvT"), self.tmp_d)
                 ln0 = (self.tmp_d, st["xin"], W(n0.a_2), st["mean0"], st["rstd0"], ds, outb, G(n0.a_2), G(n0.b_2))
                 if spare is None:
                     self._wgrad_flush(defer_reduce=True)
@@ -1294,8 +1274,7 @@ class FusedTrainer(object):
             lyr = fc.layers[i]
             if i == self.nfc - 1:                                # the last FC activation(+dropout) feeds the encoder / head
                 if self.fc_act >= 3:
-                    self.LB.check(lib.ltrx_out_act_bwd(P(ds), P(self.fc_out[i]), M * ds.shape[1], self.fc_act - 2, P(ds), self._st()),
-                                  "fc_act_bwd")
+                    KN.out_act_bwd(lib, self._st(), ds, self.fc_out[i], M * ds.shape[1], self.fc_act - 2, ds, "fc_act_bwd")
                 elif self.fc_act == 1:
                     self._relu_bwd(ds, self.fc_out[i], self.p_fc)
                 elif self.p_fc:
@@ -1306,18 +1285,16 @@ class FusedTrainer(object):
                 # nn.LayerNorm parameter gradients: dw = sum dy * xhat, db = sum dy with dy = ds W_0 (the input itself needs no
                 # gradient; ltrx_layernorm_bwd's da / db formulas only use the saved mean and rstd, its dx output is scratch)
                 self._lin_dgrad(ds, W(lyr.weight), self._wT.get(id(lyr.weight)), self.d_in)
-                self.LB.check(lib.ltrx_layernorm_bwd(P(self.d_in), P(self.x_in), P(W(self.in_norm.weight)), P(self.mean_in), P(self.rstd_in),
-                                                     None, M, self.fc_sizes[0], float(self.in_norm.eps), P(self.d_in),
-                                                     P(G(self.in_norm.weight)), P(G(self.in_norm.bias)), P(self.ws_ln_in), self._st()),
-                              "layernorm_bwd(input_norm)")
+                KN.layernorm_bwd(lib, self._st(), self.d_in, self.x_in, W(self.in_norm.weight), self.mean_in, self.rstd_in, None, M,
+                                 self.in_norm.eps, self.d_in, G(self.in_norm.weight), G(self.in_norm.bias), self.ws_ln_in,
+                                 "layernorm_bwd(input_norm)")
             if i > 0:
                 self._lin_dgrad(ds, W(lyr.weight), self._wT.get(id(lyr.weight)), self.fc_dgrad[i - 1],
                                 relu_of=self.fc_out[i - 1] if self.fc_act == 1 else None, p=self.p_fc,
                                 seed=self._site(1000 + i - 1))
                 ds = self.fc_dgrad[i - 1]
                 if self.fc_act >= 3:
-                    self.LB.check(lib.ltrx_out_act_bwd(P(ds), P(self.fc_out[i - 1]), M * ds.shape[1], self.fc_act - 2, P(ds), self._st()),
-                                  "fc_act_bwd")
+                    KN.out_act_bwd(lib, self._st(), ds, self.fc_out[i - 1], M * ds.shape[1], self.fc_act - 2, ds, "fc_act_bwd")
         self._bucket_done(len(self._buckets) - 1)
         return loss
 
@@ -1732,7 +1709,6 @@ class FusedScorer(object):
         """scores of a padded batch ``xb`` [n, L, F] (n <= B; valid items first in every slate, labels ``yb`` == -1 on padding, as
         dataset.py:28-38 pads); ``lengths``: host item counts per slate (None: counted on the device, one host sync).  Returns
         ``scores_raw``."""
-        P, LB = self.LB.ptr, self.LB
         t, B, L = self.t, self.B, self.L
         n_sl = int(xb.shape[0])
         if n_sl > B or int(xb.shape[1]) != L:
@@ -1755,12 +1731,10 @@ class FusedScorer(object):
         self.y[:n_sl].copy_(yb)
         self.y[n_sl:].fill_(float(PADDED_Y_VALUE))
         F = int(xb.shape[2])
-        LB.check(t.lib.ltrx_gather_rows_cu(P(xb), F, P(self.cu), B, L, F, self.rows, P(self.x_in), self.x_in.stride(0), P(self.idx),
-                                           t._st()), "gather_rows_cu(x)")
+        KN.gather_rows_cu(t.lib, t._st(), xb, self.cu, B, L, F, self.rows, self.x_in, self.idx, "gather_rows_cu(x)")
         if t.pos is not None:                              # int64 positions move as pairs of 32-bit words
             ib = indices.to(t.dev, torch.int64).contiguous()
-            LB.check(t.lib.ltrx_gather_rows_cu(P(ib), 2, P(self.cu), B, L, 2, self.rows, P(self.idx_rows), 2, None, t._st()),
-                     "gather_rows_cu(indices)")
+            KN.gather_rows_cu(t.lib, t._st(), ib, self.cu, B, L, 2, self.rows, self.idx_rows, None, "gather_rows_cu(indices)")
             self.idx_rows[n:self.rows].fill_(-1)           # alignment rows -> the padding position
         self._run()
         return self.scores_raw
@@ -1772,9 +1746,7 @@ class FusedScorer(object):
         if self.t.n_out != 1:
             raise NotImplementedError("FusedScorer.packed: d_output > 1 (the ordinal loss reads the padded grid)")
         if not self._y_c_fresh:
-            LB, P = self.LB, self.LB.ptr
-            LB.check(self.t.lib.ltrx_gather_rows_cu(P(self.y), 1, P(self.cu), self.B, self.L, 1, self.rows, P(self.y_c), 1, None,
-                                                    self.t._st()), "gather_rows_cu(labels)")
+            KN.gather_rows_cu(self.t.lib, self.t._st(), self.y, self.cu, self.B, self.L, 1, self.rows, self.y_c, None, "gather_rows_cu(labels)")
             self._y_c_fresh = True
         n = self.n_valid
         return self.scores_c[:n], self.y_c[:n], self.cu, self.order, self.max_len

@@ -9,6 +9,7 @@ import threading
 import torch
 
 from . import _lib as L
+from . import kernels as KN
 
 # ------------------------------------------------------------------------------------------------------------------
 # Arithmetic of the nn.Module path.  The C ABI keeps no mode of its own (every ltrx_* call carries its precision / mode
@@ -79,9 +80,7 @@ class _LayerNormFn(torch.autograd.Function):
         xsum = torch.empty_like(x2) if r2 is not None else x2
         mean = torch.empty(rows, dtype=torch.float32, device=x.device)
         rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-        L.check(L.lib().ltrx_layernorm_fwd(L.ptr(x2), L.ptr(r2), L.ptr(a), L.ptr(b), rows, D, float(eps),
-                                           L.ptr(xsum) if r2 is not None else None, L.ptr(y), L.ptr(mean), L.ptr(rstd),
-                                           0.0, 0, None, L.stream_of(x2)), "layernorm_fwd")
+        KN.layernorm_fwd(L.lib(), L.stream_of(x2), x2, r2, a, b, rows, eps, xsum if r2 is not None else None, y, mean, rstd)
         ctx.save_for_backward(xsum, a, mean, rstd)
         ctx.eps = float(eps)
         ctx.has_res = res is not None
@@ -100,10 +99,8 @@ class _LayerNormFn(torch.autograd.Function):
         da = torch.empty(D, dtype=torch.float32, device=xsum.device)
         db = torch.empty(D, dtype=torch.float32, device=xsum.device)
         lib = L.lib()
-        ws = L.workspace(lib.ltrx_layernorm_bwd_workspace_bytes(rows, D), xsum)
-        L.check(lib.ltrx_layernorm_bwd(L.ptr(dy2), L.ptr(xsum), L.ptr(a), L.ptr(mean), L.ptr(rstd), L.ptr(dres), rows, D,
-                                       ctx.eps, L.ptr(dx), L.ptr(da), L.ptr(db), L.ptr(ws), L.stream_of(xsum)),
-                "layernorm_bwd")
+        ws = KN.layernorm_bwd_workspace(lib, rows, D, xsum)
+        KN.layernorm_bwd(lib, L.stream_of(xsum), dy2, xsum, a, mean, rstd, dres, rows, ctx.eps, dx, da, db, ws)
         dx = dx.view(ctx.shape)
         return dx, (dx if ctx.has_res else None), da, db, None
 
@@ -125,7 +122,6 @@ class _AttentionFn(torch.autograd.Function):
     def forward(ctx, q, k, v, key_pad_mask, h, p_drop=0.0, seed=0):
         L.require_device(q, k, v, key_pad_mask)
         B, SL, d = q.shape
-        dk = d // h
         for t in (q, k, v):
             if t.dtype != torch.float32 or t.stride(2) != 1 or t.stride(0) != SL * t.stride(1):
                 raise ValueError("q/k/v must be fp32 [B,L,h*d_k] with unit inner stride and dense slates")
@@ -136,8 +132,7 @@ class _AttentionFn(torch.autograd.Function):
         o = torch.empty((B, SL, d), dtype=torch.float32, device=q.device)
         lse = torch.empty((B, h, SL), dtype=torch.float32, device=q.device)
         mode = get_attention_mode()
-        L.check(L.lib().ltrx_mha_fwd(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(mask), B, SL, h, dk, rs, L.ptr(o), d, L.ptr(lse),
-                                     float(p_drop), int(seed) & 0xFFFFFFFF, None, None, None, mode, L.stream_of(q)), "mha_fwd")
+        KN.mha_fwd(L.lib(), L.stream_of(q), q, k, v, mask, B, SL, h, o, lse, p_drop, int(seed) & 0xFFFFFFFF, None, None, None, mode)
         ctx.save_for_backward(q, k, v, mask, o, lse)
         ctx.h, ctx.mode = h, mode
         ctx.p_drop, ctx.seed = float(p_drop), int(seed) & 0xFFFFFFFF
@@ -148,16 +143,13 @@ class _AttentionFn(torch.autograd.Function):
         q, k, v, mask, o, lse = ctx.saved_tensors
         B, SL, d = o.shape
         h = ctx.h
-        dk_ = d // h
         do = L.f32c(do)
         # one fused [B, L, 3d] gradient buffer: dq | dk | dv are column slices (what a fused QKV projection consumes)
         dqkv = torch.empty((B, SL, 3 * d), dtype=torch.float32, device=o.device)
-        dq, dkk, dv = dqkv[:, :, 0:d], dqkv[:, :, d:2 * d], dqkv[:, :, 2 * d:3 * d]
+        dq, dkk, dv = KN.thirds(dqkv)
         lib = L.lib()
-        ws = L.workspace(lib.ltrx_mha_bwd_workspace_bytes(B, SL, h, dk_, ctx.mode), o)
-        L.check(lib.ltrx_mha_bwd(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(mask), L.ptr(o), L.ptr(do), L.ptr(lse), B, SL, h, dk_,
-                                 q.stride(1), d, L.ptr(dq), L.ptr(dkk), L.ptr(dv), 3 * d, ctx.p_drop, ctx.seed, None, None, None, ctx.mode, L.ptr(ws),
-                                 L.stream_of(o)), "mha_bwd")
+        ws = KN.mha_bwd_workspace(lib, B, SL, h, d // h, ctx.mode, o)
+        KN.mha_bwd(lib, L.stream_of(o), q, k, v, mask, o, do, lse, B, SL, h, dq, dkk, dv, ctx.p_drop, ctx.seed, None, None, None, ctx.mode, ws)
         return dq, dkk, dv, None, None, None, None
 
 
@@ -169,15 +161,14 @@ class _AttentionPackedFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, key_pad_mask, h, p_drop=0.0, seed=0):
         L.require_device(qkv, key_pad_mask)
-        qkv = L.f32c(qkv)
         B, SL, d3 = qkv.shape
+        qkv = L.f32c(qkv).view(B, SL, d3)                        # (view: standard strides, whatever a one-item axis carried)
         d = d3 // 3
         mask = key_pad_mask.to(torch.uint8).contiguous()
         o = torch.empty((B, SL, d), dtype=torch.float32, device=qkv.device)
         lse = torch.empty((B, h, SL), dtype=torch.float32, device=qkv.device)
         mode = get_attention_mode()
-        L.check(L.lib().ltrx_mha_fwd(L.ptr(qkv), qkv.data_ptr() + 4 * d, qkv.data_ptr() + 8 * d, L.ptr(mask), B, SL, h, d // h, d3, L.ptr(o),
-                                     d, L.ptr(lse), float(p_drop), int(seed) & 0xFFFFFFFF, None, None, None, mode, L.stream_of(qkv)), "mha_fwd")
+        KN.mha_fwd(L.lib(), L.stream_of(qkv), *KN.thirds(qkv), mask, B, SL, h, o, lse, p_drop, int(seed) & 0xFFFFFFFF, None, None, None, mode)
         ctx.save_for_backward(qkv, mask, o, lse)
         ctx.h, ctx.p_drop, ctx.seed, ctx.mode = h, float(p_drop), int(seed) & 0xFFFFFFFF, mode
         return o
@@ -190,10 +181,9 @@ class _AttentionPackedFn(torch.autograd.Function):
         do = L.f32c(do)
         dqkv = torch.empty((B, SL, 3 * d), dtype=torch.float32, device=o.device)
         lib = L.lib()
-        ws = L.workspace(lib.ltrx_mha_bwd_workspace_bytes(B, SL, h, d // h, ctx.mode), o)
-        L.check(lib.ltrx_mha_bwd(L.ptr(qkv), qkv.data_ptr() + 4 * d, qkv.data_ptr() + 8 * d, L.ptr(mask), L.ptr(o), L.ptr(do), L.ptr(lse),
-                                 B, SL, h, d // h, 3 * d, d, L.ptr(dqkv), dqkv.data_ptr() + 4 * d, dqkv.data_ptr() + 8 * d, 3 * d,
-                                 ctx.p_drop, ctx.seed, None, None, None, ctx.mode, L.ptr(ws), L.stream_of(o)), "mha_bwd")
+        ws = KN.mha_bwd_workspace(lib, B, SL, h, d // h, ctx.mode, o)
+        KN.mha_bwd(lib, L.stream_of(o), *KN.thirds(qkv), mask, o, do, lse, B, SL, h, *KN.thirds(dqkv), ctx.p_drop, ctx.seed, None, None, None,
+                   ctx.mode, ws)
         return dqkv, None, None, None, None
 
 
@@ -236,12 +226,11 @@ class _LinearFn(torch.autograd.Function):
         L.require_device(x, w, b)
         N, K = w.shape
         x2 = L.f32c(x).reshape(-1, K)
-        w = L.f32c(w)
+        w = L.f32c(w).view(N, K)                                 # (view: standard strides, whatever a one-row weight carried)
         b = L.f32c(b) if b is not None else None
         M = x2.shape[0]
         y = torch.empty((M, N), dtype=torch.float32, device=x.device)
-        L.check(L.lib().ltrx_gemm_nt(L.ptr(x2), K, L.ptr(w), K, None, L.ptr(y), N, M, N, K, L.ptr(b), int(act), None, 0, 0.0, 0, None, 0,
-                                     0, L.stream_of(x2)), "gemm_nt(linear fwd)")
+        KN.gemm_nt(L.lib(), L.stream_of(x2), x2, w, y, M, b, int(act), what="gemm_nt(linear fwd)")
         ctx.save_for_backward(x2, w, y if act else None)
         ctx.has_bias, ctx.act, ctx.xshape = b is not None, int(act), x.shape
         return y.view(x.shape[:-1] + (N,))
@@ -260,17 +249,15 @@ class _LinearFn(torch.autograd.Function):
             if N % 4 == 0:
                 wT = w.t().contiguous()                          # [K, N]: the NT kernel wants both operands contraction-contiguous
                 dx = torch.empty((M, K), dtype=torch.float32, device=dy2.device)
-                L.check(lib.ltrx_gemm_nt(L.ptr(dy2), N, L.ptr(wT), N, None, L.ptr(dx), K, M, K, N, None, 0, None, 0, 0.0, 0, None, 0,
-                                         0, L.stream_of(dy2)), "gemm_nt(linear dgrad)")
+                KN.gemm_nt(lib, L.stream_of(dy2), dy2, wT, dx, M, what="gemm_nt(linear dgrad)")
             else:
                 dx = dy2 @ w
             dx = dx.view(ctx.xshape)
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
             dw = torch.empty((N, K), dtype=torch.float32, device=dy2.device)
             db = torch.empty(N, dtype=torch.float32, device=dy2.device) if ctx.has_bias else None
-            ws = torch.empty(max(int(lib.ltrx_gemm_tn_workspace_bytes(M, N, K)), 64), dtype=torch.uint8, device=dy2.device)
-            L.check(lib.ltrx_gemm_tn(L.ptr(dy2), N, L.ptr(x2), K, L.ptr(dw), L.ptr(db), M, N, K, 0, 0, L.ptr(ws), L.stream_of(dy2)),
-                    "gemm_tn(linear wgrad)")
+            ws = KN.gemm_tn_workspace(lib, M, N, K, dy2)
+            KN.gemm_tn(lib, L.stream_of(dy2), dy2, x2, dw, db, M, 0, 0, ws, "gemm_tn(linear wgrad)")
         return dx, dw, db, None
 
 
@@ -299,10 +286,8 @@ class _FFNFn(torch.autograd.Function):
         lib, st = L.lib(), L.stream_of(x2)
         r = torch.empty((M, F_), dtype=torch.float32, device=x.device)
         y = torch.empty((M, N), dtype=torch.float32, device=x.device)
-        L.check(lib.ltrx_gemm_nt(L.ptr(x2), K, L.ptr(w1), K, None, L.ptr(r), F_, M, F_, K, L.ptr(b1), 1, None, 0, float(p), int(seed), None, 0, 0, st),
-                "gemm_nt(ffn w_1)")
-        L.check(lib.ltrx_gemm_nt(L.ptr(r), F_, L.ptr(w2), F_, None, L.ptr(y), N, M, N, F_, L.ptr(b2), 0, None, 0, 0.0, 0, None, 0, 0, st),
-                "gemm_nt(ffn w_2)")
+        KN.gemm_nt(lib, st, x2, w1, r, M, b1, 1, p=p, seed=int(seed), what="gemm_nt(ffn w_1)")
+        KN.gemm_nt(lib, st, r, w2, y, M, b2, what="gemm_nt(ffn w_2)")
         ctx.save_for_backward(x2, w1, w2, r)
         ctx.p, ctx.xshape = float(p), x.shape
         return y.view(x.shape[:-1] + (N,))
@@ -319,23 +304,21 @@ class _FFNFn(torch.autograd.Function):
         def wgrad(a, b_, n, k):
             gw = torch.empty((n, k), dtype=torch.float32, device=dev)
             gb = torch.empty(n, dtype=torch.float32, device=dev)
-            ws = torch.empty(max(int(lib.ltrx_gemm_tn_workspace_bytes(M, n, k)), 64), dtype=torch.uint8, device=dev)
-            L.check(lib.ltrx_gemm_tn(L.ptr(a), n, L.ptr(b_), k, L.ptr(gw), L.ptr(gb), M, n, k, 0, 0, L.ptr(ws), st), "gemm_tn(ffn wgrad)")
+            ws = KN.gemm_tn_workspace(lib, M, n, k, a)
+            KN.gemm_tn(lib, st, a, b_, gw, gb, M, 0, 0, ws, "gemm_tn(ffn wgrad)")
             return gw, gb
 
         dw2, db2 = wgrad(dy2, r, N, F_)
         w2T = w2.t().contiguous()                                # [F, N]
         dr = torch.empty((M, F_), dtype=torch.float32, device=dev)
         # d r = (dy w_2) * [r > 0] / (1 - p): r is the post-ReLU, post-dropout activation, so its sign pattern IS the combined mask
-        L.check(lib.ltrx_gemm_nt(L.ptr(dy2), N, L.ptr(w2T), N, None, L.ptr(dr), F_, M, F_, N, None, 2, L.ptr(r), F_, ctx.p, 0, None, 0, 0, st),
-                "gemm_nt(ffn dgrad w_2)")
+        KN.gemm_nt(lib, st, dy2, w2T, dr, M, None, 2, r, ctx.p, what="gemm_nt(ffn dgrad w_2)")
         dw1, db1 = wgrad(dr, x2, F_, K)
         dx = None
         if ctx.needs_input_grad[0]:
             w1T = w1.t().contiguous()                            # [K, F]
             dx = torch.empty((M, K), dtype=torch.float32, device=dev)
-            L.check(lib.ltrx_gemm_nt(L.ptr(dr), F_, L.ptr(w1T), F_, None, L.ptr(dx), K, M, K, F_, None, 0, None, 0, 0.0, 0, None, 0, 0, st),
-                    "gemm_nt(ffn dgrad w_1)")
+            KN.gemm_nt(lib, st, dr, w1T, dx, M, what="gemm_nt(ffn dgrad w_1)")
             dx = dx.view(ctx.xshape)
         return dx, dw1, db1, dw2, db2, None, None
 
@@ -362,7 +345,7 @@ class _ScoreHeadFn(torch.autograd.Function):
         w, b = L.f32c(w).reshape(-1), L.f32c(b).reshape(-1)
         M = x2.shape[0]
         sc = torch.empty(M, dtype=torch.float32, device=x.device)
-        L.check(L.lib().ltrx_score_head_fwd(L.ptr(x2), L.ptr(w), L.ptr(b), M, D, L.ptr(sc), L.stream_of(x2)), "score_head_fwd")
+        KN.score_head_fwd(L.lib(), L.stream_of(x2), x2, w, b, M, sc)
         ctx.save_for_backward(x2, w)
         ctx.xshape, ctx.wshape, ctx.bshape = x.shape, None, None
         return sc.view(x.shape[:-1])
@@ -376,9 +359,8 @@ class _ScoreHeadFn(torch.autograd.Function):
         dx = torch.empty_like(x2)
         dw = torch.empty(D, dtype=torch.float32, device=x2.device)
         db = torch.empty(1, dtype=torch.float32, device=x2.device)
-        ws = torch.empty(max(int(lib.ltrx_score_head_bwd_workspace_bytes(M, D)), 64), dtype=torch.uint8, device=x2.device)
-        L.check(lib.ltrx_score_head_bwd(L.ptr(ds), L.ptr(x2), L.ptr(w), M, D, L.ptr(dx), L.ptr(dw), L.ptr(db), L.ptr(ws), L.stream_of(x2)),
-                "score_head_bwd")
+        ws = KN.score_head_bwd_workspace(lib, M, D, x2)
+        KN.score_head_bwd(lib, L.stream_of(x2), ds, x2, w, M, dx, dw, db, ws)
         return dx.view(ctx.xshape), dw.view(1, D), db
 
 

@@ -298,7 +298,7 @@ int ltrx_norm_head_wgrad(const float* dscores, const float* xsum, const float* a
  * scaled, masked scores (the only tensor saved for backward).  fp32 in/out; contractions on the fp32 MFMA
  * (v_mfma_f32_32x32x2_f32), exact fp32 products.  d_k % 4 == 0, d_k <= 128 (zero-padded to a multiple of 32).
  * cu_seqlens (i32[B+1] in device memory, or NULL): variable-length layout -- slate b occupies rows cu[b] .. cu[b+1]-1 of
- * q/k/v/o (its valid items packed, ltrx_gather_rows), L is then only the maximum slate length (grid size and the stride of
+ * q/k/v/o (its valid items packed: ltrx_gather_rows from a row index, ltrx_gather_rows_cu from cu_seqlens itself), L is then only the maximum slate length (grid size and the stride of
  * lse / delta); key_pad_mask may be NULL in that layout (every packed row is a valid key).
  * slate_order (i32[B] in device memory, or NULL): a permutation of the slates giving the order in which their workgroups are
  * launched -- longest first balances the CUs on ragged batches; results do not depend on it. */

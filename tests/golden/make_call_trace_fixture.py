@@ -1,0 +1,282 @@
+"""Record which libltrx calls the package makes, and what they compute, over a set of small cases (needs the MI355X).
+
+    python tests/golden/make_call_trace_fixture.py [--out FILE] [--commit HASH]
+
+Writes tests/golden/call_trace_parent.json.  It was run ONCE, at the commit named in the file ("commit"), before the GEMM, attention,
+LayerNorm and head calls of allrank_amd/ops.py and allrank_amd/engine.py moved into the launchers of allrank_amd/kernels.py;
+tests/test_gpu_call_trace.py runs the same cases at every later commit and holds them to the recorded calls and results exactly.
+Re-running it at a later commit only re-records that commit against itself.
+
+Only public entry points are used (FusedTrainer, FusedScorer, allrank_amd.ops).  The object ``allrank_amd._lib.lib()`` caches is
+replaced by a proxy before anything is constructed; while a case records, the proxy logs every call as ``[name, [arguments]]``:
+an argument whose type in ``_lib.SIGNATURES`` is a pointer (the stream included) as 0 or 1 -- NULL or not -- and integers and floats
+as they are.  Per trainer case: the trace of the first step (``use_graph=False``: every step makes its calls) and SHA-256 digests of the raw
+bytes of the loss of each of 3 steps, the flat gradient after step 1, the flat parameters after step 3 and the scores.  Every case
+runs twice; a digest is stored only where the two runs agree bit for bit (``unstable`` names the others), and the two traces must
+be equal.  ``gemm="hipblaslt"`` is recorded without digests: torch's GEMMs choose their own algorithm.
+"""
+import contextlib
+import ctypes
+import hashlib
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+DEV = "cuda:0"
+FIXTURE = os.path.join(HERE, "call_trace_parent.json")
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the recording proxy
+# ------------------------------------------------------------------------------------------------------------------
+class _Proxy(object):
+    """stands where ``_lib.lib()`` keeps the bound library: passes every call on, logs it while ``log`` is a list"""
+
+    def __init__(self, real, signatures):
+        self._real, self._sig, self.log = real, signatures, None
+
+    def __getattr__(self, name):
+        fn = getattr(self._real, name)
+        types = self._sig[name][1]
+
+        def call(*args):
+            if self.log is not None:
+                self.log.append([name, [_plain(a, t) for a, t in zip(args, types)]])
+            return fn(*args)
+        return call
+
+
+def _plain(a, ctype):
+    if ctype is ctypes.c_void_p:                               # any pointer or the stream: NULL or not
+        if a is None:
+            return 0
+        if isinstance(a, ctypes.c_void_p):
+            return int(bool(a.value))
+        return int(bool(a)) if isinstance(a, int) else 1        # (arrays and byref() objects are never NULL)
+    a = getattr(a, "value", a)                                 # a ctypes scalar
+    return float(a) if ctype is ctypes.c_float else int(a)
+
+
+@contextlib.contextmanager
+def proxied():
+    """the proxy in place of the cached library object for the enclosed region"""
+    from allrank_amd import _lib
+    real = _lib.lib()
+    proxy = _Proxy(real, _lib.SIGNATURES)
+    _lib._lib = proxy
+    try:
+        yield proxy
+    finally:
+        _lib._lib = real
+
+
+@contextlib.contextmanager
+def _recording(proxy, trace):
+    proxy.log = trace
+    try:
+        yield
+    finally:
+        proxy.log = None
+
+
+def _sha(t):
+    return hashlib.sha256(t.detach().contiguous().cpu().numpy().tobytes()).hexdigest()
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# models and batches
+# ------------------------------------------------------------------------------------------------------------------
+def _model(F, sizes, N=0, d_ff=64, h=4, dropout=0.0, pe=None, input_norm=False, act=None, fc_dropout=0.0, out_act=None, d_output=1):
+    from allrank_amd.model import make_model
+    torch.manual_seed(11)
+    tr = dict(N=N, d_ff=d_ff, h=h, positional_encoding=pe, dropout=dropout) if N else None
+    return make_model(dict(sizes=list(sizes), input_norm=input_norm, activation=act, dropout=fc_dropout), tr,
+                      dict(d_output=d_output, output_activation=out_act), F).to(DEV)
+
+
+def _batch(lens, L, F, seed):
+    """padded batch (valid items first; features 0, label -1, index -1 on padding) with the given slate lengths"""
+    rng = np.random.default_rng(seed)
+    n = len(lens)
+    x = rng.standard_normal((n, L, F)).astype(np.float32)
+    y = rng.integers(0, 5, (n, L)).astype(np.float32)
+    idx = np.tile(np.arange(L, dtype=np.int64), (n, 1))
+    for b, k in enumerate(lens):
+        x[b, k:], y[b, k:], idx[b, k:] = 0, -1, -1
+    return (torch.tensor(x, device=DEV), torch.tensor(y, device=DEV), torch.tensor(idx, device=DEV),
+            torch.tensor(np.asarray(lens, dtype=np.int32)))
+
+
+SMALL = dict(F=20, sizes=[32], N=2, d_ff=64, h=4, dropout=0.1)               # the small-tile encoder, B 5, L 70
+SMALL_LENS = [70, 31, 70, 8, 55]
+LARGE = dict(F=136, sizes=[256], N=1, d_ff=512, h=4)                         # head width 64, 2048 rows: the large-tile arms
+LARGE_LENS = [128] * 12 + [100, 128, 77, 128]
+LARGE_RAGGED = [128, 90, 3, 128, 61, 128, 17, 128, 128, 45, 128, 99, 128, 128, 1, 110]
+
+
+def _train(proxy, model_kw, loss, largs, lens, L, use_idx=False, host_lengths=False, digests=True, **trainer_kw):
+    from allrank_amd.engine import FusedTrainer
+    model = _model(**model_kw)
+    ft = FusedTrainer(model, loss, largs, len(lens), L, use_graph=False, seed=1234, **trainer_kw)
+    x, y, idx, hl = _batch(lens, L, model_kw["F"], 3)
+    kw = dict(indices=idx) if use_idx else {}
+    if host_lengths:
+        kw["lengths"] = hl
+    trace, dig = [], {}
+    for s in range(3):
+        with _recording(proxy, trace if s == 0 else None):
+            loss_t = ft.step(x, y, **kw)
+        dig["loss%d" % (s + 1)] = _sha(loss_t)
+        if s == 0:
+            dig["flat_g"] = _sha(ft.flat_g)
+    dig["flat_p"], dig["scores"] = _sha(ft.flat_p), _sha(ft.scores)
+    return trace, (dig if digests else {})
+
+
+def _score(proxy):
+    from allrank_amd.engine import FusedTrainer
+    ft = FusedTrainer(_model(**SMALL), "listNet", {}, 5, 70, use_graph=False, seed=1234)
+    x, y, _, _ = _batch(SMALL_LENS, 70, 20, 3)
+    ft.step(x, y)
+    trace = []
+    with _recording(proxy, trace):
+        sc = ft.score(x, y)
+    return trace, dict(scores=_sha(sc))
+
+
+def _scorer(proxy):
+    from allrank_amd.engine import FusedTrainer
+    ft = FusedTrainer(_model(pe=dict(strategy="fixed", max_indices=100), **SMALL), "listNet", {}, 5, 70, use_graph=False, seed=1234)
+    xt, yt, it, _ = _batch(SMALL_LENS, 70, 20, 3)
+    ft.step(xt, yt, it)
+    sc = ft.scorer(5, 90, use_graph=False)
+    x, y, idx, hl = _batch([90, 1, 44, 0, 59], 90, 20, 4)
+    trace = []
+    with _recording(proxy, trace):
+        raw = sc.run(x, y, idx, lengths=hl)
+        ps, py, cu, order, max_len = sc.packed()
+    return trace, dict(scores=_sha(raw), packed_scores=_sha(ps), packed_labels=_sha(py), cu=_sha(cu), order=_sha(order))
+
+
+def _ops(fn):
+    """an ops case: ``fn(rng)`` -> (inputs that take a gradient, a function of them); forward and backward are both recorded"""
+    def run(proxy):
+        rng = np.random.default_rng(5)
+        leaves, f = fn(lambda *shape: torch.tensor(rng.standard_normal(shape).astype(np.float32), device=DEV))
+        for t in leaves:
+            t.requires_grad_(True)
+        trace = []
+        with _recording(proxy, trace):
+            out = f(*leaves)
+            outs = [o for o in (out if isinstance(out, tuple) else (out,)) if o is not None]
+            torch.manual_seed(3)
+            torch.autograd.backward(outs, [torch.randn(o.shape, device="cpu").to(DEV) for o in outs])
+        dig = {"out%d" % i: _sha(o) for i, o in enumerate(outs)}
+        dig.update({"grad%d" % i: _sha(t.grad) for i, t in enumerate(leaves)})
+        return trace, dig
+    return run
+
+
+def _key_mask(B, L, lens):
+    m = torch.zeros((B, L), dtype=torch.bool, device=DEV)
+    for b, k in enumerate(lens):
+        m[b, k:] = True
+    return m
+
+
+def _op_cases():
+    from allrank_amd import ops
+    B, L, d, h = 3, 50, 32, 4
+    mask = lambda: _key_mask(B, L, [50, 17, 33])  # noqa: E731
+    return {
+        "ops.linear": _ops(lambda r: ((r(B, L, 36), r(52, 36), r(52)), lambda x, w, b: ops.linear(x, w, b, 0))),
+        "ops.linear_relu": _ops(lambda r: ((r(B, L, 36), r(52, 36), r(52)), lambda x, w, b: ops.linear(x, w, b, 1))),
+        "ops.feed_forward": _ops(lambda r: ((r(B, L, 36), r(64, 36), r(64), r(36, 64), r(36)),
+                                            lambda x, w1, b1, w2, b2: ops.feed_forward(x, w1, b1, w2, b2, 0.2, seed=77))),
+        "ops.layer_norm": _ops(lambda r: ((r(B, L, 40), r(40), r(40)), lambda x, a, b: ops.layer_norm(x, a, b))),
+        "ops.layer_norm_residual": _ops(lambda r: ((r(B, L, 40), r(B, L, 40), r(40), r(40)),
+                                                   lambda x, res, a, b: ops.layer_norm_residual(x, res, a, b))),
+        "ops.attention": _ops(lambda r: ((r(B, L, 3 * d),), lambda qkv: ops.attention(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:],
+                                                                                      mask(), h, 0.1, seed=5))),
+        "ops.attention_packed": _ops(lambda r: ((r(B, L, 3 * d),), lambda qkv: ops.attention_packed(qkv, mask(), h, 0.1, seed=5))),
+        "ops.score_head": _ops(lambda r: ((r(B, L, 40), r(1, 40), r(1)), lambda x, w, b: ops.score_head(x, w, b))),
+    }
+
+
+def cases():
+    """{name: run(proxy) -> (trace, digests)}"""
+    fc46 = dict(F=46, sizes=[64, 32], input_norm=True, act="ReLU", fc_dropout=0.2)
+    fc_tanh = dict(F=24, sizes=[48, 32], act="Tanh", out_act="Sigmoid")
+    pe = dict(SMALL, pe=dict(strategy="learned", max_indices=100), d_output=4, out_act="Sigmoid")
+    large_drop = dict(LARGE, dropout=0.1)
+    out = {
+        "small_encoder": lambda p: _train(p, SMALL, "listNet", {}, SMALL_LENS, 70),
+        "large_tile": lambda p: _train(p, LARGE, "approxNDCGLoss", {}, LARGE_LENS, 128),
+        # 8 x 21 = 168 tiles of 256 x 256 in the feed-forward GEMMs: where ltrx_gemm_nt_relu_bits_bytes grants the one-bit ReLU mask
+        "large_tile_relu_bits": lambda p: _train(p, dict(LARGE, d_ff=5376, dropout=0.1), "approxNDCGLoss", {}, LARGE_LENS, 128),
+        "large_tile_compact_host_lengths": lambda p: _train(p, large_drop, "approxNDCGLoss", {}, LARGE_RAGGED, 128, host_lengths=True,
+                                                            compact=True),
+        "large_tile_compact_device_count": lambda p: _train(p, large_drop, "approxNDCGLoss", {}, LARGE_RAGGED, 128, compact=True),
+        "fc_input_norm_46": lambda p: _train(p, fc46, "listNet", {}, [30, 12, 30, 1], 30),
+        "fc_tanh_sigmoid": lambda p: _train(p, fc_tanh, "listNet", {}, [30, 12, 30, 1], 30),
+        "learned_pe_ordinal_clip_adamw": lambda p: _train(p, pe, "ordinal", {"n": 4}, SMALL_LENS, 70, use_idx=True,
+                                                          gradient_clipping_norm=0.5, optimizer="AdamW", weight_decay=0.01),
+        "sgd_momentum": lambda p: _train(p, SMALL, "listNet", {}, SMALL_LENS, 70, optimizer="SGD", momentum=0.9, lr=0.01),
+        "gemm_split_bf16_strict": lambda p: _train(p, SMALL, "listNet", {}, SMALL_LENS, 70, gemm="split_bf16_strict"),
+        "gemm_bf16": lambda p: _train(p, SMALL, "listNet", {}, SMALL_LENS, 70, gemm="bf16"),
+        "gemm_hipblaslt": lambda p: _train(p, SMALL, "listNet", {}, SMALL_LENS, 70, gemm="hipblaslt", digests=False),
+        "score": _score,
+        "scorer_run_packed": _scorer,
+    }
+    out.update(_op_cases())
+    return out
+
+
+def run_case(proxy, name):
+    trace, dig = cases()[name](proxy)
+    torch.cuda.synchronize()
+    return trace, dig
+
+
+def record():
+    rec = {}
+    with proxied() as proxy:
+        for name in cases():
+            (t1, d1), (t2, d2) = run_case(proxy, name), run_case(proxy, name)
+            assert t1 == t2, "%s: the two runs made different calls" % name
+            assert t1, "%s: no call recorded" % name
+            rec[name] = dict(trace=t1, digests={k: v for k, v in d1.items() if d2[k] == v},
+                             unstable=sorted(k for k, v in d1.items() if d2[k] != v))
+            print("%-36s %4d calls, %d digests, unstable: %s" % (name, len(t1), len(rec[name]["digests"]), rec[name]["unstable"]), flush=True)
+    return rec
+
+
+def main():
+    import argparse
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=FIXTURE)
+    ap.add_argument("--commit", default=None, help="the checked-out commit (default: asked of git)")
+    args = ap.parse_args()
+    commit = args.commit or subprocess.check_output(["git", "-C", ROOT, "rev-parse", "HEAD"]).decode().strip()
+    rec = record()
+    with open(args.out, "w") as fh:                           # one call per line: a changed argument is a one-line diff
+        fh.write('{"commit": %s,\n "cases": {' % json.dumps(commit))
+        for i, (name, c) in enumerate(rec.items()):
+            fh.write('%s\n  %s: {"digests": %s,\n   "unstable": %s,\n   "trace": [\n    %s\n   ]}'
+                     % ("," if i else "", json.dumps(name), json.dumps(c["digests"], sort_keys=True), json.dumps(c["unstable"]),
+                        ",\n    ".join(json.dumps(call) for call in c["trace"])))
+        fh.write("\n }\n}\n")
+    print("wrote %s: %d cases, %d calls" % (args.out, len(rec), sum(len(c["trace"]) for c in rec.values())))
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,55 @@
+"""-m gpu: the package makes the libltrx calls, and computes the bits, it did before the GEMM, attention, LayerNorm and head calls of
+allrank_amd/ops.py and allrank_amd/engine.py moved into the launchers of allrank_amd/kernels.py.
+
+tests/golden/call_trace_parent.json was recorded by tests/golden/make_call_trace_fixture.py at the parent of that change (the commit
+named in the file): per case the trace of every library call -- name, integers and floats as passed, pointers as NULL or not -- and
+SHA-256 digests of losses, gradients, parameters and scores that two runs at that commit agreed on bit for bit.  Every case is run
+again here through the same code and must give the same trace and the same digests.  ``gemm="hipblaslt"`` has no digests (torch's
+GEMMs choose their own algorithm): its trace alone is held."""
+import json
+
+import pytest
+
+from tests.golden import make_call_trace_fixture as G
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def rec():
+    with open(G.FIXTURE) as fh:
+        return json.load(fh)
+
+
+@pytest.fixture(scope="module")
+def proxy():
+    with G.proxied() as p:
+        yield p
+
+
+def test_fixture_is_the_parents_and_covers_every_case(rec):
+    assert len(rec["commit"]) == 40
+    assert sorted(rec["cases"]) == sorted(G.cases())
+    for name, c in rec["cases"].items():
+        assert c["trace"] and c["unstable"] == [], name
+        assert bool(c["digests"]) == (name != "gemm_hipblaslt"), name
+    trainers = [c for n, c in rec["cases"].items() if {"loss1", "loss2", "loss3", "flat_g", "flat_p", "scores"} <= set(c["digests"])]
+    assert len(trainers) >= 11
+    called = {call[0] for c in rec["cases"].values() for call in c["trace"]}
+    assert {"ltrx_gemm_nt", "ltrx_gemm_tn", "ltrx_mha_fwd", "ltrx_mha_bwd", "ltrx_layernorm_fwd", "ltrx_layernorm_bwd",
+            "ltrx_layernorm_bwd_partial", "ltrx_score_head_fwd", "ltrx_score_head_bwd", "ltrx_out_act_fwd", "ltrx_out_act_bwd",
+            "ltrx_gather_rows_cu", "ltrx_gemm_tn_group_ln", "ltrx_norm_head_fwd", "ltrx_mha_bwd_workspace_bytes",
+            "ltrx_gemm_tn_workspace_bytes", "ltrx_layernorm_bwd_workspace_bytes", "ltrx_score_head_bwd_workspace_bytes"} <= called
+    acts = {call[1][11] for c in rec["cases"].values() for call in c["trace"] if call[0] == "ltrx_gemm_nt"}
+    assert acts == {0, 1, 2, 3, 4, 5}                        # every epilogue of ltrx_gemm_nt, the one-bit mask pair included
+
+
+@pytest.mark.parametrize("name", sorted(G.cases()))
+def test_same_calls_same_bits(rec, proxy, name):
+    want = rec["cases"][name]
+    trace, digests = G.run_case(proxy, name)
+    assert len(trace) == len(want["trace"]), ([c[0] for c in trace], [c[0] for c in want["trace"]])
+    for i, (got, exp) in enumerate(zip(trace, want["trace"])):
+        assert got == exp, (name, i, got, exp)
+    for key, sha in want["digests"].items():
+        assert digests[key] == sha, (name, key)
