@@ -11,6 +11,7 @@
 //       y_out[b, l] = label or -1; idx_out[r] = b * L + j (-1 beyond cu[B]); pos_out[r] = j (-1 beyond cu[B]).
 //   ltrx_gather_rows_cu  : the same packing of a batch that arrives padded ([B', L, cols] words, valid items first in every slate).
 //   ltrx_scatter_rows_cu : packed rows back to the padded grid, the padded slots set to 0.
+//   ltrx_zero_rows_cu    : the alignment rows [cu[B], rows) of a row buffer set to 0 (the captured variable-length training step).
 // Rows are moved as 32-bit words (bit-exact for any 4-byte type; an int64 column is two words), 16 bytes per access where the
 // row length, strides and base addresses allow it.
 #include "ltrx_device.h"
@@ -171,6 +172,38 @@ extern "C" int ltrx_scatter_rows_cu(const float* src, int ld_src, const int32_t*
   if ((size_t)B * L > (size_t)INT32_MAX) return LTRX_EINVAL;
   hipLaunchKernelGGL(ltrx_scatter_rows_cu_kernel, dim3(grid_for((size_t)B * L * cols)), dim3(256), 0, (hipStream_t)stream,
                      reinterpret_cast<const uint32_t*>(src), ld_src, cu_seqlens, B, L, cols, rows, reinterpret_cast<uint32_t*>(dst), ld_dst);
+  LTRX_LAUNCH_CHECK();
+  return LTRX_OK;
+}
+
+// the alignment rows [cu[B], rows) of a row buffer, columns [0, cols): zero.  What a kernel that writes rows of slates only (the
+// varlen attention forward and backward) leaves untouched there, inside a captured step: the count is read here, on the device,
+// and the grid covers `rows` rows whatever it is.
+template <bool VEC>
+__global__ void __launch_bounds__(256) ltrx_zero_rows_cu_kernel(float* __restrict__ x, int ld, int cols, const int32_t* __restrict__ cu,
+                                                                int B, int rows) {
+  const int per_row = VEC ? cols / 4 : cols;
+  const int first = min(max(cu[B], 0), rows);
+  const size_t total = (size_t)(rows - first) * per_row;
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+    const int r = first + (int)(e / per_row), c = (int)(e % per_row);
+    if (VEC)
+      reinterpret_cast<float4*>(x + (size_t)r * ld)[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+    else
+      x[(size_t)r * ld + c] = 0.f;
+  }
+}
+
+extern "C" int ltrx_zero_rows_cu(float* x, int ld, int cols, const int32_t* cu_seqlens, int B, int rows, ltrx_stream_t stream) {
+  if (!x || !cu_seqlens || B <= 0 || rows <= 0 || cols <= 0 || ld < cols) return LTRX_EINVAL;
+  const bool vec = (cols % 4 == 0) && (ld % 4 == 0) && aligned16(x);
+  const size_t total = (size_t)rows * (vec ? cols / 4 : cols);
+  if (vec)
+    hipLaunchKernelGGL(ltrx_zero_rows_cu_kernel<true>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, ld, cols, cu_seqlens, B,
+                       rows);
+  else
+    hipLaunchKernelGGL(ltrx_zero_rows_cu_kernel<false>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, ld, cols, cu_seqlens, B,
+                       rows);
   LTRX_LAUNCH_CHECK();
   return LTRX_OK;
 }

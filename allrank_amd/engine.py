@@ -235,7 +235,9 @@ class _GraphLRU(object):
         #            (module load, kernel attributes) must stay outside a capture.
         #   "cache": the whole cache, once.  The training step: a new batch divisor changes only a by-value scalar of launches that
         #            have all been made before, so every later key is captured on its first visit.
-        self._slot = {"key": lambda key: key, "cache": lambda key: None}[warm]
+        #   a function of the key: the part of the key it returns.  The variable-length training step, keyed (batch divisor,
+        #            collectives on?, row bucket), counts over the row bucket: both reasons above, one per part of its key.
+        self._slot = warm if callable(warm) else {"key": lambda key: key, "cache": lambda key: None}[warm]
         # new_pool(): the memory-pool handle the captures share (None: every capture gets a private pool of the default kind).  A
         # pool whose graphs are all gone cannot be captured into again, so capture_now starts a fresh one whenever ``graphs`` is
         # empty -- however it got empty: a caller's ``graphs.clear()`` (set_lr, bench.py), an eviction with max_graphs = 1.
@@ -304,7 +306,9 @@ class FusedTrainer(object):
     * every launch of the sequence is a libltrx kernel: the dense projections are the split-bf16 MFMA GEMMs
       (ltrx_gemm_nt / ltrx_gemm_tn; ``gemm="hipblaslt"`` swaps in torch.mm/addmm as a comparison arithmetic).
     * the whole sequence is captured in a hipGraph after warm-up (``use_graph=True``) -- at 64 slates/GPU the step is
-      ~100 launches of 10-300 us, so launch latency matters.
+      ~100 launches of 10-300 us, so launch latency matters.  The variable-length step (``compact=True``)
+      runs eagerly: its row count changes per batch.  ``compact="graph"`` (opt-in) rounds that count up the scorer's row ladder and
+      captures one step per row bucket (see ``__init__``; faster or not: profiles/compact_graph.md).
     * dropout (every shipped transformer config trains with 0.1-0.4) is counter-based: a mask element is a hash of
       (site seed ^ per-step device word, element index), generated inside the producing kernel's epilogue (GEMM bias+
       ReLU+dropout, the residual sum in the epilogue of the projection that closes a sublayer, the attention probabilities)
@@ -341,6 +345,22 @@ class FusedTrainer(object):
         cu_seqlens, and scores / d loss/d scores move between the packed rows and the padded [B, L] grid the loss kernels
         work on.  Same loss and gradients as the padded step (padded rows carry no gradient and are masked as keys); the
         row count changes per batch, so this mode runs eagerly (no hipGraph).
+        compact="graph" (opt-in; ``self.compact`` is True, ``self.compact_graph`` says so): the same packed step at BUCKETED row
+        counts, captured and replayed per bucket.  The row count is ``row_bucket(n, ceil32(B * L))``, the scorer's ladder (the
+        buffers hold its largest rung), and a captured step is keyed (batch divisor, collectives on?, rows); the two eager
+        warm-up visits are counted per row bucket (a new bucket can pick GEMM tiles and LayerNorm launch shapes that were never
+        launched), a new divisor inside a warmed bucket is captured on its first visit, the LRU holds 8 captures.  Nothing
+        inside the sequence depends on a host copy of the valid-row count: packing, unpacking and the zeroing of the
+        alignment rows the attention kernels leave out read it from cu_seqlens in device memory (ltrx_gather_rows_cu,
+        ltrx_scatter_rows_cu, ltrx_zero_rows_cu).  Staging stays outside the graph and, with host ``lengths``, without a host
+        sync.  ``use_graph=False`` runs the identical launch sequence eagerly; ``self.last_mode`` is "eager", "capture" or
+        "replay" for the last step.  Costs and limits: rows n .. rows-1 are alignment rows (zero input, no slate, no gradient;
+        every buffer a later kernel reads there is written for them in the same step, so they are a function of the weights
+        alone) -- up to 31 rows below 256, up to 1/8 of the bucket above, where compact=True runs at most 31; the valid items
+        must come first in every slate (how dataset.py pads; without ``lengths`` the one counting sync also checks it and a
+        batch with interior padding raises ValueError -- that stays a compact=True capability); slate-sharded trainers raise
+        NotImplementedError (ranks see different row counts, hence different keys); whether it is faster than compact=True:
+        profiles/compact_graph.md.
         optimizer: "Adam" (betas, eps, weight_decay = L2 term), "AdamW" (decoupled weight decay) or "SGD" (momentum, nesterov,
         weight_decay; dampening 0) -- torch.optim's update rules (main.py:82) in one flat-buffer kernel.
         weight_images=False: the GEMMs split the weight operand on the fly in every tile instead of reading the per-step pre-split
@@ -425,6 +445,14 @@ class FusedTrainer(object):
             and self.lib.ltrx_fc_listnet_supported(L, self.fc_sizes[0], self.fc_sizes[1]))
         if not fc_ok:                                         # (before the module's parameters are re-pointed: a refusal leaves it untouched)
             self._check_widths()
+        if isinstance(compact, str) and compact != "graph":
+            raise ValueError("compact must be False, True or \"graph\", got %r" % (compact,))
+        # compact="graph": the packed step at bucketed row counts, captured per bucket -- not for the two jobs that drop compact below
+        graph_rows = compact == "graph" and not fc_ok and not stoch
+        if graph_rows and self.sharded:
+            raise NotImplementedError("FusedTrainer(compact=\"graph\") under slate sharding: the ranks' blocks of a batch hold different "
+                                      "numbers of valid items, so their row buckets -- the keys of the captured steps -- differ, and "
+                                      "agreeing on captured-versus-eager per step across ranks is not built; use compact=True")
         offs = self._layout_parameters(dropout)
         if fc_ok:
             if compact or not use_graph:
@@ -448,7 +476,11 @@ class FusedTrainer(object):
         F0 = self.fc_sizes[0]
         self._x_stride, self._x_k, self._x_large = input_row_plan(F0, self.fc_sizes[1], self.M, gemm, self.in_norm is not None, pad_input)
         self._x_pad = (self._x_stride, self._x_k) != (F0, F0)
-        _alloc_forward(self, self, self.M, B, L, saved=True, compact=bool(compact))
+        # rows every row buffer holds: the padded grid -- or, for the bucketed rows of compact="graph", the largest rung of the
+        # scorer's ladder (every slot valid), as FusedScorer sizes its set
+        self.compact_graph = bool(graph_rows)
+        self.cap = (self.M + 31) // 32 * 32 if self.compact_graph else self.M
+        _alloc_forward(self, self, self.cap, B, L, saved=True, compact=bool(compact))
         self.rows = B * L                                                     # rows the row-wise kernels run over
         self.n_valid = B * L
         self.y_in = torch.zeros((B, L), dtype=torch.float32, device=self.dev)
@@ -467,7 +499,10 @@ class FusedTrainer(object):
         self.shuffle_ties = True
         self._perm_gen = torch.Generator(device=self.dev)
         self._perm_gen.manual_seed(int(seed) & 0x7FFFFFFF)
-        self.use_graph = use_graph and not compact
+        self.use_graph = use_graph and (not compact or self.compact_graph)
+        self.last_mode = None                                 # "eager" / "capture" / "replay" of the last step()
+        self.mode_counts = collections.Counter()              # ... of every step() so far
+        self.bucket_counts = collections.Counter()            # compact="graph": steps per row bucket
         self._fwd_graphs = _GraphLRU(1)                       # score(): one key, captured into the default pool
         self.probe = None                                     # list collecting (start, end) events of the FFN1 GEMM (eager steps only)
         self.probe_wgrad = None                               # ... of the grouped weight-gradient launch (bench.py, eager steps only)
@@ -477,8 +512,11 @@ class FusedTrainer(object):
         # an epoch (DataLoader drop_last=False, dataset_loading.py:245; it arrives topped up with padded slates and global_batch =
         # its real slate count) gets its own capture.  The captures form an LRU of ``max_graphs`` (4) entries: a fifth distinct
         # divisor evicts the least recently used one (and says so once) instead of silently running eagerly.
-        self.max_graphs = 4
-        self._step_graphs = _GraphLRU(self.max_graphs, capture=lambda fn: self._capture(), warm="cache", on_evict=self._warn_evicted,
+        # compact="graph": the key grows by the row bucket -- (batch divisor, collectives on?, rows) -- the warm-up visits are counted
+        # per bucket (_GraphLRU: a function of the key), and the LRU holds 8 captures, as the scorer's
+        self.max_graphs = 8 if self.compact_graph else 4
+        self._step_graphs = _GraphLRU(self.max_graphs, capture=lambda fn: self._capture(),
+                                      warm=(lambda key: key[2]) if self.compact_graph else "cache", on_evict=self._warn_evicted,
                                       new_pool=torch.cuda.graph_pool_handle)
         self._graphs = self._step_graphs.graphs               # (live mapping: least recently used first)
         self.capture_fallback = None                          # why the step is not captured: the capture error after which a sharded
@@ -668,7 +706,7 @@ class FusedTrainer(object):
 
     def _alloc_backward(self, relu_bits):
         """gradient buffers and kernel workspaces of the backward (what _body and its helpers use beyond the forward buffer set)"""
-        B, L, M, d, dev, compact, gemm = self.B, self.L, self.M, self.d, self.dev, self.compact, self.gemm
+        B, L, M, d, dev, compact, gemm = self.B, self.L, self.cap, self.d, self.dev, self.compact, self.gemm   # (M: rows per buffer)
         f32 = dict(dtype=torch.float32, device=dev)
         if self.in_norm is not None:
             F_ = self.fc_sizes[0]
@@ -847,6 +885,11 @@ class FusedTrainer(object):
     def _relu_bwd(self, dr, r, p=0.0):
         """dr *= (r > 0) / (1 - p): backward of dropout(relu(z)) given the stored post-dropout activation r"""
         self.LB.check(self.lib.ltrx_relu_bwd(self.LB.ptr(dr), self.LB.ptr(r), self.rows * dr.shape[1], 1.0 / (1.0 - p), self._st()), "relu_bwd")
+
+    def _zero_alignment_rows(self, buf):
+        """buf[cu[B] : rows] = 0, the count read on the device (compact="graph": the launch is the same for every batch of a bucket)"""
+        self.LB.check(self.lib.ltrx_zero_rows_cu(self.LB.ptr(buf), buf.stride(0), buf.shape[1], self.LB.ptr(self.cu), self.B, self.rows,
+                                                 self._st()), "zero_rows_cu")
 
     def saved_activation(self, layer, key):
         """the saved activation ``key`` ("r", "xn0", "xn1", ...) of encoder layer ``layer`` of the LAST step (tests, diagnostics)"""
@@ -1123,6 +1166,8 @@ class FusedTrainer(object):
             self._lin_fwd(st["xn0"], st["wqkv"], st["bqkv"], st["qkv"], rows=M)
             KN.mha_fwd(lib, self._st(), st["q"], st["k"], st["v"], kpm, B, L, self.h, st["o"], st["lse"], dp(st["p_att"]), st["s_att"],
                        self.drop_step, bs.cu, bs.order, self._mha_mode)
+            if bs is self and self.compact_graph:                 # the attention wrote rows of slates only; the out-projection and its
+                self._zero_alignment_rows(st["o"])                # weight gradient read every row: 0 there, whatever the buffer held
             lo = lay.self_attn.linears[3]
             # x1 = x + dropout(attention branch): the residual sum is the out-projection's epilogue (act 3)
             self._lin_fwd(st["o"], W(lo.weight), W(lo.bias), st["x1"], 0, dp(st["p_s0"]), st["s_s0"], res=x, rows=M)
@@ -1159,8 +1204,8 @@ class FusedTrainer(object):
             self._lin_fwd(feat, W(out.w_1.weight), W(out.w_1.bias), sc_rows.view(-1, no), rows=M)
         if self.out_act:                                          # OutputLayer activation (model.py:117), in place
             KN.out_act_fwd(lib, self._st(), sc_rows, M * no, self.out_act, sc_rows)
-        if bs is not self:                                        # scorer: packed scores -> padded grid, padding 0, count from cu[B]
-            self.LB.check(lib.ltrx_scatter_rows_cu(P(sc_rows), no, P(bs.cu), B, L, no, M, P(bs.scores_raw), no, self._st()),
+        if bs is not self or self.compact_graph:                  # scorer, captured packed step: packed scores -> padded grid, padding
+            self.LB.check(lib.ltrx_scatter_rows_cu(P(sc_rows), no, P(bs.cu), B, L, no, M, P(bs.scores_raw), no, self._st()),   # 0, count from cu[B]
                           "scatter_rows_cu")
         elif self.compact:                                        # packed scores -> the padded [B, L] grid of the loss kernels
             self.scores_raw.zero_()
@@ -1187,7 +1232,10 @@ class FusedTrainer(object):
         # ---------------- backward ----------------
         ga, gb = self.d_a, self.d_b
         spare = self.d_c if (self.N and self.ln_in_wgrad) else None
-        if self.compact:                                          # d loss / d scores of the packed rows (alignment rows: 0)
+        if self.compact_graph:                                    # d loss / d scores of the packed rows, counted from cu_seqlens
+            KN.gather_rows_cu(lib, self._st(), dsc, self.cu, B, L, no, M, self.dsc_c, None, "gather_rows_cu(d scores)")
+            dsc = self.dsc_c
+        elif self.compact:                                        # d loss / d scores of the packed rows (alignment rows: 0)
             self.LB.check(lib.ltrx_gather_rows(P(dsc), no, P(self.idx), self.n_valid, M, no, P(self.dsc_c), no, self._st()),
                           "gather_rows")
             dsc = self.dsc_c
@@ -1248,7 +1296,9 @@ class FusedTrainer(object):
                 self._lin_dgrad(db, W(lo.weight), self._wT.get(id(lo.weight)), self.d_o)
                 KN.mha_bwd(lib, self._st(), st["q"], st["k"], st["v"], kpm, st["o"], self.d_o, st["lse"], B, L, self.h, self.dq, self.dk,
                            self.dv, st["p_att"], st["s_att"], self.drop_step, self.cu, self.order, self._mha_mode, self.ws_mha)
-                if self.compact and M > self.n_valid:              # alignment rows belong to no slate: no gradient
+                if self.compact_graph:                             # alignment rows belong to no slate: no gradient
+                    self._zero_alignment_rows(dqkv)
+                elif self.compact and M > self.n_valid:
                     dqkv[self.n_valid:M].zero_()
                 self._lin_wgrad(dqkv, st["xn0"], st["gwqkv"], st["gbqkv"], defer=True)
                 self._lin_dgrad(dqkv, st["wqkv"], st.get("wqkvT"), self.tmp_d)
@@ -1344,7 +1394,7 @@ class FusedTrainer(object):
 
     def set_lr(self, lr):
         """change the learning rate (per-epoch scheduler step): the rate is a launch argument of the Adam kernel, so a
-        captured graph is dropped and re-captured on the next step"""
+        captured graph is dropped and re-captured on the next step (the warm-up counts stay: no new eager steps)"""
         if float(lr) != float(self.lr):
             self.lr = float(lr)
             self._graphs.clear()
@@ -1380,6 +1430,40 @@ class FusedTrainer(object):
                                                 self.x_in.stride(0),
                                                 self._st()), "gather_rows")
 
+    def bucket_of(self, counts):
+        """compact="graph": the rows a step over batches of ``counts`` valid items runs -- ``row_bucket``, the scorer's ladder,
+        capped at the rows the buffers hold"""
+        return [row_bucket(max(int(n), 1), self.cap) for n in counts]
+
+    def _pack_cu(self, xb, indices, lengths):
+        """compact="graph" staging, outside any capture: cu_seqlens and the launch order of this batch, the row bucket, and the valid
+        rows of ``xb`` (and of the positions ``indices``) gathered by ltrx_gather_rows_cu, which also writes the packed-row index
+        and zero-fills the alignment rows.  Host ``lengths``: no sync.  Without them the slates are counted on the device -- one sync,
+        which also checks that the valid items of every slate come first (what the cu_seqlens kernels assume)."""
+        B, L = self.B, self.L
+        if lengths is not None:
+            n = self._stager.upload(torch.as_tensor(lengths, dtype=torch.int32).reshape(B).clamp(min=0, max=L))
+        else:
+            valid = (self.mask == 0)
+            cnt = valid.sum(1, dtype=torch.int32)
+            prefix = (valid == (torch.arange(L, device=self.dev)[None, :] < cnt[:, None])).all()
+            torch.cumsum(cnt, 0, dtype=torch.int32, out=self.cu[1:])
+            self.order.copy_(torch.argsort(cnt, descending=True, stable=True))
+            n, ok = (int(v) for v in torch.stack([self.cu[B], prefix.to(torch.int32)]).tolist())     # (host sync: n picks the bucket)
+            if not ok:
+                raise ValueError("FusedTrainer(compact=\"graph\"): a slate has padding between its valid items -- the captured step packs "
+                                 "from cu_seqlens, which needs the valid items first in every slate (compact=True takes such a batch)")
+        if n == 0:
+            raise ValueError("FusedTrainer(compact=\"graph\"): the batch has no valid item")
+        self.n_valid = n
+        self.rows = row_bucket(max(n, 1), self.cap)               # alignment rows n .. rows-1: zero input, no slate, no gradient
+        F = self.x_in.shape[1]
+        KN.gather_rows_cu(self.lib, self._st(), xb, self.cu, B, L, F, self.rows, self.x_in, self.idx, "gather_rows_cu(x)")
+        if self.pos is not None:                                  # int64 positions move as pairs of 32-bit words
+            ib = indices.to(self.dev, torch.int64).contiguous()
+            KN.gather_rows_cu(self.lib, self._st(), ib, self.cu, B, L, 2, self.rows, self.idx_rows, None, "gather_rows_cu(indices)")
+            self.idx_rows[n:self.rows].fill_(-1)                  # alignment rows -> the padding position
+
     def _reattach(self):
         """the module's parameters / gradients must alias the flat buffers (state_dict(), score() and external readers of
         .grad see what the kernels wrote): re-point anything an external zero_grad(set_to_none=True) / .to() detached."""
@@ -1406,13 +1490,16 @@ class FusedTrainer(object):
         else:
             self.y_in.copy_(yb)
             self.mask.copy_(yb == PADDED_Y_VALUE)
+        if self.pos is not None and indices is None:
+            raise ValueError("FusedTrainer: the model has a positional encoding, %s() needs `indices`" % who)
+        if self.compact_graph:
+            self._pack_cu(xb.to(self.dev, torch.float32).reshape(self.M, -1).contiguous(), indices, lengths)
+            return
         if self.compact:
             self._pack(xb.reshape(self.M, -1).contiguous(), lengths)
         elif not direct:
             self.x_in.copy_(xb.reshape(self.M, -1))
         if self.pos is not None:
-            if indices is None:
-                raise ValueError("FusedTrainer: the model has a positional encoding, %s() needs `indices`" % who)
             if self.compact:                                      # rank of every packed row; alignment rows -> padding row
                 self.idx_rows.fill_(-1)
                 self.idx_rows[:self.n_valid] = indices.reshape(-1)[self.idx[:self.n_valid].long()]
@@ -1432,16 +1519,25 @@ class FusedTrainer(object):
         key = self._key(global_batch)
         self._divisor = key[0]
         self._stage_batch(xb, yb, indices, lengths, "step")
+        if self.compact_graph:                                    # the staging picked the row bucket: the third part of the key
+            key = self._key(global_batch)
+            self.bucket_counts[self.rows] += 1
         if self.use_graph:
+            live = key in self._graphs
             self._captured(key)                                   # (a failed capture of a sharded step turns use_graph off for good)
         if self.use_graph:
-            self._step_graphs.run(key, self._eager)               # warm-up step, or replay
+            mode = self._step_graphs.run(key, self._eager)        # warm-up step, or replay
+            self.last_mode = "capture" if (mode == "replay" and not live) else mode      # (recorded just above, replayed here)
         else:
+            self.last_mode = "eager"
             self._eager()
+        self.mode_counts[self.last_mode] += 1
         return self.loss.loss
 
-    def _key(self, global_batch=None):                            # (batch divisor, collectives on?); None: a full batch on every rank
-        return float(global_batch if global_batch is not None else self.B * self.world), bool(self.comm_enabled)
+    def _key(self, global_batch=None):
+        """(batch divisor, collectives on?) -- None: a full batch on every rank -- and, compact="graph", the staged batch's row bucket"""
+        key = float(global_batch if global_batch is not None else self.B * self.world), bool(self.comm_enabled)
+        return key + (self.rows,) if self.compact_graph else key
 
     def _captured(self, key):
         """capture the step for ``key`` now unless it is live or the warm-up is not over (True: it is live); what a capture error means"""
@@ -1462,6 +1558,11 @@ class FusedTrainer(object):
 
     def _warn_evicted(self, key):
         if self._step_graphs.evictions == 1:                      # (say so once)
+            if self.compact_graph:
+                warnings.warn("allrank_amd: more than %d distinct (batch divisor, row bucket) keys in flight -- evicting the least "
+                              "recently used captured step (%d rows); every key beyond the cache costs one re-capture"
+                              % (self.max_graphs, key[2]))
+                return
             warnings.warn("allrank_amd: more than %d distinct batch divisors in flight -- evicting the least recently used captured "
                           "step (divisor %g); every new divisor costs one re-capture" % (self.max_graphs, key[0]))
 
@@ -1594,7 +1695,8 @@ class FusedTrainer(object):
         self._reattach()
         self._sync_weights()
         self._stage_batch(xb, yb, indices, lengths, "score")
-        if self.use_graph:
+        if self.use_graph and not self.compact_graph:             # (compact="graph": the row count varies, the one-key cache does not
+            #                                                        fit; the forward runs eagerly -- FusedScorer is the captured one)
             self._fwd_graphs.run(0, lambda: self._forward(False))
         else:
             self._forward(False)

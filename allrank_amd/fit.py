@@ -61,7 +61,8 @@ from .parallel import shard_slates
 log = logging.getLogger("allrank_amd.fit")
 
 last_run = {}          # what the most recent fit() used: {"engine": "fused" | "autograd", "compact": bool, "reason": str,
-#                        "sampling": the training DeviceLoader's mode ("device" | "reference"; None for any other loader), ...}
+#                        "sampling": the training DeviceLoader's mode ("device" | "reference"; None for any other loader),
+#                        "compact_graph": what the captured variable-length step did (None: off), "compact_graph_reason": str, ...}
 
 
 class _EarlyStop(object):
@@ -241,6 +242,33 @@ def _host_lengths(batch, trainer, real, pre, world):
     return torch.cat([lens, lens.new_zeros(trainer.B - real)]) if real < trainer.B else lens
 
 
+def _compact_mode(compact):
+    """fit()'s ``compact`` argument resolved: None (choose by the share of valid slots), False, True, or "graph" -- the captured
+    variable-length step, which an unmodified main.py asks for with ALLRANK_AMD_COMPACT=graph (the only value the variable takes;
+    it is read when the argument is None)"""
+    if compact is None:
+        env = os.environ.get("ALLRANK_AMD_COMPACT")
+        if not env:
+            return None
+        if env.lower() != "graph":
+            raise ValueError("ALLRANK_AMD_COMPACT must be 'graph' (or unset), got %r" % (env,))
+        return "graph"
+    if isinstance(compact, str):
+        if compact.lower() != "graph":
+            raise ValueError("compact must be None, False, True or 'graph', got %r" % (compact,))
+        return "graph"
+    return bool(compact)
+
+
+def _compact_graph_stats(trainer):
+    """last_run["compact_graph"]: what the captured variable-length step did so far (None: the mode is not active)"""
+    if not getattr(trainer, "compact_graph", False):
+        return None
+    c = trainer.mode_counts
+    return {"buckets": dict(sorted(trainer.bucket_counts.items())), "captures": c["capture"], "replays": c["replay"],
+            "eager_steps": c["eager"], "evictions": trainer._step_graphs.evictions}
+
+
 def _burn(dl, times=1):
     """Consume what ``times`` iterations over ``dl`` draw from torch's global generator without loading a batch: the worker base
     seed every ``iter(DataLoader)`` draws and the seed a RandomSampler draws at its first index (torch/utils/data/dataloader.py,
@@ -414,7 +442,11 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
         check_finite=None, val_scorer=None):
     """Same positional / keyword arguments as the reference ``fit``; ``use_fused`` / ``compact`` / ``gemm`` / ``train_metrics`` /
     ``check_finite`` are extensions (compact=None: variable-length execution when less than 80 % of the first batch's slots are valid
-    items; gemm: the arithmetic of the fused step, "split_bf16" = fp32-class parity arithmetic, "bf16" = the one-product throughput
+    items; compact="graph", or ALLRANK_AMD_COMPACT=graph under main.py (any other value raises): the variable-length step at bucketed
+    row counts, captured and replayed per bucket -- FusedTrainer(compact="graph"), opt-in, never chosen by None; where it cannot
+    apply (a sharded run, the slate-resident FC + ListNet step, stochastic NeuralNDCG) the job runs as under compact=True and
+    ``last_run["compact_graph_reason"]`` says why; ``last_run["compact"]`` stays a bool and ``last_run["compact_graph"]`` =
+    {"buckets": steps per row bucket, "captures", "replays", "eager_steps", "evictions"} (None when the mode is off); gemm: the arithmetic of the fused step, "split_bf16" = fp32-class parity arithmetic, "bf16" = the one-product throughput
     mode, see FusedTrainer; train_metrics: "fused" (default) = from the training forward, "reference" = the reference's second pass,
     train_utils.py:99; check_finite: None = ``config.detect_anomaly`` or LTRX_CHECK_FINITE=1, see the module docstring; val_scorer:
     "module" (default) = the validation batches of another slate length than the training step's run the nn.Module forward,
@@ -457,20 +489,28 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
     trainer, fused = None, False
     B_glob, L, valid_frac = _batch_shape(train_dl)
     lo, hi = shard_slates(B_glob, rank, world)
+    compact = _compact_mode(compact)
+    cg_reason = ""
     if spec is not None:
         if compact is None:
             compact = valid_frac < 0.8
+        if compact == "graph" and world > 1:                      # (the trainer would refuse; the job keeps the fused step)
+            compact, cg_reason = True, "slate-sharded run (%d ranks): the ranks' row buckets differ; compact=True" % world
         try:
             trainer = FusedTrainer(model, spec[0], spec[1], hi - lo, L, lr=spec[2], world_size=world, use_graph=True,
-                                   gradient_clipping_norm=gradient_clipping_norm, compact=bool(compact), gemm=gemm, **spec[3])
+                                   gradient_clipping_norm=gradient_clipping_norm, compact=compact, gemm=gemm, **spec[3])
             fused = True
+            if compact == "graph" and not trainer.compact_graph:
+                cg_reason = ("the slate-resident FC + ListNet step is taken: it reads the padded batch in place" if trainer.fcstep else
+                             "stochastic NeuralNDCG reads the scores of padded slots: the step stays on the padded grid")
         except (NotImplementedError, KeyError) as e:
             reason = "FusedTrainer: %s" % (e,)
     if trainer is None:
         trainer = Trainer(model, loss_func, optimizer, gradient_clipping_norm, world, None)
     last_run.clear()
     last_run.update(engine="fused" if fused else "autograd", compact=bool(trainer.compact) if fused else False, reason=reason,
-                    fcstep=getattr(trainer, "fcstep", False), sampling=getattr(train_dl, "sampling", None))
+                    fcstep=getattr(trainer, "fcstep", False), sampling=getattr(train_dl, "sampling", None),
+                    compact_graph=_compact_graph_stats(trainer), compact_graph_reason=cg_reason)
     log.info("allrank_amd.fit: %s step%s", last_run["engine"], (" (" + reason + ")") if reason else "")
     vs_reason = _packed_blocker(loss_func, fused, reason) if val_scorer_mode in ("packed", "ragged") else ""
     scorers = {} if val_scorer_mode in ("packed", "ragged") and not vs_reason else None
@@ -526,6 +566,7 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
             dist.all_reduce(stats)
         stats = stats.cpu().numpy()
         t_train = time.perf_counter() - t_epoch
+        last_run["compact_graph"] = _compact_graph_stats(trainer)
         n_all = max(stats[1], 1.0)
         train_loss = float(stats[0]) / n_all
         train_metrics, off = {}, 2

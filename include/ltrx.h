@@ -407,7 +407,10 @@ int ltrx_scatter_rows(const float* src, int ld_src, const int32_t* idx, int n, i
  *   ltrx_gather_rows_cu: the same packing of a padded batch src[B', L, ld_src] (valid items first in every slate; slates past
  *       B' must have length 0): dst[r] = src[b*L + j] for r < n, zero for n <= r < rows; idx_out (or NULL) as above.
  *   ltrx_scatter_rows_cu: dst[b*L + j] = src[cu[b] + j] for j < cu[b+1]-cu[b] (and cu[b] + j < rows), 0 in every other slot
- *       of dst[B, L, ld_dst]. */
+ *       of dst[B, L, ld_dst].
+ *   ltrx_zero_rows_cu: x[r, 0 .. cols-1] = 0 for the alignment rows n <= r < rows of a row-major buffer with row stride ld
+ *       (columns cols .. ld-1 and the rows below n untouched; nothing when n >= rows).  16-byte stores where x, ld and cols
+ *       allow, 4-byte stores otherwise.  NULL pointers, B, rows, cols <= 0 or ld < cols: LTRX_EINVAL, nothing is written. */
 int ltrx_assemble_packed(const float* x_items, const float* y_items, const int64_t* offsets, const int64_t* slates,
                          const int32_t* cu_seqlens, int B, int L, int F, int rows, float* x_out, int ld_x, float* y_out,
                          int32_t* idx_out, int64_t* pos_out, ltrx_stream_t stream);
@@ -415,6 +418,7 @@ int ltrx_gather_rows_cu(const float* src, int ld_src, const int32_t* cu_seqlens,
                         int ld_dst, int32_t* idx_out, ltrx_stream_t stream);
 int ltrx_scatter_rows_cu(const float* src, int ld_src, const int32_t* cu_seqlens, int B, int L, int cols, int rows, float* dst,
                          int ld_dst, ltrx_stream_t stream);
+int ltrx_zero_rows_cu(float* x, int ld, int cols, const int32_t* cu_seqlens, int B, int rows, ltrx_stream_t stream);
 
 /* OutputLayer with d_output == 1 (model.py:111-117): scores[m] = <x[m,:], w> + b, and its backward
  * (dx[m,:] = dscores[m] * w; dw = sum_m dscores[m] x[m,:]; db = sum_m dscores[m]). */
