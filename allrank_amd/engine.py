@@ -17,7 +17,8 @@ import warnings
 import torch
 from torch.nn.utils import clip_grad_norm_
 
-from . import kernels as KN, parallel, sharding
+from . import kernels as KN, parallel, rows as RW, sharding
+from .rows import row_bucket, _stage_host, _Stager  # noqa: F401  (their home is allrank_amd/rows.py; imported from here too)
 
 PADDED_Y_VALUE = -1
 
@@ -58,7 +59,8 @@ class Trainer(object):
 
 
 # ------------------------------------------------------------------------------------------------------------------
-# shared by FusedTrainer and FusedScorer: the forward-buffer plan, the batch stager, the forward-graph cache
+# shared by FusedTrainer and FusedScorer: the forward-buffer plan and the forward-graph cache (the row layouts, their batch stager
+# and their movers: allrank_amd/rows.py)
 # ------------------------------------------------------------------------------------------------------------------
 def input_row_plan(F, H, M, gemm, has_input_norm, pad_input):
     """How the rows the first FC projection reads are laid out: ``(stride, K, large)`` for ``F`` input features, a first FC width
@@ -78,13 +80,13 @@ def input_row_plan(F, H, M, gemm, has_input_norm, pad_input):
     return F4, F4, False
 
 
-def _alloc_forward(owner, t, rows, B, L, saved, compact):
+def _alloc_forward(owner, t, rows, B, L, saved, layout):
     """Create on ``owner`` the buffer set that ``FusedTrainer._forward`` of trainer ``t`` runs over (``B`` slates of ``L`` items, up to
     ``rows`` rows), every buffer zero-initialised.  The only place that makes forward buffers, and the list of what ``_forward`` reads
     from a buffer set ``bs``:
-      B, L, compact (rows = the packed valid items, else the padded grid); rows (of THIS pass: kept current by the owner, not here)
+      B, L, layout ("grid", "index" or "cu": allrank_amd/rows.py), saved; rows (of THIS pass: kept current by the owner, not here)
       mask [B, L] u8 key padding (None in the scorer's form: packed rows are all valid keys)
-      cu [B+1], order [B] (views of the owner's ``_stager`` tensor), idx [rows] packed row -> grid slot: compact only, else None
+      cu [B+1], order [B] (views of the owner's ``_stager`` tensor), idx [rows] packed row -> grid slot: the packed layouts, else None
       x_in [rows, F]; x_norm [rows, F], mean_in, rstd_in (input_norm only); fc_out[i].  With t._x_pad (``input_row_plan``: the
       large-tile form, or F % 4 != 0) the rows the first projection reads -- x_in, or x_norm under input_norm (x_in is then dense:
       no GEMM reads it) -- are the ``[:, :F]`` view of a buffer with rows of t._x_stride floats (x_in_buf / x_norm_buf), and x_in_k
@@ -95,7 +97,7 @@ def _alloc_forward(owner, t, rows, B, L, saved, compact):
       layers[i]: wqkv, bqkv, mod, p_*, s_* (the trainer's parameter views and dropout sites; its own dicts also hold gwqkv / gbqkv
       and later rbits / wqkvT), xsum0 (the residual stream entering layer i > 0), xn0, mean0, rstd0, qkv, o, lse, x1, xn1, mean1,
       rstd1, r, and q, k, v (the column views of qkv that the attention launches read);  xsum_f, xf, mean_f, rstd_f (the final norm; xf
-      is None where t.norm_head holds: the fused final norm + score head keeps the normalised rows in registers);  scores_c (compact only), scores_raw [B, L(, n_out)], scores [B, L]
+      is None where t.norm_head holds: the fused final norm + score head keeps the normalised rows in registers);  scores_c (packed layouts only), scores_raw [B, L(, n_out)], scores [B, L]
     ``saved=True``, the trainer's form: the backward reads the activations, so every layer has its own.  ``saved=False``, the scorer's:
     ONE activation set serves every layer -- the residual stream ping-pongs between two buffers (a layer's input is dead once its
     out-projection has added it: xsum0 of layer i = ping[i % 2], xsum_f = ping[N % 2], x_pe = ping[0], which layer 0 reads while
@@ -115,7 +117,10 @@ def _alloc_forward(owner, t, rows, B, L, saved, compact):
         return dict(xn0=ln0[0], mean0=ln0[1], rstd0=ln0[2], xn1=ln1[0], mean1=ln1[1], rstd1=ln1[2], qkv=qkv, q=q, k=k, v=v, o=z(rows, d),
                     lse=z(B, t.h, L), x1=z(rows, d), r=z(rows, t.dff))
 
-    owner.B, owner.L, owner.compact = B, L, compact
+    if layout not in ("grid", "index", "cu"):
+        raise ValueError("layout must be grid, index or cu, got %r" % (layout,))
+    owner.B, owner.L, owner.layout, owner.saved = B, L, layout, bool(saved)
+    compact = layout != "grid"
     owner.mask = torch.zeros((B, L), dtype=torch.uint8, device=dev) if saved else None
     owner._stager = _Stager(dev, B, with_ids=not saved) if compact else None
     owner.cu, owner.order = (owner._stager.cu, owner._stager.order) if compact else (None, None)
@@ -156,49 +161,6 @@ def _alloc_forward(owner, t, rows, B, L, saved, compact):
         owner.scores_c = z(rows) if no == 1 else z(rows, no)
     owner.scores_raw = z(B, L) if no == 1 else z(B, L, no)    # what the loss sees (model.forward)
     owner.scores = owner.scores_raw if no == 1 else z(B, L)   # model.score (sum over the output units)
-
-
-def _stage_host(host, B, lengths, ids=None):
-    """Pure host half of the stager: write ``[ids as int32 pairs, 2B |] cu_seqlens [B+1], stable longest-first order [B]`` of up to
-    ``B`` slate ``lengths`` into the int32 buffer ``host`` (slates past the given ones: length 0, id 0); returns the valid-row count."""
-    o = 2 * B if ids is not None else 0
-    lens = torch.as_tensor(lengths, dtype=torch.int32).reshape(-1)
-    full = torch.zeros(B, dtype=torch.int32)
-    full[:lens.numel()] = lens
-    host[o] = 0
-    torch.cumsum(full, 0, dtype=torch.int32, out=host[o + 1:o + B + 1])
-    host[o + B + 1:o + 2 * B + 1] = torch.argsort(full, descending=True, stable=True)
-    if ids is not None:
-        h64 = host[:o].view(torch.int64)
-        h64.zero_()
-        h64[:lens.numel()] = torch.as_tensor(ids, dtype=torch.int64).reshape(-1)
-    return int(host[o + B])
-
-
-class _Stager(object):
-    """Device staging of one batch -- [slate ids (i64, as int32 pairs) |] cu_seqlens [B+1], launch order [B] in ONE tensor -- filled by
-    one non-blocking upload from a ring of 4 pinned host buffers (a slot is reused after the copy that last used it has completed):
-    only these few words cross PCIe per batch, and nothing syncs."""
-
-    def __init__(self, dev, B, with_ids):
-        self.B, o = B, 2 * B if with_ids else 0
-        self.stage = torch.zeros(o + 2 * B + 1, dtype=torch.int32, device=dev)
-        self.ids = self.stage[:o].view(torch.int64) if with_ids else None
-        self.cu, self.order = self.stage[o:o + B + 1], self.stage[o + B + 1:]
-        self._ring = [(torch.zeros(o + 2 * B + 1, dtype=torch.int32).pin_memory(), torch.cuda.Event()) for _ in range(4)]
-        self._turn = 0
-
-    def upload(self, lengths, ids=None):
-        """``lengths`` (host or device ints, at most B, range-checked by the caller) and, if given, slate ``ids`` -> device; the row count"""
-        host, ev = self._ring[self._turn % len(self._ring)]
-        self._turn += 1
-        ev.synchronize()
-        if lengths.is_cuda:                                   # (a device tensor costs the sync the host lengths are meant to avoid)
-            lengths = lengths.cpu()
-        n = _stage_host(host if ids is not None else host[-(2 * self.B + 1):], self.B, lengths, ids)
-        self.stage.copy_(host, non_blocking=True)
-        ev.record()
-        return n
 
 
 @contextlib.contextmanager
@@ -345,6 +307,10 @@ class FusedTrainer(object):
         cu_seqlens, and scores / d loss/d scores move between the packed rows and the padded [B, L] grid the loss kernels
         work on.  Same loss and gradients as the padded step (padded rows carry no gradient and are masked as keys); the
         row count changes per batch, so this mode runs eagerly (no hipGraph).
+        The buffer set's ``self.layout`` (allrank_amd/rows.py) names the three forms: "grid" (compact=False: the padded B * L rows),
+        "index" (compact=True: rows packed through a host-sized index, ceil32(n) of them) and "cu" (compact="graph", and every
+        FusedScorer: rows packed from cu_seqlens in device memory, ``row_bucket`` of them); ``self.compact`` / ``self.compact_graph``
+        are read off it, and staging, ``_forward`` and ``_body`` decide by it alone.
         compact="graph" (opt-in; ``self.compact`` is True, ``self.compact_graph`` says so): the same packed step at BUCKETED row
         counts, captured and replayed per bucket.  The row count is ``row_bucket(n, ceil32(B * L))``, the scorer's ladder (the
         buffers hold its largest rung), and a captured step is keyed (batch divisor, collectives on?, rows); the two eager
@@ -478,9 +444,9 @@ class FusedTrainer(object):
         self._x_pad = (self._x_stride, self._x_k) != (F0, F0)
         # rows every row buffer holds: the padded grid -- or, for the bucketed rows of compact="graph", the largest rung of the
         # scorer's ladder (every slot valid), as FusedScorer sizes its set
-        self.compact_graph = bool(graph_rows)
-        self.cap = (self.M + 31) // 32 * 32 if self.compact_graph else self.M
-        _alloc_forward(self, self, self.cap, B, L, saved=True, compact=bool(compact))
+        layout = "cu" if graph_rows else "index" if compact else "grid"
+        self.cap = (self.M + 31) // 32 * 32 if layout == "cu" else self.M
+        _alloc_forward(self, self, self.cap, B, L, saved=True, layout=layout)
         self.rows = B * L                                                     # rows the row-wise kernels run over
         self.n_valid = B * L
         self.y_in = torch.zeros((B, L), dtype=torch.float32, device=self.dev)
@@ -533,6 +499,10 @@ class FusedTrainer(object):
             self.fcstep = "collapse"
         if self.fcstep:
             self._init_fc_step(offs)
+
+    # the public facts about variable-length execution, read off the buffer set's layout (allrank_amd/rows.py)
+    compact = property(lambda self: self.layout != "grid", doc="the step runs over the packed valid rows")
+    compact_graph = property(lambda self: self.layout == "cu", doc="... packed from cu_seqlens at bucketed row counts, captured per bucket")
 
     # ---- the named steps of __init__ ---------------------------------------------------------------------------
     def _read_model(self, model, dropout, seed):
@@ -886,11 +856,6 @@ class FusedTrainer(object):
         """dr *= (r > 0) / (1 - p): backward of dropout(relu(z)) given the stored post-dropout activation r"""
         self.LB.check(self.lib.ltrx_relu_bwd(self.LB.ptr(dr), self.LB.ptr(r), self.rows * dr.shape[1], 1.0 / (1.0 - p), self._st()), "relu_bwd")
 
-    def _zero_alignment_rows(self, buf):
-        """buf[cu[B] : rows] = 0, the count read on the device (compact="graph": the launch is the same for every batch of a bucket)"""
-        self.LB.check(self.lib.ltrx_zero_rows_cu(self.LB.ptr(buf), buf.stride(0), buf.shape[1], self.LB.ptr(self.cu), self.B, self.rows,
-                                                 self._st()), "zero_rows_cu")
-
     def saved_activation(self, layer, key):
         """the saved activation ``key`` ("r", "xn0", "xn1", ...) of encoder layer ``layer`` of the LAST step (tests, diagnostics)"""
         return self.layers[layer][key]
@@ -1127,7 +1092,8 @@ class FusedTrainer(object):
         bs = self if bs is None else bs
         P = self.LB.ptr
         lib, M, d, B, L = self.lib, bs.rows, self.d, bs.B, bs.L
-        kpm = None if bs.compact else bs.mask                     # packed rows are all valid keys
+        stream = self._st()                                       # (of the row movers: the pass stays on one stream)
+        kpm = bs.mask if bs.layout == "grid" else None            # packed rows are all valid keys
         W = self.W
         fc = self.model.input_layer
         dp = (lambda p: p) if train else (lambda p: 0.0)          # dropout rate of a site in this pass
@@ -1166,8 +1132,7 @@ class FusedTrainer(object):
             self._lin_fwd(st["xn0"], st["wqkv"], st["bqkv"], st["qkv"], rows=M)
             KN.mha_fwd(lib, self._st(), st["q"], st["k"], st["v"], kpm, B, L, self.h, st["o"], st["lse"], dp(st["p_att"]), st["s_att"],
                        self.drop_step, bs.cu, bs.order, self._mha_mode)
-            if bs is self and self.compact_graph:                 # the attention wrote rows of slates only; the out-projection and its
-                self._zero_alignment_rows(st["o"])                # weight gradient read every row: 0 there, whatever the buffer held
+            RW.zero_attention_tail(bs, lib, stream, st["o"])
             lo = lay.self_attn.linears[3]
             # x1 = x + dropout(attention branch): the residual sum is the out-projection's epilogue (act 3)
             self._lin_fwd(st["o"], W(lo.weight), W(lo.bias), st["x1"], 0, dp(st["p_s0"]), st["s_s0"], res=x, rows=M)
@@ -1187,7 +1152,7 @@ class FusedTrainer(object):
             x = nxt
         out = self.model.output_layer
         no = self.n_out
-        sc_rows = bs.scores_c if bs.compact else bs.scores_raw
+        sc_rows = bs.scores_raw if bs.layout == "grid" else bs.scores_c
         feat = x
         if self.N and not self.norm_head:
             nf = self.enc.norm
@@ -1204,13 +1169,7 @@ class FusedTrainer(object):
             self._lin_fwd(feat, W(out.w_1.weight), W(out.w_1.bias), sc_rows.view(-1, no), rows=M)
         if self.out_act:                                          # OutputLayer activation (model.py:117), in place
             KN.out_act_fwd(lib, self._st(), sc_rows, M * no, self.out_act, sc_rows)
-        if bs is not self or self.compact_graph:                  # scorer, captured packed step: packed scores -> padded grid, padding
-            self.LB.check(lib.ltrx_scatter_rows_cu(P(sc_rows), no, P(bs.cu), B, L, no, M, P(bs.scores_raw), no, self._st()),   # 0, count from cu[B]
-                          "scatter_rows_cu")
-        elif self.compact:                                        # packed scores -> the padded [B, L] grid of the loss kernels
-            self.scores_raw.zero_()
-            self.LB.check(lib.ltrx_scatter_rows(P(self.scores_c), no, P(self.idx), self.n_valid, no, P(self.scores_raw), no, self._st()),
-                          "scatter_rows")
+        RW.scores_to_grid(bs, lib, stream, sc_rows, no)           # packed scores -> the padded [B, L] grid of the loss kernels
         if no > 1:
             torch.sum(bs.scores_raw, dim=-1, out=bs.scores)       # model.score (model.py:127)
         return feat, sc_rows
@@ -1218,8 +1177,9 @@ class FusedTrainer(object):
     def _body(self):
         P = self.LB.ptr
         lib, M, d, B, L = self.lib, self.rows, self.d, self.B, self.L
+        stream = self._st()                                       # (of the row movers)
         W, G = self.W, self.G
-        kpm = None if self.compact else self.mask
+        kpm = self.mask if self.layout == "grid" else None
         fc = self.model.input_layer
         out = self.model.output_layer
         no = self.n_out
@@ -1232,13 +1192,7 @@ class FusedTrainer(object):
         # ---------------- backward ----------------
         ga, gb = self.d_a, self.d_b
         spare = self.d_c if (self.N and self.ln_in_wgrad) else None
-        if self.compact_graph:                                    # d loss / d scores of the packed rows, counted from cu_seqlens
-            KN.gather_rows_cu(lib, self._st(), dsc, self.cu, B, L, no, M, self.dsc_c, None, "gather_rows_cu(d scores)")
-            dsc = self.dsc_c
-        elif self.compact:                                        # d loss / d scores of the packed rows (alignment rows: 0)
-            self.LB.check(lib.ltrx_gather_rows(P(dsc), no, P(self.idx), self.n_valid, M, no, P(self.dsc_c), no, self._st()),
-                          "gather_rows")
-            dsc = self.dsc_c
+        dsc = RW.grid_to_rows(self, lib, stream, dsc, no)         # d loss / d scores of the packed rows (alignment rows: 0)
         if self.out_act:                                          # d loss / d pre-activation = d loss / d score * act'(score)
             KN.out_act_bwd(lib, self._st(), dsc, sc_rows, M * no, self.out_act, dsc)
         if self.norm_head:
@@ -1296,10 +1250,7 @@ class FusedTrainer(object):
                 self._lin_dgrad(db, W(lo.weight), self._wT.get(id(lo.weight)), self.d_o)
                 KN.mha_bwd(lib, self._st(), st["q"], st["k"], st["v"], kpm, st["o"], self.d_o, st["lse"], B, L, self.h, self.dq, self.dk,
                            self.dv, st["p_att"], st["s_att"], self.drop_step, self.cu, self.order, self._mha_mode, self.ws_mha)
-                if self.compact_graph:                             # alignment rows belong to no slate: no gradient
-                    self._zero_alignment_rows(dqkv)
-                elif self.compact and M > self.n_valid:
-                    dqkv[self.n_valid:M].zero_()
+                RW.zero_gradient_tail(self, lib, stream, dqkv)
                 self._lin_wgrad(dqkv, st["xn0"], st["gwqkv"], st["gbqkv"], defer=True)
                 self._lin_dgrad(dqkv, st["wqkv"], st.get("wqkvT"), self.tmp_d)
                 ln0 = (self.tmp_d, st["xin"], W(n0.a_2), st["mean0"], st["rstd0"], ds, outb, G(n0.a_2), G(n0.b_2))
@@ -1407,8 +1358,7 @@ class FusedTrainer(object):
         if lengths is not None:
             # only the B+1 prefix sums and the launch order cross PCIe (_Stager); the packed-row index is derived on the device
             n = self._stager.upload(torch.as_tensor(lengths, dtype=torch.int32).reshape(B).clamp(min=0, max=L))
-            self.LB.check(self.lib.ltrx_packed_row_index(self.LB.ptr(self.cu), B, L, n, self.LB.ptr(self.idx), self._st()),
-                          "packed_row_index")
+            KN.packed_row_index(self.lib, self._st(), self.cu, B, L, n, self.idx)
         else:
             valid = (self.mask == 0)
             cnt = valid.sum(1)
@@ -1425,10 +1375,7 @@ class FusedTrainer(object):
         # alignment rows (zero input, zero gradient) keep the row count a multiple of 32; never more rows than the buffers hold
         # (a tiny batch, B * L < 32: the old max(32, ...) ran 32 rows over M-row buffers -- ADVICE r4)
         self.rows = min(self.M, max(32, (n + 31) // 32 * 32))
-        F = self.x_in.shape[1]
-        self.LB.check(self.lib.ltrx_gather_rows(self.LB.ptr(xb), F, self.LB.ptr(self.idx), n, self.rows, F, self.LB.ptr(self.x_in),
-                                                self.x_in.stride(0),
-                                                self._st()), "gather_rows")
+        KN.gather_rows(self.lib, self._st(), xb, self.idx, n, self.rows, self.x_in.shape[1], self.x_in)
 
     def bucket_of(self, counts):
         """compact="graph": the rows a step over batches of ``counts`` valid items runs -- ``row_bucket``, the scorer's ladder,
@@ -1436,33 +1383,19 @@ class FusedTrainer(object):
         return [row_bucket(max(int(n), 1), self.cap) for n in counts]
 
     def _pack_cu(self, xb, indices, lengths):
-        """compact="graph" staging, outside any capture: cu_seqlens and the launch order of this batch, the row bucket, and the valid
-        rows of ``xb`` (and of the positions ``indices``) gathered by ltrx_gather_rows_cu, which also writes the packed-row index
-        and zero-fills the alignment rows.  Host ``lengths``: no sync.  Without them the slates are counted on the device -- one sync,
-        which also checks that the valid items of every slate come first (what the cu_seqlens kernels assume)."""
-        B, L = self.B, self.L
-        if lengths is not None:
-            n = self._stager.upload(torch.as_tensor(lengths, dtype=torch.int32).reshape(B).clamp(min=0, max=L))
-        else:
-            valid = (self.mask == 0)
-            cnt = valid.sum(1, dtype=torch.int32)
-            prefix = (valid == (torch.arange(L, device=self.dev)[None, :] < cnt[:, None])).all()
-            torch.cumsum(cnt, 0, dtype=torch.int32, out=self.cu[1:])
-            self.order.copy_(torch.argsort(cnt, descending=True, stable=True))
-            n, ok = (int(v) for v in torch.stack([self.cu[B], prefix.to(torch.int32)]).tolist())     # (host sync: n picks the bucket)
-            if not ok:
+        """compact="graph" staging (``rows.stage_cu``, outside any capture).  Host ``lengths``: no sync.  Without them the slates are
+        counted on the device -- one sync, which also checks that the valid items of every slate come first (what the cu_seqlens
+        kernels assume)."""
+        def check(got):
+            if not got.get("prefix_ok", 1):
                 raise ValueError("FusedTrainer(compact=\"graph\"): a slate has padding between its valid items -- the captured step packs "
                                  "from cu_seqlens, which needs the valid items first in every slate (compact=True takes such a batch)")
-        if n == 0:
-            raise ValueError("FusedTrainer(compact=\"graph\"): the batch has no valid item")
-        self.n_valid = n
-        self.rows = row_bucket(max(n, 1), self.cap)               # alignment rows n .. rows-1: zero input, no slate, no gradient
-        F = self.x_in.shape[1]
-        KN.gather_rows_cu(self.lib, self._st(), xb, self.cu, B, L, F, self.rows, self.x_in, self.idx, "gather_rows_cu(x)")
-        if self.pos is not None:                                  # int64 positions move as pairs of 32-bit words
-            ib = indices.to(self.dev, torch.int64).contiguous()
-            KN.gather_rows_cu(self.lib, self._st(), ib, self.cu, B, L, 2, self.rows, self.idx_rows, None, "gather_rows_cu(indices)")
-            self.idx_rows[n:self.rows].fill_(-1)                  # alignment rows -> the padding position
+            if got["n"] == 0:
+                raise ValueError("FusedTrainer(compact=\"graph\"): the batch has no valid item")
+        if lengths is not None:
+            lengths = torch.as_tensor(lengths, dtype=torch.int32).reshape(self.B).clamp(min=0, max=self.L)
+        RW.stage_cu(self, self.lib, self._st(), xb, indices if self.pos is not None else None, lengths,
+                    valid=None if lengths is not None else self.mask == 0, want=("n", "prefix_ok"), check=check)
 
     def _reattach(self):
         """the module's parameters / gradients must alias the flat buffers (state_dict(), score() and external readers of
@@ -1482,28 +1415,23 @@ class FusedTrainer(object):
                   and (self.compact or (xb.dtype == torch.float32 and xb.is_contiguous() and xb.is_cuda
                                         and xb.numel() == self.x_in.numel())))
         if direct:                                                # x, y and the padding mask in one launch
-            P = self.LB.ptr
-            self.LB.check(self.lib.ltrx_ingest_batch(None if self.compact else P(xb), P(yb), 0 if self.compact else xb.numel(), self.M,
-                                                     self.x_in.shape[1], self.x_in.stride(0), float(PADDED_Y_VALUE),
-                                                     None if self.compact else P(self.x_in), P(self.y_in), P(self.mask), self._st()),
-                          "ingest_batch")
+            KN.ingest_batch(self.lib, self._st(), None if self.compact else xb, yb, PADDED_Y_VALUE, self.x_in, self.y_in, self.mask)
         else:
             self.y_in.copy_(yb)
             self.mask.copy_(yb == PADDED_Y_VALUE)
         if self.pos is not None and indices is None:
             raise ValueError("FusedTrainer: the model has a positional encoding, %s() needs `indices`" % who)
-        if self.compact_graph:
+        if self.layout == "cu":                                   # (the positions move with the features)
             self._pack_cu(xb.to(self.dev, torch.float32).reshape(self.M, -1).contiguous(), indices, lengths)
-            return
-        if self.compact:
+        elif self.layout == "index":
             self._pack(xb.reshape(self.M, -1).contiguous(), lengths)
-        elif not direct:
-            self.x_in.copy_(xb.reshape(self.M, -1))
-        if self.pos is not None:
-            if self.compact:                                      # rank of every packed row; alignment rows -> padding row
+            if self.pos is not None:                              # rank of every packed row; alignment rows -> padding row
                 self.idx_rows.fill_(-1)
                 self.idx_rows[:self.n_valid] = indices.reshape(-1)[self.idx[:self.n_valid].long()]
-            else:
+        else:
+            if not direct:
+                self.x_in.copy_(xb.reshape(self.M, -1))
+            if self.pos is not None:
                 self.idx_rows.copy_(indices.reshape(-1))
 
     def step(self, xb, yb, indices=None, global_batch=None, lengths=None):
@@ -1519,7 +1447,7 @@ class FusedTrainer(object):
         key = self._key(global_batch)
         self._divisor = key[0]
         self._stage_batch(xb, yb, indices, lengths, "step")
-        if self.compact_graph:                                    # the staging picked the row bucket: the third part of the key
+        if self.layout == "cu":                                   # the staging picked the row bucket: the third part of the key
             key = self._key(global_batch)
             self.bucket_counts[self.rows] += 1
         if self.use_graph:
@@ -1695,7 +1623,7 @@ class FusedTrainer(object):
         self._reattach()
         self._sync_weights()
         self._stage_batch(xb, yb, indices, lengths, "score")
-        if self.use_graph and not self.compact_graph:             # (compact="graph": the row count varies, the one-key cache does not
+        if self.use_graph and self.layout != "cu":                # (compact="graph": the row count varies, the one-key cache does not
             #                                                        fit; the forward runs eagerly -- FusedScorer is the captured one)
             self._fwd_graphs.run(0, lambda: self._forward(False))
         else:
@@ -1705,16 +1633,6 @@ class FusedTrainer(object):
     def scorer(self, B, L, use_graph=True, max_graphs=8):
         """a FusedScorer for validation batches of ``B`` slates padded to ``L`` items (any L up to LTRX_MAX_METRIC_SLATE_LEN)"""
         return FusedScorer(self, B, L, use_graph=use_graph, max_graphs=max_graphs)
-
-
-def row_bucket(n, cap=None):
-    """The rung of the scorer's row ladder that holds ``n`` packed rows: 32, 64, ..., 256, then steps of max(32, rung // 8 rounded
-    down to a multiple of 32) -- every rung a multiple of 32, each at most 1/8 above the one below from 256 on, so a batch runs at
-    most 31 rows (below 256) or 1/8 of its rows (above) of alignment padding.  ``cap`` (a multiple of 32): the largest rung."""
-    b = 32
-    while b < n:
-        b += max(32, (b // 8) // 32 * 32)
-    return b if cap is None else min(b, cap)
 
 
 class FusedScorer(object):
@@ -1750,7 +1668,7 @@ class FusedScorer(object):
             raise ValueError("FusedScorer: slate length %d above LTRX_MAX_METRIC_SLATE_LEN = %d" % (L, LB.MAX_METRIC_SLATE_LEN))
         self.t, self.LB = t, LB
         self.cap = (B * L + 31) // 32 * 32                 # the largest rung: every slot of the batch valid
-        _alloc_forward(self, t, self.cap, B, L, saved=False, compact=True)
+        _alloc_forward(self, t, self.cap, B, L, saved=False, layout="cu")
         self.ids = self._stager.ids
         self.rows, self.n_valid = 32, 0
         self.y = torch.full((B, L), float(PADDED_Y_VALUE), dtype=torch.float32, device=t.dev)
@@ -1767,9 +1685,8 @@ class FusedScorer(object):
         self._graphs = self._fwd_graphs.graphs             # row bucket -> captured forward, least recently used first
         self.last_mode, self.evictions = None, 0           # "eager" / "capture" / "replay" of the last call; buckets evicted so far
 
-    def _upload(self, ids, lengths):
-        """host lengths (and slate ids) of one batch -> cu_seqlens, longest-first launch order (and ids) on the device through the
-        pinned ring; returns the valid-row count"""
+    def _host_lengths(self, lengths):
+        """host lengths of one batch, range-checked, as the int32 tensor the stager uploads; keeps the batch's ``max_len``"""
         lens = torch.as_tensor(lengths, dtype=torch.int32).reshape(-1)
         n = int(lens.numel())
         if n > self.B:
@@ -1777,11 +1694,7 @@ class FusedScorer(object):
         if n and int(lens.max()) > self.L:
             raise ValueError("FusedScorer: a slate of %d items in a scorer for slate length %d" % (int(lens.max()), self.L))
         self.max_len = max(int(lens.max()), 0) if n else 0
-        return self._stager.upload(lens.clamp(min=0), None if ids is None else torch.as_tensor(ids, dtype=torch.int64).cpu())
-
-    def _set_rows(self, n):
-        self.n_valid = n
-        self.rows = row_bucket(max(n, 1), self.cap)
+        return lens.clamp(min=0)
 
     def _sync(self):
         self.t._reattach()
@@ -1791,8 +1704,7 @@ class FusedScorer(object):
         """scores of the slates ``ids`` (host int64, at most B) of the resident set ``slates`` (a data.DeviceSlates) padded to L;
         ``lengths``: their item counts (host; every one <= L -- the padding branch of FixLength).  Also fills ``self.y`` with the
         padded labels.  Returns ``scores_raw``."""
-        P, LB = self.LB.ptr, self.LB
-        t = self.t
+        t, LB = self.t, self.LB
         ids_h = torch.as_tensor(ids, dtype=torch.int64).cpu().reshape(-1)
         if ids_h.numel() and (int(ids_h.min()) < 0 or int(ids_h.max()) >= slates.n_slates):
             raise ValueError("FusedScorer.run_resident: slate id outside the set")
@@ -1800,10 +1712,9 @@ class FusedScorer(object):
             raise ValueError("FusedScorer.run_resident: %d features, the model takes %d" % (slates.n_features, t.fc_sizes[0]))
         LB.require_device(slates.x_items)
         self._sync()
-        self._set_rows(self._upload(ids_h, lengths))
-        LB.check(t.lib.ltrx_assemble_packed(P(slates.x_items), P(slates.y_items), P(slates.offsets), P(self.ids), P(self.cu), self.B,
-                                            self.L, slates.n_features, self.rows, P(self.x_in), self.x_in.stride(0), P(self.y),
-                                            P(self.idx), P(self.idx_rows) if t.pos is not None else None, t._st()), "assemble_packed")
+        RW.set_rows(self, self._stager.upload(self._host_lengths(lengths), ids_h))     # cu_seqlens, launch order, ids: no host sync
+        KN.assemble_packed(t.lib, t._st(), slates.x_items, slates.y_items, slates.offsets, self.ids, self.cu, self.B, self.L, self.rows,
+                           self.x_in, self.y, self.idx, self.idx_rows if t.pos is not None else None)
         self._run()
         return self.scores_raw
 
@@ -1820,24 +1731,12 @@ class FusedScorer(object):
         xb = xb.to(t.dev, torch.float32).contiguous()
         yb = yb.to(t.dev, torch.float32)
         self._sync()
-        if lengths is not None:
-            n = self._upload(None, lengths)
-        else:
-            full = torch.zeros(B, dtype=torch.int32, device=t.dev)
-            full[:n_sl] = (yb != PADDED_Y_VALUE).sum(1, dtype=torch.int32)
-            self.cu[0] = 0
-            torch.cumsum(full, 0, dtype=torch.int32, out=self.cu[1:])
-            self.order.copy_(torch.argsort(full, descending=True, stable=True))
-            n, self.max_len = (int(v) for v in torch.stack([self.cu[B], full.max()]).tolist())     # (host sync: the row count picks the bucket)
-        self._set_rows(n)
         self.y[:n_sl].copy_(yb)
         self.y[n_sl:].fill_(float(PADDED_Y_VALUE))
-        F = int(xb.shape[2])
-        KN.gather_rows_cu(t.lib, t._st(), xb, self.cu, B, L, F, self.rows, self.x_in, self.idx, "gather_rows_cu(x)")
-        if t.pos is not None:                              # int64 positions move as pairs of 32-bit words
-            ib = indices.to(t.dev, torch.int64).contiguous()
-            KN.gather_rows_cu(t.lib, t._st(), ib, self.cu, B, L, 2, self.rows, self.idx_rows, None, "gather_rows_cu(indices)")
-            self.idx_rows[n:self.rows].fill_(-1)           # alignment rows -> the padding position
+        lens = self._host_lengths(lengths) if lengths is not None else None
+        got = RW.stage_cu(self, t.lib, t._st(), xb, indices if t.pos is not None else None, lens,
+                          valid=None if lens is not None else yb != PADDED_Y_VALUE, want=("n", "max_len"))
+        self.max_len = got.get("max_len", self.max_len)    # (host lengths: _host_lengths has set it)
         self._run()
         return self.scores_raw
 

@@ -232,12 +232,18 @@ def _my_block(batch, loader, rank, world):
     return xb, yb, idx, n_glob, (batch if pre else None)
 
 
-def _host_lengths(batch, trainer, real, pre, world):
-    """valid items per slate of this rank's block as HOST integers, topped up to the trainer's batch -- what variable-length
-    execution needs to size its launches without a device round trip (FusedTrainer._pack).  A DeviceLoader knows them (the slate
-    lengths of the resident set); any other loader: None (the step counts the valid items on the device, one host sync)."""
+def _host_lengths(batch, real, pre, world, trainer=None):
+    """valid items per slate of this rank's block as HOST integers -- what variable-length execution needs to size its launches
+    without a device round trip (allrank_amd/rows.py).  A DeviceLoader knows them (the slate lengths of the resident set), and they
+    are usable where they are those of this rank's ``real`` slates; any other loader: None (the valid items are counted on the
+    device, one host sync).  ``trainer``: for its step or ``score()`` -- only where it runs packed rows, topped up to its batch;
+    None: no top-up (a FusedScorer takes a short batch as it is)."""
     lens = getattr(batch, "lengths", None)
-    if lens is None or not trainer.compact or not (pre is not None or world == 1) or int(lens.numel()) != real:
+    if lens is None or not (pre is not None or world == 1) or int(lens.numel()) != real:
+        return None
+    if trainer is None:
+        return lens
+    if not trainer.compact:
         return None
     return torch.cat([lens, lens.new_zeros(trainer.B - real)]) if real < trainer.B else lens
 
@@ -353,13 +359,12 @@ def _evaluate(model, loss_func, dl, device, metrics, trainer=None, world=1, rank
                 n = int(xb.shape[0])
                 if scorers is not None and int(xb.shape[1]) <= LB.MAX_METRIC_SLATE_LEN:
                     scorer = _val_scorer(scorers, trainer, n, int(xb.shape[1]))
-                    lens = getattr(batch, "lengths", None) if (pre is not None or world == 1) else None
-                    scorer.run(xb, yb, idx, lengths=lens if lens is not None and int(lens.numel()) == n else None)
+                    scorer.run(xb, yb, idx, lengths=_host_lengths(batch, n, pre, world))
                     sc, out, yl = scorer.scores[:n], scorer.scores_raw[:max(n, 1)], scorer.y[:max(n, 1)]
                     pk = scorer
                 elif trainer is not None and scorers is None and n <= trainer.B and tuple(xb.shape[1:2]) == (trainer.L,):
                     xs, ys, ids = _pad_batch(xb, yb, idx, trainer.B)
-                    sc = trainer.score(xs, ys, ids, lengths=_host_lengths(batch, trainer, n, pre, world))[:n]
+                    sc = trainer.score(xs, ys, ids, lengths=_host_lengths(batch, n, pre, world, trainer))[:n]
                     # (an empty shard of a short last batch still enters the loss -- its normaliser all-reduce is a collective -- with
                     #  one fully padded slate: value 0, count 0)
                     out, yl = trainer.scores_raw[:max(n, 1)], ys[:max(n, 1)]
@@ -540,7 +545,7 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
             real = int(xb.shape[0])
             if fused:
                 xs, ys, ids = _pad_batch(xb, yb, idx, trainer.B)
-                loss = trainer.step(xs, ys, ids, global_batch=real_glob, lengths=_host_lengths(batch, trainer, real, pre, world))
+                loss = trainer.step(xs, ys, ids, global_batch=real_glob, lengths=_host_lengths(batch, real, pre, world, trainer))
                 scores, labels = trainer.scores[:real], trainer.y_cur[:real]
             else:
                 if real == 0:

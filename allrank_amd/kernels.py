@@ -1,7 +1,9 @@
 """The one Python statement of each scoring-model kernel call of libltrx.so (include/ltrx.h): GEMMs, attention, LayerNorm, score
-head, output activation, weight images and the cu_seqlens packer.  The autograd bindings (allrank_amd/ops.py) and the explicit
-training step (allrank_amd/engine.py) both launch through these functions, as the plugin losses and ``FusedLoss`` launch through
-the ``_launch_*`` functions of allrank_amd/losses.
+head, output activation, weight images and the packing calls -- batch ingest, the index layout's ``gather_rows`` / ``scatter_rows`` /
+``packed_row_index``, the cu_seqlens layout's ``gather_rows_cu`` / ``scatter_rows_cu`` / ``zero_rows_cu`` / ``assemble_packed``.  The
+autograd bindings (allrank_amd/ops.py), the explicit training step (allrank_amd/engine.py) and the row movers (allrank_amd/rows.py)
+launch through these functions, as the plugin losses and ``FusedLoss`` launch through the ``_launch_*`` functions of
+allrank_amd/losses.
 
 A launcher makes exactly ONE ``ltrx_*`` call on the tensors it is handed.  Shapes, row strides and the head width are read from the
 tensors (an operand may be a column-slice view of a wider buffer: its ``data_ptr()`` and ``stride`` say where it lives), so no caller
@@ -104,10 +106,59 @@ def out_act_bwd(lib, st, dy, y, n, kind, dz, what="out_act_bwd"):
     check(lib.ltrx_out_act_bwd(P(dy), P(y), n, kind, P(dz), st), what)
 
 
-# ---- weight images, the cu_seqlens packer ----------------------------------------------------------------------------
+# ---- weight images ---------------------------------------------------------------------------------------------------
 def split_image(lib, st, src, dst, what="split_image"):
     """dst = the pre-split bf16 hi / lo image of every float of ``src`` (same offsets)"""
     check(lib.ltrx_split_image(P(src), P(dst), src.numel(), st), what)
+
+
+# ---- packing: batches into the step's buffers, values between the packed rows and the padded [B, L] grid -----------------
+def _ld(t, cols):
+    """row stride of ``t`` read as rows of ``cols`` floats: a [rows, cols] matrix -- a column slice of a wider buffer included -- says
+    its own; any other shape ([B, L] scores of one column, [B, L, cols], a vector of one column) is a dense grid of such rows"""
+    return t.stride(0) if t.dim() == 2 and t.shape[1] == cols else cols
+
+
+def ingest_batch(lib, st, x, y, pad_value, x_dst, y_dst, mask_dst):
+    """y_dst = y, mask_dst = (y == pad_value) and the rows of ``x`` into the rows of ``x_dst`` (F columns each, its own row stride) in
+    one launch.  ``x`` None (the packed layouts gather the features themselves): labels and mask only -- ``x_dst`` then still
+    states the row shape, and nothing is written to it."""
+    check(lib.ltrx_ingest_batch(P(x), P(y), 0 if x is None else x.numel(), y.numel(), x_dst.shape[1], x_dst.stride(0), float(pad_value),
+                                None if x is None else P(x_dst), P(y_dst), P(mask_dst), st), "ingest_batch")
+
+
+def packed_row_index(lib, st, cu, B, L, n, idx):
+    """idx[r] = b * L + (r - cu[b]) for packed row r < n of slate b (valid items first in every slate)"""
+    check(lib.ltrx_packed_row_index(P(cu), B, L, n, P(idx), st), "packed_row_index")
+
+
+def gather_rows(lib, st, src, idx, n, n_pad, cols, dst, what="gather_rows"):
+    """dst[r] = row idx[r] of ``src`` for r < n, rows n .. n_pad-1 of ``dst`` zero (``cols`` floats per row; strides: ``_ld``)"""
+    check(lib.ltrx_gather_rows(P(src), _ld(src, cols), P(idx), n, n_pad, cols, P(dst), _ld(dst, cols), st), what)
+
+
+def scatter_rows(lib, st, src, idx, n, cols, dst):
+    """row idx[r] of ``dst`` = src[r] for r < n (the inverse of ``gather_rows``; the other rows of ``dst`` stay)"""
+    check(lib.ltrx_scatter_rows(P(src), _ld(src, cols), P(idx), n, cols, P(dst), _ld(dst, cols), st), "scatter_rows")
+
+
+def assemble_packed(lib, st, x_items, y_items, offsets, slates, cu, B, L, rows, x_out, y_out, idx_out, pos_out=None):
+    """the slates ``slates`` (device int64 ids) of a resident CSR set straight into packed rows: features into ``x_out`` [rows, F] (a
+    view with its own row stride; alignment rows 0), padded labels into ``y_out`` [B, L], the packed-row index, and -- ``pos_out`` --
+    the int64 position of every row (alignment rows: -1)"""
+    check(lib.ltrx_assemble_packed(P(x_items), P(y_items), P(offsets), P(slates), P(cu), B, L, x_out.shape[1], rows, P(x_out),
+                                   x_out.stride(0), P(y_out), P(idx_out), P(pos_out), st), "assemble_packed")
+
+
+def scatter_rows_cu(lib, st, src, cu, B, L, cols, rows, dst):
+    """the packed rows ``src`` -> the padded grid ``dst`` [B, L] of ``cols`` floats per item, 0 on padded slots; the valid count is
+    read from the device ``cu``"""
+    check(lib.ltrx_scatter_rows_cu(P(src), _ld(src, cols), P(cu), B, L, cols, rows, P(dst), _ld(dst, cols), st), "scatter_rows_cu")
+
+
+def zero_rows_cu(lib, st, x, cu, B, rows):
+    """x[cu[B] : rows] = 0, the count read on the device (the launch is the same for every batch of a row bucket)"""
+    check(lib.ltrx_zero_rows_cu(P(x), x.stride(0), x.shape[1], P(cu), B, rows, st), "zero_rows_cu")
 
 
 def gather_rows_cu(lib, st, src, cu, B, L, cols, rows, dst, idx_out=None, what="gather_rows_cu"):

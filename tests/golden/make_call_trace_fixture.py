@@ -1,11 +1,14 @@
 """Record which libltrx calls the package makes, and what they compute, over a set of small cases (needs the MI355X).
 
-    python tests/golden/make_call_trace_fixture.py [--out FILE] [--commit HASH]
+    python tests/golden/make_call_trace_fixture.py [--set calls|rows] [--out FILE] [--commit HASH]
 
-Writes tests/golden/call_trace_parent.json.  It was run ONCE, at the commit named in the file ("commit"), before the GEMM, attention,
-LayerNorm and head calls of allrank_amd/ops.py and allrank_amd/engine.py moved into the launchers of allrank_amd/kernels.py;
+Two case sets, one file each, each run ONCE at the commit named in its file ("commit"):
+  calls  tests/golden/call_trace_parent.json: before the GEMM, attention, LayerNorm and head calls of allrank_amd/ops.py and
+         allrank_amd/engine.py moved into the launchers of allrank_amd/kernels.py;
+  rows   tests/golden/call_trace_rows_parent.json: the three row layouts (padded grid, index-packed, cu_seqlens-packed) before their
+         staging and row movers moved into allrank_amd/rows.py and the packing launchers of allrank_amd/kernels.py.
 tests/test_gpu_call_trace.py runs the same cases at every later commit and holds them to the recorded calls and results exactly.
-Re-running it at a later commit only re-records that commit against itself.
+Re-running a set at a later commit only re-records that commit against itself.
 
 Only public entry points are used (FusedTrainer, FusedScorer, allrank_amd.ops).  The object ``allrank_amd._lib.lib()`` caches is
 replaced by a proxy before anything is constructed; while a case records, the proxy logs every call as ``[name, [arguments]]``:
@@ -33,6 +36,7 @@ if ROOT not in sys.path:
 
 DEV = "cuda:0"
 FIXTURE = os.path.join(HERE, "call_trace_parent.json")
+ROWS_FIXTURE = os.path.join(HERE, "call_trace_rows_parent.json")
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -153,18 +157,47 @@ def _score(proxy):
     return trace, dict(scores=_sha(sc))
 
 
-def _scorer(proxy):
+SCORER_LENS = [90, 1, 44, 0, 59]
+
+
+def _pe_trainer():
+    """the SMALL encoder with a fixed positional encoding, one step taken"""
     from allrank_amd.engine import FusedTrainer
     ft = FusedTrainer(_model(pe=dict(strategy="fixed", max_indices=100), **SMALL), "listNet", {}, 5, 70, use_graph=False, seed=1234)
     xt, yt, it, _ = _batch(SMALL_LENS, 70, 20, 3)
     ft.step(xt, yt, it)
-    sc = ft.scorer(5, 90, use_graph=False)
-    x, y, idx, hl = _batch([90, 1, 44, 0, 59], 90, 20, 4)
+    return ft
+
+
+def _packed_digests(sc, raw):
+    ps, py, cu, order, max_len = sc.packed()
+    return dict(scores=_sha(raw), packed_scores=_sha(ps), packed_labels=_sha(py), cu=_sha(cu), order=_sha(order))
+
+
+def _scorer(proxy, lens=SCORER_LENS, host_lengths=True):
+    sc = _pe_trainer().scorer(5, 90, use_graph=False)
+    x, y, idx, hl = _batch(lens, 90, 20, 4)
     trace = []
     with _recording(proxy, trace):
-        raw = sc.run(x, y, idx, lengths=hl)
-        ps, py, cu, order, max_len = sc.packed()
-    return trace, dict(scores=_sha(raw), packed_scores=_sha(ps), packed_labels=_sha(py), cu=_sha(cu), order=_sha(order))
+        raw = sc.run(x, y, idx, lengths=hl if host_lengths else None)
+        dig = _packed_digests(sc, raw)
+    return trace, dig
+
+
+def _scorer_resident(proxy):
+    from allrank_amd.data import DeviceSlates
+    lens = [9, 1, 30, 0 + 1, 17, 30]
+    rng = np.random.default_rng(6)
+    X = rng.standard_normal((sum(lens), 20)).astype(np.float32)
+    y = rng.integers(0, 5, sum(lens)).astype(np.float32)
+    ds = DeviceSlates(X, y, np.repeat(np.arange(len(lens)), lens), device=DEV)
+    sc = _pe_trainer().scorer(4, 30, use_graph=False)
+    ids = [5, 0, 2]
+    trace = []
+    with _recording(proxy, trace):
+        raw = sc.run_resident(ds, torch.tensor(ids, dtype=torch.int64), torch.tensor([lens[i] for i in ids], dtype=torch.int32))
+        dig = dict(_packed_digests(sc, raw), y=_sha(sc.y))
+    return trace, dig
 
 
 def _ops(fn):
@@ -241,16 +274,33 @@ def cases():
     return out
 
 
+def rows_cases():
+    """the second set: the cu_seqlens layout of the trainer (compact="graph") and of the scorer, the index layout's positions"""
+    pe = dict(SMALL, pe=dict(strategy="fixed", max_indices=100))
+    return {
+        "compact_graph_host_lengths": lambda p: _train(p, SMALL, "listNet", {}, SMALL_LENS, 70, host_lengths=True, compact="graph"),
+        "compact_graph_device_count": lambda p: _train(p, SMALL, "listNet", {}, SMALL_LENS, 70, compact="graph"),
+        "compact_graph_pe": lambda p: _train(p, pe, "listNet", {}, SMALL_LENS, 70, use_idx=True, host_lengths=True, compact="graph"),
+        "compact_index_pe": lambda p: _train(p, pe, "listNet", {}, SMALL_LENS, 70, use_idx=True, host_lengths=True, compact=True),
+        "scorer_run_device_count": lambda p: _scorer(p, host_lengths=False),
+        "scorer_run_short_batch": lambda p: _scorer(p, lens=SCORER_LENS[:3]),
+        "scorer_run_resident": _scorer_resident,
+    }
+
+
+SETS = {"calls": (FIXTURE, cases), "rows": (ROWS_FIXTURE, rows_cases)}
+
+
 def run_case(proxy, name):
-    trace, dig = cases()[name](proxy)
+    trace, dig = dict(cases(), **rows_cases())[name](proxy)
     torch.cuda.synchronize()
     return trace, dig
 
 
-def record():
+def record(names):
     rec = {}
     with proxied() as proxy:
-        for name in cases():
+        for name in names:
             (t1, d1), (t2, d2) = run_case(proxy, name), run_case(proxy, name)
             assert t1 == t2, "%s: the two runs made different calls" % name
             assert t1, "%s: no call recorded" % name
@@ -263,19 +313,22 @@ def record():
 def main():
     import argparse
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=FIXTURE)
+    ap.add_argument("--set", default="calls", choices=sorted(SETS), help="which case set to record")
+    ap.add_argument("--out", default=None, help="(default: the set's own file)")
     ap.add_argument("--commit", default=None, help="the checked-out commit (default: asked of git)")
     args = ap.parse_args()
     commit = args.commit or subprocess.check_output(["git", "-C", ROOT, "rev-parse", "HEAD"]).decode().strip()
-    rec = record()
-    with open(args.out, "w") as fh:                           # one call per line: a changed argument is a one-line diff
+    path, names = SETS[args.set]
+    out = args.out or path
+    rec = record(names())
+    with open(out, "w") as fh:                           # one call per line: a changed argument is a one-line diff
         fh.write('{"commit": %s,\n "cases": {' % json.dumps(commit))
         for i, (name, c) in enumerate(rec.items()):
             fh.write('%s\n  %s: {"digests": %s,\n   "unstable": %s,\n   "trace": [\n    %s\n   ]}'
                      % ("," if i else "", json.dumps(name), json.dumps(c["digests"], sort_keys=True), json.dumps(c["unstable"]),
                         ",\n    ".join(json.dumps(call) for call in c["trace"])))
         fh.write("\n }\n}\n")
-    print("wrote %s: %d cases, %d calls" % (args.out, len(rec), sum(len(c["trace"]) for c in rec.values())))
+    print("wrote %s: %d cases, %d calls" % (out, len(rec), sum(len(c["trace"]) for c in rec.values())))
 
 
 if __name__ == "__main__":

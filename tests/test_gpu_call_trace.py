@@ -5,7 +5,12 @@ tests/golden/call_trace_parent.json was recorded by tests/golden/make_call_trace
 named in the file): per case the trace of every library call -- name, integers and floats as passed, pointers as NULL or not -- and
 SHA-256 digests of losses, gradients, parameters and scores that two runs at that commit agreed on bit for bit.  Every case is run
 again here through the same code and must give the same trace and the same digests.  ``gemm="hipblaslt"`` has no digests (torch's
-GEMMs choose their own algorithm): its trace alone is held."""
+GEMMs choose their own algorithm): its trace alone is held.
+
+tests/golden/call_trace_rows_parent.json is the generator's second case set (``--set rows``), recorded the same way at the parent of
+the change that gave the three row layouts one staging path (allrank_amd/rows.py) and the packing calls their launchers: the
+cu_seqlens layout of the trainer and of the scorer, with host lengths and counted on the device, and the index layout's positions.
+It is held under the same rules."""
 import json
 
 import pytest
@@ -15,10 +20,19 @@ from tests.golden import make_call_trace_fixture as G
 pytestmark = pytest.mark.gpu
 
 
+def _load(path):
+    with open(path) as fh:
+        return json.load(fh)
+
+
 @pytest.fixture(scope="module")
 def rec():
-    with open(G.FIXTURE) as fh:
-        return json.load(fh)
+    return _load(G.FIXTURE)
+
+
+@pytest.fixture(scope="module")
+def recs():
+    return {name: _load(path) for name, (path, _) in G.SETS.items()}
 
 
 @pytest.fixture(scope="module")
@@ -44,9 +58,21 @@ def test_fixture_is_the_parents_and_covers_every_case(rec):
     assert acts == {0, 1, 2, 3, 4, 5}                        # every epilogue of ltrx_gemm_nt, the one-bit mask pair included
 
 
-@pytest.mark.parametrize("name", sorted(G.cases()))
-def test_same_calls_same_bits(rec, proxy, name):
-    want = rec["cases"][name]
+def test_rows_fixture_is_the_parents_and_covers_every_case(recs):
+    rec = recs["rows"]
+    assert len(rec["commit"]) == 40
+    assert sorted(rec["cases"]) == sorted(G.rows_cases()) and len(rec["cases"]) == 7
+    for name, c in rec["cases"].items():
+        assert c["trace"] and c["unstable"] == [] and c["digests"], name
+    called = {call[0] for c in rec["cases"].values() for call in c["trace"]}
+    assert {"ltrx_ingest_batch", "ltrx_gather_rows", "ltrx_scatter_rows", "ltrx_packed_row_index", "ltrx_gather_rows_cu",
+            "ltrx_scatter_rows_cu", "ltrx_zero_rows_cu", "ltrx_assemble_packed", "ltrx_posenc_fwd"} <= called
+    assert not set(rec["cases"]) & set(recs["calls"]["cases"])
+
+
+@pytest.mark.parametrize("name", sorted(G.cases()) + sorted(G.rows_cases()))
+def test_same_calls_same_bits(recs, proxy, name):
+    want = recs["rows" if name in G.rows_cases() else "calls"]["cases"][name]
     trace, digests = G.run_case(proxy, name)
     assert len(trace) == len(want["trace"]), ([c[0] for c in trace], [c[0] for c in want["trace"]])
     for i, (got, exp) in enumerate(zip(trace, want["trace"])):

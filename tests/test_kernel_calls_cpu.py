@@ -246,6 +246,87 @@ def test_split_image_and_gather_rows_cu():
             cols=1, rows=32, dst=y_c.data_ptr(), ld_dst=1, idx_out=None, stream=ST.value)
 
 
+def i64(n):
+    return torch.zeros(n, dtype=torch.int64)
+
+
+@pytest.mark.parametrize("with_x", [True, False])
+def test_ingest_batch(with_x):
+    B, L, F = 3, 5, 12
+    x, y = (f32(B, L, F) if with_x else None), f32(B, L)
+    x_dst, y_dst, mask = f32(B * L, 16)[:, :F], f32(B, L), u8(B * L)                  # padded operand rows: stride 16
+    rec = Recorder()
+    K.ingest_batch(rec, ST, x, y, -1, x_dst, y_dst, mask)
+    # the packed layouts' form (x None, nx 0): F and ld_dst still state the row shape, the destination is NULL
+    _expect(rec, "ltrx_ingest_batch", x=x.data_ptr() if with_x else None, y=y.data_ptr(), nx=B * L * F if with_x else 0, ny=B * L, F=F,
+            ld_dst=16, pad_value=-1.0, x_dst=x_dst.data_ptr() if with_x else None, y_dst=y_dst.data_ptr(), mask_dst=mask.data_ptr(),
+            stream=ST.value)
+
+
+def test_index_layout_movers():
+    B, L, F = 3, 5, 12
+    cu, idx = i32(B + 1), i32(32)
+    rec = Recorder()
+    K.packed_row_index(rec, ST, cu, B, L, 11, idx)
+    _expect(rec, "ltrx_packed_row_index", cu_seqlens=cu.data_ptr(), B=B, L=L, n=11, idx=idx.data_ptr(), stream=ST.value)
+    # features: rows of a wider source (stride 20) into the padded operand rows (stride 16); n 11 valid rows, 32 rows written
+    src, dst = f32(B * L, 20)[:, :F], f32(32, 16)[:, :F]
+    rec = Recorder()
+    K.gather_rows(rec, ST, src, idx, 11, 32, F, dst, "w")
+    _expect(rec, "ltrx_gather_rows", src=src.data_ptr(), ld_src=20, idx=idx.data_ptr(), n=11, n_pad=32, cols=F, dst=dst.data_ptr(),
+            ld_dst=16, stream=ST.value)
+    # d loss / d scores: the [B, L] grid of one column into a vector -- and of 4 output units into [rows, 4]
+    g1, v1 = f32(B, L), f32(32)
+    rec = Recorder()
+    K.gather_rows(rec, ST, g1, idx, 11, 32, 1, v1)
+    _expect(rec, "ltrx_gather_rows", same=("ld_src", "cols", "ld_dst"), src=g1.data_ptr(), ld_src=1, idx=idx.data_ptr(), n=11, n_pad=32,
+            cols=1, dst=v1.data_ptr(), ld_dst=1, stream=ST.value)
+    g4, v4 = f32(B, L, 4), f32(32, 6)[:, :4]
+    rec = Recorder()
+    K.gather_rows(rec, ST, g4, idx, 11, 32, 4, v4)
+    _expect(rec, "ltrx_gather_rows", same=("ld_src", "cols"), src=g4.data_ptr(), ld_src=4, idx=idx.data_ptr(), n=11, n_pad=32, cols=4,
+            dst=v4.data_ptr(), ld_dst=6, stream=ST.value)
+    rec = Recorder()
+    K.scatter_rows(rec, ST, v4, idx, 11, 4, g4)
+    _expect(rec, "ltrx_scatter_rows", same=("cols", "ld_dst"), src=v4.data_ptr(), ld_src=6, idx=idx.data_ptr(), n=11, cols=4,
+            dst=g4.data_ptr(), ld_dst=4, stream=ST.value)
+    rec = Recorder()
+    K.scatter_rows(rec, ST, v1, idx, 11, 1, g1)
+    _expect(rec, "ltrx_scatter_rows", same=("ld_src", "cols", "ld_dst"), src=v1.data_ptr(), ld_src=1, idx=idx.data_ptr(), n=11, cols=1,
+            dst=g1.data_ptr(), ld_dst=1, stream=ST.value)
+
+
+def test_cu_layout_movers():
+    B, L = 3, 5
+    cu = i32(B + 1)
+    sc, grid = f32(32, 6)[:, :4], f32(B, L, 4)                                        # packed rows of stride 6 -> the dense grid
+    rec = Recorder()
+    K.scatter_rows_cu(rec, ST, sc, cu, B, L, 4, 32, grid)
+    _expect(rec, "ltrx_scatter_rows_cu", same=("cols", "ld_dst"), src=sc.data_ptr(), ld_src=6, cu_seqlens=cu.data_ptr(), B=B, L=L, cols=4,
+            rows=32, dst=grid.data_ptr(), ld_dst=4, stream=ST.value)
+    s1, g1 = f32(32), f32(B, L)
+    rec = Recorder()
+    K.scatter_rows_cu(rec, ST, s1, cu, B, L, 1, 32, g1)
+    _expect(rec, "ltrx_scatter_rows_cu", same=("ld_src", "cols", "ld_dst"), src=s1.data_ptr(), ld_src=1, cu_seqlens=cu.data_ptr(), B=B, L=L,
+            cols=1, rows=32, dst=g1.data_ptr(), ld_dst=1, stream=ST.value)
+    buf = f32(40, 24)[:, :12]                                                          # 32 of the buffer's 40 rows
+    rec = Recorder()
+    K.zero_rows_cu(rec, ST, buf, cu, B, 32)
+    _expect(rec, "ltrx_zero_rows_cu", x=buf.data_ptr(), ld=24, cols=12, cu_seqlens=cu.data_ptr(), B=B, rows=32, stream=ST.value)
+
+
+@pytest.mark.parametrize("with_pos", [True, False])
+def test_assemble_packed(with_pos):
+    B, L, F = 3, 5, 12
+    x_items, y_items, offsets, slates, cu = f32(40, F), f32(40), i64(9), i64(B), i32(B + 1)
+    x_out, y_out, idx, pos = f32(32, 16)[:, :F], f32(B, L), i32(32), (i64(32) if with_pos else None)
+    rec = Recorder()
+    K.assemble_packed(rec, ST, x_items, y_items, offsets, slates, cu, B, L, 32, x_out, y_out, idx, pos)
+    _expect(rec, "ltrx_assemble_packed", x_items=x_items.data_ptr(), y_items=y_items.data_ptr(), offsets=offsets.data_ptr(),
+            slates=slates.data_ptr(), cu_seqlens=cu.data_ptr(), B=B, L=L, F=F, rows=32, x_out=x_out.data_ptr(), ld_x=16,
+            y_out=y_out.data_ptr(), idx_out=idx.data_ptr(), pos_out=pos.data_ptr() if with_pos else None, stream=ST.value)
+
+
 def test_a_failed_call_raises_with_its_label():
     a, b, out = f32(9, 12), f32(20, 12), f32(9, 20)
     with pytest.raises(RuntimeError, match=r"gemm_nt\(fwd\) failed: unsupported shape"):
@@ -283,7 +364,12 @@ def test_each_launched_call_is_written_once():
     the largest of several shapes)"""
     mine = {node.func.attr for path, node in _ltrx_calls()
             if path == os.path.join("allrank_amd", "kernels.py") and not node.func.attr.endswith("_workspace_bytes")}
-    assert len(mine) == 13, sorted(mine)
+    assert mine == {"ltrx_gemm_nt", "ltrx_gemm_tn", "ltrx_mha_fwd", "ltrx_mha_bwd", "ltrx_layernorm_fwd", "ltrx_layernorm_bwd",
+                    "ltrx_layernorm_bwd_partial", "ltrx_score_head_fwd", "ltrx_score_head_bwd", "ltrx_out_act_fwd", "ltrx_out_act_bwd",
+                    "ltrx_split_image", "ltrx_gather_rows_cu",
+                    # the packing calls
+                    "ltrx_gather_rows", "ltrx_scatter_rows", "ltrx_packed_row_index", "ltrx_scatter_rows_cu", "ltrx_zero_rows_cu",
+                    "ltrx_assemble_packed", "ltrx_ingest_batch"}, sorted(mine)
     count = {}
     for path, node in _ltrx_calls():
         if node.func.attr in mine:
