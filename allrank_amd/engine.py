@@ -455,7 +455,8 @@ class FusedTrainer(object):
         if self.gemm != "hipblaslt":
             self._init_weight_images()
         self.loss = FusedLoss(loss_name, B, L, self.dev, **(loss_args or {}))
-        if self.loss.stochastic:                              # Gumbel noise: a site of the step's generator, re-keyed by drop_step
+        self._loss_args = dict(loss_args or {})               # as bound by the caller (meta(): what a checkpoint is compared on)
+        if self.loss.stochastic:                             # Gumbel noise: a site of the step's generator, re-keyed by drop_step
             self.loss.set_noise_key(self._site(2000), self.drop_step)
         if (self.n_out > 1) != (loss_name == "ordinal") or (loss_name == "ordinal" and int(loss_args["n"]) != self.n_out):
             raise NotImplementedError("FusedTrainer: d_output > 1 goes with the ordinal loss of the same n (and only with it)")
@@ -1349,6 +1350,87 @@ class FusedTrainer(object):
         if float(lr) != float(self.lr):
             self.lr = float(lr)
             self._graphs.clear()
+
+    # ---- checkpointing: the state of a fused run that neither the nn.Module nor the torch.optim object sees ------------------------
+    def _named_order(self):
+        """[(name, parameter)] in ``model.named_parameters()`` order"""
+        return list(self.model.named_parameters())
+
+    def meta(self):
+        """what ``checkpoint.check_compatible`` compares: parameter names / shapes, optimizer kind and hyper-parameters, loss, clipping"""
+        from . import checkpoint as CK
+        return CK.make_meta(self._named_order(), self.optimizer,
+                            CK.hyper(self.optimizer, self.lr, self.betas, self.eps, self.weight_decay, self.momentum, self.nesterov),
+                            self.loss.name, self._loss_args, self.clip)
+
+    def state_dict(self):
+        """Everything a resumed run needs to be THIS run, as CPU tensors and plain values (one device-to-host copy, one host sync):
+        ``params`` by parameter name, the optimizer moments in the neutral schema of allrank_amd.checkpoint (unpadded, shaped like
+        the parameters: neither the 4-float segment padding nor the q / k / v adjacency of the flat buffers reaches the file) with
+        ``step`` from the device step count, the dropout / noise step word ``drop_step`` (as u32), the generator ``seed``, ``lr``,
+        the state of the ListMLE tie-shuffle generator, and the ``meta`` block.  Not state: B, L, the row layout, the gemm mode,
+        graphs and workspaces, scorers."""
+        from . import checkpoint as CK
+        n = self.nflat
+        host = torch.cat([self.flat_p, self.flat_m, self.flat_v, self.step_count, self.drop_step.view(torch.float32)]).cpu()
+        step, word = int(host[3 * n].item()), int(host[3 * n + 1:].view(torch.int32).item()) & 0xFFFFFFFF
+        slots = {"SGD": (("momentum_buffer", 1),)}.get(self.optimizer, (("exp_avg", 1), ("exp_avg_sq", 2)))
+        params, moments = {}, {}
+        for name, p in self._named_order():
+            o, shape = self._pv[id(p)]
+            seg = lambda k: host[k * n + o:k * n + o + p.numel()].view(shape).clone()
+            params[name] = seg(0)
+            moments[name] = {slot: seg(k) for slot, k in slots}
+        hyper = CK.hyper(self.optimizer, self.lr, self.betas, self.eps, self.weight_decay, self.momentum, self.nesterov)
+        return {"params": params,
+                "optimizer": {"kind": self.optimizer, "hyper": hyper, "step": step, "state": moments},
+                "drop_step": word, "seed": int(self._seed), "lr": float(self.lr), "perm_gen": self._perm_gen.get_state().cpu().clone(),
+                "meta": self.meta()}
+
+    def load_state_dict(self, sd):
+        """Put a ``state_dict()`` (of this engine, or the autograd engine's neutral one) back IN PLACE: ``copy_`` into the flat
+        buffers, ``fill_`` on the two device words -- no buffer is rebound, so captured graphs, the module's parameters and the raw
+        pointers of the slate-resident step stay valid; the segments' padding floats stay zero.  The weight images, transposes and
+        padded copies are marked stale (the next forward refreshes them: nothing bumps an autograd version counter here), the
+        learning rate goes through ``set_lr``, and another seed re-keys every dropout site and the stochastic loss and drops the
+        captured steps and ``score()``'s capture (site seeds are by-value launch arguments).  Compatibility is checked first: a
+        refusal (ValueError) leaves the trainer untouched."""
+        from . import checkpoint as CK
+        CK.check_compatible(sd["meta"], self.meta())
+        opt = sd["optimizer"]
+        if "state" not in opt:
+            raise ValueError("checkpoint: the stored optimizer state is a raw torch %s state_dict: only the autograd engine resumes it"
+                             % (opt.get("kind"),))
+        slots = {"SGD": (("momentum_buffer", 1),)}.get(self.optimizer, (("exp_avg", 1), ("exp_avg_sq", 2)))
+        n = self.nflat
+        host = torch.zeros(3 * n, dtype=torch.float32)
+        for name, p in self._named_order():
+            o, shape = self._pv[id(p)]
+            srcs = [(sd["params"].get(name), 0)] + [(opt["state"].get(name, {}).get(slot), k) for slot, k in slots]
+            for t, k in srcs:
+                if t is None or tuple(t.shape) != tuple(shape):
+                    raise ValueError("checkpoint: parameter %s: no tensor of shape %s in the %s" % (name, tuple(shape), "parameters" if k == 0 else "optimizer state"))
+                host[k * n + o:k * n + o + p.numel()].copy_(t.reshape(-1))
+        dev = host.to(self.dev)
+        self.flat_p.copy_(dev[:n])
+        self.flat_m.copy_(dev[n:2 * n])
+        self.flat_v.copy_(dev[2 * n:])
+        self.step_count.fill_(float(int(opt["step"])))
+        if sd.get("drop_step") is not None:
+            word = int(sd["drop_step"]) & 0xFFFFFFFF
+            self.drop_step.fill_(word - (1 << 32) if word >= (1 << 31) else word)
+        self._images_stale = True
+        self.set_lr(float(sd["lr"]))
+        if sd.get("seed") is not None and int(sd["seed"]) != self._seed:
+            self._seed = int(sd["seed"]) & 0xFFFFFFFF
+            for i, st in enumerate(self.layers):
+                st.update(s_att=self._site(4 * i), s_ff=self._site(4 * i + 1), s_s0=self._site(4 * i + 2), s_s1=self._site(4 * i + 3))
+            self._graphs.clear()
+            self._fwd_graphs.graphs.clear()
+            if self.loss.stochastic:
+                self.loss.set_noise_key(self._site(2000), self.drop_step)
+        if sd.get("perm_gen") is not None:
+            self._perm_gen.set_state(sd["perm_gen"].to(torch.uint8).cpu())
 
     def _pack(self, xb, lengths):
         """compact mode: build idx / cu_seqlens for this batch and gather the valid rows of xb into x_in.  ``lengths`` (host

@@ -41,7 +41,12 @@ What changes (all outside the arithmetic of a step):
     and its loss is normalised by the real slate count;
   * under an initialised ``torch.distributed`` group every rank takes its contiguous block of each global batch -- training AND
     validation batches (``_evaluate``) -- (the reference wraps the model in nn.DataParallel instead, main.py:76-78; a DataParallel
-    wrapper passed in is unwrapped).
+    wrapper passed in is unwrapped);
+  * ``checkpoint_every`` / ``resume`` (or ALLRANK_AMD_CHECKPOINT_EVERY / ALLRANK_AMD_RESUME under main.py): the reference leaves one
+    artefact, ``model.pkl``, when the loop ends; here the whole state of the run -- which under the fused step lives in the trainer's
+    flat buffers and device words, not in the optimizer object -- can be written to ``output_dir/checkpoint.pt`` at epoch boundaries
+    and a stopped job continued as the same job, bit for bit (allrank_amd.checkpoint, FusedTrainer.state_dict).  Off by default:
+    nothing is then added to a step, to ``last_run`` or to ``output_dir``.
 """
 import functools
 import logging
@@ -51,6 +56,7 @@ import time
 import numpy as np
 import torch
 
+from . import checkpoint as CK
 from . import losses as E
 from . import metrics as EM
 from . import ragged as RG
@@ -442,9 +448,62 @@ def _assert_finite(trainer, fused, loss, epoch, step, model):
                name, count, "gradient" if fused else "weight"))
 
 
+def _job_meta(trainer, fused, model, loss_func, optimizer, clip):
+    """the block a checkpoint is compared on (checkpoint.check_compatible) -- the same for both engines where the job is the same"""
+    if fused:
+        return trainer.meta()
+    g = optimizer.param_groups[0]
+    kind = CK.neutral_kind(optimizer)
+    if kind is not None:
+        hyper = CK.hyper(kind, g["lr"], g.get("betas"), g.get("eps"), g.get("weight_decay", 0.0), g.get("momentum", 0.0), g.get("nesterov", False))
+    else:
+        kind, hyper = type(optimizer).__name__, CK.group_hyper(g)
+    if isinstance(loss_func, functools.partial):
+        name, args = getattr(loss_func.func, "__name__", repr(loss_func.func)), dict(loss_func.keywords or {})
+        if loss_func.args:
+            args["*"] = list(loss_func.args)
+    else:
+        name, args = getattr(loss_func, "__name__", type(loss_func).__name__), {}
+    return CK.make_meta(list(model.named_parameters()), kind, hyper, name, args, clip)
+
+
+def _trainer_state(trainer, fused, model, optimizer, meta):
+    """the "trainer" entry of a checkpoint: FusedTrainer.state_dict(), or its counterpart for the autograd engine -- the module's
+    state_dict and the torch optimizer's state in the neutral schema (raw for a class the schema does not cover)"""
+    if fused:
+        return trainer.state_dict()
+    return {"params": {k: v.detach().cpu() for k, v in model.state_dict().items()},
+            "optimizer": CK.to_neutral(optimizer, model.named_parameters()),
+            "lr": float(optimizer.param_groups[0]["lr"]), "lrs": [float(g["lr"]) for g in optimizer.param_groups], "meta": meta}
+
+
+def _load_trainer_state(trainer, fused, model, optimizer, state, meta):
+    """a checkpoint's "trainer" entry into the live job, in place; compatibility first (ValueError, nothing touched).  Either engine
+    loads either engine's entry -- only a raw torch optimizer state is tied to the autograd engine and its own class."""
+    if fused:
+        trainer.load_state_dict(state)
+    else:
+        CK.check_compatible(state["meta"], meta)
+        raw = "torch_optimizer" in state["optimizer"]
+        if raw != (CK.neutral_kind(optimizer) is None) or (raw and state["optimizer"]["kind"] != type(optimizer).__name__):
+            raise ValueError("checkpoint: the stored optimizer state (%s, %s) does not fit the live %s"
+                             % (state["optimizer"]["kind"], "raw" if raw else "neutral", type(optimizer).__name__))
+        live = model.state_dict()
+        for n, p in model.named_parameters():
+            if n not in state["params"] or tuple(state["params"][n].shape) != tuple(p.shape):
+                raise ValueError("checkpoint: parameter %s: no tensor of shape %s in the checkpoint" % (n, tuple(p.shape)))
+        with torch.no_grad():
+            for k, v in live.items():
+                if k in state["params"] and tuple(state["params"][k].shape) == tuple(v.shape):
+                    v.copy_(state["params"][k])
+        CK.from_neutral(optimizer, model.named_parameters(), state["optimizer"])
+    for g, lr in zip(optimizer.param_groups, state.get("lrs") or [state["lr"]] * len(optimizer.param_groups)):
+        g["lr"] = float(lr)
+
+
 def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, config, gradient_clipping_norm, early_stopping_patience,
         device, output_dir, tensorboard_output_path, use_fused=True, compact=None, gemm="split_bf16", train_metrics=None,
-        check_finite=None, val_scorer=None):
+        check_finite=None, val_scorer=None, checkpoint_every=None, resume=None):
     """Same positional / keyword arguments as the reference ``fit``; ``use_fused`` / ``compact`` / ``gemm`` / ``train_metrics`` /
     ``check_finite`` are extensions (compact=None: variable-length execution when less than 80 % of the first batch's slots are valid
     items; compact="graph", or ALLRANK_AMD_COMPACT=graph under main.py (any other value raises): the variable-length step at bucketed
@@ -460,10 +519,22 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
     ndcg / dcg / mrr metrics of those batches run on the packed rows as well (allrank_amd.ragged) -- the loss when
     ``ragged.form_of(loss_func)`` exists, anything else on the padded grid exactly as under "packed";
     ``last_run["val_scorer"]`` says which one ran, ``last_run["val_scorer_reason"]`` why the packed one could not, and
-    ``last_run["val_eval"]`` = {"loss": "ragged" | "padded", "metrics": "ragged" | "padded"} what the "ragged" scorer evaluated on)."""
+    ``last_run["val_eval"]`` = {"loss": "ragged" | "padded", "metrics": "ragged" | "padded"} what the "ragged" scorer evaluated on);
+    checkpoint_every=k (or ALLRANK_AMD_CHECKPOINT_EVERY=k): after every k-th epoch, and after the last epoch the loop runs, the whole
+    state of the run -- weights, optimizer moments and step count, the fused step's generator words, learning rate, scheduler,
+    early stopping, the last metrics and every host generator -- replaces ``output_dir/checkpoint.pt`` atomically
+    (allrank_amd.checkpoint; ``last_run["checkpoint"]`` = {"path", "every", "written"}, the written epochs' ``epoch_log`` entries gain
+    "ckpt_s"); resume=path or "auto" (or ALLRANK_AMD_RESUME; "auto": ``output_dir/checkpoint.pt`` if it exists, else a fresh start)
+    continues such a run at the epoch after the stored one, bit for bit where the uninterrupted run repeats itself bit for bit
+    (``last_run["resume"]`` = {"path", "epoch"}); a file of another model, optimizer, loss or clipping norm raises ValueError, a file
+    whose run had ended returns its stored result; both options raise NotImplementedError under a process group of several ranks)."""
     import torch.distributed as dist
     device = torch.device(device)
     world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
+    checkpoint_every, resume = CK.options(checkpoint_every, resume)
+    if world > 1 and (checkpoint_every is not None or resume is not None):
+        raise NotImplementedError("allrank_amd.fit: checkpoint_every / resume under a process group of %d ranks -- per-rank generator "
+                                  "state and the write barrier are not built; run without them" % world)
     if isinstance(model, torch.nn.DataParallel):
         # main.py:76-78 wrapped the model because several GPUs are visible.  The engine does not replicate inside one process: under a
         # process group every rank already holds its replica (allrank_amd.launch rebinds the wrapper away); without one, say so --
@@ -532,7 +603,30 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
     checked = world == 1
     last_run["epoch_log"] = []            # per epoch: wall seconds of the training / validation pass, slates and slots trained on
     n_steps = 0
-    for epoch in range(epochs):
+    first_epoch, ckpt_path, ckpt_meta, rng_state = 0, os.path.join(output_dir, CK.FILE_NAME), None, None
+    if checkpoint_every is not None or resume is not None:
+        ckpt_meta = _job_meta(trainer, fused, model, loss_func, optimizer, gradient_clipping_norm)
+    if checkpoint_every is not None:
+        last_run["checkpoint"] = {"path": ckpt_path, "every": checkpoint_every, "written": 0}
+    if resume == "auto" and not os.path.exists(ckpt_path):
+        log.info("allrank_amd.fit: resume=auto and no %s: starting fresh", ckpt_path)
+        resume = None
+    if resume is not None:
+        ck = CK.load(ckpt_path if resume == "auto" else resume)
+        _load_trainer_state(trainer, fused, model, optimizer, ck["trainer"], ckpt_meta)      # (checks compatibility before it touches anything)
+        if scheduler and ck["scheduler"] is not None:
+            scheduler.load_state_dict(ck["scheduler"])
+        early_stop.best_value, early_stop.best_epoch = ck["early_stop"]["best_value"], int(ck["early_stop"]["best_epoch"])
+        epoch, n_steps = int(ck["epoch"]), int(ck["n_steps"])
+        train_metrics, val_metrics = dict(ck["train_metrics"]), dict(ck["val_metrics"])
+        first_epoch = epochs if ck["early_stop"]["stopped"] else epoch + 1
+        rng_state = ck["rng"]
+        last_run["resume"] = {"path": ckpt_path if resume == "auto" else resume, "epoch": epoch}
+        log.info("allrank_amd.fit: resumed %s (epoch %d finished%s)", last_run["resume"]["path"], epoch,
+                 "" if first_epoch < epochs else "; nothing left to train")
+    if rng_state is not None and first_epoch < epochs:
+        CK.restore_rng(rng_state, device)  # last: whatever building the job drew from the generators no longer matters
+    for epoch in range(first_epoch, epochs):
         model.train()
         t_epoch = time.perf_counter()
         tot, num, slots = torch.zeros((), device=device), 0, 0
@@ -620,6 +714,17 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
             if fused:                                              # the scheduler edits optimizer.param_groups; the fused Adam follows
                 trainer.set_lr(float(optimizer.param_groups[0]["lr"]))
         early_stop.step(current, epoch)
+        if checkpoint_every is not None and ((epoch + 1) % checkpoint_every == 0 or epoch == epochs - 1 or early_stop.stop_training(epoch)):
+            t_ck = time.perf_counter()
+            CK.save(ckpt_path, {
+                "epoch": epoch, "n_steps": n_steps, "engine": last_run["engine"],
+                "trainer": _trainer_state(trainer, fused, model, optimizer, ckpt_meta),
+                "scheduler": scheduler.state_dict() if scheduler else None,
+                "early_stop": {"best_value": early_stop.best_value, "best_epoch": early_stop.best_epoch,
+                               "stopped": bool(early_stop.stop_training(epoch))},
+                "train_metrics": train_metrics, "val_metrics": val_metrics, "rng": CK.capture_rng(device), "meta": ckpt_meta})
+            last_run["checkpoint"]["written"] += 1
+            last_run["epoch_log"][-1]["ckpt_s"] = time.perf_counter() - t_ck
         if early_stop.stop_training(epoch):
             log.info("early stopping at epoch %d since %s didn't improve from epoch no %d. Best value %s, current value %s",
                      epoch, val_metric, early_stop.best_epoch, early_stop.best_value, current)
