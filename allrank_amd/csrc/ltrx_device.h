@@ -310,6 +310,27 @@ __device__ __forceinline__ bool ltrx_is_pad(float y, float pad) {
   return !RAGGED && y == pad;
 }
 
+// The library's sort (ltrx.h, "sort tie policy"): stable descending by counting.  Item j stands before item i when its key is
+// larger, or equal with the lower index -- float compares, so -0.0 and +0.0 tie, +-inf order as floats, and a NaN key stands before
+// nothing and has nothing before it (rank 0, shared with the true maximum: the order of a slate that holds NaNs is unspecified).
+// ltrx_count_ranks: the ranks of item i under K keys at once (ltrx_ndcg.hip: prediction and label; ltrx_rank.hip: the score), one walk
+// over the slate's n items in LDS; `skip(j)` leaves item j out of the count (the padded slots of the padded layout).
+__device__ __forceinline__ bool ltrx_sorts_before(float vj, int j, float vi, int i) { return (vj > vi) || (vj == vi && j < i); }
+template <int K, typename Skip>
+__device__ __forceinline__ void ltrx_count_ranks(const float* const (&key)[K], int n, int i, int (&rank)[K], Skip skip) {
+  float vi[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    vi[k] = key[k][i];
+    rank[k] = 0;
+  }
+  for (int j = 0; j < n; ++j) {
+    if (skip(j)) continue;
+#pragma unroll
+    for (int k = 0; k < K; ++k) rank[k] += ltrx_sorts_before(key[k][j], j, vi[k], i);
+  }
+}
+
 // Final cross-slate reduction: out[0] = scale * sum_b per[b]  (fixed order -> deterministic).  One block.
 // (host launcher lives in ltrx_common.hip; kernels are never launched across translation units)
 int ltrx_launch_finalize_sum(const float* per, int B, float scale, float* out, hipStream_t s);

@@ -60,15 +60,10 @@ __global__ void __launch_bounds__(1024) ltrx_ndcg_kernel(const float* __restrict
       }
       continue;
     }
-    const float si = ss[i];
-    int rs = 0, ry = 0;
-    for (int j = 0; j < n; ++j) {
-      const float yj = ys[j];
-      if (ltrx_is_pad<RAGGED>(yj, pad)) continue;
-      const float sj = ss[j];
-      rs += (sj > si) || (sj == si && j < i);
-      ry += (yj > yi) || (yj == yi && j < i);
-    }
+    const float* const keys[2] = {ss, ys};     // predicted order, ideal order
+    int rk[2];
+    ltrx_count_ranks(keys, n, i, rk, [&](int j) { return ltrx_is_pad<RAGGED>(ys[j], pad); });
+    const int rs = rk[0], ry = rk[1];
     const float gain = gp ? gp[i] : exp2f(yi) - 1.0f;
     dg[rs] = gain / log2f((float)rs + 2.0f);
     ig[ry] = gain / log2f((float)ry + 2.0f);

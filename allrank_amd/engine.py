@@ -1782,10 +1782,11 @@ class FusedScorer(object):
         self.t._reattach()
         self.t._sync_weights()
 
-    def run_resident(self, slates, ids, lengths):
+    def run_resident(self, slates, ids, lengths, position=None):
         """scores of the slates ``ids`` (host int64, at most B) of the resident set ``slates`` (a data.DeviceSlates) padded to L;
         ``lengths``: their item counts (host; every one <= L -- the padding branch of FixLength).  Also fills ``self.y`` with the
-        padded labels.  Returns ``scores_raw``."""
+        padded labels.  ``position`` (an int; None: every item's index in its slate): the position a positional encoding sees for
+        EVERY item -- the reference's inference feeds ones (inference_utils.py:47).  Returns ``scores_raw``."""
         t, LB = self.t, self.LB
         ids_h = torch.as_tensor(ids, dtype=torch.int64).cpu().reshape(-1)
         if ids_h.numel() and (int(ids_h.min()) < 0 or int(ids_h.max()) >= slates.n_slates):
@@ -1797,6 +1798,8 @@ class FusedScorer(object):
         RW.set_rows(self, self._stager.upload(self._host_lengths(lengths), ids_h))     # cu_seqlens, launch order, ids: no host sync
         KN.assemble_packed(t.lib, t._st(), slates.x_items, slates.y_items, slates.offsets, self.ids, self.cu, self.B, self.L, self.rows,
                            self.x_in, self.y, self.idx, self.idx_rows if t.pos is not None else None)
+        if position is not None and t.pos is not None:
+            self.idx_rows[:self.n_valid].fill_(int(position))     # (the alignment rows keep the padding position -1)
         self._run()
         return self.scores_raw
 

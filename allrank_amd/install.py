@@ -8,7 +8,8 @@ allRank resolves its plugins by name at run time (SURVEY.md §5 "Config / flags"
     train_utils.py:50   getattr(allrank.models.metrics, metric_name)
 ``install()`` rebinds exactly those attributes to the MI355X implementations; everything else of the reference
 (config parsing, early stopping, logging) keeps running as is.  ``install(fit=True)`` additionally puts
-``allrank_amd.fit.fit`` (reference signature, explicit HIP training step inside) behind main.py:90.  ``uninstall()`` restores all.
+``allrank_amd.fit.fit`` (reference signature, explicit HIP training step inside) behind main.py:90.  ``install(inference=True)`` puts
+``allrank_amd.inference.rank_slates`` behind the second entry point, rank_and_click.py:86.  ``uninstall()`` restores all.
 
     import allrank_amd; allrank_amd.install(fit=True)      # then: from allrank.main import run; run()
 
@@ -92,13 +93,27 @@ def _install_data(done):
     _rebind(_LOADER_USERS, "create_data_loaders", ED.create_data_loaders, done)
 
 
-def install(losses=True, metrics=True, model=True, fit=False, distributed=None, data=None):
+def _install_inference(done):
+    """rank_and_click.py:86 -> ``allrank_amd.inference.rank_slates``: the defining module and, where it is imported, the entry point's
+    own copy of the name (rank_and_click.py:15).  Our function takes the reference's annotations (they name the reference's classes,
+    which exist only where the reference does), so ``inspect.signature`` of the two is equal."""
+    from . import inference as EI
+    ru = importlib.import_module("allrank.inference.inference_utils")
+    ref = ru.rank_slates if id(ru.rank_slates) not in _ours else _saved.get((ru.__name__, "rank_slates"))
+    if ref is not None:
+        EI.rank_slates.__annotations__ = dict(getattr(ref, "__annotations__", {}))
+    _rebind(("allrank.inference.inference_utils", "allrank.rank_and_click"), "rank_slates", EI.rank_slates, done)
+
+
+def install(losses=True, metrics=True, model=True, fit=False, distributed=None, data=None, inference=False):
     """Rebind the hot-path names inside the importable ``allrank`` package.  Returns the list of rebound names.
     ``fit=True`` also rebinds the epoch loop (train_utils.py:78; imported into main.py's namespace at main.py:18) to
     ``allrank_amd.fit.fit`` -- same signature and return value, the explicit MI355X step inside.
     ``data``: None = rebind the dataset / loader names to the device-resident loader when a GPU is present; True / False force it.
     ``distributed``: None = adopt a process group that is ALREADY initialised with more than one rank (nothing is initialised here);
-    True = bind this rank's GPU and join the group the launcher environment announces (``allrank_amd.launch.setup``); False = never."""
+    True = bind this rank's GPU and join the group the launcher environment announces (``allrank_amd.launch.setup``); False = never.
+    ``inference=True`` (opt-in): also rebinds ``rank_slates`` (inference_utils.py:14, imported into rank_and_click.py at :15) to
+    ``allrank_amd.inference.rank_slates`` -- scores from the packed scorer, slates ranked by ltrx_rank_slates_cu."""
     from . import launch as D
     if distributed:
         dev = D.setup()
@@ -141,6 +156,8 @@ def install(losses=True, metrics=True, model=True, fit=False, distributed=None, 
         _install_distributed(done)
     if data:
         _install_data(done)
+    if inference:
+        _install_inference(done)
     return done
 
 
@@ -151,3 +168,6 @@ def uninstall():
             setattr(mod, name, value)
     _saved.clear()
     _ours.clear()
+    inf = sys.modules.get(__package__ + ".inference")
+    if inf is not None:
+        inf.rank_slates.__annotations__ = {}

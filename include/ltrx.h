@@ -244,6 +244,24 @@ int ltrx_ndcg_at_cu(const float* y_pred, const float* y_true, const int32_t* cu_
 /* the batch-wide rule of metrics.py:108-109 (sum of the slates' maximum labels == 0 -> all zeros) is kept; ws: ltrx_mrr_workspace_bytes */
 int ltrx_mrr_at_cu(const float* y_pred, const float* y_true, const int32_t* cu_seqlens, const int32_t* slate_order, int B, int max_len,
                    const int* ats, int n_ats, float* mrr_out, void* ws, ltrx_stream_t stream);
+/* allrank/inference/inference_utils.py:51-56 (padded scores to -inf, sort descending, gather X and y): the slates of a ragged batch in
+ * ranked order, padded to L >= max_len items.  scores[n] = the packed scores of the valid items.  The item rows come from ONE of two
+ * sources, chosen by which pointers are non-NULL:
+ *   grid:      x[B, L, F], y[B, L] -- the padded batch the scores were computed from, valid items first in every slate;
+ *   resident:  x_items, y_items, offsets of a CSR set resident in HBM (ltrx_assemble_batch's arrays) and ids[B] (int64, device), the
+ *              slates of the batch: item i of slate b is row offsets[ids[b]] + i.  No padded copy of the features is read.
+ * perm[n] (int32, optional): perm[cu[b] + r] = the index inside slate b of the item ranked r.  x_out[B, L, F]: row r < len_b of slate b
+ * is source row perm[cu[b] + r], bit for bit, rows r >= len_b are 0.0f; y_out[B, L]: the labels in the same order, -1.0f behind them.
+ * Order: the stable descending policy above -- rank of item i = #{ j : s_j > s_i, or s_j == s_i and j < i } (-0.0 == +0.0 ties, +-inf
+ * order as floats).  The reference's torch.sort(descending=True) is NOT stable: its order on exact ties is undefined, this call defines
+ * it.  NaN scores: the slate's order is unspecified, every output element is still written (tail values where no item landed), and
+ * no access leaves the slate's rows.  Outputs must not overlap inputs.  16-byte accesses where F % 4 == 0 and the source and x_out
+ * are 16-byte aligned, 4-byte accesses otherwise.  HBM per slate: len F floats read, L F written.
+ * NULL scores / cu_seqlens / x_out / y_out, B, F, max_len <= 0, L < max_len, both source forms, none or an incomplete one:
+ * LTRX_EINVAL; max_len > LTRX_MAX_METRIC_SLATE_LEN: LTRX_EUNSUPPORTED; a refused call writes nothing.  allrank_amd/csrc/ltrx_rank.hip. */
+int ltrx_rank_slates_cu(const float* scores, const float* x, const float* y, const float* x_items, const float* y_items,
+                        const int64_t* offsets, const int64_t* ids, const int32_t* cu_seqlens, const int32_t* slate_order, int B,
+                        int max_len, int F, int L, int32_t* perm, float* x_out, float* y_out, ltrx_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Scoring model kernels (allrank/models/transformer.py).
