@@ -488,8 +488,8 @@ extern "C" int ltrx_selftest_mfma32x32x2(const float* A, const float* Bm, float*
 // ------------------------------------------------------------------------------------------------------------------
 // arithmetic of the attention contractions:
 // (`mode` is an argument of every ltrx_mha_fwd / ltrx_mha_bwd call -- the library keeps no attention mode of its own)
-//   mode 1: split-bf16 on the bf16 MFMA with the whole slate resident in LDS (ltrx_mha_res.hip) wherever the
-//           shape fits (slate length <= 256, 32 < d_k <= 64); fp32-class (three bf16 products per fp32 product, like the dense
+//   mode 1: split-bf16 on the bf16 MFMA on the LDS-resident kernels (ltrx_mha_res.hip) wherever the shape fits (any slate
+//           length: the forward streams the keys through a ring in LDS; 32 < d_k <= 64); fp32-class (three bf16 products per fp32 product, like the dense
 //           projections).  Other shapes run the exact kernels of this file.
 //   mode 0: exact fp32 MFMA (v_mfma_f32_32x32x2_f32, bit-exact fp32 products) for every shape -- the strict reference.
 //   mode 2: the kernels of mode 1 with ONE bf16 product per contraction (plain bf16 operands, fp32 accumulate and softmax):

@@ -9,7 +9,9 @@ allRank resolves its plugins by name at run time (SURVEY.md §5 "Config / flags"
 ``install()`` rebinds exactly those attributes to the MI355X implementations; everything else of the reference
 (config parsing, early stopping, logging) keeps running as is.  ``install(fit=True)`` additionally puts
 ``allrank_amd.fit.fit`` (reference signature, explicit HIP training step inside) behind main.py:90.  ``install(inference=True)`` puts
-``allrank_amd.inference.rank_slates`` behind the second entry point, rank_and_click.py:86.  ``uninstall()`` restores all.
+``allrank_amd.inference.rank_slates`` behind the second entry point, rank_and_click.py:86; ``install(clicks=True)`` puts
+``allrank_amd.clicks.click_on_slates`` / ``metrics_on_clicked_slates`` behind what that entry point does next (:88, :95).
+``uninstall()`` restores all.
 
     import allrank_amd; allrank_amd.install(fit=True)      # then: from allrank.main import run; run()
 
@@ -105,7 +107,23 @@ def _install_inference(done):
     _rebind(("allrank.inference.inference_utils", "allrank.rank_and_click"), "rank_slates", EI.rank_slates, done)
 
 
-def install(losses=True, metrics=True, model=True, fit=False, distributed=None, data=None, inference=False):
+def _install_clicks(done):
+    """rank_and_click.py:88 / :95 -> ``allrank_amd.clicks.click_on_slates`` / ``metrics_on_clicked_slates``: the defining modules and
+    the entry point's own copies of the names (rank_and_click.py:10, :15).  The reference's functions are handed to the clicks module:
+    its host path runs them.  Our functions take the reference's annotations, as ``rank_slates`` does."""
+    from . import clicks as EC
+    owners = {"click_on_slates": "allrank.click_models.click_utils", "metrics_on_clicked_slates": "allrank.inference.inference_utils"}
+    for name, owner in owners.items():
+        mod = importlib.import_module(owner)
+        ref = getattr(mod, name) if id(getattr(mod, name)) not in _ours else _saved.get((owner, name))
+        ours = getattr(EC, name)
+        if ref is not None:
+            EC._reference[name] = ref
+            ours.__annotations__ = dict(getattr(ref, "__annotations__", {}))
+        _rebind((owner, "allrank.rank_and_click"), name, ours, done)
+
+
+def install(losses=True, metrics=True, model=True, fit=False, distributed=None, data=None, inference=False, clicks=False):
     """Rebind the hot-path names inside the importable ``allrank`` package.  Returns the list of rebound names.
     ``fit=True`` also rebinds the epoch loop (train_utils.py:78; imported into main.py's namespace at main.py:18) to
     ``allrank_amd.fit.fit`` -- same signature and return value, the explicit MI355X step inside.
@@ -113,7 +131,9 @@ def install(losses=True, metrics=True, model=True, fit=False, distributed=None, 
     ``distributed``: None = adopt a process group that is ALREADY initialised with more than one rank (nothing is initialised here);
     True = bind this rank's GPU and join the group the launcher environment announces (``allrank_amd.launch.setup``); False = never.
     ``inference=True`` (opt-in): also rebinds ``rank_slates`` (inference_utils.py:14, imported into rank_and_click.py at :15) to
-    ``allrank_amd.inference.rank_slates`` -- scores from the packed scorer, slates ranked by ltrx_rank_slates_cu."""
+    ``allrank_amd.inference.rank_slates`` -- scores from the packed scorer, slates ranked by ltrx_rank_slates_cu.
+    ``clicks=True`` (opt-in, independent of ``inference``): also rebinds ``click_on_slates`` (click_utils.py:10) and
+    ``metrics_on_clicked_slates`` (inference_utils.py:73), both imported into rank_and_click.py, to ``allrank_amd.clicks``."""
     from . import launch as D
     if distributed:
         dev = D.setup()
@@ -158,6 +178,8 @@ def install(losses=True, metrics=True, model=True, fit=False, distributed=None, 
         _install_data(done)
     if inference:
         _install_inference(done)
+    if clicks:
+        _install_clicks(done)
     return done
 
 
@@ -171,3 +193,8 @@ def uninstall():
     inf = sys.modules.get(__package__ + ".inference")
     if inf is not None:
         inf.rank_slates.__annotations__ = {}
+    clk = sys.modules.get(__package__ + ".clicks")
+    if clk is not None:
+        clk._reference.clear()
+        clk.click_on_slates.__annotations__ = {}
+        clk.metrics_on_clicked_slates.__annotations__ = {}

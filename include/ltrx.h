@@ -263,6 +263,44 @@ int ltrx_rank_slates_cu(const float* scores, const float* x, const float* y, con
                         const int64_t* offsets, const int64_t* ids, const int32_t* cu_seqlens, const int32_t* slate_order, int B,
                         int max_len, int F, int L, int32_t* perm, float* x_out, float* y_out, ltrx_stream_t stream);
 
+/* allrank/click_models (behind rank_and_click.py:88): clicks on ranked slates -- BaseCascadeModel / OnlyRelevantClickModel, optionally
+ * inside MaxClicksModel, inside DiverseClicksModel, inside MaxClicksModel.  allrank_amd/csrc/ltrx_click.hip.
+ *   x[B, L, F], y[B, L]: the padded ranked slates, valid items first (what ltrx_rank_slates_cu writes); cu_seqlens gives the item counts
+ *   and the packed offsets of u; slate_order, max_len as in the ragged layout above.
+ *   u[n] (fp64, device, or NULL): one uniform per valid item, in slate order; observe_p[max_len] (fp64, device, or NULL): the observation
+ *   probability of each position.  Both or neither.
+ *   q_host: a HOST pointer to the quantile (read before the launch; needed with `diverse` only).
+ *   clicks_out[B, L]: 1.0f / 0.0f on valid items, -1.0f behind them.  margin_out[B] (fp64, or NULL): the slate's duplicate margin (0 without
+ *   `diverse`).
+ * Per slate of n items, in the reference's order of operations:
+ *   1. item i is observed iff observe_p[i] >= u[cu[b] + i] (both NULL: every item is); a candidate is an item with
+ *      (observed ? y_i : 0.0f) >= threshold -- an unobserved item is a candidate when threshold <= 0, as in the reference;
+ *   2. max_candidates >= 0 keeps the first max_candidates candidates (MaxClicksModel inside the diverse model: cumsum <= max);
+ *   3. diverse != 0: the margin is the q quantile of the n (n - 1) / 2 pairwise Euclidean distances of the valid rows by numpy's linear
+ *      rule -- v = q (N - 1), lo = floor(v), hi = min(lo + 1, N - 1), t = v - lo, a + (b - a) t for t < 0.5, else b - (b - a)(1 - t), every
+ *      operation rounded on its own; 0 for n <= 1.  Candidates are visited in rank order: one is clicked iff its distance to EVERY item
+ *      clicked so far is > margin, any other is dropped;
+ *   4. max_clicks >= 0 keeps the first max_clicks clicks (MaxClicksModel outside).
+ * Distance arithmetic is part of the contract: sqrt(sum_k (double(a_k) - double(b_k))^2) in fp64, k ascending, no fused multiply-add,
+ * a correctly rounded root, stated once in the kernel; the stored value serves the quantile and the comparisons alike; symmetric in
+ * the pair.  For an odd pair count the margin IS one of the distances and that pair compares equal to it.  No floating-point atomics: the
+ * same bits on every call.  With margin_out NULL a slate with fewer than two candidates skips its distance work (no comparison can
+ * change its result).
+ * Distances stay in LDS for slates of up to LTRX_CLICK_LDS_SLATE_LEN items; a longer slate uses its workgroup's slab of ws.  At most
+ * LTRX_CLICK_SLAB_WORKGROUPS workgroups run such a call and the slates stride over them, so
+ *   ltrx_click_workspace_bytes = min(B, LTRX_CLICK_SLAB_WORKGROUPS) * max_len (max_len - 1) / 2 * 8 bytes
+ * for diverse calls with max_len > LTRX_CLICK_LDS_SLATE_LEN, 0 otherwise: bounded whatever B is (2.1 GB at LTRX_MAX_SLATE_LEN).
+ * Refused before any HIP call, nothing written -- LTRX_EINVAL: NULL x / y / cu_seqlens / clicks_out; B, F or max_len <= 0; L < max_len;
+ * exactly one of u / observe_p; diverse without q_host; q outside [0, 1]; ws NULL where the size query is non-zero.
+ * LTRX_EUNSUPPORTED: max_len > LTRX_MAX_SLATE_LEN with diverse (a slab would be 16.8 MB per workgroup), > LTRX_MAX_METRIC_SLATE_LEN
+ * without. */
+#define LTRX_CLICK_LDS_SLATE_LEN 176
+#define LTRX_CLICK_SLAB_WORKGROUPS 128
+size_t ltrx_click_workspace_bytes(int B, int max_len, int diverse);
+int ltrx_click_slates_cu(const float* x, const float* y, const int32_t* cu_seqlens, const int32_t* slate_order, int B, int max_len,
+                         int F, int L, const double* u, const double* observe_p, float threshold, int max_candidates, int diverse,
+                         const double* q_host, int max_clicks, float* clicks_out, double* margin_out, void* ws, ltrx_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Scoring model kernels (allrank/models/transformer.py).
  * ------------------------------------------------------------------------------------------- */
@@ -322,8 +360,8 @@ int ltrx_norm_head_wgrad(const float* dscores, const float* xsum, const float* a
  * launched -- longest first balances the CUs on ragged batches; results do not depend on it. */
 /* `mode` = arithmetic of the attention contractions OF THIS CALL (the library keeps no mode; the backward must be given the
  * mode of its forward): 1 = split-bf16 on the bf16 MFMA (3 products per fp32 product, fp32-class,
- * like the dense projections) with the whole slate resident in LDS, used wherever the shape fits (slate length <= 256,
- * 32 < d_k <= 64; dropout and variable-length batches included); 0 = exact fp32 MFMA (bit-exact fp32 products) for every
+ * like the dense projections) on the LDS-resident kernels, used wherever the shape fits (any slate length -- the forward streams
+ * the keys through a ring in LDS; the backward up to LTRX_MAX_SLATE_LEN --, 32 < d_k <= 64; dropout and variable-length batches included); 0 = exact fp32 MFMA (bit-exact fp32 products) for every
  * shape -- the strict reference; 2 = the kernels of mode 1 with ONE bf16 product per contraction (plain-bf16 throughput mode,
  * about 2^-9 relative error per product: outside the parity contract, reported separately by bench.py).  Shapes that do not
  * fit always run the exact kernels. */
