@@ -31,12 +31,11 @@ HOST PATH.  A model without a plan, a slate with padding between valid items, a 
 semantics -- the original ``click_on_slates`` that install() kept, else a per-slate loop over ``click_model.click`` with
 MaskedRemainMasked's masking.  ``last_run`` = {"engine": "device" | "host", "reason": str}.  Never an exception for that reason.
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _lib as LB
+from .kernels import click_slates_cu
 from .metrics import PADDED_Y_VALUE
 
 __all__ = ["Cascade", "OnlyRelevant", "MaxClicks", "Diverse", "plan_of", "click_on_slates", "metrics_on_clicked_slates",
@@ -180,18 +179,6 @@ def plan_of(click_model):
                 return None, "a threshold of %r is no float32 value" % (f[-1],)
             plan.update(kind=kind, threshold=thr, eta=f[0] if kind == "cascade" else None)
             return plan, ""
-
-
-# ---- the ONE statement of the kernel call, in the form of allrank_amd/kernels.py (bound library and stream are arguments, one ltrx_*
-# call, nothing allocated).  It lives here, next to its only caller, as inference.rank_slates_cu does.
-def click_slates_cu(lib, st, x, y, cu, order, B, max_len, clicks_out, plan, u=None, observe_p=None, margin_out=None, ws=None):
-    """clicks of ``plan`` on slates 0 .. B-1 of the padded ranked batch ``x`` [B, L, F], ``y`` [B, L] into ``clicks_out`` [B, L]"""
-    P = LB.ptr
-    q = ctypes.c_double(plan["q"])
-    LB.check(lib.ltrx_click_slates_cu(P(x), P(y), P(cu), P(order), B, max_len, x.shape[-1], x.shape[-2], P(u), P(observe_p),
-                                      float(plan["threshold"]), plan["max_candidates"], plan["diverse"],
-                                      ctypes.c_void_p(ctypes.addressof(q)), plan["max_clicks"], P(clicks_out), P(margin_out), P(ws), st),
-             "click_slates_cu")
 
 
 # ------------------------------------------------------------------------------------------------------------------

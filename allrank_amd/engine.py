@@ -614,7 +614,7 @@ class FusedTrainer(object):
         self.step_count = torch.zeros(1, dtype=torch.float32, device=dev)
         self.clip_scale = torch.ones(1, dtype=torch.float32, device=dev)
         self.grad_norm = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.ws_clip = torch.empty(max(self.lib.ltrx_clip_workspace_bytes(n), 64), dtype=torch.uint8, device=dev)
+        self.ws_clip = KN.clip_workspace(self.lib, n, self.flat_g)
         self.drop_step = torch.zeros(1, dtype=torch.int32, device=dev)       # u32 word folded into every dropout seed
         # gradient buckets for the multi-GPU all-reduce, in the order the backward completes them: the tail of the flat
         # buffer (last encoder layer + final norm + head) first, then one bucket per earlier layer, the FC stack last
@@ -711,7 +711,7 @@ class FusedTrainer(object):
         if self.N and self.ln_in_wgrad:                       # a third one: see the layer loop of _step_body
             self.d_c = torch.zeros((M, d), **f32)
         maxn = max([3 * d, self.dff if self.N else 0] + self.fc_sizes[1:])
-        self.ws_col = torch.empty(max(self.lib.ltrx_colsum_workspace_bytes(M, maxn), 64), dtype=torch.uint8, device=dev)
+        self.ws_col = KN.colsum_workspace(self.lib, M, maxn, self.d_a)
         self.ws_head = KN.score_head_bwd_workspace(self.lib, M, d, self.d_a)
         self.fc_dgrad = [torch.zeros((M, s), **f32) for s in self.fc_sizes[1:-1]]
         if self.gemm != "hipblaslt":
@@ -777,20 +777,16 @@ class FusedTrainer(object):
         self._refresh_transposes()
 
     def _init_fc_step(self, offs):
-        """the slate-resident FC + ListNet step: its workspace and the launch arguments that never change"""
-        B, L, dev = self.B, self.L, self.dev
+        """the slate-resident FC + ListNet step: its workspace and the parameter offsets its launch takes"""
+        B, L = self.B, self.L
         F_, H_ = self.fc_sizes[0], self.fc_sizes[1]
         H4 = (H_ + 3) // 4 * 4
         offs_fc = (0, H_ * F_, H_ * F_ + H4, H_ * F_ + 2 * H4)
         assert tuple(offs) == offs_fc and self.nflat == offs_fc[3] + 4, (offs, self.nflat)
-        self._fc_ws = torch.empty(max(self.lib.ltrx_fc_listnet_workspace_bytes(B, L, F_, H_, self.nflat), 64), dtype=torch.uint8, device=dev)
-        P = self.LB.ptr
-        self._fc_a = (B, L, F_, H_, self.fc_act, P(self.flat_p), offs_fc[0], offs_fc[1], offs_fc[2], offs_fc[3], self.nflat,
-                      float(self.loss.eps), float(self.loss.pad))
+        self._fc_ws = KN.fc_listnet_workspace(self.lib, B, L, F_, H_, self.nflat, self.flat_p)
         if self.fcstep == "collapse":
-            self._fc_ws = torch.empty(max(self.lib.ltrx_fc_linear_listnet_workspace_bytes(B, F_), 64), dtype=torch.uint8, device=dev)
-            self._fc_a = self._fc_a[:4] + self._fc_a[5:]          # (no activation argument)
-        self._fc_b = (P(self.scores_raw), P(self.loss.grad))
+            self._fc_ws = KN.fc_linear_listnet_workspace(self.lib, B, F_, self.flat_p)
+        self._fc_offs = offs_fc
 
     # ---- thin launch helpers -----------------------------------------------------------------------------------
     def _st(self):
@@ -817,9 +813,7 @@ class FusedTrainer(object):
 
     def _drop_apply(self, src, dst, p, seed):
         """dst = src * keep-mask/(1-p) of the site (the backward of a dropped branch)"""
-        P = self.LB.ptr
-        self.LB.check(self.lib.ltrx_dropout_apply(P(src), P(dst), self.rows * src.shape[1], float(p), seed, P(self.drop_step), self._st()),
-                      "dropout_apply")
+        KN.dropout_apply(self.lib, self._st(), src, self.rows, p, seed, self.drop_step, dst)
 
     def _branch_grad(self, ds, p, seed):
         if p == 0.0:
@@ -849,13 +843,11 @@ class FusedTrainer(object):
         KN.layernorm_bwd(self.lib, self._st(), dy, xsum, a, mean, rstd, dres, self.rows, self.ln_eps, dx, da, db, self.ws_ln)
 
     def _colsum(self, a, out):
-        P = self.LB.ptr
-        self.LB.check(self.lib.ltrx_colsum(P(a), self.rows, a.shape[1], a.stride(0), P(out), 0, P(self.ws_col), self._st()),
-                      "colsum")
+        KN.colsum(self.lib, self._st(), a, self.rows, out, self.ws_col)
 
     def _relu_bwd(self, dr, r, p=0.0):
         """dr *= (r > 0) / (1 - p): backward of dropout(relu(z)) given the stored post-dropout activation r"""
-        self.LB.check(self.lib.ltrx_relu_bwd(self.LB.ptr(dr), self.LB.ptr(r), self.rows * dr.shape[1], 1.0 / (1.0 - p), self._st()), "relu_bwd")
+        KN.relu_bwd(self.lib, self._st(), dr, r, self.rows, 1.0 / (1.0 - p))
 
     def saved_activation(self, layer, key):
         """the saved activation ``key`` ("r", "xn0", "xn1", ...) of encoder layer ``layer`` of the LAST step (tests, diagnostics)"""
@@ -866,21 +858,17 @@ class FusedTrainer(object):
             self.woutT_pad[:, :self.n_out].copy_(self.W(self.model.output_layer.w_1.weight).t())
         if self.gemm == "hipblaslt":
             return
-        P = self.LB.ptr
         w0 = self.W(self.model.input_layer.layers[0].weight) if self._x_pad else None
         if self._fused_images:
-            pad = (P(w0), w0.shape[0], w0.shape[1], self.w0_pad.shape[1], P(self.w0_pad), P(self.w0_pad_i)) if self._x_pad else \
-                  (None, 0, 0, 0, None, None)
-            self.LB.check(self.lib.ltrx_weight_images(P(self.flat_p), self.nflat, P(self.flat_pi), P(self.flat_t), P(self.flat_ti),
-                                                      P(self._tdesc), P(self._tstart), self._tn, self._ttiles if self._tn else 0,
-                                                      *pad, self._st()), "weight_images")
+            pad = (w0, self.w0_pad, self.w0_pad_i) if self._x_pad else ()
+            KN.weight_images(self.lib, self._st(), self.flat_p, self.flat_pi, self.flat_t, self.flat_ti, self._tdesc, self._tstart, self._tn,
+                             self._ttiles if self._tn else 0, *pad)
             return
         if self._x_pad:
             self.w0_pad[:, :w0.shape[1]].copy_(w0)
             KN.split_image(self.lib, self._st(), self.w0_pad, self.w0_pad_i, "split_image(W0 padded)")
         if self._tn:
-            self.LB.check(self.lib.ltrx_transpose_batch(P(self.flat_p), P(self.flat_t), P(self._tdesc), P(self._tstart), self._tn,
-                                                        self._ttiles, self._st()), "transpose_batch")
+            KN.transpose_batch(self.lib, self._st(), self.flat_p, self.flat_t, self._tdesc, self._tstart, self._tn, self._ttiles)
             KN.split_image(self.lib, self._st(), self.flat_t, self.flat_ti, "split_image(W^T)")
         KN.split_image(self.lib, self._st(), self.flat_p, self.flat_pi, "split_image(W)")
 
@@ -1021,54 +1009,36 @@ class FusedTrainer(object):
         if not q:
             return
         n = len(q)
-        vp, ci = ctypes.c_void_p * n, ctypes.c_int * n
-        A = vp(*[t[0].data_ptr() for t in q])
-        Bm = vp(*[t[1].data_ptr() for t in q])
-        C = vp(*[t[2].data_ptr() for t in q])
-        bo = vp(*[t[3].data_ptr() for t in q])
-        lda = ci(*[t[0].stride(0) for t in q])
-        ldb = ci(*[t[1].stride(0) for t in q])
-        NP = ci(*[t[0].shape[1] for t in q])
-        KP = ci(*[t[1].shape[1] for t in q])
-        if defer_reduce:
-            so, bso, sp = vp(), vp(), ctypes.c_int(0)
-            outs = (so, bso, ctypes.byref(sp))
-        else:
-            outs = (None, None, None)
         # did the grouped kernel take this composition, or did the call fall back to one launch per problem (shapes outside the
         # large-tile kernel / not enough workspace)?  The host-side predicate the library applies, asked of the library with the
         # arguments of the call below; tests assert it
-        took = self.lib.ltrx_debug_tn_group_plan(n, self.rows, NP, KP, lda, ldb, self._prec, self.ws_tn.numel(),
-                                                 ctypes.byref(ctypes.c_int(0)), ctypes.byref(ctypes.c_size_t(0)))
-        self.wgrad_group_log.append((n, bool(took)))
+        took = KN.tn_group_plan(self.lib, q, self.rows, self._prec, self.ws_tn)
+        self.wgrad_group_log.append((n, took))
         del self.wgrad_group_log[:-16]
         if self.probe_wgrad is not None:
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
         if ln is None:
-            self.LB.check(self.lib.ltrx_gemm_tn_group(n, A, lda, Bm, ldb, C, bo, self.rows, NP, KP, self._prec, self.LB.ptr(self.ws_tn),
-                                                      self.ws_tn.numel(), *outs, self._st()), "gemm_tn_group(wgrad)")
+            slabs = KN.gemm_tn_group(self.lib, self._st(), q, self.rows, self._prec, self.ws_tn, defer_reduce, "gemm_tn_group(wgrad)")
         else:
-            P = self.LB.ptr
             dy, xsum, a, mean, rstd, dres, dx, da, db = ln
-            rows_out, side = ctypes.c_int(0), ctypes.c_int(0)
-            self.LB.check(self.lib.ltrx_gemm_tn_group_ln(n, A, lda, Bm, ldb, C, bo, self.rows, NP, KP, self._prec, P(self.ws_tn),
-                                                         self.ws_tn.numel(), *outs, P(dy), P(xsum), P(a), P(mean), P(rstd), P(dres),
-                                                         self.rows, self.d, float(self.ln_eps), P(dx), P(buf), ctypes.byref(rows_out),
-                                                         0, ctypes.byref(side), self._st()), "gemm_tn_group_ln(wgrad + layernorm_bwd)")
-            self.ln_side_log.append(side.value)
+            slabs, ln_rows, side = KN.gemm_tn_group_ln(self.lib, self._st(), q, self.rows, self._prec, self.ws_tn, dy, xsum, a, mean, rstd,
+                                                       dres, self.ln_eps, dx, buf, defer_reduce,
+                                                       "gemm_tn_group_ln(wgrad + layernorm_bwd)")
+            self.ln_side_log.append(side)
             del self.ln_side_log[:-16]
         if self.probe_wgrad is not None:
             ev1.record()
-            self.probe_wgrad.append((ev0, ev1, n, bool(took)))
-        if defer_reduce and sp.value > 0:
+            self.probe_wgrad.append((ev0, ev1, n, took))
+        if defer_reduce and slabs[2] > 0:
+            so, bso, splits = slabs
             for i, t in enumerate(q):
                 nw = t[0].shape[1] * t[1].shape[1]
-                self._red_pending.append((so[i], sp.value, nw, nw, t[2].data_ptr()))
+                self._red_pending.append((so[i], splits, nw, nw, t[2].data_ptr()))
                 if bso[i]:
-                    self._red_pending.append((bso[i], sp.value, t[0].shape[1], t[0].shape[1], t[3].data_ptr()))
+                    self._red_pending.append((bso[i], splits, t[0].shape[1], t[0].shape[1], t[3].data_ptr()))
         if ln is not None:                                        # (after the slabs: the queue position _ln_bwd's entries had)
-            self._ln_partials_queue(buf, rows_out.value, da, db)
+            self._ln_partials_queue(buf, ln_rows, da, db)
         q.clear()
 
     def _reduce_flush(self):
@@ -1078,11 +1048,7 @@ class FusedTrainer(object):
         self._ln_slot = 0
         if not q:
             return
-        n = len(q)
-        vp = ctypes.c_void_p * n
-        self.LB.check(self.lib.ltrx_reduce_group(n, vp(*[t[0] for t in q]), (ctypes.c_int * n)(*[t[1] for t in q]),
-                                                 (ctypes.c_size_t * n)(*[t[2] for t in q]), (ctypes.c_size_t * n)(*[t[3] for t in q]),
-                                                 vp(*[t[4] for t in q]), self._st()), "reduce_group")
+        KN.reduce_group(self.lib, self._st(), q)
         q.clear()
 
     # ---- the step body (capturable) ----------------------------------------------------------------------------
@@ -1091,7 +1057,6 @@ class FusedTrainer(object):
         a FusedScorer's (the valid-row count is then read from its device cu_seqlens).  ``train=False`` is model.eval(): every dropout
         rate is 0 (the activations are written all the same).  Returns (feat, sc_rows)."""
         bs = self if bs is None else bs
-        P = self.LB.ptr
         lib, M, d, B, L = self.lib, bs.rows, self.d, bs.B, bs.L
         stream = self._st()                                       # (of the row movers: the pass stays on one stream)
         kpm = bs.mask if bs.layout == "grid" else None            # packed rows are all valid keys
@@ -1100,15 +1065,12 @@ class FusedTrainer(object):
         dp = (lambda p: p) if train else (lambda p: 0.0)          # dropout rate of a site in this pass
         h = bs.x_in
         if self.in_norm is not None and self._x_pad:              # ... into the first F columns of the padded operand rows
-            self.LB.check(lib.ltrx_layernorm_torch_fwd_strided(P(h), h.stride(0), P(W(self.in_norm.weight)), P(W(self.in_norm.bias)), M,
-                                                               self.fc_sizes[0], float(self.in_norm.eps), P(bs.x_norm),
-                                                               bs.x_norm.stride(0), P(bs.mean_in), P(bs.rstd_in), self._st()),
-                          "layernorm_torch_fwd_strided")
+            KN.layernorm_torch_fwd_strided(lib, self._st(), h, W(self.in_norm.weight), W(self.in_norm.bias), M, self.in_norm.eps, bs.x_norm,
+                                           bs.mean_in, bs.rstd_in)
             h = bs.x_norm
         elif self.in_norm is not None:                            # FCModel.input_norm (model.py:39)
-            self.LB.check(lib.ltrx_layernorm_torch_fwd(P(h), P(W(self.in_norm.weight)), P(W(self.in_norm.bias)), M, self.fc_sizes[0],
-                                                       float(self.in_norm.eps), P(bs.x_norm), P(bs.mean_in), P(bs.rstd_in),
-                                                       self._st()), "layernorm_torch_fwd")
+            KN.layernorm_torch_fwd(lib, self._st(), h, W(self.in_norm.weight), W(self.in_norm.bias), M, self.in_norm.eps, bs.x_norm,
+                                   bs.mean_in, bs.rstd_in)
             h = bs.x_norm
         for i, lyr in enumerate(fc.layers):
             w_i = W(lyr.weight)
@@ -1121,8 +1083,7 @@ class FusedTrainer(object):
                 self._lin_fwd(h, w_i, W(lyr.bias), bs.fc_out[i], self.fc_act, dp(self.p_fc), self._site(1000 + i), rows=M)
             h = bs.fc_out[i]
         if self.pos is not None:                                  # transformer.py:51-52: x = sqrt(d) x + pe[rank]
-            self.LB.check(lib.ltrx_posenc_fwd(P(h), P(self._pos_table()), P(bs.idx_rows), P(kpm), M, d, self.pos_pad, float(d) ** 0.5,
-                                              P(bs.x_pe), self._st()), "posenc_fwd")
+            KN.posenc_fwd(lib, self._st(), h, self._pos_table(), bs.idx_rows, kpm, M, self.pos_pad, float(d) ** 0.5, bs.x_pe)
             h = bs.x_pe
         x = h                                                     # residual stream
         for i, st in enumerate(bs.layers):
@@ -1161,9 +1122,8 @@ class FusedTrainer(object):
             feat = bs.xf
         if self.norm_head:                                        # final norm + score head in one pass: LN(x) stays in registers
             nf, feat = self.enc.norm, None
-            self.LB.check(lib.ltrx_norm_head_fwd(P(x), P(W(nf.a_2)), P(W(nf.b_2)), P(W(out.w_1.weight)), P(W(out.w_1.bias)), M, d,
-                                                 float(self.ln_eps), P(sc_rows), P(bs.mean_f), P(bs.rstd_f), None, self._st()),
-                          "norm_head_fwd")
+            KN.norm_head_fwd(lib, self._st(), x, W(nf.a_2), W(nf.b_2), W(out.w_1.weight), W(out.w_1.bias), M, self.ln_eps, sc_rows,
+                             bs.mean_f, bs.rstd_f)
         elif no == 1:
             KN.score_head_fwd(lib, self._st(), feat, W(out.w_1.weight), W(out.w_1.bias), M, sc_rows)
         else:                                                     # Linear(d, d_output) as a GEMM (model.py:117)
@@ -1176,7 +1136,6 @@ class FusedTrainer(object):
         return feat, sc_rows
 
     def _body(self):
-        P = self.LB.ptr
         lib, M, d, B, L = self.lib, self.rows, self.d, self.B, self.L
         stream = self._st()                                       # (of the row movers)
         W, G = self.W, self.G
@@ -1201,15 +1160,12 @@ class FusedTrainer(object):
             # recomputed LN(x); then d_xf = dsc w is formed in registers and dx lands where _ln_bwd put it, the (a_2, b_2) partials
             # joining the last layer's one reducing launch as _ln_bwd's do
             nf = self.enc.norm
-            self.LB.check(lib.ltrx_norm_head_wgrad(P(dsc), P(self.xsum_f), P(W(nf.a_2)), P(W(nf.b_2)), P(self.mean_f), P(self.rstd_f), M, d,
-                                                   P(G(out.w_1.weight)), P(G(out.w_1.bias)), P(self.ws_head), self._st()),
-                          "norm_head_wgrad")
+            KN.norm_head_wgrad(lib, self._st(), dsc, self.xsum_f, W(nf.a_2), W(nf.b_2), self.mean_f, self.rstd_f, M, G(out.w_1.weight),
+                               G(out.w_1.bias), self.ws_head)
             buf = self._ln_partial_slot()                         # (never None: norm_head implies the deferred reduction, slot 0)
-            rows_out = ctypes.c_int(0)
-            self.LB.check(lib.ltrx_norm_head_bwd_partial(P(dsc), P(self.xsum_f), P(W(nf.a_2)), P(W(out.w_1.weight)), P(self.mean_f),
-                                                         P(self.rstd_f), M, d, float(self.ln_eps), P(gb), P(buf), ctypes.byref(rows_out),
-                                                         self._st()), "norm_head_bwd_partial")
-            self._ln_partials_queue(buf, rows_out.value, G(nf.a_2), G(nf.b_2))
+            nrows = KN.norm_head_bwd_partial(lib, self._st(), dsc, self.xsum_f, W(nf.a_2), W(out.w_1.weight), self.mean_f, self.rstd_f, M,
+                                             self.ln_eps, gb, buf)
+            self._ln_partials_queue(buf, nrows, G(nf.a_2), G(nf.b_2))
         elif no == 1:
             KN.score_head_bwd(lib, self._st(), dsc, feat, W(out.w_1.weight), M, ga, G(out.w_1.weight), G(out.w_1.bias), self.ws_head)
         else:                                                     # the d_output-wide head: weight / bias / input gradients as GEMMs
@@ -1268,9 +1224,8 @@ class FusedTrainer(object):
             ds, other = ga, gb
         if self.pos is not None:                                  # backward of x = sqrt(d) fc_out + pe[rank]
             if self.pos_learned:
-                self.LB.check(lib.ltrx_posenc_table_bwd(P(ds), P(self.idx_rows), P(kpm), M, d, self.pos_pad, P(G(self.pos.pe.weight)),
-                                                        self._st()), "posenc_table_bwd")
-            self.LB.check(lib.ltrx_scale_inplace(P(ds), M * d, float(d) ** 0.5, self._st()), "scale_inplace")
+                KN.posenc_table_bwd(lib, self._st(), ds, self.idx_rows, kpm, M, self.pos_pad, G(self.pos.pe.weight))
+            KN.scale_inplace(lib, self._st(), ds, M * d, float(d) ** 0.5)
         # FC stack
         for i in range(self.nfc - 1, -1, -1):
             lyr = fc.layers[i]
@@ -1304,25 +1259,19 @@ class FusedTrainer(object):
         return self.W(self.pos.pe.weight) if self.pos_learned else self.pos.pe
 
     def _adam(self):
-        P = self.LB.ptr
         if self.clip:
-            self.LB.check(self.lib.ltrx_clip_grad_norm_scale(P(self.flat_g), self.nflat, self.clip, P(self.clip_scale),
-                                                             P(self.grad_norm), P(self.ws_clip), self._st()), "clip_grad_norm")
-        gsc = P(self.clip_scale) if self.clip else None
+            KN.clip_grad_norm_scale(self.lib, self._st(), self.flat_g, self.clip, self.clip_scale, self.grad_norm, self.ws_clip)
+        gsc = self.clip_scale if self.clip else None
         if self.optimizer == "SGD":
-            self.LB.check(self.lib.ltrx_sgd_step(P(self.flat_p), P(self.flat_g), P(self.flat_m) if self.momentum else None, self.nflat,
-                                                 float(self.lr), self.momentum, 1 if self.nesterov else 0, self.weight_decay, 1.0, gsc,
-                                                 self._st()), "sgd_step")
+            KN.sgd_step(self.lib, self._st(), self.flat_p, self.flat_g, self.flat_m if self.momentum else None, self.lr, self.momentum,
+                        self.nesterov, self.weight_decay, gsc)
             return
-        self.LB.check(self.lib.ltrx_adam_step(P(self.flat_p), P(self.flat_g), P(self.flat_m), P(self.flat_v), self.nflat,
-                                              float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps),
-                                              self.weight_decay, 1 if self.optimizer == "AdamW" else 0,
-                                              P(self.step_count), 1.0, gsc, self._st()),
-                      "adam_step")
+        KN.adam_step(self.lib, self._st(), self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.lr, self.betas, self.eps,
+                     self.weight_decay, self.optimizer == "AdamW", self.step_count, gsc)
 
     def _full(self):
         if self._any_dropout or self.loss.stochastic:
-            self.LB.check(self.lib.ltrx_bump_u32(self.LB.ptr(self.drop_step), self._st()), "bump_u32")   # fresh masks / noise every step
+            KN.bump_u32(self.lib, self._st(), self.drop_step)    # fresh masks / noise every step
         loss = self._body()
         self._wait_buckets()
         self._adam()
@@ -1338,9 +1287,7 @@ class FusedTrainer(object):
             self._nf_names = [names.get(id(p), "?") for p in self._order]
             self._nf_seg = torch.tensor([self._pv[id(p)][0] for p in self._order], dtype=torch.int64, device=self.dev)
             self._nf_out = torch.zeros(2, dtype=torch.int32, device=self.dev)
-        P = self.LB.ptr
-        self.LB.check(self.lib.ltrx_first_nonfinite(P(self.flat_g), self.nflat, P(self._nf_seg), len(self._order), P(self._nf_out),
-                                                    self._st()), "first_nonfinite")
+        KN.first_nonfinite(self.lib, self._st(), self.flat_g, self._nf_seg, self._nf_out)
         first, count = (int(v) for v in self._nf_out.cpu())
         return (self._nf_names[first], count) if count else (None, 0)
 
@@ -1599,7 +1546,7 @@ class FusedTrainer(object):
         ``self.scores``, d loss / d scores in ``self.loss.grad`` (with ``keep_loss_grad``), gradients in the flat buffer, the loss in ``self.loss.loss``.  One
         GPU without clipping: the reducing launch also applies Adam (two launches per step); sharded or clipped: gradients only,
         then the all-reduce / clip and the flat-buffer Adam as in the general step."""
-        LB, P = self.LB, self.LB.ptr
+        LB = self.LB
         # (the general path's static-buffer copy accepts host batches; so does this one: a host batch is copied to the device first)
         if not xb.is_cuda:
             xb = xb.to(self.dev, non_blocking=True)
@@ -1617,19 +1564,19 @@ class FusedTrainer(object):
         self.y_cur = yb
         div = self._key(global_batch)[0]
         fused_adam = not self.sharded and not self.clip
-        hid = P(self.fc_out[0]) if self.keep_fc_out else None
+        opt = None
         if fused_adam:
-            opt = (P(self.flat_m), P(self.flat_v), P(self.step_count), float(self.lr), float(self.betas[0]), float(self.betas[1]),
-                   float(self.eps), self.weight_decay, 1 if self.optimizer == "AdamW" else 0)
-        else:
-            opt = (None, None, None, 0.0, 0.0, 0.0, 0.0, 0.0, 0)
-        dsc = self._fc_b[1] if self.keep_loss_grad else None
+            opt = (self.flat_m, self.flat_v, self.step_count, float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps),
+                   self.weight_decay, 1 if self.optimizer == "AdamW" else 0)
+        dsc = self.loss.grad if self.keep_loss_grad else None
+        H_ = self.fc_sizes[1]
         if self.fcstep == "collapse":
-            LB.check(self.lib.ltrx_fc_linear_listnet_step(P(xb), P(yb), *self._fc_a, div, self._fc_b[0], dsc, P(self.loss.loss), P(self.flat_g),
-                                                          *opt, P(self._fc_ws), self._st()), "fc_linear_listnet_step")
+            KN.fc_linear_listnet_step(self.lib, self._st(), xb, yb, self.B, self.L, H_, self.flat_p, *self._fc_offs, self.loss.eps,
+                                      self.loss.pad, div, self.scores_raw, self.loss.loss, self.flat_g, self._fc_ws, opt, dsc)
         else:
-            LB.check(self.lib.ltrx_fc_listnet_step(P(xb), P(yb), *self._fc_a, div, self._fc_b[0], dsc, hid, P(self.loss.loss), P(self.flat_g),
-                                                   *opt, P(self._fc_ws), self._st()), "fc_listnet_step")
+            KN.fc_listnet_step(self.lib, self._st(), xb, yb, self.B, self.L, H_, self.fc_act, self.flat_p, *self._fc_offs, self.loss.eps,
+                               self.loss.pad, div, self.scores_raw, self.loss.loss, self.flat_g, self._fc_ws, opt,
+                               self.fc_out[0] if self.keep_fc_out else None, dsc)
         if not fused_adam:
             if self.sharded and self.comm_enabled:
                 import torch.distributed as dist

@@ -24,24 +24,12 @@ reference, reproduced.
 import torch
 
 from . import _lib as LB
+from .kernels import rank_slates_cu
 from .metrics import PADDED_Y_VALUE
 
 __all__ = ["rank_slates", "rank_batches", "rank_slates_cu", "last_run"]
 
 last_run = {"engine": None, "reason": ""}
-
-
-# ---- the ONE statement of the kernel call, in the form of allrank_amd/kernels.py (bound library and stream are arguments, one
-# ltrx_* call, nothing allocated).  It lives here, next to its only caller: tests/test_kernel_calls_cpu.py pins the set of launches
-# that kernels.py states.
-def rank_slates_cu(lib, st, scores, cu, order, B, max_len, L, x_out, y_out, perm=None, x=None, y=None, slates=None, ids=None):
-    """slates 0 .. B-1 of a ragged batch in ranked order into ``x_out`` [.., L, F] / ``y_out`` [.., L] (``perm``: the int32 order).
-    Source rows: the padded grid ``x`` [.., L, F], ``y`` [.., L] -- or the resident set ``slates`` with the batch's device ``ids``."""
-    P = LB.ptr
-    res = slates is not None
-    LB.check(lib.ltrx_rank_slates_cu(P(scores), P(x), P(y), P(slates.x_items) if res else None, P(slates.y_items) if res else None,
-                                     P(slates.offsets) if res else None, P(ids), P(cu), P(order), B, max_len, x_out.shape[-1], L, P(perm),
-                                     P(x_out), P(y_out), st), "rank_slates_cu")
 
 
 # ------------------------------------------------------------------------------------------------------------------

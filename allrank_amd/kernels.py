@@ -1,9 +1,14 @@
-"""The one Python statement of each scoring-model kernel call of libltrx.so (include/ltrx.h): GEMMs, attention, LayerNorm, score
-head, output activation, weight images and the packing calls -- batch ingest, the index layout's ``gather_rows`` / ``scatter_rows`` /
-``packed_row_index``, the cu_seqlens layout's ``gather_rows_cu`` / ``scatter_rows_cu`` / ``zero_rows_cu`` / ``assemble_packed``.  The
-autograd bindings (allrank_amd/ops.py), the explicit training step (allrank_amd/engine.py) and the row movers (allrank_amd/rows.py)
-launch through these functions, as the plugin losses and ``FusedLoss`` launch through the ``_launch_*`` functions of
-allrank_amd/losses.
+"""The one Python statement of each kernel call of libltrx.so (include/ltrx.h) outside the losses, the metrics and the data loader:
+  * the scoring model: GEMMs, attention, LayerNorm, score head, output activation, weight images;
+  * the packing calls: batch ingest, the index layout's ``gather_rows`` / ``scatter_rows`` / ``packed_row_index``, the cu_seqlens
+    layout's ``gather_rows_cu`` / ``scatter_rows_cu`` / ``zero_rows_cu`` / ``assemble_packed``;
+  * the training step's own calls: dropout plumbing, column sums, the ReLU backward, the weight-image refresh, the grouped weight
+    gradient (with and without the LayerNorm backward at its side) and the grouped reduction, the input norm, the positional
+    encoding, the fused norm + head, clip / SGD / Adam, the finiteness check and the two slate-resident FC + ListNet steps;
+  * ranking and clicks: ``rank_slates_cu``, ``click_slates_cu``; and the MFMA lane-layout self-test.
+The autograd bindings (allrank_amd/ops.py), the explicit training step (allrank_amd/engine.py), the row movers (allrank_amd/rows.py),
+allrank_amd/inference.py and allrank_amd/clicks.py launch through these functions and state no launch of their own, as the plugin
+losses and ``FusedLoss`` launch through the ``_launch_*`` functions of allrank_amd/losses.
 
 A launcher makes exactly ONE ``ltrx_*`` call on the tensors it is handed.  Shapes, row strides and the head width are read from the
 tensors (an operand may be a column-slice view of a wider buffer: its ``data_ptr()`` and ``stride`` say where it lives), so no caller
@@ -166,3 +171,231 @@ def gather_rows_cu(lib, st, src, cu, B, L, cols, rows, dst, idx_out=None, what="
     the valid count read from the device ``cu``; an int64 tensor moves as pairs of words (cols 2, and a row stride counted in words)"""
     check(lib.ltrx_gather_rows_cu(P(src), cols, P(cu), B, L, cols, rows, P(dst), dst.stride(0) * (dst.element_size() // 4), P(idx_out),
                                   st), what)
+
+
+# ---- the training step's own calls: elementwise plumbing -------------------------------------------------------------
+def bump_u32(lib, st, word):
+    """word[0] += 1: the per-step word folded into every dropout seed (a replayed hipGraph re-keys its masks)"""
+    check(lib.ltrx_bump_u32(P(word), st), "bump_u32")
+
+
+def dropout_apply(lib, st, src, rows, p, seed, drop_step, dst):
+    """dst[:rows] = src[:rows] * keep-mask / (1 - p) of the site ``seed`` (in place where dst is src)"""
+    check(lib.ltrx_dropout_apply(P(src), P(dst), rows * src.shape[1], float(p), seed, P(drop_step), st), "dropout_apply")
+
+
+def colsum_workspace(lib, rows, N, like):
+    return workspace(lib.ltrx_colsum_workspace_bytes(rows, N), like)
+
+
+def colsum(lib, st, a, rows, out, ws):
+    """out = column sums of a[:rows] (not accumulated)"""
+    check(lib.ltrx_colsum(P(a), rows, a.shape[1], a.stride(0), P(out), 0, P(ws), st), "colsum")
+
+
+def relu_bwd(lib, st, dr, r, rows, scale):
+    """dr[:rows] *= (r > 0) * scale: backward of dropout(relu(z)) from the stored post-dropout activation ``r``"""
+    check(lib.ltrx_relu_bwd(P(dr), P(r), rows * dr.shape[1], scale, st), "relu_bwd")
+
+
+def scale_inplace(lib, st, x, n, s):
+    check(lib.ltrx_scale_inplace(P(x), n, s, st), "scale_inplace")
+
+
+# ---- weight images and transposed copies of the flat parameter buffer ------------------------------------------------------
+def weight_images(lib, st, src, src_image, dst, dst_image, desc, tile_start, n, total_tiles, pad_src=None, pad_dst=None,
+                  pad_dst_image=None):
+    """the image of ``src``, the ``n`` transposed copies ``desc`` describes in ``dst`` and their image in one launch; ``pad_src``
+    [rows, cols] (optional) also lands in ``pad_dst`` (rows of its own, wider stride) with its image in ``pad_dst_image``"""
+    pad = (0, 0, 0) if pad_src is None else (pad_src.shape[0], pad_src.shape[1], pad_dst.stride(0))
+    check(lib.ltrx_weight_images(P(src), src.numel(), P(src_image), P(dst), P(dst_image), P(desc), P(tile_start), n, total_tiles,
+                                 P(pad_src), pad[0], pad[1], pad[2], P(pad_dst), P(pad_dst_image), st), "weight_images")
+
+
+def transpose_batch(lib, st, src, dst, desc, tile_start, n, total_tiles):
+    check(lib.ltrx_transpose_batch(P(src), P(dst), P(desc), P(tile_start), n, total_tiles, st), "transpose_batch")
+
+
+# ---- the grouped weight gradient: ``problems`` = [(dy, x, gw, gb)], gw_i = dy_i[:rows]^T x_i[:rows], gb_i = column sums of dy_i ----
+def _tn_group(problems):
+    """(nprob, A, lda, B, ldb, C, bias_out, NP, KP): the ctypes arrays of the group's operands, strides and shapes"""
+    n = len(problems)
+    vp, ci = ctypes.c_void_p * n, ctypes.c_int * n
+    return (n, vp(*[t[0].data_ptr() for t in problems]), ci(*[t[0].stride(0) for t in problems]),
+            vp(*[t[1].data_ptr() for t in problems]), ci(*[t[1].stride(0) for t in problems]),
+            vp(*[t[2].data_ptr() for t in problems]), vp(*[t[3].data_ptr() for t in problems]),
+            ci(*[t[0].shape[1] for t in problems]), ci(*[t[1].shape[1] for t in problems]))
+
+
+def _tn_slabs(n, defer):
+    """the by-reference outputs of a deferred reduction (NULL x 3 otherwise), and what the caller reads of them after the call"""
+    if not defer:
+        return (None, None, None), lambda: None
+    so, bso, sp = (ctypes.c_void_p * n)(), (ctypes.c_void_p * n)(), ctypes.c_int(0)
+    return (so, bso, ctypes.byref(sp)), lambda: (list(so), list(bso), sp.value)
+
+
+def tn_group_plan(lib, problems, rows, prec, ws):
+    """does the grouped kernel take this composition with this workspace (the library's own host-side predicate), or does the call
+    run one launch per problem?"""
+    n, _, lda, _, ldb, _, _, NP, KP = _tn_group(problems)
+    return bool(lib.ltrx_debug_tn_group_plan(n, rows, NP, KP, lda, ldb, prec, ws.numel(), ctypes.byref(ctypes.c_int(0)),
+                                             ctypes.byref(ctypes.c_size_t(0))))
+
+
+def gemm_tn_group(lib, st, problems, rows, prec, ws, defer=False, what="gemm_tn_group"):
+    """every problem in one launch.  ``defer``: the partial slabs stay in ``ws`` for the caller's reducing launch; returns (slab
+    address per problem, bias-slab address -- or None -- per problem, split count: 0 = nothing left to reduce), else None"""
+    n, A, lda, B, ldb, C, bo, NP, KP = _tn_group(problems)
+    outs, result = _tn_slabs(n, defer)
+    check(lib.ltrx_gemm_tn_group(n, A, lda, B, ldb, C, bo, rows, NP, KP, prec, P(ws), ws.numel(), outs[0], outs[1], outs[2], st), what)
+    return result()
+
+
+def gemm_tn_group_ln(lib, st, problems, rows, prec, ws, dy, xsum, a, mean, rstd, dres, eps, dx, ln_ws, defer=False,
+                     what="gemm_tn_group_ln"):
+    """``gemm_tn_group`` and ``layernorm_bwd_partial(dy .. ln_ws)`` over the same rows in ONE call (the LayerNorm backward in the
+    launch's idle CUs where the library takes it).  Returns (what ``gemm_tn_group`` returns, rows of [da | db] partials left in
+    ``ln_ws``, side workgroups used: 0 = two launches)"""
+    n, A, lda, B, ldb, C, bo, NP, KP = _tn_group(problems)
+    outs, result = _tn_slabs(n, defer)
+    rows_out, side = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib.ltrx_gemm_tn_group_ln(n, A, lda, B, ldb, C, bo, rows, NP, KP, prec, P(ws), ws.numel(), outs[0], outs[1], outs[2], P(dy),
+                                    P(xsum), P(a), P(mean), P(rstd), P(dres), rows, xsum.shape[-1], float(eps), P(dx), P(ln_ws),
+                                    ctypes.byref(rows_out), 0, ctypes.byref(side), st), what)
+    return result(), rows_out.value, side.value
+
+
+def reduce_group(lib, st, entries):
+    """dst = the fixed-order sum of ``partial rows`` rows of ``columns`` floats, ``row stride`` apart, from src -- for every (src
+    address, partial rows, row stride, columns, dst address) of ``entries``, in one launch"""
+    n = len(entries)
+    vp, cs = ctypes.c_void_p * n, ctypes.c_size_t * n
+    check(lib.ltrx_reduce_group(n, vp(*[e[0] for e in entries]), (ctypes.c_int * n)(*[e[1] for e in entries]), cs(*[e[2] for e in entries]),
+                                cs(*[e[3] for e in entries]), vp(*[e[4] for e in entries]), st), "reduce_group")
+
+
+# ---- around the encoder: FCModel.input_norm (nn.LayerNorm), the positional encoding, the fused final norm + score head ----------
+def layernorm_torch_fwd(lib, st, x, w, b, rows, eps, y, mean, rstd):
+    """y = nn.LayerNorm(x) over dense rows of w.numel() columns"""
+    check(lib.ltrx_layernorm_torch_fwd(P(x), P(w), P(b), rows, w.numel(), float(eps), P(y), P(mean), P(rstd), st), "layernorm_torch_fwd")
+
+
+def layernorm_torch_fwd_strided(lib, st, x, w, b, rows, eps, y, mean, rstd):
+    """the same rows, read and written at the operands' own row strides (column slices of padded buffers)"""
+    check(lib.ltrx_layernorm_torch_fwd_strided(P(x), x.stride(0), P(w), P(b), rows, w.numel(), float(eps), P(y), y.stride(0), P(mean),
+                                               P(rstd), st), "layernorm_torch_fwd_strided")
+
+
+def posenc_fwd(lib, st, x, table, indices, mask, rows, padding_idx, scale, y):
+    """y = scale * x + table[indices] (transformer.py:51-52); ``mask`` (may be None): rows that take the padding index"""
+    check(lib.ltrx_posenc_fwd(P(x), P(table), P(indices), P(mask), rows, x.shape[1], padding_idx, scale, P(y), st), "posenc_fwd")
+
+
+def posenc_table_bwd(lib, st, dx, indices, mask, rows, padding_idx, dtable):
+    """dtable = the gradient of a learned table: the rows of ``dx`` summed per index"""
+    check(lib.ltrx_posenc_table_bwd(P(dx), P(indices), P(mask), rows, dx.shape[1], padding_idx, P(dtable), st), "posenc_table_bwd")
+
+
+def norm_head_fwd(lib, st, x, a, b, w, bias, rows, eps, scores, mean, rstd, y=None):
+    """scores = LN(x) w + bias in one pass; ``y`` (optional): LN(x) itself"""
+    check(lib.ltrx_norm_head_fwd(P(x), P(a), P(b), P(w), P(bias), rows, x.shape[-1], float(eps), P(scores), P(mean), P(rstd), P(y), st),
+          "norm_head_fwd")
+
+
+def norm_head_wgrad(lib, st, ds, xsum, a, b, mean, rstd, rows, dw, db, ws):
+    """the head's own gradients from the recomputed LN(xsum), in ``score_head_bwd``'s row order"""
+    check(lib.ltrx_norm_head_wgrad(P(ds), P(xsum), P(a), P(b), P(mean), P(rstd), rows, xsum.shape[-1], P(dw), P(db), P(ws), st),
+          "norm_head_wgrad")
+
+
+def norm_head_bwd_partial(lib, st, ds, xsum, a, w, mean, rstd, rows, eps, dx, ws):
+    """dx of the fused pair now; returns how many rows of [da | db] partials the call left in ``ws`` for the caller to sum"""
+    rows_out = ctypes.c_int(0)
+    check(lib.ltrx_norm_head_bwd_partial(P(ds), P(xsum), P(a), P(w), P(mean), P(rstd), rows, xsum.shape[-1], float(eps), P(dx), P(ws),
+                                         ctypes.byref(rows_out), st), "norm_head_bwd_partial")
+    return rows_out.value
+
+
+# ---- the optimizer over the flat buffers ----------------------------------------------------------------------------------
+def clip_workspace(lib, n, like):
+    return workspace(lib.ltrx_clip_workspace_bytes(n), like)
+
+
+def clip_grad_norm_scale(lib, st, grads, max_norm, scale, norm, ws):
+    """scale[0] = min(1, max_norm / (||grads|| + 1e-6)) -- what the optimizer launches take as ``grad_scale`` -- and norm[0] = the norm"""
+    check(lib.ltrx_clip_grad_norm_scale(P(grads), grads.numel(), max_norm, P(scale), P(norm), P(ws), st), "clip_grad_norm")
+
+
+def sgd_step(lib, st, params, grads, momentum_buf, lr, momentum, nesterov, weight_decay, grad_scale=None):
+    """torch.optim.SGD over the flat buffers; ``momentum_buf`` None: no momentum; ``grad_scale``: the device float of the clip"""
+    check(lib.ltrx_sgd_step(P(params), P(grads), P(momentum_buf), params.numel(), float(lr), momentum, 1 if nesterov else 0, weight_decay,
+                            1.0, P(grad_scale), st), "sgd_step")
+
+
+def adam_step(lib, st, params, grads, exp_avg, exp_avg_sq, lr, betas, eps, weight_decay, decoupled, step_count, grad_scale=None):
+    """torch.optim.Adam (``decoupled``: AdamW) over the flat buffers; ``grad_scale``: the device float of the clip"""
+    check(lib.ltrx_adam_step(P(params), P(grads), P(exp_avg), P(exp_avg_sq), params.numel(), float(lr), float(betas[0]), float(betas[1]),
+                             float(eps), weight_decay, 1 if decoupled else 0, P(step_count), 1.0, P(grad_scale), st), "adam_step")
+
+
+def first_nonfinite(lib, st, buf, seg_start, out):
+    """out[0] = the first segment of ``buf`` (segment s starts at seg_start[s]) that holds a NaN / Inf, out[1] = how many elements do"""
+    check(lib.ltrx_first_nonfinite(P(buf), buf.numel(), P(seg_start), seg_start.numel(), P(out), st), "first_nonfinite")
+
+
+# ---- the slate-resident FC + ListNet step: forward, loss, backward and -- with ``opt`` -- Adam in two launches ----------------
+def fc_listnet_workspace(lib, B, L, F, H, nflat, like):
+    return workspace(lib.ltrx_fc_listnet_workspace_bytes(B, L, F, H, nflat), like)
+
+
+def fc_linear_listnet_workspace(lib, B, F, like):
+    return workspace(lib.ltrx_fc_linear_listnet_workspace_bytes(B, F), like)
+
+
+_NO_OPT = (None, None, None, 0.0, 0.0, 0.0, 0.0, 0.0, 0)
+
+
+def fc_listnet_step(lib, st, x, y, B, L, H, act, params, off_w1, off_b1, off_wout, off_bout, eps, pad_value, divisor, scores, loss,
+                    grads, ws, opt=None, hidden=None, dscores=None):
+    """one step on the batch ``x`` [B * L, F], ``y`` [B, L] read in place: scores, the loss, the flat gradient.  ``opt`` = (exp_avg,
+    exp_avg_sq, step_count, lr, beta1, beta2, eps, weight_decay, decoupled): the reducing launch also applies Adam; None: gradients
+    only.  ``hidden`` / ``dscores`` (optional): the FC activation / d loss / d scores are written out too."""
+    m, v, step, lr, b1, b2, aeps, wd, dec = opt or _NO_OPT
+    check(lib.ltrx_fc_listnet_step(P(x), P(y), B, L, x.shape[-1], H, act, P(params), off_w1, off_b1, off_wout, off_bout, params.numel(),
+                                   float(eps), float(pad_value), divisor, P(scores), P(dscores), P(hidden), P(loss), P(grads), P(m), P(v),
+                                   P(step), lr, b1, b2, aeps, wd, dec, P(ws), st), "fc_listnet_step")
+
+
+def fc_linear_listnet_step(lib, st, x, y, B, L, H, params, off_w1, off_b1, off_wout, off_bout, eps, pad_value, divisor, scores, loss,
+                           grads, ws, opt=None, dscores=None):
+    """the same step for a linear scorer (no FC activation, nothing hidden to write): one matrix-vector product per slate"""
+    m, v, step, lr, b1, b2, aeps, wd, dec = opt or _NO_OPT
+    check(lib.ltrx_fc_linear_listnet_step(P(x), P(y), B, L, x.shape[-1], H, P(params), off_w1, off_b1, off_wout, off_bout, params.numel(),
+                                          float(eps), float(pad_value), divisor, P(scores), P(dscores), P(loss), P(grads), P(m), P(v),
+                                          P(step), lr, b1, b2, aeps, wd, dec, P(ws), st), "fc_linear_listnet_step")
+
+
+# ---- ranking and clicks on ragged slates (allrank_amd/inference.py, allrank_amd/clicks.py) -----------------------------------
+def rank_slates_cu(lib, st, scores, cu, order, B, max_len, L, x_out, y_out, perm=None, x=None, y=None, slates=None, ids=None):
+    """slates 0 .. B-1 of a ragged batch in ranked order into ``x_out`` [.., L, F] / ``y_out`` [.., L] (``perm``: the int32 order).
+    Source rows: the padded grid ``x`` [.., L, F], ``y`` [.., L] -- or the resident set ``slates`` with the batch's device ``ids``."""
+    res = slates is not None
+    check(lib.ltrx_rank_slates_cu(P(scores), P(x), P(y), P(slates.x_items) if res else None, P(slates.y_items) if res else None,
+                                  P(slates.offsets) if res else None, P(ids), P(cu), P(order), B, max_len, x_out.shape[-1], L, P(perm),
+                                  P(x_out), P(y_out), st), "rank_slates_cu")
+
+
+def click_slates_cu(lib, st, x, y, cu, order, B, max_len, clicks_out, plan, u=None, observe_p=None, margin_out=None, ws=None):
+    """clicks of ``plan`` on slates 0 .. B-1 of the padded ranked batch ``x`` [B, L, F], ``y`` [B, L] into ``clicks_out`` [B, L]"""
+    q = ctypes.c_double(plan["q"])
+    check(lib.ltrx_click_slates_cu(P(x), P(y), P(cu), P(order), B, max_len, x.shape[-1], x.shape[-2], P(u), P(observe_p),
+                                   float(plan["threshold"]), plan["max_candidates"], plan["diverse"],
+                                   ctypes.c_void_p(ctypes.addressof(q)), plan["max_clicks"], P(clicks_out), P(margin_out), P(ws), st),
+          "click_slates_cu")
+
+
+# ---- the lane layout the attention kernels assume ---------------------------------------------------------------------------
+def selftest_mfma32x32x2(lib, st, A, B, D):
+    """D [32, 32] = A [32, 2] B [2, 32] through one MFMA"""
+    check(lib.ltrx_selftest_mfma32x32x2(P(A), P(B), P(D), st), "selftest")

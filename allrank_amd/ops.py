@@ -374,5 +374,5 @@ def score_head(x, w, b):
 def mfma_selftest(A, Bm):
     """D = A[32,2] @ B[2,32] through one MFMA with the lane layout the attention kernels assume."""
     D = torch.empty((32, 32), dtype=torch.float32, device=A.device)
-    L.check(L.lib().ltrx_selftest_mfma32x32x2(L.ptr(L.f32c(A)), L.ptr(L.f32c(Bm)), L.ptr(D), L.stream_of(A)), "selftest")
+    KN.selftest_mfma32x32x2(L.lib(), L.stream_of(A), L.f32c(A), L.f32c(Bm), D)
     return D

@@ -1,16 +1,21 @@
 """Record which libltrx calls the package makes, and what they compute, over a set of small cases (needs the MI355X).
 
-    python tests/golden/make_call_trace_fixture.py [--set calls|rows] [--out FILE] [--commit HASH]
+    python tests/golden/make_call_trace_fixture.py [--set calls|rows|step] [--out FILE] [--commit HASH]
 
-Two case sets, one file each, each run ONCE at the commit named in its file ("commit"):
+Three case sets, one file each, each run ONCE at the commit named in its file ("commit"):
   calls  tests/golden/call_trace_parent.json: before the GEMM, attention, LayerNorm and head calls of allrank_amd/ops.py and
          allrank_amd/engine.py moved into the launchers of allrank_amd/kernels.py;
   rows   tests/golden/call_trace_rows_parent.json: the three row layouts (padded grid, index-packed, cu_seqlens-packed) before their
-         staging and row movers moved into allrank_amd/rows.py and the packing launchers of allrank_amd/kernels.py.
+         staging and row movers moved into allrank_amd/rows.py and the packing launchers of allrank_amd/kernels.py;
+  step   tests/golden/call_trace_step_parent.json: what the two sets above do not reach, before the training step's own calls, the
+         ranking call and the click call moved into allrank_amd/kernels.py -- the slate-resident FC + ListNet step (with Adam in the
+         launch, with the separate clip + Adam launches, and the linear-scorer form), SGD with Nesterov momentum and without a
+         momentum buffer, ``first_nonfinite``, ``inference.rank_batches`` from a padded batch and from a resident set, and
+         ``clicks.click_on_slates`` with a cascade and a diverse plan.
 tests/test_gpu_call_trace.py runs the same cases at every later commit and holds them to the recorded calls and results exactly.
 Re-running a set at a later commit only re-records that commit against itself.
 
-Only public entry points are used (FusedTrainer, FusedScorer, allrank_amd.ops).  The object ``allrank_amd._lib.lib()`` caches is
+Only public entry points are used (FusedTrainer, FusedScorer, allrank_amd.ops, inference.rank_batches, clicks.click_on_slates).  The object ``allrank_amd._lib.lib()`` caches is
 replaced by a proxy before anything is constructed; while a case records, the proxy logs every call as ``[name, [arguments]]``:
 an argument whose type in ``_lib.SIGNATURES`` is a pointer (the stream included) as 0 or 1 -- NULL or not -- and integers and floats
 as they are.  Per trainer case: the trace of the first step (``use_graph=False``: every step makes its calls) and SHA-256 digests of the raw
@@ -37,6 +42,7 @@ if ROOT not in sys.path:
 DEV = "cuda:0"
 FIXTURE = os.path.join(HERE, "call_trace_parent.json")
 ROWS_FIXTURE = os.path.join(HERE, "call_trace_rows_parent.json")
+STEP_FIXTURE = os.path.join(HERE, "call_trace_step_parent.json")
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -288,11 +294,86 @@ def rows_cases():
     }
 
 
-SETS = {"calls": (FIXTURE, cases), "rows": (ROWS_FIXTURE, rows_cases)}
+FC_STEP = dict(F=20, sizes=[16], act="ReLU")                                 # B 6, L 16: the slate-resident FC + ListNet step
+FC_LENS = [16, 8, 1, 0, 15, 3]
+RANK_LENS = [70, 1, 33, 12]
+
+
+def _sha_bytes(b):
+    return hashlib.sha256(b).hexdigest()
+
+
+def _first_nonfinite(proxy):
+    from allrank_amd.engine import FusedTrainer
+    ft = FusedTrainer(_model(**SMALL), "listNet", {}, 5, 70, use_graph=False, seed=1234)
+    x, y, _, _ = _batch(SMALL_LENS, 70, 20, 3)
+    ft.step(x, y)
+    trace = []
+    with _recording(proxy, trace):
+        found = ft.first_nonfinite()
+    return trace, dict(flat_g=_sha(ft.flat_g), found=_sha_bytes(repr(found).encode()))
+
+
+def _rank_batches(resident):
+    def run(proxy):
+        from allrank_amd import inference
+        from allrank_amd.data import DeviceSlates
+        model = _model(**dict(SMALL, dropout=0.0))
+        x, y, _, hl = _batch(RANK_LENS, 70, 20, 8)
+        if resident:
+            valid = (y != -1).cpu().numpy()
+            ds = DeviceSlates(x.cpu().numpy()[valid], y.cpu().numpy()[valid], np.repeat(np.arange(len(RANK_LENS)), RANK_LENS), device=DEV)
+            batch = (ds, torch.arange(len(RANK_LENS), dtype=torch.int64), hl)
+        else:
+            batch = (x, y)
+        trace = []
+        with _recording(proxy, trace):
+            (xr, yr), = list(inference.rank_batches(model, [batch], len(RANK_LENS), 70))
+            dig = dict(x_ranked=_sha(xr), y_ranked=_sha(yr))
+        assert inference.last_run["engine"] == "fused", inference.last_run
+        return trace, dig
+    return run
+
+
+def _clicks(case):
+    def run(proxy):
+        from allrank_amd import clicks
+        from tests import click_cases as CC
+        X, y = CC.inputs(case)
+        rows = [1, 4, 6, 9]                                    # 4 slates: 1, 4, 13 and 65 items
+        np.random.seed(CC.CASES[case]["seed"])
+        trace = []
+        with _recording(proxy, trace):
+            _, got = clicks.click_on_slates((torch.tensor(X[rows], device=DEV), torch.tensor(y[rows], device=DEV)),
+                                            CC.ours(CC.CASES[case]["model"]), include_empty=True)
+        assert clicks.last_run["engine"] == "device", clicks.last_run
+        return trace, dict(clicks=_sha_bytes(np.stack(got).tobytes()))
+    return run
+
+
+def step_cases():
+    """the third set: the step's own calls that the first two sets do not reach, ranking and clicks"""
+    sgd = dict(optimizer="SGD", lr=0.01)
+    return {
+        "fc_listnet_step": lambda p: _train(p, FC_STEP, "listNet", {}, FC_LENS, 16),
+        "fc_listnet_step_clip": lambda p: _train(p, FC_STEP, "listNet", {}, FC_LENS, 16, gradient_clipping_norm=0.05),
+        "fc_linear_listnet_step": lambda p: _train(p, dict(FC_STEP, act=None), "listNet", {}, FC_LENS, 16, fc_step="collapse"),
+        "sgd_nesterov_weight_decay": lambda p: _train(p, SMALL, "listNet", {}, SMALL_LENS, 70, momentum=0.9, nesterov=True,
+                                                      weight_decay=0.01, **sgd),
+        "sgd_no_momentum": lambda p: _train(p, SMALL, "listNet", {}, SMALL_LENS, 70, momentum=0.0, **sgd),
+        "first_nonfinite": _first_nonfinite,
+        "rank_batches_grid": _rank_batches(False),
+        "rank_batches_resident": _rank_batches(True),
+        "click_on_slates_cascade": _clicks("plain.cascade"),
+        "click_on_slates_diverse": _clicks("shipped.lattice.F3"),
+    }
+
+
+SETS = {"calls": (FIXTURE, cases), "rows": (ROWS_FIXTURE, rows_cases), "step": (STEP_FIXTURE, step_cases)}
 
 
 def run_case(proxy, name):
-    trace, dig = dict(cases(), **rows_cases())[name](proxy)
+    trace, dig = {n: f for _, make in SETS.values() for n, f in make().items()}[name](proxy)
     torch.cuda.synchronize()
     return trace, dig
 

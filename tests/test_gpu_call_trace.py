@@ -10,7 +10,13 @@ GEMMs choose their own algorithm): its trace alone is held.
 tests/golden/call_trace_rows_parent.json is the generator's second case set (``--set rows``), recorded the same way at the parent of
 the change that gave the three row layouts one staging path (allrank_amd/rows.py) and the packing calls their launchers: the
 cu_seqlens layout of the trainer and of the scorer, with host lengths and counted on the device, and the index layout's positions.
-It is held under the same rules."""
+It is held under the same rules.
+
+tests/golden/call_trace_step_parent.json is the third set (``--set step``), recorded at the parent of the change that moved the
+training step's own calls, the ranking call and the click call into allrank_amd/kernels.py: what the two sets above do not reach --
+the slate-resident FC + ListNet step in its three forms, SGD with Nesterov momentum and without a momentum buffer,
+``first_nonfinite`` (its return value digested too), ``inference.rank_batches`` from a padded batch and from a resident set, and
+``clicks.click_on_slates`` with a cascade and a diverse plan.  The same rules again."""
 import json
 
 import pytest
@@ -70,9 +76,26 @@ def test_rows_fixture_is_the_parents_and_covers_every_case(recs):
     assert not set(rec["cases"]) & set(recs["calls"]["cases"])
 
 
-@pytest.mark.parametrize("name", sorted(G.cases()) + sorted(G.rows_cases()))
+def test_step_fixture_is_the_parents_and_covers_every_case(recs):
+    rec = recs["step"]
+    assert len(rec["commit"]) == 40
+    assert sorted(rec["cases"]) == sorted(G.step_cases()) and len(rec["cases"]) == 10
+    for name, c in rec["cases"].items():
+        assert c["trace"] and c["unstable"] == [] and c["digests"], name
+    called = {call[0] for c in rec["cases"].values() for call in c["trace"]}
+    assert {"ltrx_fc_listnet_step", "ltrx_fc_linear_listnet_step", "ltrx_sgd_step", "ltrx_clip_grad_norm_scale", "ltrx_first_nonfinite",
+            "ltrx_rank_slates_cu", "ltrx_click_slates_cu"} <= called
+    sgd = {n: [call[1] for call in rec["cases"][n]["trace"] if call[0] == "ltrx_sgd_step"] for n in rec["cases"]}
+    assert sgd["sgd_no_momentum"][0][2] == 0 and sgd["sgd_nesterov_weight_decay"][0][2] == 1     # the momentum buffer: NULL, and not
+    assert not set(rec["cases"]) & (set(recs["calls"]["cases"]) | set(recs["rows"]["cases"]))
+
+
+CASE_SET = {name: key for key, (_, make) in G.SETS.items() for name in make()}
+
+
+@pytest.mark.parametrize("name", sorted(CASE_SET))
 def test_same_calls_same_bits(recs, proxy, name):
-    want = recs["rows" if name in G.rows_cases() else "calls"]["cases"][name]
+    want = recs[CASE_SET[name]]["cases"][name]
     trace, digests = G.run_case(proxy, name)
     assert len(trace) == len(want["trace"]), ([c[0] for c in trace], [c[0] for c in want["trace"]])
     for i, (got, exp) in enumerate(zip(trace, want["trace"])):
