@@ -158,7 +158,10 @@ __device__ __forceinline__ void block_inclusive_scan(float* a, int n, float* red
   __syncthreads();
   if (lane_id() == 63) red[wave_id()] = inc;
   __syncthreads();
-  float base = inc - tot;  // exclusive prefix inside the wave
+  // exclusive prefix inside the wave: the lane below's inclusive one.  (Not `inc - tot`: that difference is rounded at the size of inc,
+  // which reaches to the END of this thread's chunk -- with chunk >= 2 an entry far smaller than its chunk's end lost all precision.)
+  float base = __shfl_up(inc, 1, 64);
+  if (lane_id() == 0) base = 0.f;
   for (int w = 0; w < wave_id(); ++w) base += red[w];
   for (int i = lo; i < hi; ++i) a[i] += base;
   __syncthreads();

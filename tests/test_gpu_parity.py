@@ -93,6 +93,8 @@ def test_losses_match_reference_golden(losses_golden):
 
 @pytest.mark.parametrize("B,L,seed", [(64, 240, 1), (7, 33, 2), (3, 1, 3), (5, 257, 4), (2, 1024, 5)])
 def test_losses_match_oracle_random(B, L, seed):
+    """the max-norm bar (``grad_close``) on random slates; the entrywise bar of the four listwise losses lives in
+    tests/test_gpu_listwise_contract.py"""
     from tests.golden.make_inputs import make_inputs
     s, y = make_inputs(B, L, seed)
     perm = np.random.default_rng(seed).permutation(L).astype(np.int64)

@@ -2,7 +2,8 @@
 
 One batch (tests/ragged_cases.py): slates of 0, 1, 2, 3, 5, 31, 32, 33, 64, 100, 255, 256, 257 items, labels 0..4, one slate of zero
 labels, exact ties in scores and labels, at score scales 1 and 30.  Bars: those of the padded kernels' tests -- value ``close``
-(1e-5), gradient ``grad_close`` (2e-4 of the largest reference entry), argsorts and pair counts exact."""
+(1e-5), gradient ``grad_close`` (2e-4 of the largest reference entry), argsorts and pair counts exact.  The entrywise bar of the
+ragged listNet, approxNDCG and lambdaLoss calls lives in tests/test_gpu_listwise_contract.py."""
 import ctypes
 
 import numpy as np
