@@ -22,6 +22,25 @@ from .rows import row_bucket, _stage_host, _Stager  # noqa: F401  (their home is
 
 PADDED_Y_VALUE = -1
 
+# The step's operands, made once by FusedTrainer.__init__ (the flat buffers are never rebound, so a view or an address stays right):
+#   Param  one per nn.Parameter, ``FusedTrainer.params`` in flat-buffer order: its name, the parameter, its offset, and the views of
+#          flat_p / flat_g shaped like it;
+#   Lin    one per projection (nn.Linear; q, k, v of a layer are ONE [3d, d] projection): weight, bias and their gradients, ``wT`` the
+#          contiguous transposed copy inside flat_t (or None), ``w_img`` / ``wT_img`` the addresses of the pre-split images of w / wT
+#          (None without images), and for the first FC layer over padded input rows ``w_pad`` / ``w_pad_img``: the zero-padded copy
+#          the forward multiplies instead of w;
+#   Norm   one per LayerNorm: scale, shift, their gradients and eps.
+Param = collections.namedtuple("Param", "name p off w g")
+Norm = collections.namedtuple("Norm", "a b ga gb eps")
+
+
+class Lin(object):
+    __slots__ = ("w", "b", "gw", "gb", "off", "wT", "w_img", "wT_img", "w_pad", "w_pad_img")
+
+    def __init__(self, w, b, gw, gb, off):
+        self.w, self.b, self.gw, self.gb, self.off = w, b, gw, gb, off
+        self.wT = self.w_img = self.wT_img = self.w_pad = self.w_pad_img = None
+
 
 class Trainer(object):
     def __init__(self, model, loss_func, optimizer, gradient_clipping_norm=None, world_size=1, group=None):
@@ -94,8 +113,8 @@ def _alloc_forward(owner, t, rows, B, L, saved, layout):
       them again -- every staging kernel, the strided input LayerNorm included, writes F columns per row -- so the K - F surplus
       columns of the contraction multiply zeros, whatever the pad columns of w0_pad hold (zeros too)
       idx_rows (i64 rank of every row, -1 = none) and x_pe: positional encoding only
-      layers[i]: wqkv, bqkv, mod, p_*, s_* (the trainer's parameter views and dropout sites; its own dicts also hold gwqkv / gbqkv
-      and later rbits / wqkvT), xsum0 (the residual stream entering layer i > 0), xn0, mean0, rstd0, qkv, o, lse, x1, xn1, mean1,
+      layers[i]: lin_qkv, lin_o, lin_ff1, lin_ff2, norm0, norm1, p_*, s_* (the trainer's operand records and dropout sites of the
+      layer: t._layer_ops[i]; its own dicts later hold rbits), xsum0 (the residual stream entering layer i > 0), xn0, mean0, rstd0, qkv, o, lse, x1, xn1, mean1,
       rstd1, r, and q, k, v (the column views of qkv that the attention launches read);  xsum_f, xf, mean_f, rstd_f (the final norm; xf
       is None where t.norm_head holds: the fused final norm + score head keeps the normalised rows in registers);  scores_c (packed layouts only), scores_raw [B, L(, n_out)], scores [B, L]
     ``saved=True``, the trainer's form: the backward reads the activations, so every layer has its own.  ``saved=False``, the scorer's:
@@ -141,18 +160,17 @@ def _alloc_forward(owner, t, rows, B, L, saved, layout):
     owner.fc_out = [z(rows, s) for s in t.fc_sizes[1:]]
     if t.pos is not None:
         owner.idx_rows = torch.full((rows,), -1, dtype=torch.int64, device=dev)
-    heads, owner.layers = t.layers, []                        # (owner may be t: its dicts hold the parameter views so far)
+    owner.layers = []
     if t.N and saved:
-        for i, st in enumerate(heads):
-            owner.layers.append(dict(st, xsum0=z(rows, d) if i else None, **acts(ln(), ln())))
+        for i, ops in enumerate(t._layer_ops):
+            owner.layers.append(dict(ops, xsum0=z(rows, d) if i else None, **acts(ln(), ln())))
         owner.xsum_f = z(rows, d)
         owner.xf, owner.mean_f, owner.rstd_f = (None, z(rows), z(rows)) if t.norm_head else ln()
     elif t.N:
         ping, one = [z(rows, d), z(rows, d)], ln()
         shared = acts(one, one)
-        for i, st in enumerate(heads):
-            owner.layers.append(dict({k: st[k] for k in ("wqkv", "bqkv", "mod", "p_att", "p_ff", "p_s0", "p_s1", "s_att", "s_ff", "s_s0",
-                                                          "s_s1")}, xsum0=ping[i % 2], **shared))
+        for i, ops in enumerate(t._layer_ops):
+            owner.layers.append(dict(ops, xsum0=ping[i % 2], **shared))
         owner.xsum_f = ping[t.N % 2]
         owner.xf, owner.mean_f, owner.rstd_f = (None,) + one[1:] if t.norm_head else one
     if t.pos is not None:
@@ -377,7 +395,6 @@ class FusedTrainer(object):
         # attention arithmetic of THIS trainer, passed with every ltrx_mha_fwd / ltrx_mha_bwd call (the library keeps no mode):
         # 1 = three bf16 products (fp32-class, parity), 2 = one product (the "bf16" throughput mode)
         self._mha_mode = 2 if gemm == "bf16" else 1
-        self._wT = {}
         self.model = model
         self.B, self.L, self.M = B, L, B * L
         self.lr, self.betas, self.eps = lr, betas, eps
@@ -457,7 +474,7 @@ class FusedTrainer(object):
         self.loss = FusedLoss(loss_name, B, L, self.dev, **(loss_args or {}))
         self._loss_args = dict(loss_args or {})               # as bound by the caller (meta(): what a checkpoint is compared on)
         if self.loss.stochastic:                             # Gumbel noise: a site of the step's generator, re-keyed by drop_step
-            self.loss.set_noise_key(self._site(2000), self.drop_step)
+            self.loss.set_noise_key(self._site_seeds()[1], self.drop_step)
         if (self.n_out > 1) != (loss_name == "ordinal") or (loss_name == "ordinal" and int(loss_args["n"]) != self.n_out):
             raise NotImplementedError("FusedTrainer: d_output > 1 goes with the ordinal loss of the same n (and only with it)")
         # ListMLE: the reference draws torch.randperm(L) on every call (listMLE.py:17).  shuffle_ties=True (default) does
@@ -490,7 +507,7 @@ class FusedTrainer(object):
         #                                                       run fell back to eager steps, or ensure_captured()'s "not warmed up"
         self._seg_break = None                                # set while capturing: ends the current segment (see _capture)
         self._cap_stream = None
-        self._wver = [p._version for p in self._order]
+        self._wver = [r.p._version for r in self.params]
         self._images_stale = False
         self.y_cur = self.y_in                                # labels of the last step() (the caller's tensor in the fcstep path)
         self.keep_fc_out = False                              # tests: also write the FC activations to fc_out[0]
@@ -580,10 +597,17 @@ class FusedTrainer(object):
         if self.in_norm is not None and self.fc_sizes[0] < 2:
             raise NotImplementedError("FusedTrainer: input_norm over %d feature (ltrx_layernorm_bwd needs at least 2 columns)" % self.fc_sizes[0])
 
+    def _site_seeds(self):
+        """the seeds, under the current ``_seed``, of the dropout sites of every encoder layer (one dict per layer, keyed as the layer
+        dicts are) and of the stochastic loss's noise"""
+        return ([dict(s_att=self._site(4 * i), s_ff=self._site(4 * i + 1), s_s0=self._site(4 * i + 2), s_s1=self._site(4 * i + 3))
+                 for i in range(self.N)], self._site(2000))
+
     def _layout_parameters(self, dropout):
         """the flat parameter / gradient / moment buffers (16-byte aligned segments; q,k,v weights and biases adjacent) with the module's
-        parameters re-pointed at them, the gradient buckets, and the parameter views and dropout sites of every encoder layer in
-        ``self.layers`` (_alloc_forward adds the activations); returns the segment offsets"""
+        parameters re-pointed at them, the gradient buckets, and the operand records of the step: ``params`` (one Param per parameter, flat
+        order), ``norm_in``, ``fc``, ``pos_table`` / ``pos_g``, per encoder layer the four Lin, two Norm and the dropout sites in
+        ``_layer_ops`` (_alloc_forward adds the activations: ``layers``), ``norm_f`` and ``head``; returns the segment offsets"""
         model, fc, enc, out, dev = self.model, self.model.input_layer, self.enc, self.model.output_layer, self.dev
         order = []
         if self.in_norm is not None:
@@ -601,7 +625,8 @@ class FusedTrainer(object):
                           lay.sublayer[0].norm.a_2, lay.sublayer[0].norm.b_2, lay.sublayer[1].norm.a_2, lay.sublayer[1].norm.b_2]
             order += [enc.norm.a_2, enc.norm.b_2]
         order += [out.w_1.weight, out.w_1.bias]
-        assert len(order) == len(list(model.parameters()))
+        named = list(model.named_parameters())                # (the order state_dict() and meta() keep)
+        assert len(order) == len(named)
         offs, n = [], 0
         for p in order:
             offs.append(n)
@@ -616,61 +641,62 @@ class FusedTrainer(object):
         self.grad_norm = torch.zeros(1, dtype=torch.float32, device=dev)
         self.ws_clip = KN.clip_workspace(self.lib, n, self.flat_g)
         self.drop_step = torch.zeros(1, dtype=torch.int32, device=dev)       # u32 word folded into every dropout seed
-        # gradient buckets for the multi-GPU all-reduce, in the order the backward completes them: the tail of the flat
-        # buffer (last encoder layer + final norm + head) first, then one bucket per earlier layer, the FC stack last
-        offs_of = {id(p): o for p, o in zip(order, offs)}
-        starts = [offs_of[id(lay.self_attn.linears[0].weight)] for lay in enc.layers] if enc is not None else []
-        self._buckets = []
-        prev_hi = n
-        for st_ in reversed(starts):
-            self._buckets.append((st_, prev_hi))
-            prev_hi = st_
-        self._buckets.append((0, prev_hi))
         self._works = []
         self.comm_enabled = True      # bench.py measures the exposed part of the collective by switching it off
-        self._pv, self._wv, self._gv = {}, {}, {}
-        self._order = order
+        # the kernels address the flat buffers through the views of these records, never through p.data / p.grad: an external
+        # zero_grad(set_to_none=True) or .to() cannot redirect the step (step() re-attaches the module's views)
+        self.params = []
         with torch.no_grad():
             for p, o in zip(order, offs):
                 view = self.flat_p[o:o + p.numel()].view_as(p)
                 view.copy_(p.data)
                 p.data = view
                 p.grad = self.flat_g[o:o + p.numel()].view_as(p)
-                self._pv[id(p)] = (o, p.shape)
-                self._wv[id(p)] = view
-                self._gv[id(p)] = p.grad
+                self.params.append(Param(next(name for name, q in named if q is p), p, o, view, p.grad))
+        by_name = {r.name: r for r in self.params}
+        self._params_named = [by_name[name] for name, _ in named]
+        # the projections and norms, taken off the records in flat order
+        rec, d = iter(self.params), self.d
 
-        # the kernels address the flat buffers through these views, never through p.data / p.grad: an external
-        # zero_grad(set_to_none=True) or .to() cannot redirect the step (step() re-attaches the module's views)
-        def W(p):
-            return self._wv[id(p)]
+        def lin():
+            w, b = next(rec), next(rec)
+            return Lin(w.w, b.w, w.g, b.g, w.off)
 
-        def G(p):
-            return self._gv[id(p)]
+        def lin_qkv():                                        # q, k, v of a layer: adjacent segments read as one [3d, d] | [3d] projection
+            w, _, _, b, _, _ = [next(rec) for _ in range(6)]
+            return Lin(self.flat_p[w.off:w.off + 3 * d * d].view(3 * d, d), self.flat_p[b.off:b.off + 3 * d],
+                       self.flat_g[w.off:w.off + 3 * d * d].view(3 * d, d), self.flat_g[b.off:b.off + 3 * d], w.off)
 
-        self.W, self.G = W, G
+        def norm(eps):
+            a, b = next(rec), next(rec)
+            return Norm(a.w, b.w, a.g, b.g, eps)
 
-        def fused_view(buf, first, count_rows, cols=None):
-            o, _ = self._pv[id(first)]
-            if cols is None:
-                return buf[o:o + count_rows]
-            return buf[o:o + count_rows * cols].view(count_rows, cols)
-
-        d = self.d
-        self.layers = []
+        self.norm_in = norm(self.in_norm.eps) if self.in_norm is not None else None
+        self.fc = [lin() for _ in fc.layers]
+        # the positional table (transformer.py:51-52) and, for a learned one, its gradient
+        self.pos_table, self.pos_g = next(rec)[3:] if self.pos_learned else (self.pos.pe if self.pos is not None else None, None)
+        sites = self._site_seeds()[0]
+        self._layer_ops = []
         for i in range(self.N):
             lay = enc.layers[i]
-            lin = lay.self_attn.linears
-            st = dict(
-                wqkv=fused_view(self.flat_p, lin[0].weight, 3 * d, d), bqkv=fused_view(self.flat_p, lin[0].bias, 3 * d),
-                gwqkv=fused_view(self.flat_g, lin[0].weight, 3 * d, d), gbqkv=fused_view(self.flat_g, lin[0].bias, 3 * d), mod=lay,
+            self._layer_ops.append(dict(
+                lin_qkv=lin_qkv(), lin_o=lin(), lin_ff1=lin(), lin_ff2=lin(), norm0=norm(self.ln_eps), norm1=norm(self.ln_eps),
                 # dropout sites (transformer.py:105,155,227): probabilities and seeds
                 p_att=float(lay.self_attn.dropout.p) if dropout else 0.0,
                 p_ff=float(lay.feed_forward.dropout.p) if dropout else 0.0,
                 p_s0=float(lay.sublayer[0].dropout.p) if dropout else 0.0,
-                p_s1=float(lay.sublayer[1].dropout.p) if dropout else 0.0,
-                s_att=self._site(4 * i), s_ff=self._site(4 * i + 1), s_s0=self._site(4 * i + 2), s_s1=self._site(4 * i + 3))
-            self.layers.append(st)
+                p_s1=float(lay.sublayer[1].dropout.p) if dropout else 0.0, **sites[i]))
+        self.norm_f = norm(self.ln_eps) if enc is not None else None
+        self.head = lin()
+        self.layers = self._layer_ops                         # (until _alloc_forward gives every layer its activations)
+        # gradient buckets for the multi-GPU all-reduce, in the order the backward completes them: the tail of the flat
+        # buffer (last encoder layer + final norm + head) first, then one bucket per earlier layer, the FC stack last
+        self._buckets = []
+        prev_hi = n
+        for ops in reversed(self._layer_ops):
+            self._buckets.append((ops["lin_qkv"].off, prev_hi))
+            prev_hi = ops["lin_qkv"].off
+        self._buckets.append((0, prev_hi))
         # (no active dropout site -> no mask counter to advance: one launch less per step)
         self._any_dropout = bool(self.p_fc or any(st[k] for st in self.layers for k in ("p_att", "p_ff", "p_s0", "p_s1")))
         return offs
@@ -705,6 +731,7 @@ class FusedTrainer(object):
             npad = (no + 3) // 4 * 4
             self.dz_pad = torch.zeros((M, npad), **f32)        # d loss / d pre-activation, K padded to a multiple of 4 for the dgrad GEMM
             self.woutT_pad = torch.zeros((d, npad), **f32)     # W_out^T zero-padded the same way (refreshed after every optimizer step)
+            self.head.wT = self.woutT_pad                      # (outside flat_t: no image)
             self.zb = torch.zeros(no, **f32)
         self.d_a = torch.zeros((M, d), **f32)                 # gradient w.r.t. the residual stream (ping)
         self.d_b = torch.zeros((M, d), **f32)                 # (pong)
@@ -739,41 +766,46 @@ class FusedTrainer(object):
 
     def _init_weight_images(self):
         """transposed weight copies for the input-gradient GEMMs (one flat buffer, one descriptor table, refreshed after every optimizer
-        step by ONE batched transpose launch) and the pre-split images of the weights and of the copies"""
-        fc, enc, d, dev = self.model.input_layer, self.enc, self.d, self.dev
+        step by ONE batched transpose launch) and the pre-split images of the weights and of the copies; every Lin record learns its
+        ``wT`` and, with ``weight_images``, the addresses of its images"""
+        dev = self.dev
         f32 = dict(dtype=torch.float32, device=dev)
         if self._x_pad:                                           # the zero-padded copy [H, K] of W_0 the padded input rows multiply
-            self.w0_pad = torch.zeros((self.fc_sizes[1], self.x_in_k.shape[1]), **f32)
+            self.w0_pad = self.fc[0].w_pad = torch.zeros((self.fc_sizes[1], self.x_in_k.shape[1]), **f32)
             self.w0_pad_i = torch.zeros_like(self.w0_pad)
-        tw = [l.weight for l in (fc.layers if self.in_norm is not None else fc.layers[1:])]
-        srcs = [(self._pv[id(p)][0], p.shape[0], p.shape[1], ("w", id(p))) for p in tw]
-        if enc is not None:
-            for li, st in enumerate(self.layers):
-                lay = st["mod"]
-                for p in (lay.self_attn.linears[3].weight, lay.feed_forward.w_1.weight, lay.feed_forward.w_2.weight):
-                    srcs.append((self._pv[id(p)][0], p.shape[0], p.shape[1], ("w", id(p))))
-                srcs.append((self._pv[id(lay.self_attn.linears[0].weight)][0], 3 * d, d, ("qkv", li)))
-        tot = sum((r * c + 3) // 4 * 4 for _, r, c, _ in srcs)
+        # the table's order: the FC weights an input gradient is taken through (all but the first, which has one only under input_norm),
+        # then per layer out, ff1, ff2, qkv
+        lins = self.fc if self.in_norm is not None else self.fc[1:]
+        for st in self.layers:
+            lins = lins + [st["lin_o"], st["lin_ff1"], st["lin_ff2"], st["lin_qkv"]]
+        tot = sum((l.w.numel() + 3) // 4 * 4 for l in lins)
         self.flat_t = torch.zeros(max(tot, 4), **f32)
         desc, tstart, o = [], [0], 0
-        for (so, r, c, key) in srcs:
-            view = self.flat_t[o:o + r * c].view(c, r)
-            if key[0] == "w":
-                self._wT[key[1]] = view
-            else:
-                self.layers[key[1]]["wqkvT"] = view
-            desc += [so, o, r, c]
+        for l in lins:
+            r, c = l.w.shape
+            l.wT = self.flat_t[o:o + r * c].view(c, r)
+            desc += [l.off, o, r, c]
             tstart.append(tstart[-1] + ((r + 31) // 32) * ((c + 31) // 32))
             o += (r * c + 3) // 4 * 4
         self._tdesc = torch.tensor(desc if desc else [0, 0, 0, 0], dtype=torch.int64, device=dev)
         self._tstart = torch.tensor(tstart, dtype=torch.int32, device=dev)
-        self._tn, self._ttiles = len(srcs), tstart[-1]
+        self._tn, self._ttiles = len(lins), tstart[-1]
         # pre-split bf16 hi / lo IMAGES of the weights and of their transposes (same offsets as flat_p / flat_t): what the
         # large-tile NT GEMMs stage as operand B without splitting it again in every tile (ltrx_split_image, include/ltrx.h)
         self.flat_pi = torch.empty_like(self.flat_p)
         self.flat_ti = torch.zeros_like(self.flat_t)
+        if self.weight_images:
+            def image(view, base, img):                           # where ``img`` holds the image of ``view``, a piece of ``base``
+                return ctypes.c_void_p(img.data_ptr() + view.data_ptr() - base.data_ptr())
+
+            for l in self.fc + [self.head] + [st[k] for st in self.layers for k in ("lin_qkv", "lin_o", "lin_ff1", "lin_ff2")]:
+                l.w_img = image(l.w, self.flat_p, self.flat_pi)
+            for l in lins:
+                l.wT_img = image(l.wT, self.flat_t, self.flat_ti)
+            if self._x_pad:
+                self.fc[0].w_pad_img = image(self.w0_pad, self.w0_pad, self.w0_pad_i)
         # one-launch refresh (ltrx_weight_images) when every transposed matrix keeps image groups of 4 inside a row
-        self._fused_images = self.nflat % 4 == 0 and all(r % 4 == 0 for _, r, _, _ in srcs)
+        self._fused_images = self.nflat % 4 == 0 and all(l.w.shape[0] % 4 == 0 for l in lins)
         self._refresh_transposes()
 
     def _init_fc_step(self, offs):
@@ -806,9 +838,9 @@ class FusedTrainer(object):
         x = ((x ^ (x >> 15)) * 0x846CA68B) & 0xFFFFFFFF
         return x ^ (x >> 16)
 
-    def _ln_fwd(self, x, res, a, b, xsum, y, mean, rstd, p=0.0, seed=0, rows=None):
-        """y = LN(x + drop_p(res)); xsum = x + drop_p(res)   (over ``rows`` rows, default the step's)"""
-        KN.layernorm_fwd(self.lib, self._st(), x, res, a, b, self.rows if rows is None else rows, self.ln_eps, xsum, y, mean, rstd, p, seed,
+    def _ln_fwd(self, x, res, nm, xsum, y, mean, rstd, p=0.0, seed=0, rows=None):
+        """y = LN(x + drop_p(res)) of the Norm ``nm``; xsum = x + drop_p(res)   (over ``rows`` rows, default the step's)"""
+        KN.layernorm_fwd(self.lib, self._st(), x, res, nm.a, nm.b, self.rows if rows is None else rows, nm.eps, xsum, y, mean, rstd, p, seed,
                          self.drop_step)
 
     def _drop_apply(self, src, dst, p, seed):
@@ -834,13 +866,13 @@ class FusedTrainer(object):
         self._red_pending.append((buf.data_ptr(), nrows, 2 * self.d, self.d, da.data_ptr()))
         self._red_pending.append((buf.data_ptr() + 4 * self.d, nrows, 2 * self.d, self.d, db.data_ptr()))
 
-    def _ln_bwd(self, dy, xsum, a, mean, rstd, dres, dx, da, db):
+    def _ln_bwd(self, dy, xsum, nm, mean, rstd, dres, dx):
         buf = self._ln_partial_slot()
         if buf is not None:                                       # dx now, the parameter gradients with the layer's reductions
-            nrows = KN.layernorm_bwd_partial(self.lib, self._st(), dy, xsum, a, mean, rstd, dres, self.rows, self.ln_eps, dx, buf)
-            self._ln_partials_queue(buf, nrows, da, db)
+            nrows = KN.layernorm_bwd_partial(self.lib, self._st(), dy, xsum, nm.a, mean, rstd, dres, self.rows, nm.eps, dx, buf)
+            self._ln_partials_queue(buf, nrows, nm.ga, nm.gb)
             return
-        KN.layernorm_bwd(self.lib, self._st(), dy, xsum, a, mean, rstd, dres, self.rows, self.ln_eps, dx, da, db, self.ws_ln)
+        KN.layernorm_bwd(self.lib, self._st(), dy, xsum, nm.a, mean, rstd, dres, self.rows, nm.eps, dx, nm.ga, nm.gb, self.ws_ln)
 
     def _colsum(self, a, out):
         KN.colsum(self.lib, self._st(), a, self.rows, out, self.ws_col)
@@ -855,10 +887,10 @@ class FusedTrainer(object):
 
     def _refresh_transposes(self):
         if self.n_out > 1:                                        # W_out^T [d, d_output] zero-padded to a multiple of 4 columns
-            self.woutT_pad[:, :self.n_out].copy_(self.W(self.model.output_layer.w_1.weight).t())
+            self.woutT_pad[:, :self.n_out].copy_(self.head.w.t())
         if self.gemm == "hipblaslt":
             return
-        w0 = self.W(self.model.input_layer.layers[0].weight) if self._x_pad else None
+        w0 = self.fc[0].w if self._x_pad else None
         if self._fused_images:
             pad = (w0, self.w0_pad, self.w0_pad_i) if self._x_pad else ()
             KN.weight_images(self.lib, self._st(), self.flat_p, self.flat_pi, self.flat_t, self.flat_ti, self._tdesc, self._tstart, self._tn,
@@ -878,25 +910,11 @@ class FusedTrainer(object):
         re-initialisation, an external optimizer on the aliased parameters) bumps the parameters' autograd version counters --
         kernel writes through raw pointers do not -- so a changed counter (or a step of the slate-resident FC path, which never
         touches the images) means: refresh before the next forward."""
-        ver = [p._version for p in self._order]
+        ver = [r.p._version for r in self.params]
         if ver != self._wver or self._images_stale:
             self._refresh_transposes()
-            self._wver = [p._version for p in self._order]
+            self._wver = [r.p._version for r in self.params]
             self._images_stale = False
-
-    def _img(self, w):
-        """address of the pre-split image of a weight view (inside flat_p) or of a transposed copy (inside flat_t); None otherwise"""
-        if w is None or self.gemm == "hipblaslt" or not self.weight_images:
-            return None
-        a = w.data_ptr()
-        pairs = ((self.flat_p, self.flat_pi), (self.flat_t, self.flat_ti))
-        if self._x_pad:
-            pairs += ((self.w0_pad, self.w0_pad_i),)
-        for base, img in pairs:
-            lo = base.data_ptr()
-            if lo <= a < lo + 4 * base.numel():
-                return ctypes.c_void_p(img.data_ptr() + (a - lo))
-        return None
 
     def _bucket_done(self, k):
         """gradient bucket k is final: start its all-reduce(SUM) now, behind the rest of the backward (the collective runs
@@ -935,20 +953,21 @@ class FusedTrainer(object):
         need = self.lib.ltrx_gemm_nt_relu_bits_bytes(self.rows, self.dff, self.d)
         return buf if 0 < need <= buf.numel() else None
 
-    def _gemm_nt(self, a, b, out, M, bias, act, aux, p, seed, what):
+    def _gemm_nt(self, a, b, b_img, out, M, bias, act, aux, p, seed, what):
         """the ltrx_gemm_nt launch of the step: out[:M] = epi_act(a b^T + bias), dropout (p, site ``seed``) in the epilogue; ``aux`` as
-        the act code reads it (include/ltrx.h); ``b``'s split image is passed along where one exists"""
-        KN.gemm_nt(self.lib, self._st(), a, b, out, M, bias, act, aux, p, seed, self.drop_step, self._prec, 0, self._img(b), what)
+        the act code reads it (include/ltrx.h); ``b_img``: the address of ``b``'s split image, or None"""
+        KN.gemm_nt(self.lib, self._st(), a, b, out, M, bias, act, aux, p, seed, self.drop_step, self._prec, 0, b_img, what)
 
-    def _lin_fwd(self, x, w, b, out, act=0, p=0.0, seed=0, res=None, bits=None, rows=None):
-        """out = drop_p(act(x w^T + b)) [+ res]   (nn.Linear forward, act 1 = ReLU; dropout in the epilogue; ``res`` = the
+    def _lin_fwd(self, x, lin, out, act=0, p=0.0, seed=0, res=None, bits=None, rows=None):
+        """out = drop_p(act(x w^T + b)) [+ res]   (the forward of the projection ``lin``, act 1 = ReLU; dropout in the epilogue; ``res`` = the
         residual stream of the SublayerConnection this projection closes, transformer.py:98-106: added in the epilogue, so the
         sum is written once by the GEMM instead of being re-read and re-written by the LayerNorm that follows; ``rows``: the row
         count of the pass, default the step's)"""
         M = self.rows if rows is None else rows
+        b = lin.b
         if self.gemm == "hipblaslt":
             n = M
-            torch.addmm(b, x[:n], w.t(), out=out[:n])
+            torch.addmm(b, x[:n], lin.w.t(), out=out[:n])
             if act == 1:
                 torch.relu_(out[:n])
             if p:
@@ -956,34 +975,38 @@ class FusedTrainer(object):
             if res is not None:
                 out[:n].add_(res[:n])
             return
+        # (the first FC layer over padded input rows multiplies the zero-padded copy of its weight)
+        w, img = (lin.w, lin.w_img) if lin.w_pad is None else (lin.w_pad, lin.w_pad_img)
         if bits is not None and act == 1:                         # ReLU + its one-bit mask for the backward (act 4)
-            self._gemm_nt(x, w, out, M, b, 4, bits, p, seed, "gemm_nt(fwd, relu bits)")
+            self._gemm_nt(x, w, img, out, M, b, 4, bits, p, seed, "gemm_nt(fwd, relu bits)")
         elif res is not None:
-            self._gemm_nt(x, w, out, M, b, 3, res, p, seed, "gemm_nt(fwd)")
+            self._gemm_nt(x, w, img, out, M, b, 3, res, p, seed, "gemm_nt(fwd)")
         else:
-            self._gemm_nt(x, w, out, M, b, act, None, p, seed, "gemm_nt(fwd)")
+            self._gemm_nt(x, w, img, out, M, b, act, None, p, seed, "gemm_nt(fwd)")
 
-    def _lin_dgrad(self, dy, w, wT, out, relu_of=None, p=0.0, seed=0, bits=None):
-        """out = dy w   (input gradient of nn.Linear); wT = w^T contiguous.  With ``relu_of`` (the saved post-ReLU,
+    def _lin_dgrad(self, dy, lin, out, relu_of=None, p=0.0, seed=0, bits=None):
+        """out = dy w   (input gradient of the projection ``lin``, through its contiguous w^T).  With ``relu_of`` (the saved post-ReLU,
         post-dropout activation that produced the layer input) the ReLU(+dropout p) backward mask is applied in the GEMM
         epilogue; without it, p > 0 re-applies the dropout mask of site ``seed`` (identity activation)."""
         if self.gemm == "hipblaslt":
-            torch.mm(dy[:self.rows, :w.shape[0]], w, out=out[:self.rows])      # (dy may carry zero padding columns)
+            torch.mm(dy[:self.rows, :lin.w.shape[0]], lin.w, out=out[:self.rows])      # (dy may carry zero padding columns)
             if relu_of is not None:
                 self._relu_bwd(out, relu_of, p)
             elif p:
                 self._drop_apply(out, out, p, seed)
             return
+        wT, img = lin.wT, lin.wT_img
         if relu_of is None:
-            self._gemm_nt(dy, wT, out, self.rows, None, 0, None, p, seed, "gemm_nt(dgrad)")
+            self._gemm_nt(dy, wT, img, out, self.rows, None, 0, None, p, seed, "gemm_nt(dgrad)")
         elif bits is not None:                                    # the mask written by the forward launch (act 5): 1/32 of the bytes
-            self._gemm_nt(dy, wT, out, self.rows, None, 5, bits, p, seed, "gemm_nt(dgrad, relu bits)")
+            self._gemm_nt(dy, wT, img, out, self.rows, None, 5, bits, p, seed, "gemm_nt(dgrad, relu bits)")
         else:
-            self._gemm_nt(dy, wT, out, self.rows, None, 2, relu_of, p, seed, "gemm_nt(dgrad)")
+            self._gemm_nt(dy, wT, img, out, self.rows, None, 2, relu_of, p, seed, "gemm_nt(dgrad)")
 
-    def _lin_wgrad(self, dy, x, gw, gb, defer=False):
-        """gw = dy^T x, gb = column sums of dy   (weight and bias gradients of nn.Linear).  ``defer``: an encoder-layer projection
+    def _lin_wgrad(self, dy, x, lin, defer=False):
+        """lin.gw = dy^T x, lin.gb = column sums of dy   (weight and bias gradients of the projection).  ``defer``: an encoder-layer projection
         -- queued for the layer's one grouped launch (_wgrad_flush); dy and x must stay untouched until then."""
+        gw, gb = lin.gw, lin.gb
         if self.gemm == "hipblaslt":
             torch.mm(dy[:self.rows].t(), x[:self.rows], out=gw)
             self._colsum(dy, gb)
@@ -1021,9 +1044,9 @@ class FusedTrainer(object):
         if ln is None:
             slabs = KN.gemm_tn_group(self.lib, self._st(), q, self.rows, self._prec, self.ws_tn, defer_reduce, "gemm_tn_group(wgrad)")
         else:
-            dy, xsum, a, mean, rstd, dres, dx, da, db = ln
-            slabs, ln_rows, side = KN.gemm_tn_group_ln(self.lib, self._st(), q, self.rows, self._prec, self.ws_tn, dy, xsum, a, mean, rstd,
-                                                       dres, self.ln_eps, dx, buf, defer_reduce,
+            dy, xsum, nm, mean, rstd, dres, dx = ln
+            slabs, ln_rows, side = KN.gemm_tn_group_ln(self.lib, self._st(), q, self.rows, self._prec, self.ws_tn, dy, xsum, nm.a, mean, rstd,
+                                                       dres, nm.eps, dx, buf, defer_reduce,
                                                        "gemm_tn_group_ln(wgrad + layernorm_bwd)")
             self.ln_side_log.append(side)
             del self.ln_side_log[:-16]
@@ -1038,7 +1061,7 @@ class FusedTrainer(object):
                 if bso[i]:
                     self._red_pending.append((bso[i], splits, t[0].shape[1], t[0].shape[1], t[3].data_ptr()))
         if ln is not None:                                        # (after the slabs: the queue position _ln_bwd's entries had)
-            self._ln_partials_queue(buf, ln_rows, da, db)
+            self._ln_partials_queue(buf, ln_rows, nm.ga, nm.gb)
         q.clear()
 
     def _reduce_flush(self):
@@ -1060,74 +1083,63 @@ class FusedTrainer(object):
         lib, M, d, B, L = self.lib, bs.rows, self.d, bs.B, bs.L
         stream = self._st()                                       # (of the row movers: the pass stays on one stream)
         kpm = bs.mask if bs.layout == "grid" else None            # packed rows are all valid keys
-        W = self.W
-        fc = self.model.input_layer
         dp = (lambda p: p) if train else (lambda p: 0.0)          # dropout rate of a site in this pass
         h = bs.x_in
-        if self.in_norm is not None and self._x_pad:              # ... into the first F columns of the padded operand rows
-            KN.layernorm_torch_fwd_strided(lib, self._st(), h, W(self.in_norm.weight), W(self.in_norm.bias), M, self.in_norm.eps, bs.x_norm,
-                                           bs.mean_in, bs.rstd_in)
+        nm = self.norm_in
+        if nm is not None and self._x_pad:                        # ... into the first F columns of the padded operand rows
+            KN.layernorm_torch_fwd_strided(lib, self._st(), h, nm.a, nm.b, M, nm.eps, bs.x_norm, bs.mean_in, bs.rstd_in)
             h = bs.x_norm
-        elif self.in_norm is not None:                            # FCModel.input_norm (model.py:39)
-            KN.layernorm_torch_fwd(lib, self._st(), h, W(self.in_norm.weight), W(self.in_norm.bias), M, self.in_norm.eps, bs.x_norm,
-                                   bs.mean_in, bs.rstd_in)
+        elif nm is not None:                                      # FCModel.input_norm (model.py:39)
+            KN.layernorm_torch_fwd(lib, self._st(), h, nm.a, nm.b, M, nm.eps, bs.x_norm, bs.mean_in, bs.rstd_in)
             h = bs.x_norm
-        for i, lyr in enumerate(fc.layers):
-            w_i = W(lyr.weight)
-            if i == 0 and self._x_pad and self.gemm != "hipblaslt":     # F rounded up to the GEMM's K step: padded rows x padded W_0
-                h, w_i = bs.x_in_k, self.w0_pad                    # (hipblaslt: torch.addmm over the [:, :F] view and W_0 itself)
+        for i, lin in enumerate(self.fc):
+            if lin.w_pad is not None:                              # F rounded up to the GEMM's K step: padded rows x padded W_0
+                h = bs.x_in_k                                      # (hipblaslt has no w_pad: torch.addmm over the [:, :F] view and W_0 itself)
             if self.fc_act >= 3:                                   # Sigmoid / Tanh: GEMM + bias, then the activation in place
-                self._lin_fwd(h, w_i, W(lyr.bias), bs.fc_out[i], rows=M)
+                self._lin_fwd(h, lin, bs.fc_out[i], rows=M)
                 KN.out_act_fwd(lib, self._st(), bs.fc_out[i], M * bs.fc_out[i].shape[1], self.fc_act - 2, bs.fc_out[i], "fc_act_fwd")
             else:
-                self._lin_fwd(h, w_i, W(lyr.bias), bs.fc_out[i], self.fc_act, dp(self.p_fc), self._site(1000 + i), rows=M)
+                self._lin_fwd(h, lin, bs.fc_out[i], self.fc_act, dp(self.p_fc), self._site(1000 + i), rows=M)
             h = bs.fc_out[i]
         if self.pos is not None:                                  # transformer.py:51-52: x = sqrt(d) x + pe[rank]
-            KN.posenc_fwd(lib, self._st(), h, self._pos_table(), bs.idx_rows, kpm, M, self.pos_pad, float(d) ** 0.5, bs.x_pe)
+            KN.posenc_fwd(lib, self._st(), h, self.pos_table, bs.idx_rows, kpm, M, self.pos_pad, float(d) ** 0.5, bs.x_pe)
             h = bs.x_pe
         x = h                                                     # residual stream
         for i, st in enumerate(bs.layers):
-            lay = st["mod"]
-            n0, n1 = lay.sublayer[0].norm, lay.sublayer[1].norm
-            self._ln_fwd(x, None, W(n0.a_2), W(n0.b_2), None, st["xn0"], st["mean0"], st["rstd0"], rows=M)
+            self._ln_fwd(x, None, st["norm0"], None, st["xn0"], st["mean0"], st["rstd0"], rows=M)
             st["xin"] = x
-            self._lin_fwd(st["xn0"], st["wqkv"], st["bqkv"], st["qkv"], rows=M)
+            self._lin_fwd(st["xn0"], st["lin_qkv"], st["qkv"], rows=M)
             KN.mha_fwd(lib, self._st(), st["q"], st["k"], st["v"], kpm, B, L, self.h, st["o"], st["lse"], dp(st["p_att"]), st["s_att"],
                        self.drop_step, bs.cu, bs.order, self._mha_mode)
             RW.zero_attention_tail(bs, lib, stream, st["o"])
-            lo = lay.self_attn.linears[3]
             # x1 = x + dropout(attention branch): the residual sum is the out-projection's epilogue (act 3)
-            self._lin_fwd(st["o"], W(lo.weight), W(lo.bias), st["x1"], 0, dp(st["p_s0"]), st["s_s0"], res=x, rows=M)
-            self._ln_fwd(st["x1"], None, W(n1.a_2), W(n1.b_2), None, st["xn1"], st["mean1"], st["rstd1"], rows=M)
-            ff = lay.feed_forward
+            self._lin_fwd(st["o"], st["lin_o"], st["x1"], 0, dp(st["p_s0"]), st["s_s0"], res=x, rows=M)
+            self._ln_fwd(st["x1"], None, st["norm1"], None, st["xn1"], st["mean1"], st["rstd1"], rows=M)
             if self.probe is not None and train:                  # bench.py: HIP events around the roofline kernel, in the step
                 ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 ev0.record()
-            self._lin_fwd(st["xn1"], W(ff.w_1.weight), W(ff.w_1.bias), st["r"], 1, dp(st["p_ff"]), st["s_ff"],
+            self._lin_fwd(st["xn1"], st["lin_ff1"], st["r"], 1, dp(st["p_ff"]), st["s_ff"],
                           bits=self._relu_bits(st) if train else None, rows=M)
             if self.probe is not None and train:
                 ev1.record()
                 self.probe.append((ev0, ev1))
             # x(next layer) = x1 + dropout(feed-forward branch), again in the epilogue of the projection that closes the sublayer
             nxt = bs.layers[i + 1]["xsum0"] if i + 1 < len(bs.layers) else bs.xsum_f
-            self._lin_fwd(st["r"], W(ff.w_2.weight), W(ff.w_2.bias), nxt, 0, dp(st["p_s1"]), st["s_s1"], res=st["x1"], rows=M)
+            self._lin_fwd(st["r"], st["lin_ff2"], nxt, 0, dp(st["p_s1"]), st["s_s1"], res=st["x1"], rows=M)
             x = nxt
-        out = self.model.output_layer
-        no = self.n_out
+        nf, head, no = self.norm_f, self.head, self.n_out
         sc_rows = bs.scores_raw if bs.layout == "grid" else bs.scores_c
         feat = x
         if self.N and not self.norm_head:
-            nf = self.enc.norm
-            self._ln_fwd(x, None, W(nf.a_2), W(nf.b_2), None, bs.xf, bs.mean_f, bs.rstd_f, rows=M)
+            self._ln_fwd(x, None, nf, None, bs.xf, bs.mean_f, bs.rstd_f, rows=M)
             feat = bs.xf
         if self.norm_head:                                        # final norm + score head in one pass: LN(x) stays in registers
-            nf, feat = self.enc.norm, None
-            KN.norm_head_fwd(lib, self._st(), x, W(nf.a_2), W(nf.b_2), W(out.w_1.weight), W(out.w_1.bias), M, self.ln_eps, sc_rows,
-                             bs.mean_f, bs.rstd_f)
+            feat = None
+            KN.norm_head_fwd(lib, self._st(), x, nf.a, nf.b, head.w, head.b, M, nf.eps, sc_rows, bs.mean_f, bs.rstd_f)
         elif no == 1:
-            KN.score_head_fwd(lib, self._st(), feat, W(out.w_1.weight), W(out.w_1.bias), M, sc_rows)
+            KN.score_head_fwd(lib, self._st(), feat, head.w, head.b, M, sc_rows)
         else:                                                     # Linear(d, d_output) as a GEMM (model.py:117)
-            self._lin_fwd(feat, W(out.w_1.weight), W(out.w_1.bias), sc_rows.view(-1, no), rows=M)
+            self._lin_fwd(feat, head, sc_rows.view(-1, no), rows=M)
         if self.out_act:                                          # OutputLayer activation (model.py:117), in place
             KN.out_act_fwd(lib, self._st(), sc_rows, M * no, self.out_act, sc_rows)
         RW.scores_to_grid(bs, lib, stream, sc_rows, no)           # packed scores -> the padded [B, L] grid of the loss kernels
@@ -1138,11 +1150,8 @@ class FusedTrainer(object):
     def _body(self):
         lib, M, d, B, L = self.lib, self.rows, self.d, self.B, self.L
         stream = self._st()                                       # (of the row movers)
-        W, G = self.W, self.G
         kpm = self.mask if self.layout == "grid" else None
-        fc = self.model.input_layer
-        out = self.model.output_layer
-        no = self.n_out
+        nf, head, no = self.norm_f, self.head, self.n_out
         self._wg_pending.clear()                                  # (a step that raised half-way must not leave work queued)
         self._red_pending.clear()
         self._ln_slot = 0
@@ -1159,30 +1168,23 @@ class FusedTrainer(object):
             # backward of the fused pair.  The head's own gradients first, in ltrx_score_head_bwd's row order (their bits), from the
             # recomputed LN(x); then d_xf = dsc w is formed in registers and dx lands where _ln_bwd put it, the (a_2, b_2) partials
             # joining the last layer's one reducing launch as _ln_bwd's do
-            nf = self.enc.norm
-            KN.norm_head_wgrad(lib, self._st(), dsc, self.xsum_f, W(nf.a_2), W(nf.b_2), self.mean_f, self.rstd_f, M, G(out.w_1.weight),
-                               G(out.w_1.bias), self.ws_head)
+            KN.norm_head_wgrad(lib, self._st(), dsc, self.xsum_f, nf.a, nf.b, self.mean_f, self.rstd_f, M, head.gw, head.gb, self.ws_head)
             buf = self._ln_partial_slot()                         # (never None: norm_head implies the deferred reduction, slot 0)
-            nrows = KN.norm_head_bwd_partial(lib, self._st(), dsc, self.xsum_f, W(nf.a_2), W(out.w_1.weight), self.mean_f, self.rstd_f, M,
-                                             self.ln_eps, gb, buf)
-            self._ln_partials_queue(buf, nrows, G(nf.a_2), G(nf.b_2))
+            nrows = KN.norm_head_bwd_partial(lib, self._st(), dsc, self.xsum_f, nf.a, head.w, self.mean_f, self.rstd_f, M, nf.eps, gb, buf)
+            self._ln_partials_queue(buf, nrows, nf.ga, nf.gb)
         elif no == 1:
-            KN.score_head_bwd(lib, self._st(), dsc, feat, W(out.w_1.weight), M, ga, G(out.w_1.weight), G(out.w_1.bias), self.ws_head)
+            KN.score_head_bwd(lib, self._st(), dsc, feat, head.w, M, ga, head.gw, head.gb, self.ws_head)
         else:                                                     # the d_output-wide head: weight / bias / input gradients as GEMMs
             self.dz_pad[:M, :no].copy_(dsc.reshape(-1, no)[:M])
-            self._lin_wgrad(self.dz_pad[:, :no], feat, G(out.w_1.weight), G(out.w_1.bias))
-            self._lin_dgrad(self.dz_pad, W(out.w_1.weight), self.woutT_pad, ga)
+            self._lin_wgrad(self.dz_pad[:, :no], feat, head)
+            self._lin_dgrad(self.dz_pad, head, ga)                # (through woutT_pad)
         if self.N:
-            nf = self.enc.norm
             if not self.norm_head:
-                self._ln_bwd(ga, self.xsum_f, W(nf.a_2), self.mean_f, self.rstd_f, None, gb, G(nf.a_2), G(nf.b_2))
+                self._ln_bwd(ga, self.xsum_f, nf, self.mean_f, self.rstd_f, None, gb)
             ds = gb                                               # d loss / d (x1_last + ffn_last)
             other = ga
             for i in range(self.N - 1, -1, -1):
                 st = self.layers[i]
-                lay = st["mod"]
-                n0, n1 = lay.sublayer[0].norm, lay.sublayer[1].norm
-                ff = lay.feed_forward
                 d_r, dqkv = self.d_r, self.dqkv
                 # where the two LayerNorm backwards of the layer write: ping-pong over (ga, gb); with ln_in_wgrad the second one runs
                 # WHILE the weight gradients read ds (the FFN-2 dY operand), so it writes a third buffer and the three rotate
@@ -1191,26 +1193,24 @@ class FusedTrainer(object):
                 db = self._branch_grad(ds, st["p_s1"], st["s_s1"])
                 # (the four weight gradients of the layer are queued and run as one grouped launch before the first kernel that
                 #  overwrites one of their operands: the LN0 backward below, or the second use of the dropout buffer d_br)
-                self._lin_wgrad(db, st["r"], G(ff.w_2.weight), G(ff.w_2.bias), defer=True)
-                self._lin_dgrad(db, W(ff.w_2.weight), self._wT.get(id(ff.w_2.weight)), d_r, relu_of=st["r"], p=st["p_ff"],
-                                bits=self._relu_bits(st))
-                self._lin_wgrad(d_r, st["xn1"], G(ff.w_1.weight), G(ff.w_1.bias), defer=True)
-                self._lin_dgrad(d_r, W(ff.w_1.weight), self._wT.get(id(ff.w_1.weight)), self.tmp_d)
-                self._ln_bwd(self.tmp_d, st["x1"], W(n1.a_2), st["mean1"], st["rstd1"], ds, mid, G(n1.a_2), G(n1.b_2))
+                self._lin_wgrad(db, st["r"], st["lin_ff2"], defer=True)
+                self._lin_dgrad(db, st["lin_ff2"], d_r, relu_of=st["r"], p=st["p_ff"], bits=self._relu_bits(st))
+                self._lin_wgrad(d_r, st["xn1"], st["lin_ff1"], defer=True)
+                self._lin_dgrad(d_r, st["lin_ff1"], self.tmp_d)
+                self._ln_bwd(self.tmp_d, st["x1"], st["norm1"], st["mean1"], st["rstd1"], ds, mid)
                 ds = mid                                           # ds = d loss / d x1
                 # attention branch
-                lo = lay.self_attn.linears[3]
                 if st["p_s0"] and st["p_s1"]:                      # d_br still holds the FFN branch's dY
                     self._wgrad_flush()
                 db = self._branch_grad(ds, st["p_s0"], st["s_s0"])
-                self._lin_wgrad(db, st["o"], G(lo.weight), G(lo.bias), defer=True)
-                self._lin_dgrad(db, W(lo.weight), self._wT.get(id(lo.weight)), self.d_o)
+                self._lin_wgrad(db, st["o"], st["lin_o"], defer=True)
+                self._lin_dgrad(db, st["lin_o"], self.d_o)
                 KN.mha_bwd(lib, self._st(), st["q"], st["k"], st["v"], kpm, st["o"], self.d_o, st["lse"], B, L, self.h, self.dq, self.dk,
                            self.dv, st["p_att"], st["s_att"], self.drop_step, self.cu, self.order, self._mha_mode, self.ws_mha)
                 RW.zero_gradient_tail(self, lib, stream, dqkv)
-                self._lin_wgrad(dqkv, st["xn0"], st["gwqkv"], st["gbqkv"], defer=True)
-                self._lin_dgrad(dqkv, st["wqkv"], st.get("wqkvT"), self.tmp_d)
-                ln0 = (self.tmp_d, st["xin"], W(n0.a_2), st["mean0"], st["rstd0"], ds, outb, G(n0.a_2), G(n0.b_2))
+                self._lin_wgrad(dqkv, st["xn0"], st["lin_qkv"], defer=True)
+                self._lin_dgrad(dqkv, st["lin_qkv"], self.tmp_d)
+                ln0 = (self.tmp_d, st["xin"], st["norm0"], st["mean0"], st["rstd0"], ds, outb)
                 if spare is None:
                     self._wgrad_flush(defer_reduce=True)
                     self._ln_bwd(*ln0)
@@ -1224,11 +1224,11 @@ class FusedTrainer(object):
             ds, other = ga, gb
         if self.pos is not None:                                  # backward of x = sqrt(d) fc_out + pe[rank]
             if self.pos_learned:
-                KN.posenc_table_bwd(lib, self._st(), ds, self.idx_rows, kpm, M, self.pos_pad, G(self.pos.pe.weight))
+                KN.posenc_table_bwd(lib, self._st(), ds, self.idx_rows, kpm, M, self.pos_pad, self.pos_g)
             KN.scale_inplace(lib, self._st(), ds, M * d, float(d) ** 0.5)
         # FC stack
         for i in range(self.nfc - 1, -1, -1):
-            lyr = fc.layers[i]
+            lin = self.fc[i]
             if i == self.nfc - 1:                                # the last FC activation(+dropout) feeds the encoder / head
                 if self.fc_act >= 3:
                     KN.out_act_bwd(lib, self._st(), ds, self.fc_out[i], M * ds.shape[1], self.fc_act - 2, ds, "fc_act_bwd")
@@ -1237,16 +1237,16 @@ class FusedTrainer(object):
                 elif self.p_fc:
                     self._drop_apply(ds, ds, self.p_fc, self._site(1000 + i))
             inp = (self.x_norm if self.in_norm is not None else self.x_in) if i == 0 else self.fc_out[i - 1]
-            self._lin_wgrad(ds, inp, G(lyr.weight), G(lyr.bias))
+            self._lin_wgrad(ds, inp, lin)
             if i == 0 and self.in_norm is not None:
                 # nn.LayerNorm parameter gradients: dw = sum dy * xhat, db = sum dy with dy = ds W_0 (the input itself needs no
                 # gradient; ltrx_layernorm_bwd's da / db formulas only use the saved mean and rstd, its dx output is scratch)
-                self._lin_dgrad(ds, W(lyr.weight), self._wT.get(id(lyr.weight)), self.d_in)
-                KN.layernorm_bwd(lib, self._st(), self.d_in, self.x_in, W(self.in_norm.weight), self.mean_in, self.rstd_in, None, M,
-                                 self.in_norm.eps, self.d_in, G(self.in_norm.weight), G(self.in_norm.bias), self.ws_ln_in,
-                                 "layernorm_bwd(input_norm)")
+                nm = self.norm_in
+                self._lin_dgrad(ds, lin, self.d_in)
+                KN.layernorm_bwd(lib, self._st(), self.d_in, self.x_in, nm.a, self.mean_in, self.rstd_in, None, M, nm.eps, self.d_in, nm.ga,
+                                 nm.gb, self.ws_ln_in, "layernorm_bwd(input_norm)")
             if i > 0:
-                self._lin_dgrad(ds, W(lyr.weight), self._wT.get(id(lyr.weight)), self.fc_dgrad[i - 1],
+                self._lin_dgrad(ds, lin, self.fc_dgrad[i - 1],
                                 relu_of=self.fc_out[i - 1] if self.fc_act == 1 else None, p=self.p_fc,
                                 seed=self._site(1000 + i - 1))
                 ds = self.fc_dgrad[i - 1]
@@ -1254,9 +1254,6 @@ class FusedTrainer(object):
                     KN.out_act_bwd(lib, self._st(), ds, self.fc_out[i - 1], M * ds.shape[1], self.fc_act - 2, ds, "fc_act_bwd")
         self._bucket_done(len(self._buckets) - 1)
         return loss
-
-    def _pos_table(self):
-        return self.W(self.pos.pe.weight) if self.pos_learned else self.pos.pe
 
     def _adam(self):
         if self.clip:
@@ -1283,9 +1280,8 @@ class FusedTrainer(object):
         non-finite gradient elements), or (None, 0): the finiteness check that stands in for torch.autograd.detect_anomaly() on a
         step without an autograd graph (main.py:89).  One launch over the flat gradient buffer, one host sync."""
         if getattr(self, "_nf_seg", None) is None:
-            names = {id(p): n for n, p in self.model.named_parameters()}
-            self._nf_names = [names.get(id(p), "?") for p in self._order]
-            self._nf_seg = torch.tensor([self._pv[id(p)][0] for p in self._order], dtype=torch.int64, device=self.dev)
+            self._nf_names = [r.name for r in self.params]
+            self._nf_seg = torch.tensor([r.off for r in self.params], dtype=torch.int64, device=self.dev)
             self._nf_out = torch.zeros(2, dtype=torch.int32, device=self.dev)
         KN.first_nonfinite(self.lib, self._st(), self.flat_g, self._nf_seg, self._nf_out)
         first, count = (int(v) for v in self._nf_out.cpu())
@@ -1299,16 +1295,20 @@ class FusedTrainer(object):
             self._graphs.clear()
 
     # ---- checkpointing: the state of a fused run that neither the nn.Module nor the torch.optim object sees ------------------------
-    def _named_order(self):
-        """[(name, parameter)] in ``model.named_parameters()`` order"""
-        return list(self.model.named_parameters())
+    def _moment_slots(self):
+        """the optimizer's moment slots in the neutral schema of allrank_amd.checkpoint, each with the flat buffer that holds it
+        (1: flat_m, 2: flat_v)"""
+        return (("momentum_buffer", 1),) if self.optimizer == "SGD" else (("exp_avg", 1), ("exp_avg_sq", 2))
+
+    def _hyper(self):
+        from . import checkpoint as CK
+        return CK.hyper(self.optimizer, self.lr, self.betas, self.eps, self.weight_decay, self.momentum, self.nesterov)
 
     def meta(self):
         """what ``checkpoint.check_compatible`` compares: parameter names / shapes, optimizer kind and hyper-parameters, loss, clipping"""
         from . import checkpoint as CK
-        return CK.make_meta(self._named_order(), self.optimizer,
-                            CK.hyper(self.optimizer, self.lr, self.betas, self.eps, self.weight_decay, self.momentum, self.nesterov),
-                            self.loss.name, self._loss_args, self.clip)
+        return CK.make_meta([(r.name, r.p) for r in self._params_named], self.optimizer, self._hyper(), self.loss.name, self._loss_args,
+                            self.clip)
 
     def state_dict(self):
         """Everything a resumed run needs to be THIS run, as CPU tensors and plain values (one device-to-host copy, one host sync):
@@ -1317,20 +1317,16 @@ class FusedTrainer(object):
         ``step`` from the device step count, the dropout / noise step word ``drop_step`` (as u32), the generator ``seed``, ``lr``,
         the state of the ListMLE tie-shuffle generator, and the ``meta`` block.  Not state: B, L, the row layout, the gemm mode,
         graphs and workspaces, scorers."""
-        from . import checkpoint as CK
         n = self.nflat
         host = torch.cat([self.flat_p, self.flat_m, self.flat_v, self.step_count, self.drop_step.view(torch.float32)]).cpu()
         step, word = int(host[3 * n].item()), int(host[3 * n + 1:].view(torch.int32).item()) & 0xFFFFFFFF
-        slots = {"SGD": (("momentum_buffer", 1),)}.get(self.optimizer, (("exp_avg", 1), ("exp_avg_sq", 2)))
         params, moments = {}, {}
-        for name, p in self._named_order():
-            o, shape = self._pv[id(p)]
-            seg = lambda k: host[k * n + o:k * n + o + p.numel()].view(shape).clone()
-            params[name] = seg(0)
-            moments[name] = {slot: seg(k) for slot, k in slots}
-        hyper = CK.hyper(self.optimizer, self.lr, self.betas, self.eps, self.weight_decay, self.momentum, self.nesterov)
+        for r in self._params_named:
+            seg = lambda k: host[k * n + r.off:k * n + r.off + r.w.numel()].view(r.w.shape).clone()
+            params[r.name] = seg(0)
+            moments[r.name] = {slot: seg(k) for slot, k in self._moment_slots()}
         return {"params": params,
-                "optimizer": {"kind": self.optimizer, "hyper": hyper, "step": step, "state": moments},
+                "optimizer": {"kind": self.optimizer, "hyper": self._hyper(), "step": step, "state": moments},
                 "drop_step": word, "seed": int(self._seed), "lr": float(self.lr), "perm_gen": self._perm_gen.get_state().cpu().clone(),
                 "meta": self.meta()}
 
@@ -1348,16 +1344,15 @@ class FusedTrainer(object):
         if "state" not in opt:
             raise ValueError("checkpoint: the stored optimizer state is a raw torch %s state_dict: only the autograd engine resumes it"
                              % (opt.get("kind"),))
-        slots = {"SGD": (("momentum_buffer", 1),)}.get(self.optimizer, (("exp_avg", 1), ("exp_avg_sq", 2)))
         n = self.nflat
         host = torch.zeros(3 * n, dtype=torch.float32)
-        for name, p in self._named_order():
-            o, shape = self._pv[id(p)]
-            srcs = [(sd["params"].get(name), 0)] + [(opt["state"].get(name, {}).get(slot), k) for slot, k in slots]
+        for r in self._params_named:
+            name, o, shape = r.name, r.off, r.w.shape
+            srcs = [(sd["params"].get(name), 0)] + [(opt["state"].get(name, {}).get(slot), k) for slot, k in self._moment_slots()]
             for t, k in srcs:
                 if t is None or tuple(t.shape) != tuple(shape):
                     raise ValueError("checkpoint: parameter %s: no tensor of shape %s in the %s" % (name, tuple(shape), "parameters" if k == 0 else "optimizer state"))
-                host[k * n + o:k * n + o + p.numel()].copy_(t.reshape(-1))
+                host[k * n + o:k * n + o + r.w.numel()].copy_(t.reshape(-1))
         dev = host.to(self.dev)
         self.flat_p.copy_(dev[:n])
         self.flat_m.copy_(dev[n:2 * n])
@@ -1370,12 +1365,14 @@ class FusedTrainer(object):
         self.set_lr(float(sd["lr"]))
         if sd.get("seed") is not None and int(sd["seed"]) != self._seed:
             self._seed = int(sd["seed"]) & 0xFFFFFFFF
-            for i, st in enumerate(self.layers):
-                st.update(s_att=self._site(4 * i), s_ff=self._site(4 * i + 1), s_s0=self._site(4 * i + 2), s_s1=self._site(4 * i + 3))
+            sites, noise = self._site_seeds()
+            for ops, st, seeds in zip(self._layer_ops, self.layers, sites):
+                ops.update(seeds)
+                st.update(seeds)
             self._graphs.clear()
             self._fwd_graphs.graphs.clear()
             if self.loss.stochastic:
-                self.loss.set_noise_key(self._site(2000), self.drop_step)
+                self.loss.set_noise_key(noise, self.drop_step)
         if sd.get("perm_gen") is not None:
             self._perm_gen.set_state(sd["perm_gen"].to(torch.uint8).cpu())
 
@@ -1429,8 +1426,7 @@ class FusedTrainer(object):
     def _reattach(self):
         """the module's parameters / gradients must alias the flat buffers (state_dict(), score() and external readers of
         .grad see what the kernels wrote): re-point anything an external zero_grad(set_to_none=True) / .to() detached."""
-        for p in self._order:
-            w, g = self._wv[id(p)], self._gv[id(p)]
+        for _, p, _, w, g in self.params:
             if p.data.data_ptr() != w.data_ptr():
                 p.data = w
             if p.grad is None or p.grad.data_ptr() != g.data_ptr():

@@ -1,8 +1,8 @@
 """Record which libltrx calls the package makes, and what they compute, over a set of small cases (needs the MI355X).
 
-    python tests/golden/make_call_trace_fixture.py [--set calls|rows|step] [--out FILE] [--commit HASH]
+    python tests/golden/make_call_trace_fixture.py [--set calls|rows|step|options] [--out FILE] [--commit HASH]
 
-Three case sets, one file each, each run ONCE at the commit named in its file ("commit"):
+Four case sets, one file each, each run ONCE at the commit named in its file ("commit"):
   calls  tests/golden/call_trace_parent.json: before the GEMM, attention, LayerNorm and head calls of allrank_amd/ops.py and
          allrank_amd/engine.py moved into the launchers of allrank_amd/kernels.py;
   rows   tests/golden/call_trace_rows_parent.json: the three row layouts (padded grid, index-packed, cu_seqlens-packed) before their
@@ -11,7 +11,12 @@ Three case sets, one file each, each run ONCE at the commit named in its file ("
          ranking call and the click call moved into allrank_amd/kernels.py -- the slate-resident FC + ListNet step (with Adam in the
          launch, with the separate clip + Adam launches, and the linear-scorer form), SGD with Nesterov momentum and without a
          momentum buffer, ``first_nonfinite``, ``inference.rank_batches`` from a padded batch and from a resident set, and
-         ``clicks.click_on_slates`` with a cascade and a diverse plan.
+         ``clicks.click_on_slates`` with a cascade and a diverse plan;
+  options tests/golden/call_trace_options_parent.json: before the step's operands (parameter views, transposed copies, weight images)
+         became records built once at construction -- each A/B switch of the large-tile step off on its own, the two-group
+         weight-gradient composition under sublayer dropout, an FC stack of three layers, the fixed positional encoding on the
+         padded grid, ``score()`` between two steps, ``load_state_dict`` with another seed, and a scorer over an ``input_norm`` model
+         with 46 features.  Its traces begin at the constructor: the size and support queries made there are held too.
 tests/test_gpu_call_trace.py runs the same cases at every later commit and holds them to the recorded calls and results exactly.
 Re-running a set at a later commit only re-records that commit against itself.
 
@@ -43,6 +48,7 @@ DEV = "cuda:0"
 FIXTURE = os.path.join(HERE, "call_trace_parent.json")
 ROWS_FIXTURE = os.path.join(HERE, "call_trace_rows_parent.json")
 STEP_FIXTURE = os.path.join(HERE, "call_trace_step_parent.json")
+OPTIONS_FIXTURE = os.path.join(HERE, "call_trace_options_parent.json")
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -133,15 +139,17 @@ LARGE_LENS = [128] * 12 + [100, 128, 77, 128]
 LARGE_RAGGED = [128, 90, 3, 128, 61, 128, 17, 128, 128, 45, 128, 99, 128, 128, 1, 110]
 
 
-def _train(proxy, model_kw, loss, largs, lens, L, use_idx=False, host_lengths=False, digests=True, **trainer_kw):
+def _train(proxy, model_kw, loss, largs, lens, L, use_idx=False, host_lengths=False, digests=True, construct=False, **trainer_kw):
+    """``construct``: the trace begins with the calls the constructor makes (size and support queries, the first image refresh)"""
     from allrank_amd.engine import FusedTrainer
     model = _model(**model_kw)
-    ft = FusedTrainer(model, loss, largs, len(lens), L, use_graph=False, seed=1234, **trainer_kw)
+    trace, dig = [], {}
+    with _recording(proxy, trace if construct else None):
+        ft = FusedTrainer(model, loss, largs, len(lens), L, use_graph=False, seed=1234, **trainer_kw)
     x, y, idx, hl = _batch(lens, L, model_kw["F"], 3)
     kw = dict(indices=idx) if use_idx else {}
     if host_lengths:
         kw["lengths"] = hl
-    trace, dig = [], {}
     for s in range(3):
         with _recording(proxy, trace if s == 0 else None):
             loss_t = ft.step(x, y, **kw)
@@ -369,7 +377,77 @@ def step_cases():
     }
 
 
-SETS = {"calls": (FIXTURE, cases), "rows": (ROWS_FIXTURE, rows_cases), "step": (STEP_FIXTURE, step_cases)}
+def _step_score_step(proxy):
+    from allrank_amd.engine import FusedTrainer
+    trace, dig = [], {}
+    with _recording(proxy, trace):
+        ft = FusedTrainer(_model(**SMALL), "listNet", {}, 5, 70, use_graph=False, seed=1234)
+        x, y, _, _ = _batch(SMALL_LENS, 70, 20, 3)
+        dig["loss1"], dig["flat_g1"] = _sha(ft.step(x, y)), _sha(ft.flat_g)
+        dig["scores_eval"] = _sha(ft.score(x, y))
+        dig["loss2"] = _sha(ft.step(x, y))
+    dig.update(flat_g=_sha(ft.flat_g), flat_p=_sha(ft.flat_p), scores=_sha(ft.scores))
+    return trace, dig
+
+
+def _reload_other_seed(proxy):
+    from allrank_amd.engine import FusedTrainer
+    trace, dig = [], {}
+    with _recording(proxy, trace):
+        ft = FusedTrainer(_model(**SMALL), "listNet", {}, 5, 70, use_graph=False, seed=1234)
+        x, y, _, _ = _batch(SMALL_LENS, 70, 20, 3)
+        dig["loss1"] = _sha(ft.step(x, y))
+        sd = ft.state_dict()
+        dig["state"] = _sha(torch.cat([t.reshape(-1) for n in sorted(sd["params"])
+                                       for t in [sd["params"][n]] + [sd["optimizer"]["state"][n][k] for k in sorted(sd["optimizer"]["state"][n])]]))
+        dig["meta"] = _sha_bytes(json.dumps(sd["meta"], sort_keys=True, default=repr).encode())
+        ft.load_state_dict(dict(sd, seed=(sd["seed"] + 77) & 0xFFFFFFFF))
+        dig["loaded"] = _sha(torch.cat([ft.flat_p, ft.flat_m, ft.flat_v, ft.step_count]))
+        dig["loss2"] = _sha(ft.step(x, y))
+    dig.update(flat_g=_sha(ft.flat_g), flat_p=_sha(ft.flat_p), scores=_sha(ft.scores))
+    return trace, dig
+
+
+def _scorer_input_norm_46(proxy):
+    from allrank_amd.engine import FusedTrainer
+    trace = []
+    with _recording(proxy, trace):
+        ft = FusedTrainer(_model(**dict(SMALL, F=46, input_norm=True)), "listNet", {}, 5, 70, use_graph=False, seed=1234)
+        xt, yt, _, _ = _batch(SMALL_LENS, 70, 46, 3)
+        ft.step(xt, yt)
+        sc = ft.scorer(5, 90, use_graph=False)
+        x, y, _, hl = _batch(SCORER_LENS, 90, 46, 4)
+        raw = sc.run(x, y, lengths=hl)
+        dig = _packed_digests(sc, raw)
+    return trace, dig
+
+
+def options_cases():
+    """the fourth set: every A/B switch of the large-tile step off on its own, and the paths of construction, scoring and state I/O
+    the first three sets do not reach; every trace begins at the constructor"""
+    def large(model_kw=LARGE, **kw):
+        return lambda p: _train(p, model_kw, "approxNDCGLoss", {}, LARGE_LENS, 128, construct=True, **kw)
+    fc3 = dict(SMALL, sizes=[48, 40, 32], act="ReLU", fc_dropout=0.2)
+    pe = dict(SMALL, pe=dict(strategy="fixed", max_indices=100))
+    return {
+        "large_weight_images_off": large(weight_images=False),
+        "large_group_wgrad_off": large(group_wgrad=False),
+        "large_ln_in_wgrad_off": large(ln_in_wgrad=False),
+        "large_norm_head_off": large(_norm_head=False),
+        "large_pad_input_off": large(pad_input=False),
+        # both sublayer dropouts on: the dropout buffer is reused between the branches, so the layer's weight gradients run as two
+        # groups of two
+        "large_sublayer_dropout": large(dict(LARGE, dropout=0.1)),
+        "fc_stack_three_relu_dropout": lambda p: _train(p, fc3, "listNet", {}, SMALL_LENS, 70, construct=True),
+        "fixed_pe_grid": lambda p: _train(p, pe, "listNet", {}, SMALL_LENS, 70, use_idx=True, construct=True),
+        "step_score_step": _step_score_step,
+        "reload_other_seed": _reload_other_seed,
+        "scorer_input_norm_46": _scorer_input_norm_46,
+    }
+
+
+SETS = {"calls": (FIXTURE, cases), "rows": (ROWS_FIXTURE, rows_cases), "step": (STEP_FIXTURE, step_cases),
+        "options": (OPTIONS_FIXTURE, options_cases)}
 
 
 def run_case(proxy, name):

@@ -45,7 +45,7 @@ def main():
         eag = FusedTrainer(build(norm), "approxNDCGLoss", {}, B, L, lr=1e-3, world_size=1, use_graph=False, force_dist=True)
         assert cap.sharded and eag.sharded and not plain.sharded and cap._x_pad and cap._x_stride == 48
         assert cap._buckets == plain._buckets and cap.nflat == plain.nflat
-        assert [cap._pv[id(p)][0] for p in cap._order] == [plain._pv[id(p)][0] for p in plain._order]
+        assert [r.off for r in cap.params] == [r.off for r in plain.params]
         for step in range(5):                                     # two eager warm-ups, the capture step, two replays
             lp, lc, le = (tr.step(x, y).clone() for tr in (plain, cap, eag))
             assert torch.isfinite(lp).all() and torch.equal(lp, lc) and torch.equal(lp, le), (norm, step, "loss")

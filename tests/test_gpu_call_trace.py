@@ -16,7 +16,13 @@ tests/golden/call_trace_step_parent.json is the third set (``--set step``), reco
 training step's own calls, the ranking call and the click call into allrank_amd/kernels.py: what the two sets above do not reach --
 the slate-resident FC + ListNet step in its three forms, SGD with Nesterov momentum and without a momentum buffer,
 ``first_nonfinite`` (its return value digested too), ``inference.rank_batches`` from a padded batch and from a resident set, and
-``clicks.click_on_slates`` with a cascade and a diverse plan.  The same rules again."""
+``clicks.click_on_slates`` with a cascade and a diverse plan.  The same rules again.
+
+tests/golden/call_trace_options_parent.json is the fourth set (``--set options``), recorded at the parent of the change that made the
+step's operands records built once at construction: each A/B switch of the large-tile step off on its own, the two-group
+weight-gradient composition under sublayer dropout, a three-layer FC stack, the fixed positional encoding on the padded grid,
+``score()`` between two steps, ``load_state_dict`` with another seed, and a scorer over an ``input_norm`` model with 46 features.
+Its traces begin at the constructor, so the size and support queries made there are held as well.  The same rules once more."""
 import json
 
 import pytest
@@ -88,6 +94,33 @@ def test_step_fixture_is_the_parents_and_covers_every_case(recs):
     sgd = {n: [call[1] for call in rec["cases"][n]["trace"] if call[0] == "ltrx_sgd_step"] for n in rec["cases"]}
     assert sgd["sgd_no_momentum"][0][2] == 0 and sgd["sgd_nesterov_weight_decay"][0][2] == 1     # the momentum buffer: NULL, and not
     assert not set(rec["cases"]) & (set(recs["calls"]["cases"]) | set(recs["rows"]["cases"]))
+
+
+def test_options_fixture_is_the_parents_and_covers_every_case(recs):
+    rec = recs["options"]
+    assert len(rec["commit"]) == 40
+    assert sorted(rec["cases"]) == sorted(G.options_cases()) and len(rec["cases"]) == 11
+    for name, c in rec["cases"].items():
+        assert c["trace"] and c["unstable"] == [] and c["digests"], name
+        assert c["trace"][0][0] == "ltrx_mha_head_width_supported", name                  # every trace begins at the constructor
+    calls = {n: [call[0] for call in c["trace"]] for n, c in rec["cases"].items()}
+    # what each switch turns off is absent from its case and present in a case that leaves it on
+    b_image = lambda n: {call[1][4] for call in rec["cases"][n]["trace"] if call[0] == "ltrx_gemm_nt"}  # noqa: E731
+    assert b_image("large_weight_images_off") == {0} and b_image("large_group_wgrad_off") == {1}
+    assert "ltrx_gemm_tn_group_ln" not in calls["large_group_wgrad_off"] and calls["large_group_wgrad_off"].count("ltrx_gemm_tn") == 5
+    assert "ltrx_gemm_tn_group_ln" not in calls["large_ln_in_wgrad_off"] and "ltrx_gemm_tn_group" in calls["large_ln_in_wgrad_off"]
+    assert "ltrx_norm_head_fwd" not in calls["large_norm_head_off"] and "ltrx_norm_head_fwd" in calls["large_pad_input_off"]
+    first_nt = {n: next(call[1] for call in rec["cases"][n]["trace"] if call[0] == "ltrx_gemm_nt") for n in calls}
+    assert first_nt["large_pad_input_off"][1] == 136 and first_nt["large_norm_head_off"][1] == 256      # row stride of the FC operand
+    # both sublayer dropouts on: two grouped launches per layer, and the constructor asks about three compositions
+    assert calls["large_sublayer_dropout"].count("ltrx_debug_tn_group_plan") == 2
+    assert calls["large_sublayer_dropout"].count("ltrx_gemm_tn_group_workspace_bytes") == 3
+    assert calls["fc_stack_three_relu_dropout"].count("ltrx_gemm_tn") == 3 and "ltrx_relu_bwd" in calls["fc_stack_three_relu_dropout"]
+    assert "ltrx_posenc_fwd" in calls["fixed_pe_grid"] and "ltrx_scale_inplace" in calls["fixed_pe_grid"]
+    assert calls["step_score_step"].count("ltrx_adam_step") == 2 and calls["step_score_step"].count("ltrx_score_head_fwd") == 3
+    assert calls["reload_other_seed"].count("ltrx_weight_images") == 4                      # construction, two steps, the stale images
+    assert calls["scorer_input_norm_46"].count("ltrx_layernorm_torch_fwd_strided") == 2
+    assert not set(rec["cases"]) & (set(recs["calls"]["cases"]) | set(recs["rows"]["cases"]) | set(recs["step"]["cases"]))
 
 
 CASE_SET = {name: key for key, (_, make) in G.SETS.items() for name in make()}

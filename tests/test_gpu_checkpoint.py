@@ -234,7 +234,8 @@ def test_trainer_state_dict_restores_in_place_into_a_trainer_with_captured_graph
     ptrs = {k: getattr(b, k).data_ptr() for k in bufs}
     b.load_state_dict(sd)
     assert {k: getattr(b, k).data_ptr() for k in bufs} == ptrs                  # restored in place: nothing was rebound
-    assert all(p.data_ptr() == b._wv[id(p)].data_ptr() for p in model_b.parameters())
+    views_b = {id(r.p): r.w for r in b.params}
+    assert all(p.data_ptr() == views_b[id(p)].data_ptr() for p in model_b.parameters())
     losses_b = [b.step(*batch((x, y, idx), k)).clone() for k in (3, 4)]
     assert torch.equal(losses_b[0], losses_a[3]) and torch.equal(losses_b[1], losses_a[4]), (losses_a, losses_b)
     for k in ("flat_p", "flat_m", "flat_v", "step_count", "drop_step"):
@@ -297,8 +298,9 @@ def test_a_fused_checkpoint_resumes_under_the_autograd_engine_and_the_other_way_
             assert torch.equal(back["optimizer"]["state"][name][slot], state["optimizer"]["state"][name][slot]), (name, slot)
     n = t.nflat                                                                # the segments' padding floats stay zero
     covered = torch.zeros(n, dtype=torch.bool)
+    offs = {id(r.p): r.off for r in t.params}
     for p in model.parameters():
-        o, _ = t._pv[id(p)]
+        o = offs[id(p)]
         covered[o:o + p.numel()] = True
     assert not bool(covered.all()) and all(float(buf.cpu()[~covered].abs().max()) == 0.0 for buf in (t.flat_p, t.flat_m, t.flat_v))
 

@@ -57,9 +57,10 @@ def _run(B, dropout, use_graph, steps):
         assert torch.equal(l_on, l_off) and bool(torch.isfinite(l_on).all()), (i, l_on, l_off)
         assert torch.equal(on.scores, off.scores), i
     p_off = dict(m_off.named_parameters())
+    g_on, g_off = {id(r.p): r.g for r in on.params}, {id(r.p): r.g for r in off.params}
     for n_, p in m_on.named_parameters():
         assert torch.equal(p.data, p_off[n_].data), n_
-        assert torch.equal(on.G(p), off.G(p_off[n_])), n_
+        assert torch.equal(g_on[id(p)], g_off[id(p_off[n_])]), n_
     assert all(took for _, took in on.wgrad_group_log), on.wgrad_group_log
     return on, off
 

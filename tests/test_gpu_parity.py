@@ -1151,8 +1151,9 @@ def test_fused_step_dropout_gradients_match_finite_differences(gemm, fc_act, com
     g = ft.flat_g.clone()
     p0 = ft.flat_p.clone()
     rows, bad = [], []
+    offs = {id(r.p): (r.off, r.w.shape) for r in ft.params}
     for name, prm in model.named_parameters():
-        o, shape = ft._pv[id(prm)]
+        o, shape = offs[id(prm)]
         n = prm.numel()
         gn = float(g[o:o + n].norm().item())
         if gn < 2e-3:

@@ -104,7 +104,7 @@ def test_flat_offsets_stay_16_byte_aligned_with_odd_input_norm_vectors(lib):
         t.LB, t.lib, t.group, t.world, t.model = LB, lib, None, 1, model
         t._read_model(model, True, 0)
         offs = t._layout_parameters(True)
-        assert t._order[0] is model.input_layer.input_norm.weight and t._order[0].numel() == F
+        assert t.params[0].p is model.input_layer.input_norm.weight and t.params[0].p.numel() == F
         assert all(o % 4 == 0 for o in offs) and t.nflat % 4 == 0, (F, offs)
-        assert all(w.data_ptr() % 16 == 0 for w in t._wv.values()) and all(g.data_ptr() % 16 == 0 for g in t._gv.values()), F
+        assert all(r.w.data_ptr() % 16 == 0 for r in t.params) and all(r.g.data_ptr() % 16 == 0 for r in t.params), F
         assert [tuple(v.shape) for v in model.state_dict().values()][:3] == [(F,), (F,), (32, F)]
