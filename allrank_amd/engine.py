@@ -10,6 +10,7 @@ the device; call ``.item()`` when you want it), gradients live in one flat buffe
 import collections
 import contextlib
 import ctypes
+import functools
 import gc
 import logging
 import warnings
@@ -43,14 +44,80 @@ class Lin(object):
 
 
 class Trainer(object):
+    """The autograd engine.  What the epoch loop (fit.py) needs, it and FusedTrainer offer under the same names: ``step_block``,
+    ``score_block``, ``first_nonfinite`` / ``scanned``, ``set_lr``, ``meta`` / ``state_dict`` / ``load_state_dict``, ``compact`` ..."""
+    compact = compact_graph = fcstep = False      # the variable-length layouts and the slate-resident step are FusedTrainer's
+    scanned = "weight"                            # what first_nonfinite() reads
+
     def __init__(self, model, loss_func, optimizer, gradient_clipping_norm=None, world_size=1, group=None):
-        self.model = model
-        self.loss_func = loss_func
-        self.opt = optimizer
-        self.clip = gradient_clipping_norm
-        self.world = world_size
-        self.group = group
+        self.model, self.loss_func, self.opt = model, loss_func, optimizer
+        self.clip, self.world, self.group = gradient_clipping_norm, world_size, group
         self.flat = parallel.FlatGradients(model.parameters(), group)
+        self._meta = None                             # meta(), made once
+
+    def step_block(self, xb, yb, indices, global_batch, lengths=None):
+        """``step`` on this rank's block of a global batch, short or empty; leaves ``scores[:n]`` / ``y_cur[:n]`` (as FusedTrainer's)"""
+        if xb.shape[0] == 0:
+            # (sharded: this rank's block of a short last batch is empty -- the step still has to run, its gradient all-reduce
+            #  is a collective: one fully padded slate, i.e. zero loss and zero gradients.  Found by the 2-rank autograd job of
+            #  tests/dist_fit_worker.py in round 5: the nn.Module forward raised on 0 rows while the peer sat in the all-reduce.)
+            xb, yb, indices = pad_batch(xb, yb, indices, 1)
+        loss = self.step(xb, yb, indices, global_batch=global_batch)
+        self.scores, self.y_cur = self.last_scores, yb
+        return loss
+
+    def score_block(self, xb, yb, indices, lengths=None):
+        return None                               # no forward of its own: validation runs the nn.Module (FusedTrainer.score_block)
+
+    def first_nonfinite(self):
+        """as FusedTrainer's, over the WEIGHTS the last step left: ``flat.zero()`` has run, the gradients are gone"""
+        bad = [(n, int((~torch.isfinite(p.detach())).sum().item())) for n, p in self.model.named_parameters()]
+        return next((n for n, k in bad if k), None), sum(k for _, k in bad)
+
+    def set_lr(self, lr):
+        """nothing to do: the optimizer object a scheduler edits is the one that steps (FusedTrainer: a launch argument)"""
+
+    # ---- checkpointing: FusedTrainer's three members for the nn.Module and the torch optimizer, in the schema of checkpoint.py -----
+    def meta(self):
+        """what ``checkpoint.check_compatible`` compares, as FusedTrainer's; made once: its lr is the job's first (never compared)"""
+        from . import checkpoint as CK
+        if self._meta is None:
+            g, kind, f = self.opt.param_groups[0], CK.neutral_kind(self.opt), self.loss_func
+            hyper = CK.group_hyper(g) if kind is None else CK.hyper(kind, g["lr"], g.get("betas"), g.get("eps"), g.get("weight_decay", 0.0),
+                                                                    g.get("momentum", 0.0), g.get("nesterov", False))
+            if isinstance(f, functools.partial):
+                name, args = getattr(f.func, "__name__", repr(f.func)), dict(f.keywords or {})
+                if f.args:
+                    args["*"] = list(f.args)
+            else:
+                name, args = getattr(f, "__name__", type(f).__name__), {}
+            self._meta = CK.make_meta(list(self.model.named_parameters()), kind or type(self.opt).__name__, hyper, name, args, self.clip)
+        return self._meta
+
+    def state_dict(self):
+        """a checkpoint's "trainer" entry: the module's state_dict, the optimizer's state in the neutral schema (raw outside it)"""
+        from . import checkpoint as CK
+        return {"params": {k: v.detach().cpu() for k, v in self.model.state_dict().items()},
+                "optimizer": CK.to_neutral(self.opt, self.model.named_parameters()),
+                "lr": float(self.opt.param_groups[0]["lr"]), "lrs": [float(g["lr"]) for g in self.opt.param_groups], "meta": self.meta()}
+
+    def load_state_dict(self, state):
+        """a checkpoint's "trainer" entry into the live job, in place; compatibility first (ValueError, nothing touched).  Either
+        engine loads either engine's entry -- only a raw torch optimizer state is tied to this engine and its own class."""
+        from . import checkpoint as CK
+        CK.check_compatible(state["meta"], self.meta())
+        raw = "torch_optimizer" in state["optimizer"]
+        if raw != (CK.neutral_kind(self.opt) is None) or (raw and state["optimizer"]["kind"] != type(self.opt).__name__):
+            raise ValueError("checkpoint: the stored optimizer state (%s, %s) does not fit the live %s"
+                             % (state["optimizer"]["kind"], "raw" if raw else "neutral", type(self.opt).__name__))
+        for n, p in self.model.named_parameters():
+            if n not in state["params"] or tuple(state["params"][n].shape) != tuple(p.shape):
+                raise ValueError("checkpoint: parameter %s: no tensor of shape %s in the checkpoint" % (n, tuple(p.shape)))
+        with torch.no_grad():
+            for k, v in self.model.state_dict().items():
+                if k in state["params"] and tuple(state["params"][k].shape) == tuple(v.shape):
+                    v.copy_(state["params"][k])
+        CK.from_neutral(self.opt, self.model.named_parameters(), state["optimizer"])
 
     def step(self, xb, yb, indices=None, global_batch=None):
         """one training step on this rank's slates; returns the (device) loss tensor -- this rank's share of the
@@ -58,11 +125,7 @@ class Trainer(object):
         self.flat.check()         # .grad must still alias the flat buffer (an external zero_grad(set_to_none=True) detaches it)
         mask = (yb == PADDED_Y_VALUE)
         gb = global_batch if global_batch is not None else xb.shape[0] * self.world
-        if self.world > 1:
-            with sharding.shard_context(gb, self.group):
-                out = self.model(xb, mask, indices)
-                loss = self.loss_func(out, yb)
-        else:
+        with sharding.shard_context(gb, self.group) if self.world > 1 else contextlib.nullcontext():
             out = self.model(xb, mask, indices)
             loss = self.loss_func(out, yb)
         # scores of THIS forward (model.py:82-92: d_output > 1 sums the last axis), for train metrics without a second pass
@@ -1459,6 +1522,23 @@ class FusedTrainer(object):
             if self.pos is not None:
                 self.idx_rows.copy_(indices.reshape(-1))
 
+    scanned = "gradient"                          # what first_nonfinite() reads
+
+    def _block(self, xb, yb, indices, lengths):
+        """a block of up to B slates topped up to the static shape: fully padded slates and, where packed rows run, zero lengths"""
+        n = int(xb.shape[0])
+        if not self.compact:
+            lengths = None
+        elif lengths is not None and n < self.B:
+            lengths = torch.cat([lengths, lengths.new_zeros(self.B - n)])
+        return pad_batch(xb, yb, indices, self.B) + (lengths,)
+
+    def step_block(self, xb, yb, indices, global_batch, lengths=None):
+        """``step`` on this rank's block of a global batch of ``global_batch`` slates as the loader delivered it, short or empty (the
+        loss is normalised by the real slate count); returns the loss and leaves ``scores[:n]`` / ``y_cur[:n]`` of the step"""
+        xs, ys, ids, lengths = self._block(xb, yb, indices, lengths)
+        return self.step(xs, ys, ids, global_batch=global_batch, lengths=lengths)
+
     def step(self, xb, yb, indices=None, global_batch=None, lengths=None):
         """copy the batch into the static input buffers and run (or replay) the step; returns the device loss [1]."""
         self._reattach()
@@ -1654,6 +1734,16 @@ class FusedTrainer(object):
         else:
             self._forward(False)
         return self.scores
+
+    def score_block(self, xb, yb, indices, lengths=None):
+        """``score`` for a validation block of n <= B slates of the training slate length, topped up as ``step_block`` does: (scores
+        [n, L], the model output and the labels of max(n, 1) slates for the loss -- an empty shard still enters it, with one fully
+        padded slate), or None for a block of another shape"""
+        n = int(xb.shape[0])
+        if n > self.B or tuple(xb.shape[1:2]) != (self.L,):
+            return None
+        xs, ys, ids, lengths = self._block(xb, yb, indices, lengths)
+        return self.score(xs, ys, ids, lengths=lengths)[:n], self.scores_raw[:max(n, 1)], ys[:max(n, 1)]
 
     def scorer(self, B, L, use_graph=True, max_graphs=8):
         """a FusedScorer for validation batches of ``B`` slates padded to ``L`` items (any L up to LTRX_MAX_METRIC_SLATE_LEN)"""

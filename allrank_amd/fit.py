@@ -10,44 +10,34 @@ reference's writer is importable, and the returned dict {"epochs", "train_metric
 
 What changes (all outside the arithmetic of a step):
   * a training step is ``FusedTrainer.step`` (hand-written HIP forward/backward/Adam, hipGraph replay) when the model family, the
-    loss and the optimizer allow it -- an allrank_amd LTRModel, a loss from allrank_amd.losses bound with functools.partial (what
-    main.py:83 builds once install() has rebound the names), torch.optim.Adam / AdamW / SGD (one parameter group, any betas / eps /
-    weight decay / momentum; no amsgrad, maximize or dampening) -- and the
-    autograd ``Trainer`` (same kernels for attention / LayerNorm / loss, torch autograd + the given optimizer) otherwise;
-  * host batches are copied on a separate stream one batch ahead (``_Prefetcher``) instead of ``.to(device)`` on the compute
-    stream in front of every step (train_utils.py:95);
+    loss and the optimizer allow it (``_fused_spec``) and the autograd ``Trainer`` (same kernels for attention / LayerNorm / loss,
+    torch autograd + the given optimizer) otherwise.  The two engines offer the loop the same members (engine.Trainer's docstring);
+    after the construction block ``fit()`` talks to "the trainer" and does not ask which one it is;
+  * host batches are copied on a separate stream one batch ahead (``_Prefetcher``) instead of ``.to(device)`` per step (:95);
   * no ``loss.item()`` per step: the running loss is accumulated on the device, one host sync per epoch (train_utils.py:29);
-  * the validation pass runs through ``FusedTrainer.score`` (the forward half of the explicit step, dropout off, its own hipGraph)
-    instead of the nn.Module forward; with ``val_scorer="packed"`` (or ALLRANK_AMD_VAL_SCORER=packed) every validation batch,
-    whatever its slate length, runs the packed, captured forward-only scorer (engine.FusedScorer) on its valid items only; with
-    ``val_scorer="ragged"`` the loss and the metrics of those batches run on the valid items too (allrank_amd.ragged: the cu_seqlens
-    layout of the loss and metric kernels) wherever they have a ragged form, and on the padded grid as under "packed" otherwise;
+  * a validation batch is scored by one of four sources (``_score_batch``): the forward half of the explicit step where the batch
+    has the training shape, else the nn.Module forward; with ``val_scorer="packed"`` / ``"ragged"`` the packed, captured
+    forward-only scorer (engine.FusedScorer), fed from the resident set or from the padded batch (fit()'s docstring);
   * train metrics come from the scores of the training forward itself instead of a second full pass over ``train_dl`` in train()
     mode (train_utils.py:99; same mode, same data).  ``train_metrics="reference"`` (or the environment variable
-    ALLRANK_AMD_TRAIN_METRICS=reference -- main.py passes only config.training's keys) runs the reference's second pass instead: one
-    pass over ``train_dl`` per metric name with the END-of-epoch weights, so ``experiment_result.json``'s ``train_metrics/*`` are the
-    reference's numbers (dropout is off in that pass; the reference leaves it on, so with dropout > 0 its numbers carry that noise);
-  * the loaders' draws from torch's global generator stay in step with the reference's loop: the reference iterates ``train_dl``
-    1 + (number of metric names) times and ``valid_dl`` 1 + (number of metric names) times per epoch (train_utils.py:95-107, :36-43),
-    each iteration drawing a worker base seed and -- shuffled -- a sampler seed; the passes skipped here are replaced by ``_burn``, so
-    under main.py:36-38's seeds epoch e trains on the reference's batches in the reference's order;
-  * batches that are already on the device pass straight through (``allrank_amd.data.DeviceLoader``: the training set lives in HBM,
-    install() binds it behind main.py:57-68); under a process group such a loader yields only this rank's block of each global
-    batch (``ShardBatch``) and nothing is sliced here;
+    ALLRANK_AMD_TRAIN_METRICS=reference) runs the reference's second pass instead: one pass over ``train_dl`` per metric name with
+    the END-of-epoch weights (dropout is off in that pass; the reference leaves it on, so its numbers carry that noise);
+  * the loaders' draws from torch's global generator stay in step with the reference's loop, which iterates ``train_dl`` and
+    ``valid_dl`` 1 + (number of metric names) times per epoch (train_utils.py:95-107, :36-43): the passes skipped here are replaced by
+    ``_burn``, so under main.py:36-38's seeds epoch e trains on the reference's batches in the reference's order;
+  * batches that are already on the device pass straight through (``allrank_amd.data.DeviceLoader``, bound behind main.py:57-68 by
+    install()); under a process group such a loader yields only this rank's block of each global batch (``ShardBatch``);
   * ``config.detect_anomaly`` (main.py:89; the explicit step has no autograd graph for torch's anomaly mode to watch) or
-    LTRX_CHECK_FINITE=1: every step's loss and flat gradient buffer are checked for non-finite values (one fused reduction, one
-    host sync per step) and the first offending parameter tensor is named in the error;
-  * the last, short batch of an epoch (DataLoader drop_last=False) is topped up with fully padded slates for the static-shape step
-    and its loss is normalised by the real slate count;
-  * under an initialised ``torch.distributed`` group every rank takes its contiguous block of each global batch -- training AND
-    validation batches (``_evaluate``) -- (the reference wraps the model in nn.DataParallel instead, main.py:76-78; a DataParallel
-    wrapper passed in is unwrapped);
-  * ``checkpoint_every`` / ``resume`` (or ALLRANK_AMD_CHECKPOINT_EVERY / ALLRANK_AMD_RESUME under main.py): the reference leaves one
-    artefact, ``model.pkl``, when the loop ends; here the whole state of the run -- which under the fused step lives in the trainer's
-    flat buffers and device words, not in the optimizer object -- can be written to ``output_dir/checkpoint.pt`` at epoch boundaries
-    and a stopped job continued as the same job, bit for bit (allrank_amd.checkpoint, FusedTrainer.state_dict).  Off by default:
-    nothing is then added to a step, to ``last_run`` or to ``output_dir``.
+    LTRX_CHECK_FINITE=1: ``_assert_finite`` after every step (one host sync) names the first offending parameter tensor;
+  * the last, short batch of an epoch (DataLoader drop_last=False) trains as it is delivered (``step_block``: the fused engine tops
+    it up with fully padded slates for its static shape); its loss is normalised by the real slate count;
+  * under an initialised ``torch.distributed`` group every rank takes its contiguous block of each global batch, training AND
+    validation (the reference wraps the model in nn.DataParallel instead, main.py:76-78; such a wrapper passed in is unwrapped);
+  * ``checkpoint_every`` / ``resume``: the whole state of the run can be written to ``output_dir/checkpoint.pt`` at epoch boundaries
+    and a stopped job continued as the same job, bit for bit (fit()'s docstring, allrank_amd.checkpoint).  Off by default.
 """
+import collections
+import contextlib
 import functools
 import logging
 import os
@@ -238,20 +228,12 @@ def _my_block(batch, loader, rank, world):
     return xb, yb, idx, n_glob, (batch if pre else None)
 
 
-def _host_lengths(batch, real, pre, world, trainer=None):
+def _host_lengths(batch, real, pre, world):
     """valid items per slate of this rank's block as HOST integers -- what variable-length execution needs to size its launches
     without a device round trip (allrank_amd/rows.py).  A DeviceLoader knows them (the slate lengths of the resident set), and they
-    are usable where they are those of this rank's ``real`` slates; any other loader: None (the valid items are counted on the
-    device, one host sync).  ``trainer``: for its step or ``score()`` -- only where it runs packed rows, topped up to its batch;
-    None: no top-up (a FusedScorer takes a short batch as it is)."""
+    are usable where they are those of this rank's ``real`` slates; any other loader: None (counted on the device, one host sync)."""
     lens = getattr(batch, "lengths", None)
-    if lens is None or not (pre is not None or world == 1) or int(lens.numel()) != real:
-        return None
-    if trainer is None:
-        return lens
-    if not trainer.compact:
-        return None
-    return torch.cat([lens, lens.new_zeros(trainer.B - real)]) if real < trainer.B else lens
+    return lens if lens is not None and (pre is not None or world == 1) and int(lens.numel()) == real else None
 
 
 def _compact_mode(compact):
@@ -274,7 +256,7 @@ def _compact_mode(compact):
 
 def _compact_graph_stats(trainer):
     """last_run["compact_graph"]: what the captured variable-length step did so far (None: the mode is not active)"""
-    if not getattr(trainer, "compact_graph", False):
+    if not getattr(trainer, "compact_graph", False):              # (tools hand it objects that are no trainer)
         return None
     c = trainer.mode_counts
     return {"buckets": dict(sorted(trainer.bucket_counts.items())), "captures": c["capture"], "replays": c["replay"],
@@ -328,116 +310,122 @@ def _ragged_plan(loss_func, trainer, metrics):
             "metrics": tuple(name for name in metrics if RG.form_of(getattr(EM, name, None)) is not None)}
 
 
+class _EpochStats(object):
+    """What an epoch's pass adds up on this rank -- its detached fp32 share of each global batch's loss x that batch's slates, its own
+    slates, per-metric sums over slates -- and the ONE ``cat`` / ``all_reduce`` / host copy that ends the pass."""
+
+    def __init__(self, metrics, device):
+        self.metrics, self.device = metrics, device
+        self.tot, self.num, self.sums = torch.zeros((), device=device), 0, {name: None for name in metrics}
+
+    def add(self, share, n_glob, n):
+        self.tot += share.reshape(()) * n_glob
+        self.num += n
+
+    def add_metric(self, name, v):
+        self.sums[name] = v if self.sums[name] is None else self.sums[name] + v
+
+    def finish(self, world, zero_fill):
+        """(loss sum, slate count, {"name_at": sum}) over all ranks, as the fp32 numpy scalars of the host copy.  A metric never added
+        is left out (training under train_metrics="reference") or, ``zero_fill``, counts as zeros (validation: every rank one layout)."""
+        names = [name for name in self.metrics if zero_fill or self.sums[name] is not None]
+        sums = [self.sums[name].float() if self.sums[name] is not None else torch.zeros(len(self.metrics[name]), device=self.device)
+                for name in names]
+        stats = torch.cat([self.tot.reshape(1), torch.tensor([float(self.num)], device=self.device)] + sums)
+        if world > 1:
+            import torch.distributed as dist
+            dist.all_reduce(stats)
+        stats = stats.cpu().numpy()
+        return stats[0], stats[1], dict(zip(["%s_%d" % (name, at) for name in names for at in self.metrics[name]], stats[2:]))
+
+
+# one validation batch as its score source left it: ``scores`` [n, L] and ``y`` (first n rows) for the padded metrics, ``out`` and
+# ``labels`` (max(n, 1) slates) for the padded loss, ``n`` of ``n_glob`` slates, ``packed``: the scorer that ran (ragged plan) or None
+_ValBatch = collections.namedtuple("_ValBatch", "scores y out labels n n_glob packed")
+
+
+def _score_batch(batch, loader, resident, model, trainer, scorers, ragged, world, rank):
+    """Score one validation batch through the one source that serves it: a FusedScorer fed from the resident set (``resident``) or
+    from the padded batch (``scorers``; slates above LTRX_MAX_METRIC_SLATE_LEN: the nn.Module), the trainer's own forward
+    (``score_block``: the step's kernels, dropout off, hipGraph replay) or the nn.Module (fp32 library GEMMs).  Every ``max(n, 1)``:
+    an empty shard still enters the loss (its normaliser all-reduce is a collective) with one fully padded slate: value 0, count 0."""
+    from . import _lib as LB
+    if resident:                                                  # packed straight from the resident set: no padded features
+        n = len(batch.ids)
+        scorer = _val_scorer(scorers, trainer, -(-loader.batch_size // world), loader.slate_length)
+        scorer.run_resident(batch.slates, batch.ids, batch.lengths)
+        return _ValBatch(scorer.scores[:n], scorer.y, scorer.scores_raw[:max(n, 1)], scorer.y[:max(n, 1)], n, batch.global_slates, scorer)
+    xb, yb, idx, n_glob, pre = _my_block(batch, loader, rank, world)
+    n = int(xb.shape[0])
+    if scorers is not None and int(xb.shape[1]) <= LB.MAX_METRIC_SLATE_LEN:
+        scorer = _val_scorer(scorers, trainer, n, int(xb.shape[1]))
+        scorer.run(xb, yb, idx, lengths=_host_lengths(batch, n, pre, world))
+        return _ValBatch(scorer.scores[:n], yb, scorer.scores_raw[:max(n, 1)], scorer.y[:max(n, 1)], n, n_glob, scorer)
+    own = trainer.score_block(xb, yb, idx, _host_lengths(batch, n, pre, world)) if trainer is not None and scorers is None else None
+    if own is not None:
+        return _ValBatch(own[0], yb, own[1], own[2], n, n_glob, None)
+    if scorers is not None:
+        last_run["val_scorer_reason"] = ("a slate length of %d is above LTRX_MAX_METRIC_SLATE_LEN = %d: module path"
+                                         % (int(xb.shape[1]), LB.MAX_METRIC_SLATE_LEN))
+    if ragged is not None:
+        last_run["val_eval"] = {"loss": "padded", "metrics": "padded"}      # a batch no scorer could take
+    if n == 0:
+        xb, yb, idx = _pad_batch(xb, yb, idx, 1)
+    mask = yb == PADDED_Y_VALUE
+    out = model(xb, mask, idx)
+    return _ValBatch((out if out.dim() == 2 else model.score(xb, mask, idx))[:n], yb, out, yb, n, n_glob, None)
+
+
+def _cu_layout(packed, k, B):
+    """layout arguments of a ragged loss / metric over the first ``k`` slates of ``FusedScorer.packed()`` (launch order: all B only)"""
+    _, _, cu, order, max_len = packed
+    return dict(cu_seqlens=cu[:k + 1], max_len=max(max_len, 1), slate_order=order if k == B else None)
+
+
 def _evaluate(model, loss_func, dl, device, metrics, trainer=None, world=1, rank=0, scorers=None, ragged=None):
-    """validation pass of train_utils.py:101-107: mean loss (weighted by batch size) and metric means, no autograd.  With a
-    FusedTrainer the scores come from its forward-only pass (``FusedTrainer.score``: the kernels of the training step, dropout
-    off, hipGraph replay) instead of the nn.Module forward (fp32 library GEMMs).
-    ``scorers`` (a dict, fit(val_scorer="packed")): EVERY batch goes through a packed, captured FusedScorer of its slate length
-    (kept in the dict across epochs) -- straight from the resident set when the loader is a packable DeviceLoader
-    (``id_batches``), else from the padded batch; slates above LTRX_MAX_METRIC_SLATE_LEN take the nn.Module path and
-    ``last_run["val_scorer_reason"]`` says so.
+    """validation pass of train_utils.py:101-107: mean loss (weighted by batch size) and metric means, no autograd.  Which forward
+    scores a batch: ``_score_batch``.  ``scorers`` (a dict, fit(val_scorer="packed")): the FusedScorers, one per slate length, kept
+    across epochs; the batches come as ``id_batches`` when the loader is a packable DeviceLoader.
     ``ragged`` (a ``_ragged_plan``, fit(val_scorer="ragged")): for the batches a scorer ran, the loss and the metrics the plan names
-    are computed from ``FusedScorer.packed()`` -- packed scores and labels, cu_seqlens, launch order, the batch's own longest slate --
-    instead of the grid padded to the set's longest slate; same values (the ragged contract, include/ltrx.h), same accumulation.
-    Sharded (``world`` > 1, round 5): every rank scores its contiguous block of each validation batch -- the same partition as the
-    training step -- under ``shard_context(global batch)``, so its loss is its share of the reference's loss on the whole batch
-    (global divisors / normalisers); shares, slate counts and per-slate metric sums are all-reduced once at the end, and
-    every rank returns the same numbers (scheduler and early stopping stay in step).  Before, every rank evaluated the whole set."""
-    import torch.distributed as dist
+    are computed from ``FusedScorer.packed()`` instead of the padded grid; same values (the ragged contract, include/ltrx.h).
+    Sharded (``world`` > 1): every rank scores its block of each batch -- the training step's partition -- under
+    ``shard_context(global batch)``, so its loss is its share of the reference's loss on the whole batch; one all-reduce
+    at the end, and every rank returns the same numbers (scheduler and early stopping stay in step)."""
     from . import _lib as LB, sharding
-    tot, num = torch.zeros((), device=device), 0
-    acc = {name: None for name in metrics}
+    stats = _EpochStats(metrics, device)
     pf = dl if isinstance(dl, _Prefetcher) else _Prefetcher(dl, device)
     loader = pf.loader
     resident = (scorers is not None and getattr(loader, "packable", False) and getattr(loader, "world", 1) == world
                 and loader.slate_length <= LB.MAX_METRIC_SLATE_LEN)
     with torch.no_grad():
         for batch in (loader.id_batches() if resident else pf):
-            pk = None                                                 # the scorer whose packed batch the ragged plan may read
-            if resident:                                              # packed straight from the resident set: no padded features
-                n, n_glob = len(batch.ids), batch.global_slates
-                scorer = _val_scorer(scorers, trainer, -(-loader.batch_size // world), loader.slate_length)
-                scorer.run_resident(batch.slates, batch.ids, batch.lengths)
-                sc, out, yl, yb = scorer.scores[:n], scorer.scores_raw[:max(n, 1)], scorer.y[:max(n, 1)], scorer.y
-                pk = scorer
-            else:
-                xb, yb, idx, n_glob, pre = _my_block(batch, loader, rank, world)
-                n = int(xb.shape[0])
-                if scorers is not None and int(xb.shape[1]) <= LB.MAX_METRIC_SLATE_LEN:
-                    scorer = _val_scorer(scorers, trainer, n, int(xb.shape[1]))
-                    scorer.run(xb, yb, idx, lengths=_host_lengths(batch, n, pre, world))
-                    sc, out, yl = scorer.scores[:n], scorer.scores_raw[:max(n, 1)], scorer.y[:max(n, 1)]
-                    pk = scorer
-                elif trainer is not None and scorers is None and n <= trainer.B and tuple(xb.shape[1:2]) == (trainer.L,):
-                    xs, ys, ids = _pad_batch(xb, yb, idx, trainer.B)
-                    sc = trainer.score(xs, ys, ids, lengths=_host_lengths(batch, n, pre, world, trainer))[:n]
-                    # (an empty shard of a short last batch still enters the loss -- its normaliser all-reduce is a collective -- with
-                    #  one fully padded slate: value 0, count 0)
-                    out, yl = trainer.scores_raw[:max(n, 1)], ys[:max(n, 1)]
-                else:
-                    if scorers is not None:
-                        last_run["val_scorer_reason"] = ("a slate length of %d is above LTRX_MAX_METRIC_SLATE_LEN = %d: module path"
-                                                         % (int(xb.shape[1]), LB.MAX_METRIC_SLATE_LEN))
-                    if n == 0:
-                        xb, yb, idx = _pad_batch(xb, yb, idx, 1)
-                    mask = yb == PADDED_Y_VALUE
-                    out = model(xb, mask, idx)
-                    sc = (out if out.dim() == 2 else model.score(xb, mask, idx))[:n]
-                    yl = yb
-            rag_loss, rag_metrics, call = None, (), lambda: loss_func(out, yl)
-            if ragged is not None and pk is not None:
-                rag_loss, rag_metrics = ragged["loss"], ragged["metrics"]
-                if rag_loss is not None or (rag_metrics and n > 0):
-                    s_p, y_p, cu, order, max_len = pk.packed()
-                    # the batch's slates (one empty slate for an empty shard, as the padded path's one padded slate); the launch order
-                    # covers the scorer's B slates, so a short batch goes without it
-                    lay = lambda k: dict(cu_seqlens=cu[:k + 1], max_len=max(max_len, 1), slate_order=order if k == pk.B else None)
-                    call = lambda: rag_loss(s_p, y_p, **lay(max(n, 1)))
-            elif ragged is not None:
-                last_run["val_eval"] = {"loss": "padded", "metrics": "padded"}      # a batch no scorer could take: the module path
+            vb = _score_batch(batch, loader, resident, model, trainer, scorers, ragged, world, rank)
+            n, pk = vb.n, vb.packed if ragged is not None else None
+            rag_loss, rag_metrics = (ragged["loss"], ragged["metrics"]) if pk is not None else (None, ())
+            # (an empty shard: one empty slate in the ragged loss, as the padded path's one padded slate, and no metric)
+            packed = pk.packed() if rag_loss is not None or (rag_metrics and n > 0) else None
             if loss_func is None:                                     # (metrics only: the reference's compute_metrics pass)
-                share = tot.new_zeros(())
-            elif world > 1:
-                with sharding.shard_context(n_glob):
-                    share = (call() if rag_loss is not None else loss_func(out, yl)).detach().float()
+                share = stats.tot.new_zeros(())
             else:
-                share = (call() if rag_loss is not None else loss_func(out, yl)).detach().float()
-            tot += share.reshape(()) * n_glob
-            num += n
+                fn, args, kw = ((rag_loss, packed[:2], _cu_layout(packed, max(n, 1), pk.B)) if rag_loss is not None else
+                                (loss_func, (vb.out, vb.labels), {}))
+                with sharding.shard_context(vb.n_glob) if world > 1 else contextlib.nullcontext():
+                    share = fn(*args, **kw).detach().float()
+            stats.add(share, vb.n_glob, n)
             if n > 0:
                 for name, ats in metrics.items():
-                    if name in rag_metrics:
-                        v = getattr(RG, name)(s_p, y_p, ats=ats, **lay(n)).sum(0)
-                    else:
-                        v = getattr(EM, name)(sc, yb[:n], ats=ats).sum(0)
-                    acc[name] = v if acc[name] is None else acc[name] + v
-    sums = [acc[name].float() if acc[name] is not None else torch.zeros(len(metrics[name]), device=device) for name in metrics]
-    stats = torch.cat([tot.reshape(1), torch.tensor([float(num)], device=device)] + sums)
-    if world > 1:
-        dist.all_reduce(stats)
-    stats = stats.cpu().numpy()
-    n_all = max(float(stats[1]), 1.0)
-    out, off = {}, 2
-    for name, ats in metrics.items():
-        for at in ats:
-            out["%s_%d" % (name, at)] = np.float32(stats[off] / n_all)
-            off += 1
-    return float(stats[0]) / n_all, out
+                    v = (getattr(RG, name)(packed[0], packed[1], ats=ats, **_cu_layout(packed, n, pk.B)) if name in rag_metrics else
+                         getattr(EM, name)(vb.scores, vb.y[:n], ats=ats))
+                    stats.add_metric(name, v.sum(0))
+    loss_sum, n_slates, sums = stats.finish(world, zero_fill=True)
+    n_all = max(float(n_slates), 1.0)
+    return float(loss_sum) / n_all, {k: np.float32(v / n_all) for k, v in sums.items()}
 
 
-def _assert_finite(trainer, fused, loss, epoch, step, model):
-    """the anomaly switch of the explicit step (main.py:89): raise on the first step whose loss or gradients are not finite and
-    name the first offending parameter tensor.  The fused step has already applied the update when this runs (the check reads the
-    gradient buffer the step left behind) -- the run stops here either way."""
-    if fused:
-        name, count = trainer.first_nonfinite()
-    else:
-        name, count = None, 0
-        for n, p in model.named_parameters():                      # (autograd step: flat.zero() has run; check the weights it left)
-            bad = int((~torch.isfinite(p.detach())).sum().item())
-            if bad and name is None:
-                name = n
-            count += bad
+def _assert_finite(trainer, loss, epoch, step):
+    """the anomaly switch (main.py:89): raise on the first step whose loss, or what the engine's ``first_nonfinite`` scans, is not
+    finite and name the first offending parameter tensor.  The step has already applied the update -- the run stops either way."""
+    name, count = trainer.first_nonfinite()
     loss_ok = bool(torch.isfinite(loss.detach()).all().item())
     if name is not None or not loss_ok:
         raise FloatingPointError(
@@ -445,60 +433,7 @@ def _assert_finite(trainer, fused, loss, epoch, step, model):
             "tensor: %s (%d non-finite %s element(s) in all).  Usual causes: non-finite input features, a learning rate that "
             "diverged, a slate with no valid item in a loss that divides by its normaliser."
             % (step, epoch, "a non-finite loss" if not loss_ok else "a finite loss", "" if name is None else " and non-finite values",
-               name, count, "gradient" if fused else "weight"))
-
-
-def _job_meta(trainer, fused, model, loss_func, optimizer, clip):
-    """the block a checkpoint is compared on (checkpoint.check_compatible) -- the same for both engines where the job is the same"""
-    if fused:
-        return trainer.meta()
-    g = optimizer.param_groups[0]
-    kind = CK.neutral_kind(optimizer)
-    if kind is not None:
-        hyper = CK.hyper(kind, g["lr"], g.get("betas"), g.get("eps"), g.get("weight_decay", 0.0), g.get("momentum", 0.0), g.get("nesterov", False))
-    else:
-        kind, hyper = type(optimizer).__name__, CK.group_hyper(g)
-    if isinstance(loss_func, functools.partial):
-        name, args = getattr(loss_func.func, "__name__", repr(loss_func.func)), dict(loss_func.keywords or {})
-        if loss_func.args:
-            args["*"] = list(loss_func.args)
-    else:
-        name, args = getattr(loss_func, "__name__", type(loss_func).__name__), {}
-    return CK.make_meta(list(model.named_parameters()), kind, hyper, name, args, clip)
-
-
-def _trainer_state(trainer, fused, model, optimizer, meta):
-    """the "trainer" entry of a checkpoint: FusedTrainer.state_dict(), or its counterpart for the autograd engine -- the module's
-    state_dict and the torch optimizer's state in the neutral schema (raw for a class the schema does not cover)"""
-    if fused:
-        return trainer.state_dict()
-    return {"params": {k: v.detach().cpu() for k, v in model.state_dict().items()},
-            "optimizer": CK.to_neutral(optimizer, model.named_parameters()),
-            "lr": float(optimizer.param_groups[0]["lr"]), "lrs": [float(g["lr"]) for g in optimizer.param_groups], "meta": meta}
-
-
-def _load_trainer_state(trainer, fused, model, optimizer, state, meta):
-    """a checkpoint's "trainer" entry into the live job, in place; compatibility first (ValueError, nothing touched).  Either engine
-    loads either engine's entry -- only a raw torch optimizer state is tied to the autograd engine and its own class."""
-    if fused:
-        trainer.load_state_dict(state)
-    else:
-        CK.check_compatible(state["meta"], meta)
-        raw = "torch_optimizer" in state["optimizer"]
-        if raw != (CK.neutral_kind(optimizer) is None) or (raw and state["optimizer"]["kind"] != type(optimizer).__name__):
-            raise ValueError("checkpoint: the stored optimizer state (%s, %s) does not fit the live %s"
-                             % (state["optimizer"]["kind"], "raw" if raw else "neutral", type(optimizer).__name__))
-        live = model.state_dict()
-        for n, p in model.named_parameters():
-            if n not in state["params"] or tuple(state["params"][n].shape) != tuple(p.shape):
-                raise ValueError("checkpoint: parameter %s: no tensor of shape %s in the checkpoint" % (n, tuple(p.shape)))
-        with torch.no_grad():
-            for k, v in live.items():
-                if k in state["params"] and tuple(state["params"][k].shape) == tuple(v.shape):
-                    v.copy_(state["params"][k])
-        CK.from_neutral(optimizer, model.named_parameters(), state["optimizer"])
-    for g, lr in zip(optimizer.param_groups, state.get("lrs") or [state["lr"]] * len(optimizer.param_groups)):
-        g["lr"] = float(lr)
+               name, count, trainer.scanned))
 
 
 def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, config, gradient_clipping_norm, early_stopping_patience,
@@ -576,6 +511,8 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
             trainer = FusedTrainer(model, spec[0], spec[1], hi - lo, L, lr=spec[2], world_size=world, use_graph=True,
                                    gradient_clipping_norm=gradient_clipping_norm, compact=compact, gemm=gemm, **spec[3])
             fused = True
+            optimizer._opt_called = True   # (torch's "scheduler.step() before optimizer.step()" check: in the fused run the
+            #                                 optimizer object only carries the learning rate, its step() is never called)
             if compact == "graph" and not trainer.compact_graph:
                 cg_reason = ("the slate-resident FC + ListNet step is taken: it reads the padded batch in place" if trainer.fcstep else
                              "stochastic NeuralNDCG reads the scores of padded slots: the step stays on the padded grid")
@@ -584,8 +521,8 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
     if trainer is None:
         trainer = Trainer(model, loss_func, optimizer, gradient_clipping_norm, world, None)
     last_run.clear()
-    last_run.update(engine="fused" if fused else "autograd", compact=bool(trainer.compact) if fused else False, reason=reason,
-                    fcstep=getattr(trainer, "fcstep", False), sampling=getattr(train_dl, "sampling", None),
+    last_run.update(engine="fused" if fused else "autograd", compact=bool(trainer.compact), reason=reason,
+                    fcstep=trainer.fcstep, sampling=getattr(train_dl, "sampling", None),
                     compact_graph=_compact_graph_stats(trainer), compact_graph_reason=cg_reason)
     log.info("allrank_amd.fit: %s step%s", last_run["engine"], (" (" + reason + ")") if reason else "")
     vs_reason = _packed_blocker(loss_func, fused, reason) if val_scorer_mode in ("packed", "ragged") else ""
@@ -603,9 +540,8 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
     checked = world == 1
     last_run["epoch_log"] = []            # per epoch: wall seconds of the training / validation pass, slates and slots trained on
     n_steps = 0
-    first_epoch, ckpt_path, ckpt_meta, rng_state = 0, os.path.join(output_dir, CK.FILE_NAME), None, None
-    if checkpoint_every is not None or resume is not None:
-        ckpt_meta = _job_meta(trainer, fused, model, loss_func, optimizer, gradient_clipping_norm)
+    first_epoch, ckpt_path, rng_state = 0, os.path.join(output_dir, CK.FILE_NAME), None
+    ckpt_meta = trainer.meta() if checkpoint_every is not None or resume is not None else None
     if checkpoint_every is not None:
         last_run["checkpoint"] = {"path": ckpt_path, "every": checkpoint_every, "written": 0}
     if resume == "auto" and not os.path.exists(ckpt_path):
@@ -613,7 +549,9 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
         resume = None
     if resume is not None:
         ck = CK.load(ckpt_path if resume == "auto" else resume)
-        _load_trainer_state(trainer, fused, model, optimizer, ck["trainer"], ckpt_meta)      # (checks compatibility before it touches anything)
+        trainer.load_state_dict(ck["trainer"])                    # (checks compatibility before it touches anything)
+        for g, lr in zip(optimizer.param_groups, ck["trainer"].get("lrs") or [ck["trainer"]["lr"]] * len(optimizer.param_groups)):
+            g["lr"] = float(lr)
         if scheduler and ck["scheduler"] is not None:
             scheduler.load_state_dict(ck["scheduler"])
         early_stop.best_value, early_stop.best_epoch = ck["early_stop"]["best_value"], int(ck["early_stop"]["best_epoch"])
@@ -629,73 +567,49 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
     for epoch in range(first_epoch, epochs):
         model.train()
         t_epoch = time.perf_counter()
-        tot, num, slots = torch.zeros((), device=device), 0, 0
-        tm = {name: None for name in metrics}
+        stats, slots = _EpochStats(metrics, device), 0
         for batch in train_pf:
             xb, yb, idx, real_glob, pre = _my_block(batch, train_dl, rank, world)
             if not checked:
                 _check_same_batch(batch[0], batch[1], world, pre)
                 checked = True
             real = int(xb.shape[0])
-            if fused:
-                xs, ys, ids = _pad_batch(xb, yb, idx, trainer.B)
-                loss = trainer.step(xs, ys, ids, global_batch=real_glob, lengths=_host_lengths(batch, real, pre, world, trainer))
-                scores, labels = trainer.scores[:real], trainer.y_cur[:real]
-            else:
-                if real == 0:
-                    # (sharded: this rank's block of a short last batch is empty -- the step still has to run, its gradient all-reduce
-                    #  is a collective: one fully padded slate, i.e. zero loss and zero gradients.  Found by the 2-rank autograd job of
-                    #  tests/dist_fit_worker.py in round 5: the nn.Module forward raised on 0 rows while the peer sat in the all-reduce.)
-                    xb, yb, idx = _pad_batch(xb, yb, idx, 1)
-                loss = trainer.step(xb, yb, idx, global_batch=real_glob)
-                scores, labels = trainer.last_scores[:real], yb[:real]
+            loss = trainer.step_block(xb, yb, idx, real_glob, _host_lengths(batch, real, pre, world))
             n_steps += 1
             if check_finite:
-                _assert_finite(trainer, fused, loss, epoch, n_steps, model)
-            tot += loss.detach().float().reshape(()) * real_glob          # (sharded: this rank's share of the global-batch loss)
-            num += real
+                _assert_finite(trainer, loss, epoch, n_steps)
+            stats.add(loss.detach().float(), real_glob, real)         # (sharded: this rank's share of the global-batch loss)
             slots += real * int(yb.shape[1])
             if train_metrics_mode == "fused":
                 for name, ats in metrics.items():
                     # (a rank whose shard of a short last batch is empty contributes zeros -- every rank keeps the same stats layout)
-                    v = getattr(EM, name)(scores, labels, ats=ats).sum(0) if real > 0 else torch.zeros(len(ats), device=device)
-                    tm[name] = v if tm[name] is None else tm[name] + v
-        stats = torch.cat([tot.reshape(1), torch.tensor([float(num)], device=device)] + [tm[n].float() for n in metrics if tm[n] is not None])
-        if world > 1:
-            dist.all_reduce(stats)
-        stats = stats.cpu().numpy()
+                    stats.add_metric(name, getattr(EM, name)(trainer.scores[:real], trainer.y_cur[:real], ats=ats).sum(0) if real > 0
+                                     else torch.zeros(len(ats), device=device))
+        loss_sum, n_slates, sums = stats.finish(world, zero_fill=False)
         t_train = time.perf_counter() - t_epoch
         last_run["compact_graph"] = _compact_graph_stats(trainer)
-        n_all = max(stats[1], 1.0)
-        train_loss = float(stats[0]) / n_all
-        train_metrics, off = {}, 2
-        for name, ats in metrics.items():
-            if tm[name] is None:
-                continue
-            for at in ats:
-                train_metrics["%s_%d" % (name, at)] = float(stats[off]) / n_all
-                off += 1
+        n_all = max(n_slates, 1.0)
+        train_loss = float(loss_sum) / n_all
+        train_metrics = {k: float(v) / n_all for k, v in sums.items()}
         if train_metrics_mode == "reference":
             # train_utils.py:99: compute_metrics(config.metrics, model, train_dl, device) -- one more pass over train_dl per metric
             # name (:46-54), with the end-of-epoch weights, the model still in train() mode
             train_metrics = {}
             for name, ats in metrics.items():
-                _, one = _evaluate(model, None, train_pf, device, {name: ats}, trainer if fused else None, world, rank)
+                _, one = _evaluate(model, None, train_pf, device, {name: ats}, trainer, world, rank)
                 train_metrics.update({k: float(v) for k, v in one.items()})
         else:
             _burn(train_dl, len(metrics))                          # the generator draws of the passes not made (module docstring)
 
         model.eval()
         t_val = time.perf_counter()
-        val_loss, val_metrics = _evaluate(model, loss_func, valid_pf, device, metrics, trainer if fused else None, world, rank, scorers,
-                                          rag_plan)
+        val_loss, val_metrics = _evaluate(model, loss_func, valid_pf, device, metrics, trainer, world, rank, scorers, rag_plan)
         _burn(valid_dl, len(metrics))                              # train_utils.py:107 iterates valid_dl once more per metric name
-        last_run["epoch_log"].append({"train_s": t_train, "val_s": time.perf_counter() - t_val, "slates": int(stats[1]),
+        last_run["epoch_log"].append({"train_s": t_train, "val_s": time.perf_counter() - t_val, "slates": int(n_slates),
                                       "slots": int(slots), "val_loss": val_loss})
 
-        lr_now = optimizer.param_groups[0]["lr"]
         if writer is not None:
-            tb = {("train", "loss"): train_loss, ("val", "loss"): val_loss, ("train", "lr"): lr_now}
+            tb = {("train", "loss"): train_loss, ("val", "loss"): val_loss, ("train", "lr"): optimizer.param_groups[0]["lr"]}
             tb.update({("train", k): v for k, v in train_metrics.items()})
             tb.update({("val", k): v for k, v in val_metrics.items()})
             writer.save_to_tensorboard(tb, epoch)
@@ -704,21 +618,17 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
 
         current = val_metrics.get(val_metric)
         if scheduler:                                              # train_utils.py:117-122
-            if fused:
-                optimizer._opt_called = True                       # (torch's "scheduler.step() before optimizer.step()" check: in
-                #                                                     the fused run the optimizer object only carries the learning rate)
             if type(scheduler) is torch.optim.lr_scheduler.ReduceLROnPlateau:
                 scheduler.step(val_metrics[val_metric])
             else:
                 scheduler.step()
-            if fused:                                              # the scheduler edits optimizer.param_groups; the fused Adam follows
-                trainer.set_lr(float(optimizer.param_groups[0]["lr"]))
+            trainer.set_lr(float(optimizer.param_groups[0]["lr"]))  # the scheduler edits optimizer.param_groups; the engine follows
         early_stop.step(current, epoch)
         if checkpoint_every is not None and ((epoch + 1) % checkpoint_every == 0 or epoch == epochs - 1 or early_stop.stop_training(epoch)):
             t_ck = time.perf_counter()
             CK.save(ckpt_path, {
                 "epoch": epoch, "n_steps": n_steps, "engine": last_run["engine"],
-                "trainer": _trainer_state(trainer, fused, model, optimizer, ckpt_meta),
+                "trainer": trainer.state_dict(),
                 "scheduler": scheduler.state_dict() if scheduler else None,
                 "early_stop": {"best_value": early_stop.best_value, "best_epoch": early_stop.best_epoch,
                                "stopped": bool(early_stop.stop_training(epoch))},

@@ -1,8 +1,8 @@
 """Record which libltrx calls the package makes, and what they compute, over a set of small cases (needs the MI355X).
 
-    python tests/golden/make_call_trace_fixture.py [--set calls|rows|step|options] [--out FILE] [--commit HASH]
+    python tests/golden/make_call_trace_fixture.py [--set calls|rows|step|options|fit] [--out FILE] [--commit HASH]
 
-Four case sets, one file each, each run ONCE at the commit named in its file ("commit"):
+Five case sets, one file each, each run ONCE at the commit named in its file ("commit"):
   calls  tests/golden/call_trace_parent.json: before the GEMM, attention, LayerNorm and head calls of allrank_amd/ops.py and
          allrank_amd/engine.py moved into the launchers of allrank_amd/kernels.py;
   rows   tests/golden/call_trace_rows_parent.json: the three row layouts (padded grid, index-packed, cu_seqlens-packed) before their
@@ -17,6 +17,11 @@ Four case sets, one file each, each run ONCE at the commit named in its file ("c
          weight-gradient composition under sublayer dropout, an FC stack of three layers, the fixed positional encoding on the
          padded grid, ``score()`` between two steps, ``load_state_dict`` with another seed, and a scorer over an ``input_norm`` model
          with 46 features.  Its traces begin at the constructor: the size and support queries made there are held too.
+  fit    tests/golden/call_trace_fit_parent.json: before the two engines shared one interface under ``fit()`` -- whole ``fit()`` calls
+         (hipGraph capture on, as a user runs them) over a small libsvm set written here: both engines, the four validation score
+         sources, the ragged evaluation, schedulers, early stopping, the finiteness check, checkpoint and resume.  Per case the
+         trace of the whole call, digests of the result, ``last_run``, the validation losses, ``model.pkl`` and the checkpoint, and
+         ``notes``: plain facts (engine, batches per score source, the error text) that the two runs must agree on as well.
 tests/test_gpu_call_trace.py runs the same cases at every later commit and holds them to the recorded calls and results exactly.
 Re-running a set at a later commit only re-records that commit against itself.
 
@@ -28,11 +33,14 @@ bytes of the loss of each of 3 steps, the flat gradient after step 1, the flat p
 runs twice; a digest is stored only where the two runs agree bit for bit (``unstable`` names the others), and the two traces must
 be equal.  ``gemm="hipblaslt"`` is recorded without digests: torch's GEMMs choose their own algorithm.
 """
+import atexit
 import contextlib
 import ctypes
+import functools
 import hashlib
 import json
 import os
+import shutil
 import subprocess
 import sys
 
@@ -49,6 +57,7 @@ FIXTURE = os.path.join(HERE, "call_trace_parent.json")
 ROWS_FIXTURE = os.path.join(HERE, "call_trace_rows_parent.json")
 STEP_FIXTURE = os.path.join(HERE, "call_trace_step_parent.json")
 OPTIONS_FIXTURE = os.path.join(HERE, "call_trace_options_parent.json")
+FIT_FIXTURE = os.path.join(HERE, "call_trace_fit_parent.json")
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -446,26 +455,242 @@ def options_cases():
     }
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# the fifth set: whole fit() calls
+# ------------------------------------------------------------------------------------------------------------------
+FIT_F, FIT_L, FIT_BS = 20, 20, 16                                            # 40 queries of 3..20 items: batches of 16, 16 and a short 8
+_FIT_DATA = {}
+_WALL_CLOCK_AND_PATHS = ("train_s", "val_s", "ckpt_s", "path")
+
+
+def _fit_arrays(role):
+    """(lengths, X, y) of one file: features on the 4-decimal grid of [0, 1) (the text holds them exactly), labels 0..4"""
+    rng = np.random.default_rng({"train": 21, "vali": 22, "vali_long": 23}[role])
+    if role == "train":
+        lens = rng.integers(3, FIT_L + 1, 40)
+    else:
+        lens = rng.integers(3, FIT_L + 1, 24)
+        lens[7] = FIT_L if role == "vali" else 27                 # "vali": the training step's slate length, so trainer.score() serves it
+    n = int(lens.sum())
+    X = (rng.integers(0, 10000, (n, FIT_F)) / 10000.0).astype(np.float32)
+    w = rng.standard_normal(FIT_F)
+    y = np.clip(np.round((X.astype(np.float64) - 0.5) @ w * 1.2 + 1.5), 0, 4).astype(np.float32)
+    return lens, X, y
+
+
+def _fit_data():
+    """the libsvm files (written once per process into a temp dir), the resident sets read back from them, and the same slates as
+    padded host tensors for a plain DataLoader"""
+    import tempfile
+    from allrank_amd import data as ED
+    if not _FIT_DATA:
+        root = tempfile.mkdtemp(prefix="call_trace_fit_")
+        atexit.register(shutil.rmtree, root, ignore_errors=True)
+        host = {}
+        for role in ("train", "vali", "vali_long"):
+            lens, X, y = _fit_arrays(role)
+            d = os.path.join(root, "long" if role == "vali_long" else "same")
+            os.makedirs(d, exist_ok=True)
+            q = np.repeat(np.arange(len(lens)), lens)
+            for path in [os.path.join(d, role.split("_")[0] + ".txt")] + ([os.path.join(root, "long", "train.txt")] if role == "train" else []):
+                os.makedirs(os.path.dirname(path), exist_ok=True)
+                with open(path, "w") as fh:
+                    for i in range(len(y)):
+                        fh.write("%d qid:%d %s\n" % (int(y[i]), 100 + q[i], " ".join("%d:%.4f" % (k + 1, X[i, k]) for k in range(FIT_F))))
+            L = FIT_L if role == "train" else int(lens.max())
+            xp, yp = np.zeros((len(lens), L, FIT_F), np.float32), np.full((len(lens), L), -1.0, np.float32)
+            ip, o = np.full((len(lens), L), -1, np.int64), 0
+            for b, k in enumerate(lens):
+                xp[b, :k], yp[b, :k], ip[b, :k] = X[o:o + k], y[o:o + k], np.arange(k)
+                o += k
+            host[role] = (torch.tensor(xp), torch.tensor(yp), torch.tensor(ip))
+        _FIT_DATA.update(host=host, same=ED.load_libsvm_dataset(os.path.join(root, "same"), FIT_L, "vali", device=DEV),
+                         long=ED.load_libsvm_dataset(os.path.join(root, "long"), FIT_L, "vali", device=DEV))
+    return _FIT_DATA
+
+
+def _fit_loaders(kind, vali, nan):
+    from torch.utils.data import DataLoader, TensorDataset
+    from allrank_amd import data as ED
+    d = _fit_data()
+    if kind == "device":
+        tr, va = d["long" if vali == "long" else "same"]
+        return ED.DeviceLoader(tr, FIT_BS, shuffle=True, sampling="device"), ED.DeviceLoader(va, FIT_BS, shuffle=False)
+    xt, yt, it = d["host"]["train"]
+    if nan:
+        xt = xt.clone()
+        xt[5, 0, 3] = float("nan")
+    return (DataLoader(TensorDataset(xt, yt, it), batch_size=FIT_BS, shuffle=False),
+            DataLoader(TensorDataset(*d["host"]["vali_long" if vali == "long" else "vali"]), batch_size=FIT_BS, shuffle=False))
+
+
+def _canon(v):
+    """a value as JSON that keeps its type: tensors by digest, floats as float.hex, wall-clock entries and paths dropped"""
+    if torch.is_tensor(v):
+        return ["tensor", str(v.dtype), list(v.shape), _sha(v)]
+    if isinstance(v, dict):
+        return {str(k): _canon(x) for k, x in sorted(v.items(), key=lambda kv: str(kv[0])) if k not in _WALL_CLOCK_AND_PATHS}
+    if isinstance(v, (list, tuple)):
+        return [type(v).__name__, [_canon(x) for x in v]]
+    if isinstance(v, (float, np.floating)):
+        return [type(v).__name__, float(v).hex()]
+    if isinstance(v, (int, np.integer)) and not isinstance(v, bool):
+        return [type(v).__name__, str(int(v))]
+    return [type(v).__name__, repr(v)]
+
+
+def _digest(v):
+    return _sha_bytes(json.dumps(_canon(v), sort_keys=True).encode())
+
+
+@contextlib.contextmanager
+def _score_sources(model, seen):
+    """count, per validation score source, the batches it served: FusedScorer.run_resident, FusedScorer.run, FusedTrainer.score and
+    the nn.Module forward with autograd off (a training forward of the autograd engine runs with it on)"""
+    from allrank_amd import engine as EN
+    saved = []
+
+    def counted(cls, name, key):
+        fn = getattr(cls, name)
+        saved.append((cls, name, fn))
+
+        def wrapper(*a, **kw):
+            seen[key] = seen.get(key, 0) + 1
+            return fn(*a, **kw)
+        setattr(cls, name, wrapper)
+    counted(EN.FusedScorer, "run_resident", "resident")
+    counted(EN.FusedScorer, "run", "packed")
+    counted(EN.FusedTrainer, "score", "trainer_score")
+    hook = model.register_forward_hook(lambda *a: None if torch.is_grad_enabled() else seen.__setitem__("module", seen.get("module", 0) + 1))
+    try:
+        yield
+    finally:
+        hook.remove()
+        for cls, name, fn in saved:
+            setattr(cls, name, fn)
+
+
+def _fit_case(loss=("listNet", {}), loaders="device", vali="same", model_kw=None, opt=("Adam", dict(lr=2e-3)), sched=None, epochs=3,
+              patience=10, nan=False, resume_to=None, **fit_kw):
+    """one fit() job as a case: returns run(proxy) -> (trace, digests, notes).  ``resume_to``: the job is run for ``epochs`` epochs,
+    then built afresh under other seeds and continued with resume="auto" up to ``resume_to`` -- both calls in one trace"""
+    def build(seeds):
+        from allrank_amd import losses as E
+        model = _model(**dict(dict(F=FIT_F, sizes=[32], N=1, d_ff=64, h=4, dropout=0.1), **(model_kw or {})))
+        torch.manual_seed(seeds[0]), np.random.seed(seeds[1])
+        o = getattr(torch.optim, opt[0])(model.parameters(), **opt[1])
+        s = None if sched is None else getattr(torch.optim.lr_scheduler, sched[0])(o, **sched[1])
+        return model, functools.partial(getattr(E, loss[0]), **loss[1]), o, s
+
+    def call(proxy, trace, out_dir, seeds, n_epochs, notes, **kw):
+        import types
+        from allrank_amd import fit as EF
+        model, loss_func, o, s = build(seeds)
+        train_dl, valid_dl = _fit_loaders(loaders, vali, nan)
+        cfg = types.SimpleNamespace(metrics={"ndcg": [5], "mrr": [10]}, val_metric="ndcg_5")
+        res, seen = None, notes.setdefault("sources", {})
+        with _recording(proxy, trace), _score_sources(model, seen):
+            try:
+                res = EF.fit(epochs=n_epochs, model=model, loss_func=loss_func, optimizer=o, scheduler=s, train_dl=train_dl, valid_dl=valid_dl,
+                             config=cfg, gradient_clipping_norm=None, early_stopping_patience=patience, device=torch.device(DEV),
+                             output_dir=out_dir, tensorboard_output_path=None, **dict(fit_kw, **kw))
+            except FloatingPointError as e:
+                notes["error"] = str(e)
+        torch.cuda.synchronize()
+        return res, dict(EF.last_run), o
+
+    def run(proxy):
+        import tempfile
+        with tempfile.TemporaryDirectory(prefix="call_trace_fit_out_") as out_dir:
+            return job(proxy, out_dir)
+
+    def job(proxy, out_dir):
+        trace, dig, notes = [], {}, {}
+        parts = [("", (42, 43), epochs, {})] if resume_to is None else [("first_", (42, 43), epochs, {}), ("", (52, 53), resume_to, dict(resume="auto"))]
+        for tag, seeds, n_epochs, kw in parts:
+            res, last, o = call(proxy, trace, out_dir, seeds, n_epochs, notes, **kw)
+            notes.update(engine=last.get("engine"), fcstep=bool(last.get("fcstep")), compact=last.get("compact"), val_scorer=last.get("val_scorer"),
+                         val_scorer_reason=last.get("val_scorer_reason"), val_eval=last.get("val_eval"),
+                         compact_graph=last.get("compact_graph") is not None, epochs=None if res is None else int(res["epochs"]))
+            dig[tag + "last_run"] = _digest(last)
+            dig[tag + "val_loss"] = _digest([e["val_loss"] for e in last.get("epoch_log", [])])
+            dig[tag + "lr"] = _digest(o.param_groups[0]["lr"])
+            if "error" in notes:
+                dig[tag + "error"] = _sha_bytes(notes["error"].encode())
+                continue
+            dig[tag + "result"] = _digest(res)
+            dig[tag + "model_pkl"] = _digest(torch.load(os.path.join(out_dir, "model.pkl"), map_location="cpu"))
+            if "checkpoint_every" in fit_kw:
+                from allrank_amd import checkpoint as CK
+                ck = CK.load(os.path.join(out_dir, "checkpoint.pt"))
+                dig[tag + "ckpt_trainer"] = _digest(ck["trainer"])
+                dig[tag + "ckpt_rest"] = _digest({k: v for k, v in ck.items() if k not in ("trainer", "rng")})
+        return trace, dig, notes
+    return run
+
+
+def fit_cases():
+    """the fifth set: whole ``fit()`` calls over a small libsvm set -- both engines, the four validation score sources, the ragged
+    evaluation, schedulers, early stopping, the finiteness check and checkpoint / resume"""
+    step_lr = ("StepLR", dict(step_size=1, gamma=0.5))
+    ordinal = dict(loss=("ordinal", {"n": 3}), model_kw=dict(d_output=3, out_act="Sigmoid"))
+    ckpt = dict(sched=step_lr, epochs=2, resume_to=4, checkpoint_every=1)
+    return {
+        "fit_fused_grid_trainer_score": _fit_case(compact=False, val_scorer="module"),
+        "fit_fused_grid_module_val": _fit_case(compact=False, val_scorer="module", vali="long"),
+        "fit_fused_compact": _fit_case(compact=True),
+        "fit_fused_compact_graph_packed_val": _fit_case(compact="graph", val_scorer="packed"),
+        "fit_fused_host_loader_ragged_val": _fit_case(loaders="host", val_scorer="ragged", vali="long"),
+        "fit_autograd_step_lr": _fit_case(use_fused=False, sched=step_lr),
+        "fit_autograd_reference_metrics_plateau": _fit_case(use_fused=False, train_metrics="reference",
+                                                            sched=("ReduceLROnPlateau", dict(mode="max", factor=0.5, patience=0))),
+        "fit_fused_step_lr_early_stop": _fit_case(opt=("Adam", dict(lr=0.05)), sched=("StepLR", dict(step_size=2, gamma=0.5)), epochs=8,
+                                                  patience=0),
+        "fit_fc_listnet_step": _fit_case(model_kw=dict(N=0), compact=True),
+        "fit_stochastic_neural_ndcg_packed_val": _fit_case(loss=("neuralNDCG", dict(stochastic=True, n_samples=4)), val_scorer="packed"),
+        "fit_ordinal_fused": _fit_case(**ordinal),
+        "fit_ordinal_autograd": _fit_case(use_fused=False, **ordinal),
+        "fit_check_finite_healthy": _fit_case(check_finite=True),
+        "fit_check_finite_nan_fused": _fit_case(loaders="host", nan=True, check_finite=True),
+        "fit_check_finite_nan_autograd": _fit_case(loaders="host", nan=True, check_finite=True, use_fused=False),
+        "fit_checkpoint_resume_fused": _fit_case(**ckpt),
+        "fit_checkpoint_resume_autograd": _fit_case(use_fused=False, **ckpt),
+    }
+
+
 SETS = {"calls": (FIXTURE, cases), "rows": (ROWS_FIXTURE, rows_cases), "step": (STEP_FIXTURE, step_cases),
-        "options": (OPTIONS_FIXTURE, options_cases)}
+        "options": (OPTIONS_FIXTURE, options_cases), "fit": (FIT_FIXTURE, fit_cases)}
 
 
 def run_case(proxy, name):
-    trace, dig = {n: f for _, make in SETS.values() for n, f in make().items()}[name](proxy)
+    """(trace, digests, notes) of one case; ``notes`` ({} outside the fit set): plain facts about the run, held like the digests"""
+    got = {n: f for _, make in SETS.values() for n, f in make().items()}[name](proxy)
     torch.cuda.synchronize()
-    return trace, dig
+    return got if len(got) == 3 else got + ({},)
 
 
 def record(names):
     rec = {}
     with proxied() as proxy:
         for name in names:
-            (t1, d1), (t2, d2) = run_case(proxy, name), run_case(proxy, name)
+            (t1, d1, n1), (t2, d2, n2) = run_case(proxy, name), run_case(proxy, name)
             assert t1 == t2, "%s: the two runs made different calls" % name
             assert t1, "%s: no call recorded" % name
+            assert n1 == n2, "%s: the two runs differ in %s" % (name, sorted(k for k in n1 if n1[k] != n2.get(k)))
             rec[name] = dict(trace=t1, digests={k: v for k, v in d1.items() if d2[k] == v},
-                             unstable=sorted(k for k, v in d1.items() if d2[k] != v))
-            print("%-36s %4d calls, %d digests, unstable: %s" % (name, len(t1), len(rec[name]["digests"]), rec[name]["unstable"]), flush=True)
+                             unstable=sorted(k for k, v in d1.items() if d2[k] != v), notes=n1)
+            print("%-36s %4d calls, %d digests, unstable: %s %s" % (name, len(t1), len(rec[name]["digests"]), rec[name]["unstable"],
+                                                                    json.dumps(n1, sort_keys=True) if n1 else ""), flush=True)
+    return rec
+
+
+def expand(rec):
+    """a loaded fixture with every trace as the list of calls: the fit set stores each distinct call once ("calls") and a trace as
+    indices into that table -- the steps of a fit() repeat their calls, and the file stays small"""
+    table = rec.get("calls")
+    if table is not None:
+        for c in rec["cases"].values():
+            c["trace"] = [table[i] for i in c["trace"]]
     return rec
 
 
@@ -480,13 +705,21 @@ def main():
     path, names = SETS[args.set]
     out = args.out or path
     rec = record(names())
+    table = {}
     with open(out, "w") as fh:                           # one call per line: a changed argument is a one-line diff
         fh.write('{"commit": %s,\n "cases": {' % json.dumps(commit))
         for i, (name, c) in enumerate(rec.items()):
-            fh.write('%s\n  %s: {"digests": %s,\n   "unstable": %s,\n   "trace": [\n    %s\n   ]}'
-                     % ("," if i else "", json.dumps(name), json.dumps(c["digests"], sort_keys=True), json.dumps(c["unstable"]),
-                        ",\n    ".join(json.dumps(call) for call in c["trace"])))
-        fh.write("\n }\n}\n")
+            head = '%s\n  %s: {"digests": %s,\n   "unstable": %s,\n' % ("," if i else "", json.dumps(name), json.dumps(c["digests"], sort_keys=True),
+                                                                       json.dumps(c["unstable"]))
+            if args.set == "fit":                        # (see ``expand``)
+                idx = [table.setdefault(json.dumps(call), len(table)) for call in c["trace"]]
+                fh.write('%s   "notes": %s,\n   "trace": %s}' % (head, json.dumps(c["notes"], sort_keys=True), json.dumps(idx, separators=(",", ":"))))
+            else:
+                fh.write('%s   "trace": [\n    %s\n   ]}' % (head, ",\n    ".join(json.dumps(call) for call in c["trace"])))
+        fh.write("\n }")
+        if table:
+            fh.write(',\n "calls": [\n  %s\n ]' % ",\n  ".join(table))
+        fh.write("\n}\n")
     print("wrote %s: %d cases, %d calls" % (out, len(rec), sum(len(c["trace"]) for c in rec.values())))
 
 

@@ -22,7 +22,17 @@ tests/golden/call_trace_options_parent.json is the fourth set (``--set options``
 step's operands records built once at construction: each A/B switch of the large-tile step off on its own, the two-group
 weight-gradient composition under sublayer dropout, a three-layer FC stack, the fixed positional encoding on the padded grid,
 ``score()`` between two steps, ``load_state_dict`` with another seed, and a scorer over an ``input_norm`` model with 46 features.
-Its traces begin at the constructor, so the size and support queries made there are held as well.  The same rules once more."""
+Its traces begin at the constructor, so the size and support queries made there are held as well.  The same rules once more.
+
+tests/golden/call_trace_fit_parent.json is the fifth set (``--set fit``), recorded at the parent of the change that gave the two
+engines one interface under ``fit()``, ``_evaluate`` one score source per batch and the epoch statistics one accumulator: whole
+``fit()`` calls over a small libsvm set the generator writes (40 queries of 3 to 20 items, batches of 16, so the last one is
+short) -- both engines, the four validation score sources, the ragged evaluation, schedulers, early stopping, the finiteness
+check with its full error text, checkpoint and resume.  A case holds the trace of the whole call and digests of the returned dict
+(every value as ``float.hex`` with its type name), of ``last_run`` without wall-clock entries and paths, of the per-epoch
+validation loss, of every tensor of ``model.pkl`` and, where one is written, of the checkpoint; its ``notes`` -- the engine, how
+many batches each score source served, the error text -- are held like the digests.  The file stores each distinct call once and
+a trace as indices into that table (``expand``)."""
 import json
 
 import pytest
@@ -34,7 +44,7 @@ pytestmark = pytest.mark.gpu
 
 def _load(path):
     with open(path) as fh:
-        return json.load(fh)
+        return G.expand(json.load(fh))
 
 
 @pytest.fixture(scope="module")
@@ -123,13 +133,41 @@ def test_options_fixture_is_the_parents_and_covers_every_case(recs):
     assert not set(rec["cases"]) & (set(recs["calls"]["cases"]) | set(recs["rows"]["cases"]) | set(recs["step"]["cases"]))
 
 
+def test_fit_fixture_is_the_parents_and_covers_every_case(recs):
+    rec = recs["fit"]
+    assert len(rec["commit"]) == 40
+    assert sorted(rec["cases"]) == sorted(G.fit_cases()) and len(rec["cases"]) == 17
+    for name, c in rec["cases"].items():
+        assert c["trace"] and c["unstable"] == [] and c["digests"], name
+    notes = {n: c["notes"] for n, c in rec["cases"].items()}
+    served = lambda n: {k for k, v in notes[n]["sources"].items() if v}  # noqa: E731
+    assert {"resident", "packed", "trainer_score", "module"} == set().union(*(served(n) for n in notes))     # the four score sources
+    assert served("fit_fused_grid_trainer_score") == {"trainer_score"} and served("fit_fused_grid_module_val") == {"module"}
+    assert served("fit_fused_compact_graph_packed_val") == {"resident"} and served("fit_fused_host_loader_ragged_val") == {"packed"}
+    assert {v["engine"] for v in notes.values()} == {"fused", "autograd"}
+    assert notes["fit_fused_host_loader_ragged_val"]["val_eval"] == {"loss": "ragged", "metrics": "ragged"}       # both ragged evaluations
+    assert notes["fit_fc_listnet_step"]["fcstep"] and not notes["fit_fc_listnet_step"]["compact"]
+    assert notes["fit_fused_compact_graph_packed_val"]["compact_graph"] and notes["fit_fused_compact"]["compact"]
+    assert "stochastic NeuralNDCG" in notes["fit_stochastic_neural_ndcg_packed_val"]["val_scorer_reason"]
+    assert notes["fit_fused_step_lr_early_stop"]["epochs"] < 7                                 # early stopping fired
+    assert "gradient element(s)" in notes["fit_check_finite_nan_fused"]["error"]
+    assert "weight element(s)" in notes["fit_check_finite_nan_autograd"]["error"]
+    for n in ("fit_checkpoint_resume_fused", "fit_checkpoint_resume_autograd"):
+        assert {"first_ckpt_trainer", "ckpt_trainer", "first_model_pkl", "model_pkl"} <= set(rec["cases"][n]["digests"]) and notes[n]["epochs"] == 3
+    called = {call[0] for c in rec["cases"].values() for call in c["trace"]}
+    assert {"ltrx_fc_listnet_step", "ltrx_first_nonfinite", "ltrx_adam_step", "ltrx_listnet_fwd_bwd_cu", "ltrx_ndcg_at_cu",
+            "ltrx_mrr_at_cu"} <= called                                                      # (the ragged loss and both ragged metrics)
+    assert not set(rec["cases"]) & {n for k in ("calls", "rows", "step", "options") for n in recs[k]["cases"]}
+
+
 CASE_SET = {name: key for key, (_, make) in G.SETS.items() for name in make()}
 
 
 @pytest.mark.parametrize("name", sorted(CASE_SET))
 def test_same_calls_same_bits(recs, proxy, name):
     want = recs[CASE_SET[name]]["cases"][name]
-    trace, digests = G.run_case(proxy, name)
+    trace, digests, notes = G.run_case(proxy, name)
+    assert notes == want.get("notes", {}), (name, notes)
     assert len(trace) == len(want["trace"]), ([c[0] for c in trace], [c[0] for c in want["trace"]])
     for i, (got, exp) in enumerate(zip(trace, want["trace"])):
         assert got == exp, (name, i, got, exp)
