@@ -634,10 +634,68 @@ def load_libsvm_dataset_role(role, input_path, slate_length, device=None):
     return ds
 
 
-def load_libsvm_dataset(input_path, slate_length, validation_ds_role, device=None):
-    """dataset_loading.py:197-209: (train, validation) datasets -- resident in HBM"""
-    return (load_libsvm_dataset_role("train", input_path, slate_length, device),
-            load_libsvm_dataset_role(validation_ds_role, input_path, slate_length, device))
+NORMALIZE_ENV = "ALLRANK_AMD_NORMALIZE"
+NORMALIZE_ROLES = ("train", "test", "vali")             # the files reproducibility/normalize_features.py reads (:31-33)
+
+
+def _normalizer_from(settings):
+    """the FeatureNormalizer ``settings`` names: one already built, or the path of a settings file"""
+    from .normalize import FeatureNormalizer
+    if isinstance(settings, FeatureNormalizer):
+        return settings
+    try:
+        return FeatureNormalizer.from_settings(settings)
+    except (OSError, ValueError) as e:
+        raise type(e)("allrank_amd.data: cannot read the feature normalisation settings %r (%s, or load_libsvm_dataset's normalize=): %s"
+                      % (settings, NORMALIZE_ENV, e))
+
+
+def _normalize_loaded(nz, input_path, loaded, also=()):
+    """Fit ``nz`` on the train role and apply it to every data set of ``loaded`` ({role: DeviceLibSVMDataset}) and of ``also`` (further
+    copies of a loaded role).  The decision which columns are >= 0 is taken over train, test and vali as the reference script takes
+    it -- over those of the three files that exist in ``input_path``: a role that was not loaded is parsed on the device, reduced to its
+    per-column minimum and freed; a missing one is logged and left out of ``nz.roles``."""
+    import os
+    x_train = loaded["train"].slates.x_items
+    roles, minima = [], []
+    for role in NORMALIZE_ROLES + tuple(r for r in loaded if r not in NORMALIZE_ROLES):     # (a validation role of another name counts too)
+        if role in loaded:
+            minima.append(nz.minimum(loaded[role].slates.x_items))
+        elif os.path.exists(_local_path(input_path, role)):
+            log.info("feature normalisation: reading %s for the sign decision only", _local_path(input_path, role))
+            X, _, _ = parse_svm_file_on_device(_local_path(input_path, role), x_train.device)
+            minima.append(nz.minimum(X))
+            del X
+        else:
+            log.warning("feature normalisation: %s is missing -- the decision which features take the logarithm is taken without the "
+                        "%s role", _local_path(input_path, role), role)
+            continue
+        roles.append(role)
+    nz.fit_with_minima(x_train, minima, roles)
+    for ds in list(loaded.values()) + list(also):
+        nz.apply(ds.slates)
+        ds.normalizer = nz
+    log.info("feature normalisation: statistics from %s, roles %s, %d of %d features take the logarithm, %d wanted it and hold negative "
+             "values: %s", _local_path(input_path, "train"), roles, nz.report["log"], nz.n_features, len(nz.no_log_negative),
+             nz.no_log_negative)
+
+
+def load_libsvm_dataset(input_path, slate_length, validation_ds_role, device=None, normalize=None):
+    """dataset_loading.py:197-209: (train, validation) datasets -- resident in HBM.  ``normalize`` (a settings file's path or a
+    ``FeatureNormalizer``; default: the environment variable ALLRANK_AMD_NORMALIZE, which main.py's callers set) normalises the features
+    of both on the device with statistics of ``train.txt`` (allrank_amd/normalize.py) and hangs the normaliser on them as
+    ``ds.normalizer``; without it the data sets are what they always were."""
+    import os
+    settings = normalize if normalize is not None else (os.environ.get(NORMALIZE_ENV) or None)
+    nz = _normalizer_from(settings) if settings is not None else None
+    train = load_libsvm_dataset_role("train", input_path, slate_length, device)
+    val = load_libsvm_dataset_role(validation_ds_role, input_path, slate_length, device)
+    if nz is not None:
+        if validation_ds_role == "train":                # two copies of one role: each is normalised once
+            _normalize_loaded(nz, input_path, {"train": train}, also=(val,))
+        else:
+            _normalize_loaded(nz, input_path, {"train": train, validation_ds_role: val})
+    return train, val
 
 
 def processing_units():

@@ -56,9 +56,12 @@ from .parallel import shard_slates
 
 log = logging.getLogger("allrank_amd.fit")
 
+NORMALIZATION_FILE = "feature_normalization.npz"      # beside model.pkl when the training data set carries a FeatureNormalizer
+
 last_run = {}          # what the most recent fit() used: {"engine": "fused" | "autograd", "compact": bool, "reason": str,
 #                        "sampling": the training DeviceLoader's mode ("device" | "reference"; None for any other loader),
-#                        "compact_graph": what the captured variable-length step did (None: off), "compact_graph_reason": str, ...}
+#                        "compact_graph": what the captured variable-length step did (None: off), "compact_graph_reason": str, ...;
+#                        "normalize": {"roles", "log", "no_log_negative"} only when the training data set carries a normaliser}
 
 
 class _EarlyStop(object):
@@ -525,6 +528,9 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
                     fcstep=trainer.fcstep, sampling=getattr(train_dl, "sampling", None),
                     compact_graph=_compact_graph_stats(trainer), compact_graph_reason=cg_reason)
     log.info("allrank_amd.fit: %s step%s", last_run["engine"], (" (" + reason + ")") if reason else "")
+    normalizer = getattr(getattr(train_dl, "dataset", None), "normalizer", None)      # load_libsvm_dataset(normalize=...) hung it there
+    if normalizer is not None:
+        last_run["normalize"] = normalizer.report
     vs_reason = _packed_blocker(loss_func, fused, reason) if val_scorer_mode in ("packed", "ragged") else ""
     scorers = {} if val_scorer_mode in ("packed", "ragged") and not vs_reason else None
     last_run.update(val_scorer=val_scorer_mode if scorers is not None else "module", val_scorer_reason=vs_reason)
@@ -642,6 +648,8 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
 
     if rank == 0:
         torch.save({k: v.detach().clone() for k, v in model.state_dict().items()}, os.path.join(output_dir, "model.pkl"))
+        if normalizer is not None:                       # what the model's inputs went through: needed to score raw features later
+            normalizer.save(os.path.join(output_dir, NORMALIZATION_FILE))
     if writer is not None:
         writer.close_all_writers()
     return make_result(epoch, train_metrics, val_metrics, num_params)

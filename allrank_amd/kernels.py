@@ -1,4 +1,5 @@
-"""The one Python statement of each kernel call of libltrx.so (include/ltrx.h) outside the losses, the metrics and the data loader:
+"""The one Python statement of each kernel call of libltrx.so (include/ltrx.h) outside the losses, the metrics, the data loader and the
+feature normalisation of resident data (allrank_amd/normalize.py states its three calls in this module's form):
   * the scoring model: GEMMs, attention, LayerNorm, score head, output activation, weight images;
   * the packing calls: batch ingest, the index layout's ``gather_rows`` / ``scatter_rows`` / ``packed_row_index``, the cu_seqlens
     layout's ``gather_rows_cu`` / ``scatter_rows_cu`` / ``zero_rows_cu`` / ``assemble_packed``;

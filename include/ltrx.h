@@ -719,6 +719,33 @@ int ltrx_assemble_batch_picked(const float* x_items, const float* y_items, const
 int ltrx_libsvm_parse(const uint8_t* text, const int64_t* line_start, int64_t n_lines, int64_t n_bytes, float* y, int64_t* qid, float* X,
                       int n_features, int index_base, int* minmax_index, int* bad_lines, ltrx_stream_t stream);
 
+/* Feature normalisation of a resident item array (the reference: reproducibility/normalize_features.py, a host script over three
+ * libsvm files).  allrank_amd/csrc/ltrx_featnorm.hip.
+ *   x[n, F]: fp32 rows, `ld` floats apart (ld >= F; the ld - F floats behind a row are never read and never written).
+ *   negate[F], take_log[F]: device uint8 flags per column.  With s = -1 where negate[f] is set, else 1:
+ *       t(x) = s x,  and  t(x) = log(s x + eps_log)  where take_log[f] is set -- evaluated in fp64 from the fp32 value.
+ *   eps_log_host, eps_host: HOST pointers to the two fp64 constants (read before the launch).
+ *   ltrx_feature_min:       min_out[f] = min over the rows of s x (fp32, exact).  -0.0 and +0.0 compare equal, so a column of zeros
+ *                           of either sign has a minimum that is >= 0.  Called once per role; the caller takes the minimum over roles.
+ *   ltrx_feature_moments:   mean_out[f] = (sum of t) / n, then std_out[f] = sqrt((sum of (t - mean_out[f])^2) / n): TWO passes over
+ *                           x, as np.mean / np.std take them, never E[t^2] - E[t]^2.
+ *   ltrx_feature_normalize: x = (float)((t(x) - mean[f]) / (std[f] + eps)), in place.
+ * A workgroup owns a block of rows and a thread a fixed set of columns: its partial results stay in registers, the threads of a
+ * workgroup that share columns are combined by a tree of fixed shape in LDS, every workgroup leaves one row of F fp64 partials in
+ * `ws`, and a second small launch combines those rows in a fixed order.  No floating-point atomics: the same bits on every call with
+ * the same arguments.  Rows are read (and written) in 16-byte pieces where ld % 4 == 0 and x is 16-byte aligned, in 4-byte pieces
+ * otherwise; any F.  HBM: 4 n F bytes read per pass (one pass for the minimum, two for the moments), as many written by normalize.
+ * The calls allocate nothing and synchronise nothing.  *_workspace_bytes: one row of F doubles per workgroup, never fewer for a
+ * larger n; 0 for n <= 0 or F <= 0.
+ * NULL x / negate / take_log / an output / ws / a host pointer, n <= 0, F <= 0 or ld < F: LTRX_EINVAL, nothing launched. */
+size_t ltrx_feature_min_workspace_bytes(int n, int F);
+int ltrx_feature_min(const float* x, int n, int F, int ld, const uint8_t* negate, float* min_out, void* ws, ltrx_stream_t stream);
+size_t ltrx_feature_moments_workspace_bytes(int n, int F);
+int ltrx_feature_moments(const float* x, int n, int F, int ld, const uint8_t* negate, const uint8_t* take_log,
+                         const double* eps_log_host, double* mean_out, double* std_out, void* ws, ltrx_stream_t stream);
+int ltrx_feature_normalize(float* x, int n, int F, int ld, const uint8_t* negate, const uint8_t* take_log, const double* eps_log_host,
+                           const double* mean, const double* std, const double* eps_host, ltrx_stream_t stream);
+
 /* Test hook: D[32x32] = A[32x2] * B[2x32] with ONE v_mfma_f32_32x32x2_f32, written through the operand / result
  * lane layout the attention kernels assume.  Lets the parity suite tell a layout bug from a logic bug. */
 int ltrx_selftest_mfma32x32x2(const float* A, const float* B, float* D, ltrx_stream_t stream);
