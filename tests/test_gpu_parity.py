@@ -94,7 +94,8 @@ def test_losses_match_reference_golden(losses_golden):
 @pytest.mark.parametrize("B,L,seed", [(64, 240, 1), (7, 33, 2), (3, 1, 3), (5, 257, 4), (2, 1024, 5)])
 def test_losses_match_oracle_random(B, L, seed):
     """the max-norm bar (``grad_close``) on random slates; the entrywise bar of the four listwise losses lives in
-    tests/test_gpu_listwise_contract.py"""
+    tests/test_gpu_listwise_contract.py, that of NeuralNDCG (against fp64, every kernel arm, the rewind, interior pads) in
+    tests/test_gpu_neural_contract.py"""
     from tests.golden.make_inputs import make_inputs
     s, y = make_inputs(B, L, seed)
     perm = np.random.default_rng(seed).permutation(L).astype(np.int64)
@@ -840,7 +841,8 @@ def test_sharded_fit_with_uneven_last_batch_equals_one_rank():
 def test_neuralndcg_block_resident_path_equals_general_path():
     """the block-resident kernels (L <= 240: 2 x 2 / 4 x 4 / 6 x 6 tiles on 16 waves, 15 x 5 tiles on 12 waves) and the general
     L2-streaming kernels agree with each other and the oracle; L = 250 runs the general kernels on both paths; the 3-item slates
-    converge below tol before max_iter (batch-global early exit: the rewind of the backward kernel runs)."""
+    converge below tol before max_iter (batch-global early exit: the rewind of the backward kernel runs).  The entrywise fp64 contract
+    of each path on its own, with a guarded early exit on every tile geometry, is tests/test_gpu_neural_contract.py."""
     from allrank_amd import losses as E, _lib as LB
     from tests.golden.make_inputs import make_inputs
     lib = LB.lib()
