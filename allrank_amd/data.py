@@ -130,6 +130,7 @@ class DeviceSlates(object):
         self.n_features = int(X.shape[1])
         self.longest_query_length = int(lens.max())
         self.lengths_host = torch.from_numpy(lens.astype(np.int32))
+        self.slate_qids = torch.from_numpy(q[starts].astype(np.int64))      # host: every slate's query id as the source gave it
         self.x_items = Xt
         self.y_items = yt
         self.offsets = torch.from_numpy(offsets).to(self.device)
@@ -153,6 +154,24 @@ class DeviceSlates(object):
         from sklearn.datasets import load_svmlight_file
         X, y, qid = load_svmlight_file(path, query_id=True)
         return cls(X, y, qid, device)
+
+    def write_svm_file(self, path, zero_based=True):
+        """the resident items as libsvm text at ``path``, with their labels and original query ids (``slate_qids``), formatted on the
+        device (allrank_amd/saving.py) -- so a set normalised in place (allrank_amd/normalize.py) is saved as the text
+        reproducibility/normalize_features.py would have dumped: ``dump_svmlight_file(X, y, path, query_id=qid)``, zero-based indices.
+        Every item is a row (labels of -1 included: nothing here is padding).
+        The reference's own quirk, kept: a zero is not written, so with zero-based indices and a column 0 that is zero in EVERY row no
+        index 0 appears in the file, and a reader that guesses the base (scikit-learn's ``zero_based="auto"``, the reference's
+        loader, ``from_svm_file``) takes the file for one-based and shifts every index down by one.  ``zero_based=False`` writes
+        one-based indices, which such a reader always gets right."""
+        from . import saving as SV
+        F, dev = self.n_features, self.device
+        engine, why = SV._engine(F, (self.x_items, self.y_items))
+        qid_items = self.slate_qids.to(dev).repeat_interleave(self.lengths)
+        per = max(1, int(SV.CHUNK_BYTES // max(1, F * 4)))
+        n = int(self.x_items.shape[0])
+        chunks = ((self.x_items[a:a + per], self.y_items[a:a + per], qid_items[a:a + per]) for a in range(0, n, per))
+        SV.write_rows(path, chunks, engine, why, pad_value=float("nan"), index_base=0 if zero_based else 1)
 
     def __len__(self):
         return self.n_slates

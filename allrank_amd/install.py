@@ -10,7 +10,9 @@ allRank resolves its plugins by name at run time (SURVEY.md §5 "Config / flags"
 (config parsing, early stopping, logging) keeps running as is.  ``install(fit=True)`` additionally puts
 ``allrank_amd.fit.fit`` (reference signature, explicit HIP training step inside) behind main.py:90.  ``install(inference=True)`` puts
 ``allrank_amd.inference.rank_slates`` behind the second entry point, rank_and_click.py:86; ``install(clicks=True)`` puts
-``allrank_amd.clicks.click_on_slates`` / ``metrics_on_clicked_slates`` behind what that entry point does next (:88, :95).
+``allrank_amd.clicks.click_on_slates`` / ``metrics_on_clicked_slates`` behind what that entry point does next (:88, :95);
+``install(saving=True)`` puts ``allrank_amd.saving.write_to_libsvm_without_masked`` behind its last stage (:92), so
+``install(inference=True, clicks=True, saving=True)`` runs all three stages of rank_and_click.py on the device.
 ``uninstall()`` restores all.
 
     import allrank_amd; allrank_amd.install(fit=True)      # then: from allrank.main import run; run()
@@ -123,7 +125,21 @@ def _install_clicks(done):
         _rebind((owner, "allrank.rank_and_click"), name, ours, done)
 
 
-def install(losses=True, metrics=True, model=True, fit=False, distributed=None, data=None, inference=False, clicks=False):
+def _install_saving(done):
+    """rank_and_click.py:92 -> ``allrank_amd.saving.write_to_libsvm_without_masked``: the defining module
+    (allrank/data/dataset_saving.py:9) and the entry point's own copy of the name (rank_and_click.py:14).  Our function takes the
+    reference's annotations, as ``rank_slates`` does."""
+    from . import saving as ES
+    rs = importlib.import_module("allrank.data.dataset_saving")
+    name = "write_to_libsvm_without_masked"
+    ref = getattr(rs, name) if id(getattr(rs, name)) not in _ours else _saved.get((rs.__name__, name))
+    if ref is not None:
+        ES.write_to_libsvm_without_masked.__annotations__ = dict(getattr(ref, "__annotations__", {}))
+    _rebind(("allrank.data.dataset_saving", "allrank.rank_and_click"), "write_to_libsvm_without_masked", ES.write_to_libsvm_without_masked,
+            done)
+
+
+def install(losses=True, metrics=True, model=True, fit=False, distributed=None, data=None, inference=False, clicks=False, saving=False):
     """Rebind the hot-path names inside the importable ``allrank`` package.  Returns the list of rebound names.
     ``fit=True`` also rebinds the epoch loop (train_utils.py:78; imported into main.py's namespace at main.py:18) to
     ``allrank_amd.fit.fit`` -- same signature and return value, the explicit MI355X step inside.
@@ -133,7 +149,9 @@ def install(losses=True, metrics=True, model=True, fit=False, distributed=None, 
     ``inference=True`` (opt-in): also rebinds ``rank_slates`` (inference_utils.py:14, imported into rank_and_click.py at :15) to
     ``allrank_amd.inference.rank_slates`` -- scores from the packed scorer, slates ranked by ltrx_rank_slates_cu.
     ``clicks=True`` (opt-in, independent of ``inference``): also rebinds ``click_on_slates`` (click_utils.py:10) and
-    ``metrics_on_clicked_slates`` (inference_utils.py:73), both imported into rank_and_click.py, to ``allrank_amd.clicks``."""
+    ``metrics_on_clicked_slates`` (inference_utils.py:73), both imported into rank_and_click.py, to ``allrank_amd.clicks``.
+    ``saving=True`` (opt-in, independent of both): also rebinds ``write_to_libsvm_without_masked`` (dataset_saving.py:9, imported into
+    rank_and_click.py at :14) to ``allrank_amd.saving`` -- the same file, formatted on the device."""
     from . import launch as D
     if distributed:
         dev = D.setup()
@@ -180,6 +198,8 @@ def install(losses=True, metrics=True, model=True, fit=False, distributed=None, 
         _install_inference(done)
     if clicks:
         _install_clicks(done)
+    if saving:
+        _install_saving(done)
     return done
 
 
@@ -198,3 +218,6 @@ def uninstall():
         clk._reference.clear()
         clk.click_on_slates.__annotations__ = {}
         clk.metrics_on_clicked_slates.__annotations__ = {}
+    sav = sys.modules.get(__package__ + ".saving")
+    if sav is not None:
+        sav.write_to_libsvm_without_masked.__annotations__ = {}

@@ -746,6 +746,32 @@ int ltrx_feature_moments(const float* x, int n, int F, int ld, const uint8_t* ne
 int ltrx_feature_normalize(float* x, int n, int F, int ld, const uint8_t* negate, const uint8_t* take_log, const double* eps_log_host,
                            const double* mean, const double* std, const double* eps_host, ltrx_stream_t stream);
 
+/* libsvm text written on the device: the inverse of ltrx_libsvm_parse (the reference: dataset_saving.py:32, scikit-learn's
+ * dump_svmlight_file on the host, 22 bytes of text per value).  allrank_amd/csrc/ltrx_svmwrite.hip, ltrx_fmt.h.
+ *   X[n_rows, F]: fp32 rows, `ldx` floats apart (ldx >= F);  y[n_rows] fp32 labels;  qid[n_rows] int64;  all in device memory.
+ *   A row is KEPT unless y[r] == pad_value (a NaN pad_value keeps every row).  The line of a kept row:
+ *       <%.16g of y[r]> qid:<%d of qid[r]>   then   " <f + index_base>:<%.16g of X[r][f]>"   for each f with X[r][f] != 0, rising f,
+ *       then "\n";  a row without a non-zero value ends "qid:N \n", with the space.  -0.0 counts as zero and is left out.
+ *   "%.16g" is the text Python's '%.16g' % float(numpy.float32(v)) gives, for EVERY fp32 bit pattern: the correctly rounded sixteen
+ *   significant digits of the exact binary value (half-even on exact ties), trailing zeros stripped, fixed notation for decimal
+ *   exponents -4 .. 15 and d.ddde+XX otherwise, "-0", "nan", "inf", "-inf".  Integer arithmetic only (multi-word division and
+ *   multiplication by 10^9); the host and the device run the same function.
+ *   ltrx_libsvm_line_bytes (pass A): line_bytes[r] = the byte length of row r's line, 0 for a row that is not kept;  *bad (device int,
+ *       zero-initialised by the caller) += the number of kept rows that hold a non-finite label or value.
+ *   ltrx_libsvm_format (pass B): row r's line at text + line_start[r], where line_start = the exclusive prefix sum of line_bytes (the
+ *       caller's, e.g. torch.cumsum) and n_bytes = its total.  Offsets are int64.  Nothing outside [0, n_bytes) is written, whatever
+ *       line_start holds.  Placement is deterministic: one wave per row, a wave scan of the token lengths, no atomics.
+ *   Both passes format every value (a token's length is known only once it is rounded); neither allocates or synchronises.
+ *   NULL X / y / qid / an output, n_rows <= 0, F <= 0, ldx < F, index_base < 0, F + index_base > INT_MAX, n_bytes <= 0: LTRX_EINVAL,
+ *   nothing launched.  Not covered by the test suite: a text above 2 GiB in one call.
+ *   ltrx_debug_format_g16: HOST-ONLY test hook, no launch -- v[n], text[24 n] and len[n] are host pointers; len[i] bytes (at most 22)
+ *       of the text of v[i] start at text + 24 i.  It runs the function the kernels run, compiled for the host. */
+int ltrx_libsvm_line_bytes(const float* X, int64_t ldx, const float* y, const int64_t* qid, int64_t n_rows, int F, float pad_value,
+                           int index_base, int64_t* line_bytes, int* bad, ltrx_stream_t stream);
+int ltrx_libsvm_format(const float* X, int64_t ldx, const float* y, const int64_t* qid, int64_t n_rows, int F, float pad_value,
+                       int index_base, const int64_t* line_start, int64_t n_bytes, uint8_t* text, ltrx_stream_t stream);
+int ltrx_debug_format_g16(const float* v, int64_t n, uint8_t* text, int32_t* len);
+
 /* Test hook: D[32x32] = A[32x2] * B[2x32] with ONE v_mfma_f32_32x32x2_f32, written through the operand / result
  * lane layout the attention kernels assume.  Lets the parity suite tell a layout bug from a logic bug. */
 int ltrx_selftest_mfma32x32x2(const float* A, const float* B, float* D, ltrx_stream_t stream);
