@@ -15,6 +15,11 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libltrx.so")
 STAMP = os.path.join(HERE, ".libltrx.stamp")
 ARCH = "gfx950"
+# per-source flags on top of the common ones.  ltrx_outhead.hip is compiled without the packed-fp32 instructions (two fp32 operations
+# per lane in one VALU instruction): with them its n_out accumulators pair up into v_pk_fma_f32, which the kernel's contract (exact
+# scalar fused multiply-adds in a stated order) does not want.  The host pass of hipcc warns that it does not know the feature.
+_NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+EXTRA_FLAGS = {"ltrx_outhead.hip": _NO_PACKED_FP32}
 
 
 def _sources():
@@ -46,8 +51,8 @@ def build(force=False, verbose=True):
     for src in _sources():
         obj = os.path.join(objdir, os.path.basename(src)[:-4] + ".o")
         objs.append(obj)
-        cmd = [hipcc, "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
-               "-c", src, "-o", obj]
+        cmd = [hipcc, "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
+        cmd += EXTRA_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
         procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
     failed = False
     for src, p in procs:

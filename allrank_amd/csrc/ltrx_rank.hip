@@ -1,4 +1,5 @@
-// Ranked slates: packed scores -> every slate's items (features and labels) in descending score order, padded to L.
+// Ranked slates: packed scores -- or the packed output rows of a model with several output units, whose sum is the score -- -> every
+// slate's items (features and labels) in descending score order, padded to L.
 // Reference: allrank/inference/inference_utils.py:51-56 -- padded scores to -inf, scores.sort(descending=True), torch.gather of X and y.
 //
 // ORDER.  rank of item i = #{ j : s_j > s_i, or s_j == s_i and j < i }: the stable descending policy of ltrx_ndcg_at_cu, counted by the
@@ -23,9 +24,28 @@
 
 using namespace ltrx;
 
-// T: the unit a lane moves, float4 (C = F / 4 units per row) or float (C = F)
-template <typename T, bool RESIDENT>
-__global__ void __launch_bounds__(1024) ltrx_rank_kernel(const float* __restrict__ scores, const float* __restrict__ xs,
+// THE SORT KEY of packed item `item` is what a key loader returns while phase 1 fills the slate's keys in LDS; everything after that
+// load -- the counting sort, the gather, the tails -- is one body for both entry points.
+//   LtrxKeyRead    ltrx_rank_slates_cu: the item's packed score, read.
+//   LtrxKeyRowSum  ltrx_rank_slates_rows_cu: a model with n_out output units -- the item's output row out[item, 0 .. n_out-1], folded
+//                  p_0 + p_1 + ... in that order in fp32 (model.score's sum, the order of ltrx_out_head_fwd): the ranking needs no
+//                  score array and no launch before it.  4 n_out bytes per item instead of 4.
+// A loader is handed the kernel's own __restrict__ key pointer, its row width and the first packed item of the slate.
+struct LtrxKeyRead {
+  static __device__ __forceinline__ float load(const float* __restrict__ keys, int, size_t row0, int i) { return (keys + row0)[i]; }
+};
+struct LtrxKeyRowSum {
+  static __device__ __forceinline__ float load(const float* __restrict__ keys, int n_out, size_t row0, int i) {
+    const float* p = keys + (row0 + (size_t)i) * (size_t)n_out;
+    float s = p[0];
+    for (int k = 1; k < n_out; ++k) s += p[k];
+    return s;
+  }
+};
+
+// T: the unit a lane moves, float4 (C = F / 4 units per row) or float (C = F); Key: the key loader
+template <typename T, bool RESIDENT, typename Key>
+__global__ void __launch_bounds__(1024) ltrx_rank_kernel(const float* __restrict__ keys, int width, const float* __restrict__ xs,
                                                         const float* __restrict__ ys, const int64_t* __restrict__ offsets,
                                                         const int64_t* __restrict__ ids, const int32_t* __restrict__ cu,
                                                         const int32_t* __restrict__ order, int max_len, int C, int L,
@@ -47,9 +67,8 @@ __global__ void __launch_bounds__(1024) ltrx_rank_kernel(const float* __restrict
   T zero;
   __builtin_memset(&zero, 0, sizeof(T));
   T* xo = reinterpret_cast<T*>(x_out) + (size_t)sl.b * L * C;
-  const float* sp = scores + sl.row0;
   for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    ss[i] = sp[i];
+    ss[i] = Key::load(keys, width, sl.row0, i);
     inv[i] = -1;
   }
   __syncthreads();
@@ -86,30 +105,32 @@ __global__ void __launch_bounds__(1024) ltrx_rank_kernel(const float* __restrict
   for (int r = n + threadIdx.x; r < L; r += blockDim.x) yo[r] = -1.0f;
 }
 
-template <typename T, bool RESIDENT>
-static int rank_launch(const float* scores, const float* xs, const float* ys, const int64_t* offsets, const int64_t* ids, const int32_t* cu,
+template <typename T, bool RESIDENT, typename Key>
+static int rank_launch(const float* keys, int width, const float* xs, const float* ys, const int64_t* offsets, const int64_t* ids, const int32_t* cu,
                        const int32_t* order, int B, int max_len, int C, int L, int32_t* perm, float* x_out, float* y_out, hipStream_t s) {
   const size_t lds = 2 * (size_t)max_len * sizeof(float);
   if (lds > LTRX_DEFAULT_DYNAMIC_LDS_BYTES) {
     static std::atomic<uint64_t> attr_done{0};
-    const int arc = ltrx_allow_dynamic_lds(attr_done, {{ltrx_rank_kernel<T, RESIDENT>, 2 * LTRX_MAX_METRIC_SLATE_LEN * sizeof(float)}});
+    const int arc = ltrx_allow_dynamic_lds(attr_done, {{ltrx_rank_kernel<T, RESIDENT, Key>, 2 * LTRX_MAX_METRIC_SLATE_LEN * sizeof(float)}});
     if (arc != LTRX_OK) return arc;
   }
   // the thread with the most items of the longest slate walks all of that slate's partners: 16 waves as soon as 4 would give a thread
   // a second item (the ragged rule of ltrx_ndcg_at_cu); the row moves of phase 2 and the tail only gain from more waves in flight
   const dim3 block(max_len > 256 ? 1024 : 256);
-  hipLaunchKernelGGL((ltrx_rank_kernel<T, RESIDENT>), dim3(B), block, lds, s, scores, xs, ys, offsets, ids, cu, order, max_len, C, L, perm,
+  hipLaunchKernelGGL((ltrx_rank_kernel<T, RESIDENT, Key>), dim3(B), block, lds, s, keys, width, xs, ys, offsets, ids, cu, order, max_len, C, L, perm,
                      x_out, y_out);
   LTRX_LAUNCH_CHECK();
   return LTRX_OK;
 }
 
-extern "C" int ltrx_rank_slates_cu(const float* scores, const float* x, const float* y, const float* x_items, const float* y_items,
-                                   const int64_t* offsets, const int64_t* ids, const int32_t* cu_seqlens, const int32_t* slate_order,
-                                   int B, int max_len, int F, int L, int32_t* perm, float* x_out, float* y_out, ltrx_stream_t stream) {
+// the argument checks and the dispatch of both entry points; keys[n, width]: what the loader Key reads (width 1: the scores)
+template <typename Key>
+static int rank_slates(const float* keys, int width, const float* x, const float* y, const float* x_items, const float* y_items,
+                       const int64_t* offsets, const int64_t* ids, const int32_t* cu_seqlens, const int32_t* slate_order, int B, int max_len,
+                       int F, int L, int32_t* perm, float* x_out, float* y_out, ltrx_stream_t stream) {
   const bool grid = x && y, resident = x_items && y_items && offsets && ids;
   const bool any_grid = x || y, any_resident = x_items || y_items || offsets || ids;
-  if (!scores || !cu_seqlens || !x_out || !y_out || B <= 0 || F <= 0 || max_len <= 0 || L < max_len) return LTRX_EINVAL;
+  if (!keys || width <= 0 || !cu_seqlens || !x_out || !y_out || B <= 0 || F <= 0 || max_len <= 0 || L < max_len) return LTRX_EINVAL;
   if (grid == resident || (any_grid && !grid) || (any_resident && !resident)) return LTRX_EINVAL;     // exactly one complete source form
   if (max_len > LTRX_MAX_METRIC_SLATE_LEN) return LTRX_EUNSUPPORTED;
   const float* xs = grid ? x : x_items;
@@ -117,8 +138,23 @@ extern "C" int ltrx_rank_slates_cu(const float* scores, const float* x, const fl
   const bool vec = F % 4 == 0 && (((uintptr_t)xs | (uintptr_t)x_out) & 15) == 0;
   hipStream_t s = (hipStream_t)stream;
   if (vec)
-    return grid ? rank_launch<float4, false>(scores, xs, ys, nullptr, nullptr, cu_seqlens, slate_order, B, max_len, F / 4, L, perm, x_out, y_out, s)
-                : rank_launch<float4, true>(scores, xs, ys, offsets, ids, cu_seqlens, slate_order, B, max_len, F / 4, L, perm, x_out, y_out, s);
-  return grid ? rank_launch<float, false>(scores, xs, ys, nullptr, nullptr, cu_seqlens, slate_order, B, max_len, F, L, perm, x_out, y_out, s)
-              : rank_launch<float, true>(scores, xs, ys, offsets, ids, cu_seqlens, slate_order, B, max_len, F, L, perm, x_out, y_out, s);
+    return grid ? rank_launch<float4, false, Key>(keys, width, xs, ys, nullptr, nullptr, cu_seqlens, slate_order, B, max_len, F / 4, L, perm, x_out, y_out, s)
+                : rank_launch<float4, true, Key>(keys, width, xs, ys, offsets, ids, cu_seqlens, slate_order, B, max_len, F / 4, L, perm, x_out, y_out, s);
+  return grid ? rank_launch<float, false, Key>(keys, width, xs, ys, nullptr, nullptr, cu_seqlens, slate_order, B, max_len, F, L, perm, x_out, y_out, s)
+              : rank_launch<float, true, Key>(keys, width, xs, ys, offsets, ids, cu_seqlens, slate_order, B, max_len, F, L, perm, x_out, y_out, s);
+}
+
+extern "C" int ltrx_rank_slates_cu(const float* scores, const float* x, const float* y, const float* x_items, const float* y_items,
+                                   const int64_t* offsets, const int64_t* ids, const int32_t* cu_seqlens, const int32_t* slate_order,
+                                   int B, int max_len, int F, int L, int32_t* perm, float* x_out, float* y_out, ltrx_stream_t stream) {
+  return rank_slates<LtrxKeyRead>(scores, 1, x, y, x_items, y_items, offsets, ids, cu_seqlens, slate_order, B, max_len, F, L,
+                     perm, x_out, y_out, stream);
+}
+
+extern "C" int ltrx_rank_slates_rows_cu(const float* out, int n_out, const float* x, const float* y, const float* x_items,
+                                        const float* y_items, const int64_t* offsets, const int64_t* ids, const int32_t* cu_seqlens,
+                                        const int32_t* slate_order, int B, int max_len, int F, int L, int32_t* perm, float* x_out,
+                                        float* y_out, ltrx_stream_t stream) {
+  return rank_slates<LtrxKeyRowSum>(out, n_out, x, y, x_items, y_items, offsets, ids, cu_seqlens, slate_order,
+                     B, max_len, F, L, perm, x_out, y_out, stream);
 }

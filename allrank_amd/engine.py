@@ -179,7 +179,7 @@ def _alloc_forward(owner, t, rows, B, L, saved, layout):
       layers[i]: lin_qkv, lin_o, lin_ff1, lin_ff2, norm0, norm1, p_*, s_* (the trainer's operand records and dropout sites of the
       layer: t._layer_ops[i]; its own dicts later hold rbits), xsum0 (the residual stream entering layer i > 0), xn0, mean0, rstd0, qkv, o, lse, x1, xn1, mean1,
       rstd1, r, and q, k, v (the column views of qkv that the attention launches read);  xsum_f, xf, mean_f, rstd_f (the final norm; xf
-      is None where t.norm_head holds: the fused final norm + score head keeps the normalised rows in registers);  scores_c (packed layouts only), scores_raw [B, L(, n_out)], scores [B, L]
+      is None where t.norm_head holds: the fused final norm + score head keeps the normalised rows in registers);  scores_c (packed layouts only; score_c [rows], their sum over the output units: the scorer's form with n_out > 1), scores_raw [B, L(, n_out)], scores [B, L]
     ``saved=True``, the trainer's form: the backward reads the activations, so every layer has its own.  ``saved=False``, the scorer's:
     ONE activation set serves every layer -- the residual stream ping-pongs between two buffers (a layer's input is dead once its
     out-projection has added it: xsum0 of layer i = ping[i % 2], xsum_f = ping[N % 2], x_pe = ping[0], which layer 0 reads while
@@ -240,6 +240,8 @@ def _alloc_forward(owner, t, rows, B, L, saved, layout):
         owner.x_pe = ping[0] if (t.N and not saved) else z(rows, d)
     if compact:
         owner.scores_c = z(rows) if no == 1 else z(rows, no)
+        if no > 1 and not saved:
+            owner.score_c = z(rows)                           # the packed sum over the output units (FusedScorer.packed)
     owner.scores_raw = z(B, L) if no == 1 else z(B, L, no)    # what the loss sees (model.forward)
     owner.scores = owner.scores_raw if no == 1 else z(B, L)   # model.score (sum over the output units)
 
@@ -1196,6 +1198,15 @@ class FusedTrainer(object):
         if self.N and not self.norm_head:
             self._ln_fwd(x, None, nf, None, bs.xf, bs.mean_f, bs.rstd_f, rows=M)
             feat = bs.xf
+        # a forward-only scorer that asks for it (FusedScorer(out_head=True): packed rows, d_output > 1): Linear, activation and
+        # model.score's sum in ONE exact-fp32 launch that writes the packed output rows and the packed score; where the library
+        # does not take the shape nothing was launched, and the GEMM sequence below runs
+        if (not train and no > 1 and getattr(bs, "out_head", False) and bs.layout == "cu"
+                and KN.out_head_fwd(lib, self._st(), feat, head.w, head.b, M, self.out_act, sc_rows, bs.score_c)):
+            bs.head_path = "out_head"                             # (a property of the scorer's shapes: the same at every call)
+            RW.scores_to_grid(bs, lib, stream, sc_rows, no)
+            KN.scatter_rows_cu(lib, stream, bs.score_c, bs.cu, bs.B, bs.L, 1, bs.rows, bs.scores)    # model.score: the packed sum's scatter
+            return feat, sc_rows
         if self.norm_head:                                        # final norm + score head in one pass: LN(x) stays in registers
             feat = None
             KN.norm_head_fwd(lib, self._st(), x, nf.a, nf.b, head.w, head.b, M, nf.eps, sc_rows, bs.mean_f, bs.rstd_f)
@@ -1745,9 +1756,9 @@ class FusedTrainer(object):
         xs, ys, ids, lengths = self._block(xb, yb, indices, lengths)
         return self.score(xs, ys, ids, lengths=lengths)[:n], self.scores_raw[:max(n, 1)], ys[:max(n, 1)]
 
-    def scorer(self, B, L, use_graph=True, max_graphs=8):
+    def scorer(self, B, L, use_graph=True, max_graphs=8, out_head=False):
         """a FusedScorer for validation batches of ``B`` slates padded to ``L`` items (any L up to LTRX_MAX_METRIC_SLATE_LEN)"""
-        return FusedScorer(self, B, L, use_graph=use_graph, max_graphs=max_graphs)
+        return FusedScorer(self, B, L, use_graph=use_graph, max_graphs=max_graphs, out_head=out_head)
 
 
 class FusedScorer(object):
@@ -1773,7 +1784,7 @@ class FusedScorer(object):
     wrote (before the scatter), the packed labels, ``cu``, ``order`` and the batch's host ``max_len`` -- for a loss and metrics that
     run on the valid items only."""
 
-    def __init__(self, trainer, B, L, use_graph=True, max_graphs=8):
+    def __init__(self, trainer, B, L, use_graph=True, max_graphs=8, out_head=False):
         from . import _lib as LB
         t = trainer
         B, L = int(B), int(L)
@@ -1789,6 +1800,10 @@ class FusedScorer(object):
         self.y = torch.full((B, L), float(PADDED_Y_VALUE), dtype=torch.float32, device=t.dev)
         self.y_c = torch.zeros(self.cap, dtype=torch.float32, device=t.dev)     # the labels of the packed rows (``packed()``)
         self.max_len, self._y_c_fresh = 0, False           # longest slate of the last batch (host); y_c holds that batch's labels
+        # d_output > 1.  ``out_head``: the head runs as ltrx_out_head_fwd (exact fp32, one launch) where the library takes the shape --
+        # other bits than the GEMM head, which every scorer that does not ask keeps; ``head_path`` says which one the forward ran.
+        # ``score_c`` then holds the packed sum after every run; on the GEMM head ``packed()`` fills it on its first call after a run.
+        self.out_head, self.head_path, self._score_c_fresh = bool(out_head), "gemm", False
         seen, nb = set(), 0
         for v in list(vars(self).values()) + [v for st in self.layers for v in st.values()]:
             if torch.is_tensor(v) and v.is_cuda and v.untyped_storage().data_ptr() not in seen:
@@ -1861,18 +1876,28 @@ class FusedScorer(object):
     def packed(self):
         """The last batch in the ragged layout (include/ltrx.h): (scores [n], labels [n], cu_seqlens [B+1], launch order [B], host
         max_len).  The scores are the rows the forward wrote before scattering them (d_output == 1), the labels are packed from
-        ``self.y`` on the first call after a run; both stay valid until the next run."""
-        if self.t.n_out != 1:
-            raise NotImplementedError("FusedScorer.packed: d_output > 1 (the ordinal loss reads the padded grid)")
+        ``self.y`` on the first call after a run; both stay valid until the next run.  d_output > 1: the scores are model.score's sum
+        over the output units per valid item (``score_c``) -- what ltrx_out_head_fwd wrote beside the rows of ``packed_outputs()``,
+        or, on the GEMM head, the grid ``scores`` packed on the first call after a run."""
+        t = self.t
         if not self._y_c_fresh:
-            KN.gather_rows_cu(self.t.lib, self.t._st(), self.y, self.cu, self.B, self.L, 1, self.rows, self.y_c, None, "gather_rows_cu(labels)")
+            KN.gather_rows_cu(t.lib, t._st(), self.y, self.cu, self.B, self.L, 1, self.rows, self.y_c, None, "gather_rows_cu(labels)")
             self._y_c_fresh = True
         n = self.n_valid
-        return self.scores_c[:n], self.y_c[:n], self.cu, self.order, self.max_len
+        if t.n_out == 1:
+            return self.scores_c[:n], self.y_c[:n], self.cu, self.order, self.max_len
+        if self.head_path != "out_head" and not self._score_c_fresh:
+            KN.gather_rows_cu(t.lib, t._st(), self.scores, self.cu, self.B, self.L, 1, self.rows, self.score_c, None, "gather_rows_cu(scores)")
+            self._score_c_fresh = True
+        return self.score_c[:n], self.y_c[:n], self.cu, self.order, self.max_len
+
+    def packed_outputs(self):
+        """the packed output rows [n, d_output] of the last batch's valid items (model.forward's values; valid until the next run)"""
+        return self.scores_c[:self.n_valid].view(self.n_valid, self.t.n_out)
 
     def _run(self):
-        self._y_c_fresh = False
-        fwd = lambda: self.t._forward(False, self)
+        self._y_c_fresh = self._score_c_fresh = False
+        fwd =lambda: self.t._forward(False, self)
         if self.use_graph:
             self.last_mode = self._fwd_graphs.run(self.rows, fwd)
             self.evictions = self._fwd_graphs.evictions

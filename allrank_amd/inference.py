@@ -18,18 +18,27 @@ path and on the module path (``stable=True``) alike.
 nn.Module path (``model.score``, ``-inf``, ``torch.sort(stable=True)``, ``gather``) served it where the scorer could not -- a model
 the fused engine refuses, ``d_output > 1``, a slate length above LTRX_MAX_METRIC_SLATE_LEN, CPU tensors.  Never an exception.
 
+SEVERAL OUTPUT UNITS (``d_output > 1``: the ordinal configurations).  By default such a model takes the module path, with a reason
+that names ``d_output``.  With ``allrank_amd.inference.multi_output = True`` (or ``Ranker(model, multi_output=True)`` handed to
+``rank_batches``) it is ranked on the device: its scorer runs the head as ltrx_out_head_fwd -- Linear, activation and model.score's
+sum over the output units in one exact-fp32 launch -- and ``ltrx_rank_slates_rows_cu`` forms every item's sort key from the packed
+output rows (``FusedScorer.packed_outputs()``) inside the ranking launch.  ``last_run`` then also holds ``"head"`` ("out_head", or
+"gemm" where the library does not take the head's shape) and ``"n_out"``.  The option is a switch and not the default because the
+exact-fp32 head rounds differently from the module's: items whose module scores are closer than that difference may swap places.
+
 A model with a positional encoding is scored with ``indices = ones`` for every item (inference_utils.py:47): a quirk of the
 reference, reproduced.
 """
 import torch
 
 from . import _lib as LB
-from .kernels import rank_slates_cu
+from .kernels import rank_slates_cu, rank_slates_rows_cu
 from .metrics import PADDED_Y_VALUE
 
-__all__ = ["rank_slates", "rank_batches", "rank_slates_cu", "last_run"]
+__all__ = ["rank_slates", "rank_batches", "rank_slates_cu", "rank_slates_rows_cu", "last_run", "multi_output"]
 
 last_run = {"engine": None, "reason": ""}
+multi_output = False          # opt-in: rank models with d_output > 1 on the device (module docstring); read when a Ranker is built
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -60,9 +69,11 @@ class Ranker(object):
     the smallest batch, its step never called (the scorer reads the trainer's flat parameters, weight images and transposes) -- plus
     the ranked output buffers.  ``reason`` != "": the fused engine cannot serve this model, every batch takes the module path."""
 
-    def __init__(self, model):
+    def __init__(self, model, multi_output=None):
         self.model, self.trainer, self.reason = model, None, ""
         self._scorers, self._out = {}, {}
+        self.head = None                                      # d_output > 1: the head the last ranked batch's scorer ran
+        multi_output = globals()["multi_output"] if multi_output is None else multi_output
         try:
             p = next(model.parameters())
         except (StopIteration, AttributeError):
@@ -70,12 +81,14 @@ class Ranker(object):
         if p is None or not p.is_cuda:
             self.reason = "CPU tensors: the model is not on a GPU"
             return
-        if int(getattr(getattr(model, "output_layer", None), "d_output", 1)) > 1:
-            self.reason = "d_output > 1: the packed scorer hands out one score per item"
+        n_out = int(getattr(getattr(model, "output_layer", None), "d_output", 1))
+        if n_out > 1 and not multi_output:
+            self.reason = "d_output > 1 without the multi_output option"
             return
         try:
             from .engine import FusedTrainer
-            self.trainer = FusedTrainer(model, "listNet", {}, 1, 8, use_graph=False, fc_step=False)
+            loss = ("ordinal", {"n": n_out}) if n_out > 1 else ("listNet", {})     # (the loss the engine pairs with the head; never run)
+            self.trainer = FusedTrainer(model, loss[0], loss[1], 1, 8, use_graph=False, fc_step=False)
         except NotImplementedError as e:
             self.reason = "the fused engine refuses the model: %s" % (e,)
 
@@ -90,7 +103,7 @@ class Ranker(object):
     def scorer(self, B, L):
         s = self._scorers.get((B, L))
         if s is None:
-            s = self._scorers[(B, L)] = self.trainer.scorer(B, L)
+            s = self._scorers[(B, L)] = self.trainer.scorer(B, L, out_head=self.trainer.n_out > 1)
         return s
 
     def _buffers(self, B, L, F):
@@ -103,11 +116,15 @@ class Ranker(object):
 
     def _rank(self, sc, n, L, F, **source):
         t = self.trainer
-        scores, _, cu, order, max_len = sc.packed()
         x_out, y_out = self._buffers(sc.B, L, F)
         # slates 0 .. n-1: the launch order is a STABLE longest-first argsort over the scorer's B slots and the slots past n are empty,
         # so its first n entries are a permutation of the batch's slates
-        rank_slates_cu(t.lib, t._st(), scores, cu, order, n, max(max_len, 1), L, x_out, y_out, **source)
+        if t.n_out > 1:                                       # the key is formed from the packed output rows: no score array is read
+            self.head = sc.head_path
+            rank_slates_rows_cu(t.lib, t._st(), sc.packed_outputs(), sc.cu, sc.order, n, max(sc.max_len, 1), L, x_out, y_out, **source)
+        else:
+            scores, _, cu, order, max_len = sc.packed()
+            rank_slates_cu(t.lib, t._st(), scores, cu, order, n, max(max_len, 1), L, x_out, y_out, **source)
         return x_out[:n], y_out[:n]
 
     def rank_grid(self, B, xb, yb, lengths=None):
@@ -220,6 +237,7 @@ def rank_slates(datasets, model, config):
     :return: dictionary of role -> ranked dataset
         every dataset is a Tuple of torch.Tensor - storing X and y in the descending order of the scores (CPU, float32).
     """
+    last_run.clear()
     last_run.update(engine=None, reason="")
     rk = Ranker(model)
     out = {}
@@ -232,4 +250,6 @@ def rank_slates(datasets, model, config):
         out[role] = (torch.cat(xs), torch.cat(ys))
     if last_run["engine"] is None:
         last_run.update(engine="module" if rk.reason else "fused", reason=rk.reason)
+    if rk.head is not None:
+        last_run.update(head=rk.head, n_out=rk.trainer.n_out)
     return out

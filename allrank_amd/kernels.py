@@ -6,7 +6,9 @@ feature normalisation of resident data (allrank_amd/normalize.py states its thre
   * the training step's own calls: dropout plumbing, column sums, the ReLU backward, the weight-image refresh, the grouped weight
     gradient (with and without the LayerNorm backward at its side) and the grouped reduction, the input norm, the positional
     encoding, the fused norm + head, clip / SGD / Adam, the finiteness check and the two slate-resident FC + ListNet steps;
-  * ranking and clicks: ``rank_slates_cu``, ``click_slates_cu``; and the MFMA lane-layout self-test.
+  * ranking and clicks: ``rank_slates_cu``, ``click_slates_cu``; and the MFMA lane-layout self-test;
+  * handed on from allrank_amd/outhead.py, which states them in this module's form (and tests/test_out_head_abi.py holds them to the
+    header's parameter names): ``out_head_fwd`` and ``rank_slates_rows_cu``, the calls of a model with several output units.
 The autograd bindings (allrank_amd/ops.py), the explicit training step (allrank_amd/engine.py), the row movers (allrank_amd/rows.py),
 allrank_amd/inference.py and allrank_amd/clicks.py launch through these functions and state no launch of their own, as the plugin
 losses and ``FusedLoss`` launch through the ``_launch_*`` functions of allrank_amd/losses.
@@ -21,6 +23,7 @@ are the exception that allocates: they ask the library for the byte count and re
 import ctypes
 
 from ._lib import check, ptr as P, workspace
+from .outhead import out_head_fwd, rank_slates_rows_cu        # noqa: F401  (stated there, launched through this module)
 
 
 # ---- dense projections ---------------------------------------------------------------------------------------------

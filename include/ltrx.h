@@ -262,6 +262,17 @@ int ltrx_mrr_at_cu(const float* y_pred, const float* y_true, const int32_t* cu_s
 int ltrx_rank_slates_cu(const float* scores, const float* x, const float* y, const float* x_items, const float* y_items,
                         const int64_t* offsets, const int64_t* ids, const int32_t* cu_seqlens, const int32_t* slate_order, int B,
                         int max_len, int F, int L, int32_t* perm, float* x_out, float* y_out, ltrx_stream_t stream);
+/* The same call for a model with n_out > 1 output units (OutputLayer(d, d_output), the ordinal configurations): every argument and
+ * every rule of ltrx_rank_slates_cu, except that the sort key of an item is not read but FORMED.  out[n, n_out] holds the packed output
+ * rows of the valid items (what ltrx_out_head_fwd writes), and the key of item i is model.score's sum (model.py:127)
+ *   out[i][0] + out[i][1] + ... + out[i][n_out - 1], added in that order in fp32,
+ * folded while the slate's keys are loaded into LDS: no score array is written or read, and no launch precedes the ranking.  The sort,
+ * the gather, the tails and the tie policy are the one kernel body of ltrx_rank_slates_cu (a template over the key loader), so with
+ * n_out == 1 the outputs equal ltrx_rank_slates_cu's on the same scores bit for bit.  4 n_out bytes per item are read for the keys.
+ * NULL out or n_out <= 0: LTRX_EINVAL; the other refusals are ltrx_rank_slates_cu's.  No time has been measured for this entry point. */
+int ltrx_rank_slates_rows_cu(const float* out, int n_out, const float* x, const float* y, const float* x_items, const float* y_items,
+                             const int64_t* offsets, const int64_t* ids, const int32_t* cu_seqlens, const int32_t* slate_order, int B,
+                             int max_len, int F, int L, int32_t* perm, float* x_out, float* y_out, ltrx_stream_t stream);
 
 /* allrank/click_models (behind rank_and_click.py:88): clicks on ranked slates -- BaseCascadeModel / OnlyRelevantClickModel, optionally
  * inside MaxClicksModel, inside DiverseClicksModel, inside MaxClicksModel.  allrank_amd/csrc/ltrx_click.hip.
@@ -651,6 +662,22 @@ int ltrx_posenc_table_bwd(const float* dx, const int64_t* indices, const uint8_t
 int ltrx_scale_inplace(float* x, size_t n, float s, ltrx_stream_t stream);
 int ltrx_out_act_fwd(const float* z, size_t n, int kind, float* y, ltrx_stream_t stream);
 int ltrx_out_act_bwd(const float* dy, const float* y, size_t n, int kind, float* dz, ltrx_stream_t stream);
+
+/* OutputLayer with d_output > 1 in eval mode (model.py:111-117) and model.score's sum over the output units (model.py:127) in ONE
+ * launch, forward only (allrank_amd/csrc/ltrx_outhead.hip).  Per row r of x[rows, D] (row stride ldx floats):
+ *   z_k = <x[r, :], W[k, :]> + bias[k]  (k < n_out),   p_k = act(z_k),   score[r] = p_0 + p_1 + ... + p_{n_out-1} (that order, fp32)
+ * W[n_out, D] is the module's weight, dense row-major (no transpose, no padding); act: 0 = none, 1 = Sigmoid, 2 = Tanh, the formulae
+ * of ltrx_out_act_fwd.  out[rows, n_out] (dense) receives the p_k, score[rows] the sum; either may be NULL, not both, and one alone
+ * holds the values it holds with the other.
+ * Arithmetic: exact fp32 fused multiply-adds, no bf16 split.  One wave per row; lane l owns the columns 4 (l + 64 i) .. + 3 for
+ * i = 0, 1, .. and adds them in ascending order into n_out accumulators at once, then the library's fixed-order wave sum: a row's
+ * results depend on nothing but the row, W and bias -- not on rows, the grid or the launch.  W is staged once per workgroup in LDS
+ * (4 n_out D bytes, at most 32 KB); x is read from HBM once, 4 D bytes per row, which is the kernel's roofline.
+ * LTRX_EINVAL, before any HIP call: NULL x / W / bias, out and score both NULL, rows, D or n_out <= 0, ldx < D, act outside 0 .. 2.
+ * LTRX_EUNSUPPORTED: n_out > 8, D % 4 != 0, D > 1024, ldx % 4 != 0 or x off 16-byte alignment (the rows move as float4) -- the caller
+ * keeps the GEMM + ltrx_out_act_fwd sequence.  No time has been measured for this entry point. */
+int ltrx_out_head_fwd(const float* x, int ldx, const float* W, const float* bias, int rows, int D, int n_out, int act, float* out,
+                      float* score, ltrx_stream_t stream);
 
 /* Slate-resident training step of an FCModel([H]) -> OutputLayer(H, 1) -> listNet model (BASELINE configs[1]): forward, loss,
  * backward and -- optionally -- the Adam update in TWO launches that read the features from HBM once
