@@ -94,6 +94,11 @@ def lib():
     return _lib
 
 
+def mha_wide_fits(L, d_k):
+    """ltrx_mha_wide_fits: does ltrx_mha_fwd_wide take slates of up to ``L`` items at head width ``d_k``?  Host only, launches nothing."""
+    return bool(lib().ltrx_mha_wide_fits(int(L), int(d_k)))
+
+
 def check(rc, what):
     if rc != 0:
         kinds = {-1: "invalid argument",

@@ -316,3 +316,6 @@ def check_compatible(saved_meta, live_meta):
             raise ValueError("checkpoint: loss argument %s: stored %r, live %r" % (k, sa.get(k, "<unset>"), la.get(k, "<unset>")))
     if _canon(saved_meta.get("clip")) != _canon(live_meta.get("clip")):
         raise ValueError("checkpoint: gradient_clipping_norm: stored %r, live %r" % (saved_meta.get("clip"), live_meta.get("clip")))
+    if bool(saved_meta.get("wide_heads")) != bool(live_meta.get("wide_heads")):      # (the key exists only where the option is on)
+        raise ValueError("checkpoint: wide_heads (the split-bf16 attention forward for head widths 65..128): stored %r, live %r"
+                         % (bool(saved_meta.get("wide_heads")), bool(live_meta.get("wide_heads"))))

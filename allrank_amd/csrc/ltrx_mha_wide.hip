@@ -1,0 +1,456 @@
+// Masked self-attention FORWARD on the bf16 matrix cores with fp32-class accuracy for WIDE heads, 64 < d_k <= 128
+// (allrank/models/transformer.py:137-156; the shipped 96 / 1 and 144 / 2 transformer configs have head widths 96 and 72).
+//
+// ltrx_mha_res.hip stops at d_k 64; wider heads otherwise run the exact kernels of ltrx_mha.hip on v_mfma_f32_32x32x2_f32, 1/16 of the
+// bf16 matrix rate.  This kernel has the arithmetic and every convention of ltrx_mha_fwd_res_kernel -- each contraction is three
+// v_mfma_f32_32x32x16_bf16 products X Y ~= Xhi Yhi + Xhi Ylo + Xlo Yhi (PL: only the first; mode 2), Q pre-scaled by scale * log2 e
+// before its split, a log2-domain online softmax with the lazy reference (kLazyTau), the natural-log lse at [slate, head, row],
+// dropout on P regenerated from (seed, query row, key) by drop_row_seed / drop_scale_rk, both layouts through which_slate() -- so
+// its o / lse feed ltrx_mha_bwd of the same mode, which runs the exact backward at these widths.  Opt-in (ltrx_mha_fwd_wide):
+// it rounds differently from the exact arm that ltrx_mha_fwd keeps dispatching here.
+//
+// What is different is how the work is laid out, because nothing of the resident design fits at these row widths:
+//   * LDS.  Four bf16 planes (K hi / lo, V hi / lo) cost 8 DKP bytes per key row: a 256-row image would be 192 / 256 KB of the CU's
+//     160.  K and V therefore STREAM through a ring of TWO 32-row tile slots (2 x 4 planes x 32 x DKP bf16 = 48 KB at DKP 96, 64 KB at
+//     DKP 128).  A tile is split into hi / lo once, by the staging threads on its way from registers into its slot; the loads of tile
+//     t + 1 are in flight while the waves compute on tile t.
+//   * write-after-read with a two-slot ring and ONE barrier per tile.  Iteration t is: store tile t into slot t & 1; barrier t;
+//     compute on slot t & 1.  A thread that stores tile t has passed barrier t - 1, so every wave has ARRIVED at barrier t - 1, and a
+//     wave's compute of tile t - 2 -- the previous tenant of slot t & 1 -- precedes its arrival there in program order.  The only tile
+//     a slow wave can still be reading is t - 1, in the other slot.  Two slots are thus enough and a deeper ring buys nothing: the
+//     store of tile t + 1 cannot be issued before barrier t anyway, its data sits in registers.  (The resident kernel needed the
+//     argument "a slot is written once per 256 keys"; this one needs "once per 64 keys, and 32 of them lie behind a barrier".)
+//     The per-slot mask bias and the tile flag follow the same rule.
+//   * workgroup.  FOUR waves (256 threads), 32 queries each: 128 queries per workgroup, grid (B h, ceil(L / 128)).  One wave per SIMD
+//     may use up to the whole 512-entry register file: the Q hi / lo fragments (DKP / 16 pairs of bf16x8 = 48 / 64 registers) and the O
+//     accumulators (DKP / 32 f32x16 = 48 / 64) stay in registers across the key loop next to S, P, the K / V fragments and the
+//     staging registers of the next tile (64 DKP / 256 (row, 8-column) positions of 8 floats per thread) -- no scratch (the figures per
+//     instantiation: profiles/mha_wide.md).  At DKP 96 all of that fits 256 registers, so the kernel is built for two waves per SIMD
+//     and two workgroups (2 x 48 KB) share a CU; at DKP 128 it takes 330 and one workgroup has the CU.  Every workgroup streams all keys
+//     of its slate; a 240-item slate is two workgroups.
+//   * Q is read straight from memory in the fragment layout (lane = query row, 2 x 16 bytes per 16-column step): the LDS exchange
+//     of the resident kernel's prologue would need 16 KB per wave here, i.e. the whole ring and a barrier of its own.
+//   * image layout.  Row r of a plane is DKP * 2 bytes = CH = 12 / 16 sixteen-byte chunks; an LDS bank row is 16 chunks (64 banks).
+//       DKP 128 (a row IS a bank row): chunk c of row r at position c ^ s(r), s(r) = (r & 3) << 2 | ((r >> 2) & 3).
+//       DKP  96 (12 r + c mod 16: four rows walk through the four 4-chunk groups of a bank row): chunk c of row r at position
+//               c ^ ((r >> 2) & 3) -- only the two low bits move, so the position stays inside the row's 12 chunks.
+//     Row-wise K fragments (ds_read_b128: 16 lanes = rows r .. r + 15 mod 16, one chunk c): at 128, s is a bijection of r & 15, so
+//     the 16 positions c ^ s(r) are the 16 different chunks of a bank row.  At 96 the bank position is 4 ((c / 4 - r) & 3) +
+//     ((c & 3) ^ ((r >> 2) & 3)): r & 3 picks the group, (r >> 2) & 3 the chunk inside it -- 16 different ones again.
+//     Transposed V reads (ds_read_b64_tr_b16: 32 lanes = rows r0 .. r0 + 3, r0 a multiple of 4, chunks 4 ct .. 4 ct + 3): at 128 the
+//     position is ((ct ^ j) << 2) | (cc ^ a) for row r0 + j and chunk 4 ct + cc (a = (r0 >> 2) & 3); at 96 it is
+//     4 ((ct - r0 - j) & 3) + (cc ^ a): the row picks the 4-chunk group, the chunk the place in it -- 16 different 16-byte positions,
+//     every bank once, both times.  Tile slots and planes start at multiples of 256 bytes, so the argument holds in every slot.
+//     The staging stores (16 lanes = 16 consecutive chunks of one or two rows) permute inside groups of 4 chunks: conflict-free.
+//   * barriers.  Every wave takes every barrier.  A wave whose queries lie beyond the slate (`active` false) keeps staging; the only
+//     early return is the workgroup-uniform one before the first barrier.  No thread reads a row at or beyond the slate's length.
+// Compiled without the packed-fp32 VALU instructions (allrank_amd/build.py), and the code uses no two-float vector arithmetic.
+#include "ltrx_mfma.h"
+
+using namespace ltrx;
+
+namespace {
+
+constexpr int NWAVE = 4;                  // waves of a workgroup
+constexpr int QBLK = 32 * NWAVE;          // queries of a workgroup
+constexpr int NTHREAD = 64 * NWAVE;
+constexpr int NSLOT = 2;                  // tile slots of the ring
+constexpr float kLog2e = 1.4426950408889634f;
+constexpr float kLn2 = 0.6931471805599453f;
+constexpr float kLazyTau = 8.0f;          // ltrx_mha_res.hip's: a query's reference moves when a tile exceeds it by 2^8
+
+template <int DKP>
+struct Geo {
+  static_assert(DKP == 96 || DKP == 128, "the image layouts below are built for 12 and 16 chunks per row");
+  static constexpr int CH = DKP / 8;                      // 16-byte chunks (8 bf16 columns) per row
+  static constexpr int KS = DKP / 16;                     // 16-column steps of Q K^T
+  static constexpr int NCT = DKP / 32;                    // 32-column blocks of O
+  static constexpr int ROWB = DKP * 2;                    // bytes of a row of one plane
+  static constexpr int TILEB = 32 * ROWB;                 // one plane of a tile
+  static constexpr int SLOTB = 4 * TILEB;                 // K hi, K lo, V hi, V lo
+  static constexpr int NPOS = 64 * CH / NTHREAD;          // (row, chunk) positions of K and V a thread stages per tile
+  static constexpr int WPE = DKP == 96 ? 2 : 1;           // waves per SIMD the register budget is set for (workgroups per CU)
+  static constexpr size_t SMEM = (size_t)NSLOT * SLOTB + NSLOT * 32 * sizeof(float) + 16;      // + mask bias per slot + tile flags
+};
+
+// byte offset of 16-byte chunk `chunk` of row `row` inside one plane of a tile (see the header for why it is conflict-free)
+template <int DKP>
+__device__ __forceinline__ int wide_off(int row, int chunk) {
+  const int s = (DKP == 128) ? (((row & 3) << 2) | ((row >> 2) & 3)) : ((row >> 2) & 3);
+  return row * (DKP * 2) + ((chunk ^ s) << 4);
+}
+
+struct Slate {
+  int b, head, bh, Lmax, len;
+  size_t row0;
+};
+__device__ __forceinline__ Slate which_slate(int L, int h, const int* __restrict__ cu, const int* __restrict__ order) {
+  Slate s;
+  s.head = blockIdx.x % h;
+  s.b = order ? order[blockIdx.x / h] : (int)(blockIdx.x / h);
+  s.bh = s.b * h + s.head;
+  s.Lmax = L;
+  s.row0 = cu ? (size_t)cu[s.b] : (size_t)s.b * L;
+  s.len = cu ? cu[s.b + 1] - cu[s.b] : L;
+  return s;
+}
+
+__device__ __forceinline__ float max_across_halves(float x) {     // lane i <-> lane i ^ 32
+  const unsigned u = __float_as_uint(x);
+  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+__device__ __forceinline__ float sum_across_halves(float x) {
+  const unsigned u = __float_as_uint(x);
+  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+
+#define LTRX_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
+
+// the tile-invariant part of a thread's staging work: position i = threadIdx.x + 256 j of the 64 CH positions of a tile, K's
+// 32 CH first, then V's
+template <int DKP>
+struct Stager {
+  const float* src[Geo<DKP>::NPOS];     // first float of the position in tile 0
+  int row[Geo<DKP>::NPOS];              // row inside a tile
+  int dst[Geo<DKP>::NPOS];              // byte offset inside a slot (hi plane; lo: + TILEB)
+  bool ca[Geo<DKP>::NPOS], cb[Geo<DKP>::NPOS];      // columns c .. c + 3, c + 4 .. c + 7 inside the head
+  float4 a[Geo<DKP>::NPOS], b[Geo<DKP>::NPOS];
+};
+template <int DKP>
+__device__ __forceinline__ void stager_init(Stager<DKP>& st, const float* __restrict__ kb, const float* __restrict__ vb, int dk, int rs) {
+  using G = Geo<DKP>;
+#pragma unroll
+  for (int j = 0; j < G::NPOS; ++j) {
+    const int i = threadIdx.x + NTHREAD * j;
+    const bool isv = i >= 32 * G::CH;
+    const int w = isv ? i - 32 * G::CH : i;
+    const int row = w / G::CH, chunk = w % G::CH, c = chunk * 8;
+    st.row[j] = row;
+    st.ca[j] = c < dk;
+    st.cb[j] = c + 4 < dk;
+    st.src[j] = (isv ? vb : kb) + (size_t)row * rs + (st.ca[j] ? c : 0);
+    st.dst[j] = (isv ? 2 * G::TILEB : 0) + wide_off<DKP>(row, chunk);
+  }
+}
+template <int DKP>
+__device__ __forceinline__ void stager_gload(Stager<DKP>& st, int tile, int len, int rs) {
+#pragma unroll
+  for (int j = 0; j < Geo<DKP>::NPOS; ++j) {
+    const bool ok = tile * 32 + st.row[j] < len;
+    const float* p = st.src[j] + (size_t)tile * 32 * rs;
+    st.a[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    st.b[j] = st.a[j];
+    if (ok && st.ca[j]) st.a[j] = *reinterpret_cast<const float4*>(p);
+    if (ok && st.cb[j]) st.b[j] = *reinterpret_cast<const float4*>(p + 4);
+  }
+}
+template <int DKP, bool PL>
+__device__ __forceinline__ void stager_sstore(const Stager<DKP>& st, unsigned char* slot) {
+#pragma unroll
+  for (int j = 0; j < Geo<DKP>::NPOS; ++j) {
+    const float x[8] = {st.a[j].x, st.a[j].y, st.a[j].z, st.a[j].w, st.b[j].x, st.b[j].y, st.b[j].z, st.b[j].w};
+    bf16x8 h, l;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      LTRX_SPLIT_BF16(x[e], h[e], l[e]);
+    }
+    *reinterpret_cast<bf16x8*>(slot + st.dst[j]) = h;
+    if (!PL) *reinterpret_cast<bf16x8*>(slot + st.dst[j] + Geo<DKP>::TILEB) = l;
+  }
+}
+
+// per-lane byte offsets inside a slot that do not depend on the tile
+template <int DKP>
+struct TileOffsets {
+  int k[Geo<DKP>::KS];             // K fragment ks: chunk 2 ks + half of row l31 (K hi plane; lo: + TILEB)
+  int v[2][Geo<DKP>::NCT][2];      // V transposed reads [u][ct][rows r0 / r0 + 8] (V hi plane; lo: + TILEB)
+};
+template <int DKP>
+__device__ __forceinline__ TileOffsets<DKP> tile_offsets() {
+  using G = Geo<DKP>;
+  const int lane = threadIdx.x & 63, l31 = lane & 31, half = lane >> 5, i16 = lane & 15, g16 = (lane >> 4) & 1;
+  const int rsub = i16 >> 2, c8 = (i16 & 3) >> 1, b8 = (i16 & 1) * 8;
+  TileOffsets<DKP> f;
+#pragma unroll
+  for (int ks = 0; ks < G::KS; ++ks) f.k[ks] = wide_off<DKP>(l31, 2 * ks + half);
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+#pragma unroll
+    for (int ct = 0; ct < G::NCT; ++ct) {
+      const int r0 = 16 * u + 4 * half + rsub, chunk = (2 * ct + g16) * 2 + c8;
+      f.v[u][ct][0] = 2 * G::TILEB + wide_off<DKP>(r0, chunk) + b8;
+      f.v[u][ct][1] = 2 * G::TILEB + wide_off<DKP>(r0 + 8, chunk) + b8;
+    }
+  return f;
+}
+
+// two fp32 values -> one register of two bf16 hi parts and one of two bf16 lo parts
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+template <bool PL>
+__device__ __forceinline__ void split_pair(float x0, float x1, uint32_t& h, uint32_t& l) {
+  const bf16x2 hp = {(__bf16)x0, (__bf16)x1};
+  h = __builtin_bit_cast(uint32_t, hp);
+  if (!PL) {
+    const float d0 = x0 - __uint_as_float(h << 16), d1 = x1 - __uint_as_float(h & 0xffff0000u);
+    const bf16x2 lp = {(__bf16)d0, (__bf16)d1};
+    l = __builtin_bit_cast(uint32_t, lp);
+  }
+}
+
+// the wave's Q fragments: row q0 + l31, columns 16 ks + 8 half + 0..7, times `pre`, split
+template <int DKP>
+__device__ __forceinline__ void q_fragments(bf16x8 (&qh)[Geo<DKP>::KS], bf16x8 (&ql)[Geo<DKP>::KS], const float* __restrict__ qb, int q0, int len,
+                                            int dk, int rs, float pre) {
+  const int lane = threadIdx.x & 63, l31 = lane & 31, half = lane >> 5;
+  const bool rok = q0 + l31 < len;
+  const float* rowp = qb + (size_t)(rok ? q0 + l31 : 0) * rs;                  // (row 0 exists)
+  f32x4 a[Geo<DKP>::KS], b[Geo<DKP>::KS];
+#pragma unroll
+  for (int ks = 0; ks < Geo<DKP>::KS; ++ks) {                                  // every load is issued before the first split
+    const int c = 16 * ks + 8 * half;
+    const bool oa = rok && c < dk, ob = rok && c + 4 < dk;
+    const f32x4 va = *reinterpret_cast<const f32x4*>(rowp + (oa ? c : 0));
+    const f32x4 vb = *reinterpret_cast<const f32x4*>(rowp + (ob ? c + 4 : 0));
+    a[ks] = oa ? va : f32x4{0.f, 0.f, 0.f, 0.f};
+    b[ks] = ob ? vb : f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+#pragma unroll
+  for (int ks = 0; ks < Geo<DKP>::KS; ++ks) {
+    const float x[8] = {a[ks][0] * pre, a[ks][1] * pre, a[ks][2] * pre, a[ks][3] * pre, b[ks][0] * pre, b[ks][1] * pre, b[ks][2] * pre, b[ks][3] * pre};
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      LTRX_SPLIT_BF16(x[e], qh[ks][e], ql[ks][e]);
+    }
+  }
+}
+
+// S^T[key = rowmap(r, half)][query = l31] of the tile in `slot`, in one accumulator
+template <int DKP, bool PL>
+__device__ __forceinline__ f32x16 score_tile(const unsigned char* slot, const TileOffsets<DKP>& fo, const bf16x8 (&qh)[Geo<DKP>::KS],
+                                             const bf16x8 (&ql)[Geo<DKP>::KS]) {
+  using G = Geo<DKP>;
+  bf16x8 xh[G::KS], xl[G::KS];
+#pragma unroll
+  for (int ks = 0; ks < G::KS; ++ks) {
+    xh[ks] = *reinterpret_cast<const bf16x8*>(slot + fo.k[ks]);
+    if (!PL) xl[ks] = *reinterpret_cast<const bf16x8*>(slot + fo.k[ks] + G::TILEB);
+  }
+  f32x16 a;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) a[r] = 0.f;
+  if (!PL) {
+#pragma unroll
+    for (int ks = 0; ks < G::KS; ++ks) a = LTRX_MFMA(xl[ks], qh[ks], a);
+#pragma unroll
+    for (int ks = 0; ks < G::KS; ++ks) a = LTRX_MFMA(xh[ks], ql[ks], a);
+  }
+#pragma unroll
+  for (int ks = 0; ks < G::KS; ++ks) a = LTRX_MFMA(xh[ks], qh[ks], a);
+  return a;
+}
+
+// O^T[d][query] += V^T[d][key] P^T[key][query] of the tile in `slot` (p in D layout: register r <-> key rowmap(r, half)).  The A
+// fragment of block ct -- column 32 ct + l31, keys {16 u + 4 half + 0..3, 16 u + 8 + 4 half + 0..3}, the keys a lane's P registers
+// 8 u .. 8 u + 7 hold -- comes from two transposed reads of the row-major image: P never moves between lanes.
+template <int DKP, bool PL>
+__device__ __forceinline__ void value_tile(const unsigned char* slot, const TileOffsets<DKP>& fo, const f32x16& p, f32x16 (&out)[Geo<DKP>::NCT]) {
+  using G = Geo<DKP>;
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    u32x4 hw, lw = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      uint32_t hj, lj = 0u;
+      split_pair<PL>(p[8 * u + 2 * j], p[8 * u + 2 * j + 1], hj, lj);
+      hw[j] = hj;
+      lw[j] = lj;
+    }
+    const bf16x8 ph = __builtin_bit_cast(bf16x8, hw), pl = __builtin_bit_cast(bf16x8, lw);
+#pragma unroll
+    for (int ct = 0; ct < G::NCT; ++ct) {
+      const bf16x4 h0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(slot + fo.v[u][ct][0]));
+      const bf16x4 h1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(slot + fo.v[u][ct][1]));
+      const bf16x8 vh = {h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
+      if (!PL) {
+        const bf16x4 l0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(slot + fo.v[u][ct][0] + G::TILEB));
+        const bf16x4 l1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(slot + fo.v[u][ct][1] + G::TILEB));
+        const bf16x8 vl = {l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
+        out[ct] = LTRX_MFMA(vl, ph, out[ct]);
+        out[ct] = LTRX_MFMA(vh, pl, out[ct]);
+      }
+      out[ct] = LTRX_MFMA(vh, ph, out[ct]);
+    }
+  }
+}
+
+// lane owns output row row0 + l31; register 4 g + e of out[ct] is column 32 ct + 8 g + 4 half + e.  Written through a wave-private
+// 4-KB LDS scratch one [32 rows][32 columns] block at a time, so that a store instruction covers 8 rows x 128 contiguous bytes
+// (chunk c of row r at c ^ ((r >> 1) & 7), as ltrx_mha_res.hip's store_rows)
+template <int NCT>
+__device__ __forceinline__ void store_rows(float* __restrict__ base, int row0, int nrows, int dk, size_t rs, const f32x16 (&out)[NCT], float scale,
+                                           f32x4* scratch) {
+  const int lane = threadIdx.x & 63, l31 = lane & 31, half = lane >> 5;
+#pragma unroll
+  for (int ct = 0; ct < NCT; ++ct) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+      scratch[l31 * 8 + ((2 * g + half) ^ ((l31 >> 1) & 7))] =
+          f32x4{out[ct][4 * g + 0] * scale, out[ct][4 * g + 1] * scale, out[ct][4 * g + 2] * scale, out[ct][4 * g + 3] * scale};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int r = (lane >> 3) + 8 * j, c = 32 * ct + 4 * (lane & 7);
+      const f32x4 v = scratch[r * 8 + ((lane & 7) ^ ((r >> 1) & 7))];
+      if (row0 + r < nrows && c < dk) *reinterpret_cast<f32x4*>(base + (size_t)(row0 + r) * rs + c) = v;
+    }
+  }
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------------------------------
+// forward: workgroup (slate * h + head, query block of 128); wave w owns queries 128 blockIdx.y + 32 w .. + 31
+// ------------------------------------------------------------------------------------------------------------------
+template <int DKP, bool DROP, bool PL>
+__global__ void __launch_bounds__(NTHREAD) __attribute__((amdgpu_waves_per_eu(Geo<DKP>::WPE, Geo<DKP>::WPE))) ltrx_mha_fwd_wide_kernel(const float* __restrict__ q, const float* __restrict__ k,
+                                                                    const float* __restrict__ v, const uint8_t* __restrict__ kpm, int L, int h,
+                                                                    int dk, int rs, float* __restrict__ o, int ors, float* __restrict__ lse,
+                                                                    float scale, DropCfg drop, const uint32_t* __restrict__ drop_step,
+                                                                    const int* __restrict__ cu, const int* __restrict__ order) {
+  using G = Geo<DKP>;
+  extern __shared__ __attribute__((aligned(256))) unsigned char smem[];
+  float* kbias = reinterpret_cast<float*>(smem + NSLOT * G::SLOTB);      // [slot][32]: -inf for a masked or out-of-range key, else 0
+  int* kflag = reinterpret_cast<int*>(kbias + NSLOT * 32);               // [slot]: does the tile hold such a key?
+  if (DROP && drop_step) drop.seed ^= drop_step[0] * 0x9E3779B9u;
+  const Slate sl = which_slate(L, h, cu, order);
+  const int len = sl.len;
+  if ((int)(blockIdx.y * QBLK) >= len) return;         // whole workgroup beyond this slate (uniform: before any barrier)
+  const int lane = threadIdx.x & 63, half = lane >> 5, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const size_t head0 = sl.row0 * rs + (size_t)sl.head * dk;
+  Stager<DKP> sg;
+  stager_init<DKP>(sg, k + head0, v + head0, dk, rs);
+  stager_gload<DKP>(sg, 0, len, rs);
+  uint8_t km_n = 0;                                    // threads 0-31: padding-mask byte of key 32 kt + threadIdx.x of the tile being staged
+  if (threadIdx.x < 32 && kpm && (int)threadIdx.x < len) km_n = kpm[sl.row0 + threadIdx.x];
+  const int q0 = blockIdx.y * QBLK + wave * 32;
+  const bool active = q0 < len;                        // (inactive waves still stage and take every barrier)
+  bf16x8 qh[G::KS], ql[G::KS];
+  q_fragments<DKP>(qh, ql, q + head0, q0, len, dk, rs, scale * kLog2e);      // S comes out of the MFMAs in the softmax's log2 domain
+  const TileOffsets<DKP> fo = tile_offsets<DKP>();
+  f32x16 oacc[G::NCT];
+#pragma unroll
+  for (int ct = 0; ct < G::NCT; ++ct)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) oacc[ct][r] = 0.f;
+  float m = -INFINITY, l = 0.f;
+  const uint32_t drow = DROP ? drop_row_seed(drop, sl.bh, sl.Lmax, q0 + (lane & 31)) : 0u;
+  const int nkt = (len + 31) / 32;
+  for (int kt = 0; kt < nkt; ++kt) {
+    const int sidx = kt & (NSLOT - 1);
+    unsigned char* slot = smem + sidx * G::SLOTB;
+    stager_sstore<DKP, PL>(sg, slot);
+    if (threadIdx.x < 32) {
+      const bool off = kt * 32 + (int)threadIdx.x >= len || km_n;
+      kbias[sidx * 32 + threadIdx.x] = off ? -INFINITY : 0.f;
+      const bool any_off = __builtin_amdgcn_ballot_w64(off) != 0;
+      if (threadIdx.x == 0) kflag[sidx] = any_off ? 1 : 0;
+    }
+    if (kt + 1 < nkt) {
+      stager_gload<DKP>(sg, kt + 1, len, rs);          // in flight during this tile's MFMAs
+      if (threadIdx.x < 32 && kpm && (kt + 1) * 32 + (int)threadIdx.x < len) km_n = kpm[sl.row0 + (kt + 1) * 32 + threadIdx.x];
+    }
+    lds_only_barrier();
+    if (!active) continue;
+    f32x16 s = score_tile<DKP, PL>(slot, fo, qh, ql);
+    if (__builtin_amdgcn_readfirstlane(kflag[sidx])) {          // (wave-uniform) a masked or out-of-range key in this tile
+      const float* kb = kbias + sidx * 32 + 4 * half;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const f32x4 b4 = *reinterpret_cast<const f32x4*>(kb + 8 * g);       // keys 8 g + 4 half + 0..3 = rowmap(4 g + e, half)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s[4 * g + e] += b4[e];
+      }
+    }
+    float mt = fmaxf(s[0], s[1]);
+#pragma unroll
+    for (int r = 2; r < 16; ++r) mt = fmaxf(mt, s[r]);
+    mt = max_across_halves(mt);
+    const bool grow = mt > m + kLazyTau;               // (first tile: m = -inf; nothing but masked keys so far: mt = -inf -> no)
+    const float mn = grow ? mt : m;
+    const float mref = (mn == -INFINITY) ? 0.f : mn;
+    if (__builtin_amdgcn_ballot_w64(grow) != 0) {      // some query's reference moves: rescale what was accumulated under the old one
+      const float alpha = grow ? fast_exp2(m - mref) : 1.0f;
+      l *= alpha;
+#pragma unroll
+      for (int ct = 0; ct < G::NCT; ++ct)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) oacc[ct][r] *= alpha;
+    }
+    m = mn;
+    f32x16 p;
+    float ps0 = 0.f, ps1 = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; r += 2) {
+      p[r] = fast_exp2(s[r] - mref);
+      p[r + 1] = fast_exp2(s[r + 1] - mref);
+      ps0 += p[r];
+      ps1 += p[r + 1];
+    }
+    l += ps0 + ps1;
+    if (DROP) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) p[r] *= drop_scale_rk(drop, drow, kt * 32 + rowmap(r, half));
+    }
+    value_tile<DKP, PL>(slot, fo, p, oacc);
+  }
+  if (!active) return;
+  const float lt = sum_across_halves(l);
+  const float inv = (lt > 0.f) ? 1.0f / lt : 0.f;
+  // scratch: the slot that does NOT hold the last tile -- its tenant, tile nkt - 2, lies behind barrier nkt - 1, which this wave has
+  // passed; nothing is staged any more
+  f32x4* scratch = reinterpret_cast<f32x4*>(smem + (((nkt - 1) & (NSLOT - 1)) ^ 1) * G::SLOTB + wave * 4096);
+  store_rows<G::NCT>(o + sl.row0 * ors + (size_t)sl.head * dk, q0, len, dk, ors, oacc, inv, scratch);
+  const int qrow = q0 + (lane & 31);
+  if (half == 0 && qrow < len) lse[((size_t)sl.b * h + sl.head) * sl.Lmax + qrow] = (lt > 0.f) ? (m + log2f(lt)) * kLn2 : 0.f;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// host side (the C entry point ltrx_mha_fwd_wide lives next to ltrx_mha_fwd in ltrx_mha.hip and shares its argument checks)
+// ------------------------------------------------------------------------------------------------------------------
+extern "C" int ltrx_mha_wide_fits(int L, int d_k) {
+  return (L > 0 && (L + QBLK - 1) / QBLK <= 65535 && d_k > 64 && d_k <= 128 && d_k % 4 == 0) ? 1 : 0;
+}
+
+template <int DKP>
+static int launch_wide(const float* q, const float* k, const float* v, const uint8_t* kpm, int B, int L, int h, int dk, int rs, float* o, int ors,
+                       float* lse, float p_drop, uint32_t seed, const uint32_t* seed_step, const int* cu, const int* order, bool plain,
+                       hipStream_t s) {
+  constexpr size_t SM = Geo<DKP>::SMEM;
+  static std::atomic<uint64_t> attr_done{0};
+  const int arc = ltrx_allow_dynamic_lds(attr_done, {{ltrx_mha_fwd_wide_kernel<DKP, false, false>, SM}, {ltrx_mha_fwd_wide_kernel<DKP, true, false>, SM},
+                                                     {ltrx_mha_fwd_wide_kernel<DKP, false, true>, SM}, {ltrx_mha_fwd_wide_kernel<DKP, true, true>, SM}});
+  if (arc != LTRX_OK) return arc;
+  const DropCfg drop = ltrx_make_drop(p_drop, seed);
+  const float scale = 1.0f / sqrtf((float)dk);
+  const dim3 grid(B * h, (L + QBLK - 1) / QBLK);
+#define LTRX_WIDE(D_, P_)                                                                                                                \
+  hipLaunchKernelGGL((ltrx_mha_fwd_wide_kernel<DKP, D_, P_>), grid, dim3(NTHREAD), SM, s, q, k, v, kpm, L, h, dk, rs, o, ors, lse, scale, drop, \
+                     seed_step, cu, order)
+  if (drop.thresh != 0u) {
+    if (plain) LTRX_WIDE(true, true); else LTRX_WIDE(true, false);
+  } else {
+    if (plain) LTRX_WIDE(false, true); else LTRX_WIDE(false, false);
+  }
+#undef LTRX_WIDE
+  LTRX_LAUNCH_CHECK();
+  return LTRX_OK;
+}
+
+int ltrx_mha_fwd_wide_launch(const float* q, const float* k, const float* v, const uint8_t* kpm, int B, int L, int h, int dk, int rs, float* o,
+                             int ors, float* lse, float p_drop, uint32_t seed, const uint32_t* seed_step, const int* cu, const int* order,
+                             bool plain, hipStream_t s) {
+  if (dk <= 96) return launch_wide<96>(q, k, v, kpm, B, L, h, dk, rs, o, ors, lse, p_drop, seed, seed_step, cu, order, plain, s);
+  return launch_wide<128>(q, k, v, kpm, B, L, h, dk, rs, o, ors, lse, p_drop, seed, seed_step, cu, order, plain, s);
+}

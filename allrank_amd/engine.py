@@ -377,7 +377,7 @@ class FusedTrainer(object):
                  optimizer="Adam", weight_decay=0.0, momentum=0.0, nesterov=False,
                  use_graph=True, gemm="split_bf16", dropout=True, seed=None, gradient_clipping_norm=None, compact=False,
                  weight_images=True, fc_step=True, group_wgrad=True, relu_bits=True, pad_input=True, force_dist=False,
-                 _norm_head=True, ln_in_wgrad=True):
+                 _norm_head=True, ln_in_wgrad=True, wide_heads=False):
         """gemm: "split_bf16" -- libltrx fp32-accurate GEMMs on the bf16 MFMA (3 products), "split_bf16_strict" (6
         products), "hipblaslt" (torch.mm/addmm, exact-fp32 library GEMMs), or "bf16" -- the THROUGHPUT mode: one bf16
         product per contraction in the dense projections AND in attention (fp32 storage, accumulation, LayerNorm, softmax,
@@ -440,7 +440,12 @@ class FusedTrainer(object):
         ln_in_wgrad=True (with group_wgrad): the first-sublayer LayerNorm backward of an encoder layer runs INSIDE the layer's grouped
         weight-gradient launch, on the CUs that launch leaves without a workgroup (ltrx_gemm_tn_group_ln: 48 tiles x 5 splits = 240 of 256),
         instead of as a launch of its own behind it; the residual-stream gradient then rotates over three buffers, because that
-        LayerNorm backward may no longer write into the buffer the weight gradient is reading.  Same bits; False = the two launches."""
+        LayerNorm backward may no longer write into the buffer the weight gradient is reading.  Same bits; False = the two launches.
+        wide_heads=True (opt-in): the attention FORWARD of a model whose head width d_model / h lies in 65..128 -- the training forward,
+        ``score()`` and every FusedScorer, which share ``_forward`` -- runs the split-bf16 kernel of ltrx_mha_fwd_wide instead of the exact
+        fp32 arm ltrx_mha_fwd has for these widths; the backward keeps the exact kernels (same lse and dropout conventions).  A switch
+        because it rounds differently from the exact arm.  ``self.attention_forward`` is "wide" where it applies, else "default"
+        (other head widths, no encoder); ``meta()`` carries the flag only when it is on."""
         from . import _lib as LB
         from .losses import FusedLoss
         self.LB = LB
@@ -460,6 +465,7 @@ class FusedTrainer(object):
         # attention arithmetic of THIS trainer, passed with every ltrx_mha_fwd / ltrx_mha_bwd call (the library keeps no mode):
         # 1 = three bf16 products (fp32-class, parity), 2 = one product (the "bf16" throughput mode)
         self._mha_mode = 2 if gemm == "bf16" else 1
+        self.wide_heads = bool(wide_heads)
         self.model = model
         self.B, self.L, self.M = B, L, B * L
         self.lr, self.betas, self.eps = lr, betas, eps
@@ -789,6 +795,7 @@ class FusedTrainer(object):
             # deferred parameter-gradient partials of up to three LayerNorm backwards per encoder layer (_reduce_flush)
             self.ws_ln_g = [self.ws_ln] + [torch.empty_like(self.ws_ln) for _ in range(2)]
             self.ws_mha = KN.mha_bwd_workspace(self.lib, B, L, self.h, d // self.h, self._mha_mode, self.d_o)
+        self.attention_forward = "wide" if self._wide_fits(L) else "default"
         no = self.n_out
         if compact:
             self.dsc_c = torch.zeros(M if no == 1 else (M, no), **f32)
@@ -1139,6 +1146,10 @@ class FusedTrainer(object):
         KN.reduce_group(self.lib, self._st(), q)
         q.clear()
 
+    def _wide_fits(self, L):
+        """does the attention forward of slates up to ``L`` items run ltrx_mha_fwd_wide?  (``wide_heads``; the head width decides)"""
+        return bool(self.wide_heads and self.N and self._mha_mode != 0 and self.LB.mha_wide_fits(L, self.d // self.h))
+
     # ---- the step body (capturable) ----------------------------------------------------------------------------
     def _forward(self, train=True, bs=None):
         """input buffers -> scores of the buffer set ``bs`` (what that is: ``_alloc_forward``): the step's own (``bs`` None = self) or
@@ -1149,6 +1160,7 @@ class FusedTrainer(object):
         stream = self._st()                                       # (of the row movers: the pass stays on one stream)
         kpm = bs.mask if bs.layout == "grid" else None            # packed rows are all valid keys
         dp = (lambda p: p) if train else (lambda p: 0.0)          # dropout rate of a site in this pass
+        mha_fwd = KN.mha_fwd_wide if self._wide_fits(L) else KN.mha_fwd
         h = bs.x_in
         nm = self.norm_in
         if nm is not None and self._x_pad:                        # ... into the first F columns of the padded operand rows
@@ -1174,8 +1186,8 @@ class FusedTrainer(object):
             self._ln_fwd(x, None, st["norm0"], None, st["xn0"], st["mean0"], st["rstd0"], rows=M)
             st["xin"] = x
             self._lin_fwd(st["xn0"], st["lin_qkv"], st["qkv"], rows=M)
-            KN.mha_fwd(lib, self._st(), st["q"], st["k"], st["v"], kpm, B, L, self.h, st["o"], st["lse"], dp(st["p_att"]), st["s_att"],
-                       self.drop_step, bs.cu, bs.order, self._mha_mode)
+            mha_fwd(lib, self._st(), st["q"], st["k"], st["v"], kpm, B, L, self.h, st["o"], st["lse"], dp(st["p_att"]), st["s_att"],
+                    self.drop_step, bs.cu, bs.order, self._mha_mode)
             RW.zero_attention_tail(bs, lib, stream, st["o"])
             # x1 = x + dropout(attention branch): the residual sum is the out-projection's epilogue (act 3)
             self._lin_fwd(st["o"], st["lin_o"], st["x1"], 0, dp(st["p_s0"]), st["s_s0"], res=x, rows=M)
@@ -1381,8 +1393,11 @@ class FusedTrainer(object):
     def meta(self):
         """what ``checkpoint.check_compatible`` compares: parameter names / shapes, optimizer kind and hyper-parameters, loss, clipping"""
         from . import checkpoint as CK
-        return CK.make_meta([(r.name, r.p) for r in self._params_named], self.optimizer, self._hyper(), self.loss.name, self._loss_args,
+        meta = CK.make_meta([(r.name, r.p) for r in self._params_named], self.optimizer, self._hyper(), self.loss.name, self._loss_args,
                             self.clip)
+        if self.wide_heads:                   # (only when on: a run without the option writes the block it always wrote)
+            meta["wide_heads"] = True
+        return meta
 
     def state_dict(self):
         """Everything a resumed run needs to be THIS run, as CPU tensors and plain values (one device-to-host copy, one host sync):

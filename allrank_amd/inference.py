@@ -26,6 +26,11 @@ output rows (``FusedScorer.packed_outputs()``) inside the ranking launch.  ``las
 "gemm" where the library does not take the head's shape) and ``"n_out"``.  The option is a switch and not the default because the
 exact-fp32 head rounds differently from the module's: items whose module scores are closer than that difference may swap places.
 
+WIDE HEADS.  ``allrank_amd.inference.wide_heads = True`` (or ``Ranker(model, wide_heads=True)``) builds the ranking engine with
+``FusedTrainer(wide_heads=True)``: a model whose head width d_model / h lies in 65..128 is scored through the split-bf16 attention
+forward of ltrx_mha_fwd_wide instead of the exact fp32 arm.  ``last_run["attention_forward"]`` ("wide" | "default") records what a
+fused ``rank_slates`` ran.  A switch for the same reason: the scores round differently, near-ties may swap.
+
 A model with a positional encoding is scored with ``indices = ones`` for every item (inference_utils.py:47): a quirk of the
 reference, reproduced.
 """
@@ -35,10 +40,11 @@ from . import _lib as LB
 from .kernels import rank_slates_cu, rank_slates_rows_cu
 from .metrics import PADDED_Y_VALUE
 
-__all__ = ["rank_slates", "rank_batches", "rank_slates_cu", "rank_slates_rows_cu", "last_run", "multi_output"]
+__all__ = ["rank_slates", "rank_batches", "rank_slates_cu", "rank_slates_rows_cu", "last_run", "multi_output", "wide_heads"]
 
 last_run = {"engine": None, "reason": ""}
 multi_output = False          # opt-in: rank models with d_output > 1 on the device (module docstring); read when a Ranker is built
+wide_heads = False            # opt-in: FusedTrainer(wide_heads=True) for the ranking engine (module docstring); read when a Ranker is built
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -69,11 +75,12 @@ class Ranker(object):
     the smallest batch, its step never called (the scorer reads the trainer's flat parameters, weight images and transposes) -- plus
     the ranked output buffers.  ``reason`` != "": the fused engine cannot serve this model, every batch takes the module path."""
 
-    def __init__(self, model, multi_output=None):
+    def __init__(self, model, multi_output=None, wide_heads=None):
         self.model, self.trainer, self.reason = model, None, ""
         self._scorers, self._out = {}, {}
         self.head = None                                      # d_output > 1: the head the last ranked batch's scorer ran
         multi_output = globals()["multi_output"] if multi_output is None else multi_output
+        wide_heads = globals()["wide_heads"] if wide_heads is None else wide_heads
         try:
             p = next(model.parameters())
         except (StopIteration, AttributeError):
@@ -88,7 +95,7 @@ class Ranker(object):
         try:
             from .engine import FusedTrainer
             loss = ("ordinal", {"n": n_out}) if n_out > 1 else ("listNet", {})     # (the loss the engine pairs with the head; never run)
-            self.trainer = FusedTrainer(model, loss[0], loss[1], 1, 8, use_graph=False, fc_step=False)
+            self.trainer = FusedTrainer(model, loss[0], loss[1], 1, 8, use_graph=False, fc_step=False, wide_heads=bool(wide_heads))
         except NotImplementedError as e:
             self.reason = "the fused engine refuses the model: %s" % (e,)
 
@@ -252,4 +259,6 @@ def rank_slates(datasets, model, config):
         last_run.update(engine="module" if rk.reason else "fused", reason=rk.reason)
     if rk.head is not None:
         last_run.update(head=rk.head, n_out=rk.trainer.n_out)
+    if rk.trainer is not None and rk.trainer.wide_heads:        # (only under the option: the default run reports what it always did)
+        last_run.update(attention_forward=rk.trainer.attention_forward)
     return out

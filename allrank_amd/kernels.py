@@ -21,6 +21,7 @@ every call to the header's parameter names with CPU tensors and a recording stan
 are the exception that allocates: they ask the library for the byte count and return ``_lib.workspace`` of it.
 """
 import ctypes
+import types
 
 from ._lib import check, ptr as P, workspace
 from .outhead import out_head_fwd, rank_slates_rows_cu        # noqa: F401  (stated there, launched through this module)
@@ -57,6 +58,12 @@ def thirds(t):
 def mha_fwd(lib, st, q, k, v, kpm, B, L, h, o, lse, p, seed, drop_step, cu, order, mode):
     check(lib.ltrx_mha_fwd(P(q), P(k), P(v), P(kpm), B, L, h, q.shape[-1] // h, q.stride(-2), P(o), o.stride(-2), P(lse), float(p), seed,
                            P(drop_step), P(cu), P(order), mode, st), "mha_fwd")
+
+
+def mha_fwd_wide(lib, *args):
+    """``mha_fwd`` on the opt-in split-bf16 forward for head widths 65..128.  ltrx_mha_fwd_wide has ltrx_mha_fwd's parameters, so the
+    marshalling above stays the one statement of both: it runs against a view of the library whose forward is the wide entry point."""
+    mha_fwd(types.SimpleNamespace(ltrx_mha_fwd=lib.ltrx_mha_fwd_wide), *args)
 
 
 def mha_bwd_workspace(lib, B, L, h, d_k, mode, like):
