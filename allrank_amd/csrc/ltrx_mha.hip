@@ -625,3 +625,27 @@ extern "C" int ltrx_mha_bwd(const float* q, const float* k, const float* v, cons
   LTRX_LAUNCH_CHECK();
   return LTRX_OK;
 }
+
+// The opt-in backward for wide heads (ltrx_mha_wide.hip): ltrx_mha_bwd's arguments and checks, modes 1 / 2 only, and only the shapes
+// ltrx_mha_wide_fits takes.  `ws` is the B L h floats (delta) ltrx_mha_bwd_workspace_bytes returns at these widths.  ltrx_mha_bwd
+// itself keeps sending these widths to the exact kernels above.
+int ltrx_mha_bwd_wide_launch(const float* q, const float* k, const float* v, const uint8_t* kpm, const float* o, const float* dout,
+                             const float* lse, int B, int L, int h, int dk, int rs, int ors, float* dq, float* dkk, float* dv, int drs,
+                             float* delta, float p_drop, uint32_t seed, const uint32_t* seed_step, const int* cu, const int* order, bool plain,
+                             hipStream_t s);
+
+extern "C" int ltrx_mha_bwd_wide(const float* q, const float* k, const float* v, const uint8_t* key_pad_mask, const float* o,
+                                 const float* dout, const float* lse, int B, int L, int h, int d_k, int row_stride,
+                                 int o_row_stride, float* dq, float* dk, float* dv, int d_row_stride, float p_drop,
+                                 uint32_t seed, const uint32_t* seed_step, const int32_t* cu_seqlens, const int32_t* slate_order,
+                                 int mode, void* ws, ltrx_stream_t stream) {
+  if (!q || !k || !v || (!key_pad_mask && !cu_seqlens) || !o || !dout || !lse || !dq || !dk || !dv || !ws) return LTRX_EINVAL;
+  if (mode != 1 && mode != 2) return LTRX_EINVAL;
+  if (!(p_drop >= 0.f) || p_drop >= 1.f) return LTRX_EINVAL;
+  int rc = mha_check(B, L, h, d_k, row_stride, o_row_stride);
+  if (rc != LTRX_OK) return rc;
+  if (d_row_stride % 4 != 0 || d_row_stride < h * d_k) return LTRX_EUNSUPPORTED;
+  if (!ltrx_mha_wide_fits(L, d_k)) return LTRX_EUNSUPPORTED;
+  return ltrx_mha_bwd_wide_launch(q, k, v, key_pad_mask, o, dout, lse, B, L, h, d_k, row_stride, o_row_stride, dq, dk, dv, d_row_stride,
+                                  (float*)ws, p_drop, seed, seed_step, cu_seqlens, slate_order, mode == 2, (hipStream_t)stream);
+}

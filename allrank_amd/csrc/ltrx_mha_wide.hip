@@ -45,6 +45,32 @@
 //   * barriers.  Every wave takes every barrier.  A wave whose queries lie beyond the slate (`active` false) keeps staging; the only
 //     early return is the workgroup-uniform one before the first barrier.  No thread reads a row at or beyond the slate's length.
 // Compiled without the packed-fp32 VALU instructions (allrank_amd/build.py), and the code uses no two-float vector arithmetic.
+//
+// ---- BACKWARD (ltrx_mha_bwd_wide: ltrx_mha_bwd_wide_dq_kernel, then ltrx_mha_bwd_wide_dkdv_kernel on the same stream) ------------
+// The same workgroup (four waves, 128 rows of one slate-head, grid (B h, ceil(L / 128))), ring (two 32-row slots of four bf16
+// planes, one barrier per tile, the write-after-read argument above), image layout, three-product arithmetic and log2 domain.  P is
+// recomputed from the saved natural-log lse -- P = exp2(S + key bias - lse log2 e) -- so there is no running reference here.
+//   dQ kernel.  A wave owns 32 queries.  In registers for the whole key loop: Q hi / lo (pre-scaled by scale log2 e before the split),
+//     dO hi / lo, the dQ accumulators.  A slot holds V hi, V lo, K hi, K lo.  Per tile: S^T = K Q^T (row-wise reads of K),
+//     dP^T = V dO^T (row-wise reads of V), dS = P (dP keep - delta) scale in the accumulator layout, dQ^T += K^T dS^T (transposed
+//     reads of K: dS never moves between lanes).  delta_q = <dO_q, O_q> is summed in fp32 in the prologue from the unsplit rows the
+//     lane loads for its dO fragments, and written to ws[slate-head][q] for the second kernel.
+//   dK/dV kernel.  A wave owns 32 keys.  In registers: K hi / lo (pre-scaled: K enters only S here), V hi / lo, the dK and dV
+//     accumulators, the key's bias (-inf: masked or >= len).  A slot holds Q hi, Q lo, dO hi, dO lo (unscaled) and 32 entries each of
+//     lse log2 e (+inf for a row >= len: P = 0), delta and, under dropout, the row seed, written by threads 0-31 under the rule of the
+//     forward's kbias.  Per tile: S = Q K^T (row-wise Q), dP = dO V^T (row-wise dO), P keep and dS in one pass,
+//     dV^T += dO^T (P keep) (transposed dO), dK^T += Q^T dS (transposed Q).  A masked key has P = 0 in every tile: its dK and dV rows are exact zeros.
+//   * operand layout: REGISTERS, not a wave-private LDS image of dO.  One wave per SIMD owns the 512-entry register file; the fixed
+//     operands and accumulators are 192 (dQ) / 256 (dK/dV) of them at DKP 128 and the rest -- S, dP, dS, the streamed fragments, the
+//     staging registers -- fits beside them without scratch (profiles/mha_wide.md has the table), so the extra LDS reads and the
+//     12 / 16 KB per wave of an image are not spent.
+//   * bank conflicts: wide_off() is the layout of EVERY plane, planes and slots start at multiples of 256 bytes, and both kernels read
+//     with the forward's two lane assignments (TileOffsets): the row-wise reads of K, V, Q and dO are score_tile's (16 lanes = 16 rows,
+//     one chunk), the transposed reads of K, dO and Q are value_tile's (32 lanes = 4 rows x 4 chunks of one 4-chunk group).  The
+//     forward's argument is about row and chunk numbers inside a plane only, so it covers all of them; the staging stores are the
+//     forward's as well.  The 32-entry statistics of a slot are read as the forward reads kbias (b128, two addresses per wave).
+//   * barriers: every wave takes every barrier, a wave beyond the slate keeps staging, the only early return is the workgroup-uniform
+//     one before the first barrier, and no thread reads a row at or beyond the slate's length (statistics included).
 #include "ltrx_mfma.h"
 
 using namespace ltrx;
@@ -417,6 +443,283 @@ __global__ void __launch_bounds__(NTHREAD) __attribute__((amdgpu_waves_per_eu(Ge
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// backward (header: BACKWARD).  Both kernels: workgroup (slate * h + head, row block of 128); wave w owns rows 128 blockIdx.y + 32 w ..
+// ------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// the staging of two streamed operands with row strides of their own (Q: rs, dO: ors) -- stager_init / stager_gload otherwise
+template <int DKP>
+__device__ __forceinline__ void stager_init2(Stager<DKP>& st, const float* __restrict__ xb, int xrs, const float* __restrict__ yb, int yrs, int dk) {
+  using G = Geo<DKP>;
+#pragma unroll
+  for (int j = 0; j < G::NPOS; ++j) {
+    const int i = threadIdx.x + NTHREAD * j;
+    const bool isy = i >= 32 * G::CH;
+    const int w = isy ? i - 32 * G::CH : i;
+    const int row = w / G::CH, chunk = w % G::CH, c = chunk * 8;
+    st.row[j] = row;
+    st.ca[j] = c < dk;
+    st.cb[j] = c + 4 < dk;
+    st.src[j] = (isy ? yb : xb) + (size_t)row * (isy ? yrs : xrs) + (st.ca[j] ? c : 0);
+    st.dst[j] = (isy ? 2 * G::TILEB : 0) + wide_off<DKP>(row, chunk);
+  }
+}
+template <int DKP>
+__device__ __forceinline__ void stager_gload2(Stager<DKP>& st, int tile, int len, int xrs, int yrs) {
+#pragma unroll
+  for (int j = 0; j < Geo<DKP>::NPOS; ++j) {
+    const bool isy = (int)threadIdx.x + NTHREAD * j >= 32 * Geo<DKP>::CH;
+    const bool ok = tile * 32 + st.row[j] < len;
+    const float* p = st.src[j] + (size_t)tile * 32 * (isy ? yrs : xrs);
+    st.a[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    st.b[j] = st.a[j];
+    if (ok && st.ca[j]) st.a[j] = *reinterpret_cast<const float4*>(p);
+    if (ok && st.cb[j]) st.b[j] = *reinterpret_cast<const float4*>(p + 4);
+  }
+}
+
+// the wave's dO fragments (q_fragments, unscaled) and delta = <dO row, O row>, summed in fp32 over the unsplit values of both halves
+template <int DKP>
+__device__ __forceinline__ float do_fragments(bf16x8 (&dh)[Geo<DKP>::KS], bf16x8 (&dl)[Geo<DKP>::KS], const float* __restrict__ dob,
+                                              const float* __restrict__ ob, int q0, int len, int dk, int ors) {
+  const int lane = threadIdx.x & 63, l31 = lane & 31, half = lane >> 5;
+  const bool rok = q0 + l31 < len;
+  const size_t ro = (size_t)(rok ? q0 + l31 : 0) * ors;                        // (row 0 exists)
+  float del = 0.f;
+#pragma unroll
+  for (int ks = 0; ks < Geo<DKP>::KS; ++ks) {
+    const int c = 16 * ks + 8 * half;
+    const bool oa = rok && c < dk, ob2 = rok && c + 4 < dk;
+    const f32x4 da = *reinterpret_cast<const f32x4*>(dob + ro + (oa ? c : 0)), db = *reinterpret_cast<const f32x4*>(dob + ro + (ob2 ? c + 4 : 0));
+    const f32x4 xa = *reinterpret_cast<const f32x4*>(ob + ro + (oa ? c : 0)), xb = *reinterpret_cast<const f32x4*>(ob + ro + (ob2 ? c + 4 : 0));
+    float x[8];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      x[e] = oa ? da[e] : 0.f;
+      x[4 + e] = ob2 ? db[e] : 0.f;
+      del += x[e] * xa[e];
+      del += x[4 + e] * xb[e];
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      LTRX_SPLIT_BF16(x[e], dh[ks][e], dl[ks][e]);
+    }
+  }
+  return sum_across_halves(del);
+}
+
+template <int NCT>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[NCT]) {
+#pragma unroll
+  for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[ct][r] = 0.f;
+}
+
+// two score_tile()s at once, for the kernel that has no registers to spare: X[row][fixed] of the plane pair at `xs` against (xfh, xfl)
+// and of the pair at `ys` against (yfh, yfl).  The streamed fragments are fetched one 16-column step at a time -- 16 registers in
+// flight instead of score_tile's 4 KS per product -- and the two accumulator chains alternate.
+template <int DKP, bool PL>
+__device__ __forceinline__ void score_tiles2(const unsigned char* xs, const unsigned char* ys, const TileOffsets<DKP>& fo,
+                                             const bf16x8 (&xfh)[Geo<DKP>::KS], const bf16x8 (&xfl)[Geo<DKP>::KS],
+                                             const bf16x8 (&yfh)[Geo<DKP>::KS], const bf16x8 (&yfl)[Geo<DKP>::KS], f32x16& x, f32x16& y) {
+  using G = Geo<DKP>;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) x[r] = y[r] = 0.f;
+#pragma unroll
+  for (int ks = 0; ks < G::KS; ++ks) {
+    const bf16x8 xh = *reinterpret_cast<const bf16x8*>(xs + fo.k[ks]), yh = *reinterpret_cast<const bf16x8*>(ys + fo.k[ks]);
+    if (!PL) {
+      const bf16x8 xl = *reinterpret_cast<const bf16x8*>(xs + fo.k[ks] + G::TILEB), yl = *reinterpret_cast<const bf16x8*>(ys + fo.k[ks] + G::TILEB);
+      x = LTRX_MFMA(xl, xfh[ks], x);
+      y = LTRX_MFMA(yl, yfh[ks], y);
+      x = LTRX_MFMA(xh, xfl[ks], x);
+      y = LTRX_MFMA(yh, yfl[ks], y);
+    }
+    x = LTRX_MFMA(xh, xfh[ks], x);
+    y = LTRX_MFMA(yh, yfh[ks], y);
+  }
+}
+
+template <int DKP>
+constexpr size_t kDkdvSmem = (size_t)NSLOT * Geo<DKP>::SLOTB + NSLOT * 3 * 32 * sizeof(float);      // + lse, delta, row seed per slot
+
+}  // namespace
+
+template <int DKP, bool DROP, bool PL>
+__global__ void __launch_bounds__(NTHREAD) __attribute__((amdgpu_waves_per_eu(1, 1))) ltrx_mha_bwd_wide_dq_kernel(
+    const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v, const uint8_t* __restrict__ kpm,
+    const float* __restrict__ o, const float* __restrict__ dout, const float* __restrict__ lse, float* __restrict__ delta, int L, int h, int dk,
+    int rs, int ors, float* __restrict__ dq, int drs, float scale, DropCfg drop, const uint32_t* __restrict__ drop_step,
+    const int* __restrict__ cu, const int* __restrict__ order) {
+  using G = Geo<DKP>;
+  extern __shared__ __attribute__((aligned(256))) unsigned char smem[];      // slot: V hi, V lo, K hi, K lo
+  float* kbias = reinterpret_cast<float*>(smem + NSLOT * G::SLOTB);      // [slot][32]: -inf for a masked or out-of-range key, else 0
+  int* kflag = reinterpret_cast<int*>(kbias + NSLOT * 32);               // [slot]: does the tile hold such a key?
+  if (DROP && drop_step) drop.seed ^= drop_step[0] * 0x9E3779B9u;
+  const Slate sl = which_slate(L, h, cu, order);
+  const int len = sl.len;
+  if ((int)(blockIdx.y * QBLK) >= len) return;         // whole workgroup beyond this slate (uniform: before any barrier)
+  const int lane = threadIdx.x & 63, half = lane >> 5, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const size_t head0 = sl.row0 * rs + (size_t)sl.head * dk, ohead0 = sl.row0 * ors + (size_t)sl.head * dk;
+  Stager<DKP> sg;
+  stager_init<DKP>(sg, v + head0, k + head0, dk, rs);  // V in the first plane pair, K in the second: value_tile() then reads K^T
+  stager_gload<DKP>(sg, 0, len, rs);
+  uint8_t km_n = 0;
+  if (threadIdx.x < 32 && kpm && (int)threadIdx.x < len) km_n = kpm[sl.row0 + threadIdx.x];
+  const int q0 = blockIdx.y * QBLK + wave * 32;
+  const bool active = q0 < len;                        // (inactive waves still stage and take every barrier)
+  bf16x8 qh[G::KS], ql[G::KS], dh[G::KS], dl[G::KS];
+  q_fragments<DKP>(qh, ql, q + head0, q0, len, dk, rs, scale * kLog2e);
+  const float del_q = do_fragments<DKP>(dh, dl, dout + ohead0, o + ohead0, q0, len, dk, ors);
+  const int qrow = q0 + (lane & 31);
+  const size_t stat = (size_t)sl.bh * sl.Lmax + qrow;
+  const float lse_q = (qrow < len) ? lse[stat] * kLog2e : 0.f;
+  if (half == 0 && qrow < len) delta[stat] = del_q;
+  const TileOffsets<DKP> fo = tile_offsets<DKP>();
+  f32x16 dqacc[G::NCT];
+  zero_acc<G::NCT>(dqacc);
+  const uint32_t drow = DROP ? drop_row_seed(drop, sl.bh, sl.Lmax, qrow) : 0u;
+  const int nkt = (len + 31) / 32;
+  for (int kt = 0; kt < nkt; ++kt) {
+    const int sidx = kt & (NSLOT - 1);
+    unsigned char* slot = smem + sidx * G::SLOTB;
+    stager_sstore<DKP, PL>(sg, slot);
+    if (threadIdx.x < 32) {
+      const bool off = kt * 32 + (int)threadIdx.x >= len || km_n;
+      kbias[sidx * 32 + threadIdx.x] = off ? -INFINITY : 0.f;
+      const bool any_off = __builtin_amdgcn_ballot_w64(off) != 0;
+      if (threadIdx.x == 0) kflag[sidx] = any_off ? 1 : 0;
+    }
+    if (kt + 1 < nkt) {
+      stager_gload<DKP>(sg, kt + 1, len, rs);          // in flight during this tile's MFMAs
+      if (threadIdx.x < 32 && kpm && (kt + 1) * 32 + (int)threadIdx.x < len) km_n = kpm[sl.row0 + (kt + 1) * 32 + threadIdx.x];
+    }
+    lds_only_barrier();
+    if (!active) continue;
+    f32x16 s = score_tile<DKP, PL>(slot + 2 * G::TILEB, fo, qh, ql);          // S^T[key][query], log2 domain
+    if (__builtin_amdgcn_readfirstlane(kflag[sidx])) {
+      const float* kb = kbias + sidx * 32 + 4 * half;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const f32x4 b4 = *reinterpret_cast<const f32x4*>(kb + 8 * g);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s[4 * g + e] += b4[e];
+      }
+    }
+    const f32x16 dp = score_tile<DKP, PL>(slot, fo, dh, dl);                   // dP^T[key][query] (before the dropout mask)
+    f32x16 ds;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float p = fast_exp2(s[r] - lse_q);
+      const float keep = DROP ? drop_scale_rk(drop, drow, kt * 32 + rowmap(r, half)) : 1.0f;
+      ds[r] = p * (dp[r] * keep - del_q) * scale;
+    }
+    value_tile<DKP, PL>(slot, fo, ds, dqacc);                                  // dQ^T[d][query] += K^T[d][key] dS^T[key][query]
+  }
+  if (!active) return;
+  f32x4* scratch = reinterpret_cast<f32x4*>(smem + (((nkt - 1) & (NSLOT - 1)) ^ 1) * G::SLOTB + wave * 4096);      // (as the forward)
+  store_rows<G::NCT>(dq + sl.row0 * drs + (size_t)sl.head * dk, q0, len, dk, drs, dqacc, 1.0f, scratch);
+}
+
+template <int DKP, bool DROP, bool PL>
+__global__ void __launch_bounds__(NTHREAD) __attribute__((amdgpu_waves_per_eu(1, 1))) ltrx_mha_bwd_wide_dkdv_kernel(
+    const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v, const uint8_t* __restrict__ kpm,
+    const float* __restrict__ dout, const float* __restrict__ lse, const float* __restrict__ delta, int L, int h, int dk, int rs, int ors,
+    float* __restrict__ dkout, float* __restrict__ dvout, int drs, float scale, DropCfg drop, const uint32_t* __restrict__ drop_step,
+    const int* __restrict__ cu, const int* __restrict__ order) {
+  using G = Geo<DKP>;
+  extern __shared__ __attribute__((aligned(256))) unsigned char smem[];      // slot: Q hi, Q lo, dO hi, dO lo
+  float* lse_t = reinterpret_cast<float*>(smem + NSLOT * G::SLOTB);      // [slot][32]: lse log2 e of the tile's queries, +inf beyond the slate
+  float* del_t = lse_t + NSLOT * 32;                                     // [slot][32]: delta
+  uint32_t* seed_t = reinterpret_cast<uint32_t*>(del_t + NSLOT * 32);    // [slot][32]: dropout row seed (DROP)
+  if (DROP && drop_step) drop.seed ^= drop_step[0] * 0x9E3779B9u;
+  const Slate sl = which_slate(L, h, cu, order);
+  const int len = sl.len;
+  if ((int)(blockIdx.y * QBLK) >= len) return;         // whole workgroup beyond this slate (uniform: before any barrier)
+  const int lane = threadIdx.x & 63, half = lane >> 5, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const size_t head0 = sl.row0 * rs + (size_t)sl.head * dk, ohead0 = sl.row0 * ors + (size_t)sl.head * dk;
+  const size_t stat0 = (size_t)sl.bh * sl.Lmax;
+  Stager<DKP> sg;
+  stager_init2<DKP>(sg, q + head0, rs, dout + ohead0, ors, dk);
+  stager_gload2<DKP>(sg, 0, len, rs, ors);
+  float lse_n = INFINITY, del_n = 0.f;                 // threads 0-31: statistics of query 32 qt + threadIdx.x of the tile being staged
+  if (threadIdx.x < 32 && (int)threadIdx.x < len) {
+    lse_n = lse[stat0 + threadIdx.x] * kLog2e;
+    del_n = delta[stat0 + threadIdx.x];
+  }
+  const int k0 = blockIdx.y * QBLK + wave * 32;
+  const bool active = k0 < len;                        // (inactive waves still stage and take every barrier)
+  bf16x8 kh[G::KS], kl[G::KS], vh[G::KS], vl[G::KS];
+  q_fragments<DKP>(kh, kl, k + head0, k0, len, dk, rs, scale * kLog2e);
+  q_fragments<DKP>(vh, vl, v + head0, k0, len, dk, rs, 1.0f);
+  const int key = k0 + (lane & 31);
+  const float kbias = (key >= len || (kpm && kpm[sl.row0 + key])) ? -INFINITY : 0.f;
+  const TileOffsets<DKP> fo = tile_offsets<DKP>();
+  TileOffsets<DKP> fq = fo;                            // value_tile()'s transposed reads, moved from the second plane pair to the first
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+#pragma unroll
+    for (int ct = 0; ct < G::NCT; ++ct) {
+      fq.v[u][ct][0] -= 2 * G::TILEB;
+      fq.v[u][ct][1] -= 2 * G::TILEB;
+    }
+  f32x16 dkacc[G::NCT], dvacc[G::NCT];
+  zero_acc<G::NCT>(dkacc);
+  zero_acc<G::NCT>(dvacc);
+  const int nqt = (len + 31) / 32;
+  for (int qt = 0; qt < nqt; ++qt) {
+    const int sidx = qt & (NSLOT - 1);
+    unsigned char* slot = smem + sidx * G::SLOTB;
+    stager_sstore<DKP, PL>(sg, slot);
+    if (threadIdx.x < 32) {
+      lse_t[sidx * 32 + threadIdx.x] = lse_n;
+      del_t[sidx * 32 + threadIdx.x] = del_n;
+      if (DROP) seed_t[sidx * 32 + threadIdx.x] = drop_row_seed(drop, sl.bh, sl.Lmax, qt * 32 + threadIdx.x);
+    }
+    if (qt + 1 < nqt) {
+      stager_gload2<DKP>(sg, qt + 1, len, rs, ors);    // in flight during this tile's MFMAs
+      if (threadIdx.x < 32) {
+        const int qn = (qt + 1) * 32 + threadIdx.x;
+        lse_n = INFINITY;
+        del_n = 0.f;
+        if (qn < len) {
+          lse_n = lse[stat0 + qn] * kLog2e;
+          del_n = delta[stat0 + qn];
+        }
+      }
+    }
+    lds_only_barrier();
+    if (!active) continue;
+    // both row-wise products first, then P keep and dS in one pass: the two accumulators and their two results are all that lives
+    // across the transposed products, next to the 256 registers of the fixed operands
+    f32x16 s, dp, pd, ds;                              // S[query][key] (log2 domain), dP[query][key] (before the dropout mask)
+    score_tiles2<DKP, PL>(slot, slot + 2 * G::TILEB, fo, kh, kl, vh, vl, s, dp);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {                                              // queries 8 g + 4 half + 0..3 = rowmap(4 g + e, half)
+      const int at = sidx * 32 + 4 * half + 8 * g;
+      const f32x4 l4 = *reinterpret_cast<const f32x4*>(lse_t + at), d4 = *reinterpret_cast<const f32x4*>(del_t + at);
+      u32x4 s4 = {0u, 0u, 0u, 0u};
+      if (DROP) s4 = *reinterpret_cast<const u32x4*>(seed_t + at);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float p = fast_exp2(s[4 * g + e] + kbias - l4[e]);
+        const float keep = DROP ? drop_scale_rk(drop, s4[e], key) : 1.0f;
+        pd[4 * g + e] = p * keep;
+        ds[4 * g + e] = p * (dp[4 * g + e] * keep - d4[e]) * scale;
+      }
+    }
+    value_tile<DKP, PL>(slot, fo, pd, dvacc);                                  // dV^T[d][key] += dO^T[d][query] (P keep)[query][key]
+    value_tile<DKP, PL>(slot, fq, ds, dkacc);                                  // dK^T[d][key] += Q^T[d][query] dS[query][key]
+  }
+  if (!active) return;
+  // the free slot, as in the forward; the wave's 4 KB are used twice, one store_rows after the other
+  f32x4* scratch = reinterpret_cast<f32x4*>(smem + (((nqt - 1) & (NSLOT - 1)) ^ 1) * G::SLOTB + wave * 4096);
+  store_rows<G::NCT>(dkout + sl.row0 * drs + (size_t)sl.head * dk, k0, len, dk, drs, dkacc, 1.0f, scratch);
+  store_rows<G::NCT>(dvout + sl.row0 * drs + (size_t)sl.head * dk, k0, len, dk, drs, dvacc, 1.0f, scratch);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // host side (the C entry point ltrx_mha_fwd_wide lives next to ltrx_mha_fwd in ltrx_mha.hip and shares its argument checks)
 // ------------------------------------------------------------------------------------------------------------------
 extern "C" int ltrx_mha_wide_fits(int L, int d_k) {
@@ -453,4 +756,54 @@ int ltrx_mha_fwd_wide_launch(const float* q, const float* k, const float* v, con
                              bool plain, hipStream_t s) {
   if (dk <= 96) return launch_wide<96>(q, k, v, kpm, B, L, h, dk, rs, o, ors, lse, p_drop, seed, seed_step, cu, order, plain, s);
   return launch_wide<128>(q, k, v, kpm, B, L, h, dk, rs, o, ors, lse, p_drop, seed, seed_step, cu, order, plain, s);
+}
+
+// the backward: the dQ kernel (which also writes delta[B, h, L] into `delta`), then the dK/dV kernel on the same stream
+template <int DKP>
+static int launch_wide_bwd(const float* q, const float* k, const float* v, const uint8_t* kpm, const float* o, const float* dout, const float* lse,
+                           int B, int L, int h, int dk, int rs, int ors, float* dq, float* dkk, float* dv, int drs, float* delta, float p_drop,
+                           uint32_t seed, const uint32_t* seed_step, const int* cu, const int* order, bool plain, hipStream_t s) {
+  constexpr size_t SQ = Geo<DKP>::SMEM, SK = kDkdvSmem<DKP>;
+  static std::atomic<uint64_t> attr_done{0};
+  const int arc = ltrx_allow_dynamic_lds(
+      attr_done, {{ltrx_mha_bwd_wide_dq_kernel<DKP, false, false>, SQ}, {ltrx_mha_bwd_wide_dq_kernel<DKP, true, false>, SQ},
+                  {ltrx_mha_bwd_wide_dq_kernel<DKP, false, true>, SQ}, {ltrx_mha_bwd_wide_dq_kernel<DKP, true, true>, SQ},
+                  {ltrx_mha_bwd_wide_dkdv_kernel<DKP, false, false>, SK}, {ltrx_mha_bwd_wide_dkdv_kernel<DKP, true, false>, SK},
+                  {ltrx_mha_bwd_wide_dkdv_kernel<DKP, false, true>, SK}, {ltrx_mha_bwd_wide_dkdv_kernel<DKP, true, true>, SK}});
+  if (arc != LTRX_OK) return arc;
+  const DropCfg drop = ltrx_make_drop(p_drop, seed);
+  const float scale = 1.0f / sqrtf((float)dk);
+  const dim3 grid(B * h, (L + QBLK - 1) / QBLK);
+#define LTRX_WIDE_DQ(D_, P_)                                                                                                               \
+  hipLaunchKernelGGL((ltrx_mha_bwd_wide_dq_kernel<DKP, D_, P_>), grid, dim3(NTHREAD), SQ, s, q, k, v, kpm, o, dout, lse, delta, L, h, dk, rs, ors, \
+                     dq, drs, scale, drop, seed_step, cu, order)
+#define LTRX_WIDE_DKDV(D_, P_)                                                                                                             \
+  hipLaunchKernelGGL((ltrx_mha_bwd_wide_dkdv_kernel<DKP, D_, P_>), grid, dim3(NTHREAD), SK, s, q, k, v, kpm, dout, lse, delta, L, h, dk, rs, ors, \
+                     dkk, dv, drs, scale, drop, seed_step, cu, order)
+  if (drop.thresh != 0u) {
+    if (plain) LTRX_WIDE_DQ(true, true); else LTRX_WIDE_DQ(true, false);
+  } else {
+    if (plain) LTRX_WIDE_DQ(false, true); else LTRX_WIDE_DQ(false, false);
+  }
+  LTRX_LAUNCH_CHECK();
+  if (drop.thresh != 0u) {
+    if (plain) LTRX_WIDE_DKDV(true, true); else LTRX_WIDE_DKDV(true, false);
+  } else {
+    if (plain) LTRX_WIDE_DKDV(false, true); else LTRX_WIDE_DKDV(false, false);
+  }
+#undef LTRX_WIDE_DQ
+#undef LTRX_WIDE_DKDV
+  LTRX_LAUNCH_CHECK();
+  return LTRX_OK;
+}
+
+int ltrx_mha_bwd_wide_launch(const float* q, const float* k, const float* v, const uint8_t* kpm, const float* o, const float* dout,
+                             const float* lse, int B, int L, int h, int dk, int rs, int ors, float* dq, float* dkk, float* dv, int drs,
+                             float* delta, float p_drop, uint32_t seed, const uint32_t* seed_step, const int* cu, const int* order, bool plain,
+                             hipStream_t s) {
+  if (dk <= 96)
+    return launch_wide_bwd<96>(q, k, v, kpm, o, dout, lse, B, L, h, dk, rs, ors, dq, dkk, dv, drs, delta, p_drop, seed, seed_step, cu, order,
+                               plain, s);
+  return launch_wide_bwd<128>(q, k, v, kpm, o, dout, lse, B, L, h, dk, rs, ors, dq, dkk, dv, drs, delta, p_drop, seed, seed_step, cu, order,
+                              plain, s);
 }

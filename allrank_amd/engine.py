@@ -377,7 +377,7 @@ class FusedTrainer(object):
                  optimizer="Adam", weight_decay=0.0, momentum=0.0, nesterov=False,
                  use_graph=True, gemm="split_bf16", dropout=True, seed=None, gradient_clipping_norm=None, compact=False,
                  weight_images=True, fc_step=True, group_wgrad=True, relu_bits=True, pad_input=True, force_dist=False,
-                 _norm_head=True, ln_in_wgrad=True, wide_heads=False):
+                 _norm_head=True, ln_in_wgrad=True, wide_heads=False, wide_backward=False):
         """gemm: "split_bf16" -- libltrx fp32-accurate GEMMs on the bf16 MFMA (3 products), "split_bf16_strict" (6
         products), "hipblaslt" (torch.mm/addmm, exact-fp32 library GEMMs), or "bf16" -- the THROUGHPUT mode: one bf16
         product per contraction in the dense projections AND in attention (fp32 storage, accumulation, LayerNorm, softmax,
@@ -443,9 +443,13 @@ class FusedTrainer(object):
         LayerNorm backward may no longer write into the buffer the weight gradient is reading.  Same bits; False = the two launches.
         wide_heads=True (opt-in): the attention FORWARD of a model whose head width d_model / h lies in 65..128 -- the training forward,
         ``score()`` and every FusedScorer, which share ``_forward`` -- runs the split-bf16 kernel of ltrx_mha_fwd_wide instead of the exact
-        fp32 arm ltrx_mha_fwd has for these widths; the backward keeps the exact kernels (same lse and dropout conventions).  A switch
+        fp32 arm ltrx_mha_fwd has for these widths; the backward keeps the exact kernels unless ``wide_backward`` is on (same lse and dropout conventions).  A switch
         because it rounds differently from the exact arm.  ``self.attention_forward`` is "wide" where it applies, else "default"
-        (other head widths, no encoder); ``meta()`` carries the flag only when it is on."""
+        (other head widths, no encoder); ``meta()`` carries the flag only when it is on.
+        wide_backward=True (opt-in, independent of ``wide_heads``): the attention BACKWARD at those head widths -- in the padded, compact
+        and captured steps alike -- runs the split-bf16 kernels of ltrx_mha_bwd_wide (P recomputed from the saved lse, same dropout draw)
+        instead of the exact fp32 arm of ltrx_mha_bwd; it takes the o / lse of either forward.  ``self.attention_backward`` is "wide"
+        where it applies, else "default"; ``meta()`` carries "wide_backward" only when the option is on."""
         from . import _lib as LB
         from .losses import FusedLoss
         self.LB = LB
@@ -466,6 +470,7 @@ class FusedTrainer(object):
         # 1 = three bf16 products (fp32-class, parity), 2 = one product (the "bf16" throughput mode)
         self._mha_mode = 2 if gemm == "bf16" else 1
         self.wide_heads = bool(wide_heads)
+        self.wide_backward = bool(wide_backward)
         self.model = model
         self.B, self.L, self.M = B, L, B * L
         self.lr, self.betas, self.eps = lr, betas, eps
@@ -796,6 +801,7 @@ class FusedTrainer(object):
             self.ws_ln_g = [self.ws_ln] + [torch.empty_like(self.ws_ln) for _ in range(2)]
             self.ws_mha = KN.mha_bwd_workspace(self.lib, B, L, self.h, d // self.h, self._mha_mode, self.d_o)
         self.attention_forward = "wide" if self._wide_fits(L) else "default"
+        self.attention_backward = "wide" if self._wide_bwd_fits(L) else "default"
         no = self.n_out
         if compact:
             self.dsc_c = torch.zeros(M if no == 1 else (M, no), **f32)
@@ -1150,6 +1156,10 @@ class FusedTrainer(object):
         """does the attention forward of slates up to ``L`` items run ltrx_mha_fwd_wide?  (``wide_heads``; the head width decides)"""
         return bool(self.wide_heads and self.N and self._mha_mode != 0 and self.LB.mha_wide_fits(L, self.d // self.h))
 
+    def _wide_bwd_fits(self, L):
+        """does the attention backward of slates up to ``L`` items run ltrx_mha_bwd_wide?  (``wide_backward``; the head width decides)"""
+        return bool(self.wide_backward and self.N and self._mha_mode != 0 and self.LB.mha_wide_fits(L, self.d // self.h))
+
     # ---- the step body (capturable) ----------------------------------------------------------------------------
     def _forward(self, train=True, bs=None):
         """input buffers -> scores of the buffer set ``bs`` (what that is: ``_alloc_forward``): the step's own (``bs`` None = self) or
@@ -1268,6 +1278,7 @@ class FusedTrainer(object):
             if not self.norm_head:
                 self._ln_bwd(ga, self.xsum_f, nf, self.mean_f, self.rstd_f, None, gb)
             ds = gb                                               # d loss / d (x1_last + ffn_last)
+            mha_bwd = KN.mha_bwd_wide if self._wide_bwd_fits(L) else KN.mha_bwd
             other = ga
             for i in range(self.N - 1, -1, -1):
                 st = self.layers[i]
@@ -1291,8 +1302,8 @@ class FusedTrainer(object):
                 db = self._branch_grad(ds, st["p_s0"], st["s_s0"])
                 self._lin_wgrad(db, st["o"], st["lin_o"], defer=True)
                 self._lin_dgrad(db, st["lin_o"], self.d_o)
-                KN.mha_bwd(lib, self._st(), st["q"], st["k"], st["v"], kpm, st["o"], self.d_o, st["lse"], B, L, self.h, self.dq, self.dk,
-                           self.dv, st["p_att"], st["s_att"], self.drop_step, self.cu, self.order, self._mha_mode, self.ws_mha)
+                mha_bwd(lib, self._st(), st["q"], st["k"], st["v"], kpm, st["o"], self.d_o, st["lse"], B, L, self.h, self.dq, self.dk,
+                        self.dv, st["p_att"], st["s_att"], self.drop_step, self.cu, self.order, self._mha_mode, self.ws_mha)
                 RW.zero_gradient_tail(self, lib, stream, dqkv)
                 self._lin_wgrad(dqkv, st["xn0"], st["lin_qkv"], defer=True)
                 self._lin_dgrad(dqkv, st["lin_qkv"], self.tmp_d)
@@ -1397,6 +1408,8 @@ class FusedTrainer(object):
                             self.clip)
         if self.wide_heads:                   # (only when on: a run without the option writes the block it always wrote)
             meta["wide_heads"] = True
+        if getattr(self, "wide_backward", False):
+            meta["wide_backward"] = True
         return meta
 
     def state_dict(self):

@@ -257,15 +257,20 @@ def _compact_mode(compact):
     return bool(compact)
 
 
-def _wide_heads_mode(wide_heads):
+def _wide_heads_mode(wide_heads, name="ALLRANK_AMD_WIDE_HEADS"):
     """fit()'s ``wide_heads`` argument resolved: None reads ALLRANK_AMD_WIDE_HEADS ("1" = on; unset, "" or "0" = off; anything
     else raises), so that an unmodified main.py can opt in"""
     if wide_heads is None:
-        env = os.environ.get("ALLRANK_AMD_WIDE_HEADS", "")
+        env = os.environ.get(name, "")
         if env not in ("", "0", "1"):
-            raise ValueError("ALLRANK_AMD_WIDE_HEADS must be '1', '0' or unset, got %r" % (env,))
+            raise ValueError("%s must be '1', '0' or unset, got %r" % (name, env))
         return env == "1"
     return bool(wide_heads)
+
+
+def _wide_backward_mode(wide_backward):
+    """fit()'s ``wide_backward`` argument resolved the same way, from ALLRANK_AMD_WIDE_BACKWARD"""
+    return _wide_heads_mode(wide_backward, "ALLRANK_AMD_WIDE_BACKWARD")
 
 
 def _compact_graph_stats(trainer):
@@ -452,7 +457,7 @@ def _assert_finite(trainer, loss, epoch, step):
 
 def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, config, gradient_clipping_norm, early_stopping_patience,
         device, output_dir, tensorboard_output_path, use_fused=True, compact=None, gemm="split_bf16", train_metrics=None,
-        check_finite=None, wide_heads=None, val_scorer=None, checkpoint_every=None, resume=None):
+        check_finite=None, wide_heads=None, wide_backward=None, val_scorer=None, checkpoint_every=None, resume=None):
     """Same positional / keyword arguments as the reference ``fit``; ``use_fused`` / ``compact`` / ``gemm`` / ``train_metrics`` /
     ``check_finite`` are extensions (compact=None: variable-length execution when less than 80 % of the first batch's slots are valid
     items; compact="graph", or ALLRANK_AMD_COMPACT=graph under main.py (any other value raises): the variable-length step at bucketed
@@ -479,7 +484,9 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
     whose run had ended returns its stored result; both options raise NotImplementedError under a process group of several ranks);
     wide_heads=True (None: ALLRANK_AMD_WIDE_HEADS=1): FusedTrainer(wide_heads=True) -- the split-bf16 attention forward for head widths
     65..128, in training, validation scoring and ``score()``; ``last_run["attention_forward"]`` = "wide" | "default" then says what ran
-    ("default": another head width, or the autograd engine; the key exists only under the option)."""
+    ("default": another head width, or the autograd engine; the key exists only under the option);
+    wide_backward=True (None: ALLRANK_AMD_WIDE_BACKWARD=1): FusedTrainer(wide_backward=True) -- the split-bf16 attention backward for
+    the same head widths, independent of ``wide_heads``; ``last_run["attention_backward"]`` = "wide" | "default", only under the option."""
     import torch.distributed as dist
     device = torch.device(device)
     world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
@@ -519,6 +526,7 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
     lo, hi = shard_slates(B_glob, rank, world)
     compact = _compact_mode(compact)
     wide_heads = _wide_heads_mode(wide_heads)
+    wide_backward = _wide_backward_mode(wide_backward)
     cg_reason = ""
     if spec is not None:
         if compact is None:
@@ -527,7 +535,8 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
             compact, cg_reason = True, "slate-sharded run (%d ranks): the ranks' row buckets differ; compact=True" % world
         try:
             trainer = FusedTrainer(model, spec[0], spec[1], hi - lo, L, lr=spec[2], world_size=world, use_graph=True,
-                                   gradient_clipping_norm=gradient_clipping_norm, compact=compact, gemm=gemm, wide_heads=wide_heads, **spec[3])
+                                   gradient_clipping_norm=gradient_clipping_norm, compact=compact, gemm=gemm, wide_heads=wide_heads,
+                                   wide_backward=wide_backward, **spec[3])
             fused = True
             optimizer._opt_called = True   # (torch's "scheduler.step() before optimizer.step()" check: in the fused run the
             #                                 optimizer object only carries the learning rate, its step() is never called)
@@ -544,6 +553,8 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
                     compact_graph=_compact_graph_stats(trainer), compact_graph_reason=cg_reason)
     if wide_heads:                            # (only under the option: a run without it reports what it always did)
         last_run["attention_forward"] = getattr(trainer, "attention_forward", "default")
+    if wide_backward:
+        last_run["attention_backward"] = getattr(trainer, "attention_backward", "default")
     log.info("allrank_amd.fit: %s step%s", last_run["engine"], (" (" + reason + ")") if reason else "")
     normalizer = getattr(getattr(train_dl, "dataset", None), "normalizer", None)      # load_libsvm_dataset(normalize=...) hung it there
     if normalizer is not None:

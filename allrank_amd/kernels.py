@@ -75,6 +75,12 @@ def mha_bwd(lib, st, q, k, v, kpm, o, do, lse, B, L, h, dq, dk, dv, p, seed, dro
                            P(dk), P(dv), dq.stride(-2), float(p), seed, P(drop_step), P(cu), P(order), mode, P(ws), st), "mha_bwd")
 
 
+def mha_bwd_wide(lib, *args):
+    """``mha_bwd`` on the opt-in split-bf16 backward for head widths 65..128 (ltrx_mha_bwd_wide has ltrx_mha_bwd's parameters): the
+    marshalling above against a view of the library whose backward is the wide entry point, as ``mha_fwd_wide``."""
+    mha_bwd(types.SimpleNamespace(ltrx_mha_bwd=lib.ltrx_mha_bwd_wide), *args)
+
+
 # ---- LayerNorm (transformer.py:73-81) over rows of x.shape[-1] columns -----------------------------------------------
 def layernorm_fwd(lib, st, x, res, a, b, rows, eps, xsum, y, mean, rstd, p=0.0, seed=0, drop_step=None):
     """y = LN(x + drop_p(res)); xsum (may be None) = x + drop_p(res)"""
