@@ -19,8 +19,8 @@ ARCH = "gfx950"
 # per lane in one VALU instruction): with them its n_out accumulators pair up into v_pk_fma_f32, which the kernel's contract (exact
 # scalar fused multiply-adds in a stated order) does not want.  The host pass of hipcc warns that it does not know the feature.
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-# ltrx_mha_wide.hip: its softmax is written as scalar fp32 operations and is compiled as such.
-EXTRA_FLAGS = {"ltrx_outhead.hip": _NO_PACKED_FP32, "ltrx_mha_wide.hip": _NO_PACKED_FP32}
+# ltrx_mha_wide.hip, ltrx_mha_narrow.hip: their softmax is written as scalar fp32 operations and is compiled as such.
+EXTRA_FLAGS = {"ltrx_outhead.hip": _NO_PACKED_FP32, "ltrx_mha_wide.hip": _NO_PACKED_FP32, "ltrx_mha_narrow.hip": _NO_PACKED_FP32}
 
 
 def _sources():

@@ -322,3 +322,6 @@ def check_compatible(saved_meta, live_meta):
     if bool(saved_meta.get("wide_backward")) != bool(live_meta.get("wide_backward")):
         raise ValueError("checkpoint: wide_backward (the split-bf16 attention backward for head widths 65..128): stored %r, live %r"
                          % (bool(saved_meta.get("wide_backward")), bool(live_meta.get("wide_backward"))))
+    if bool(saved_meta.get("narrow_heads")) != bool(live_meta.get("narrow_heads")):
+        raise ValueError("checkpoint: narrow_heads (the split-bf16 attention forward for head widths up to 32): stored %r, live %r"
+                         % (bool(saved_meta.get("narrow_heads")), bool(live_meta.get("narrow_heads"))))

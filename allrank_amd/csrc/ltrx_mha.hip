@@ -508,6 +508,10 @@ size_t ltrx_mha_res_bwd_ws_bytes(int B, int L, int h);
 int ltrx_mha_fwd_wide_launch(const float* q, const float* k, const float* v, const uint8_t* kpm, int B, int L, int h, int dk, int rs,
                              float* o, int ors, float* lse, float p_drop, uint32_t seed, const uint32_t* seed_step, const int* cu,
                              const int* order, bool plain, hipStream_t s);
+// ltrx_mha_narrow.hip: the opt-in split-bf16 forward for d_k <= 32 (ltrx_mha_fwd_narrow below)
+int ltrx_mha_fwd_narrow_launch(const float* q, const float* k, const float* v, const uint8_t* kpm, int B, int L, int h, int dk, int rs,
+                               float* o, int ors, float* lse, float p_drop, uint32_t seed, const uint32_t* seed_step, const int* cu,
+                               const int* order, bool plain, hipStream_t s);
 
 static int mha_check(int B, int L, int h, int dk, int rs, int ors) {
   if (B <= 0 || L <= 0 || h <= 0 || dk <= 0) return LTRX_EINVAL;
@@ -569,6 +573,21 @@ extern "C" int ltrx_mha_fwd_wide(const float* q, const float* k, const float* v,
   if (!ltrx_mha_wide_fits(L, d_k)) return LTRX_EUNSUPPORTED;
   return ltrx_mha_fwd_wide_launch(q, k, v, key_pad_mask, B, L, h, d_k, row_stride, o, o_row_stride, lse_out, p_drop, seed, seed_step,
                                   cu_seqlens, slate_order, mode == 2, (hipStream_t)stream);
+}
+
+// The opt-in forward for narrow heads (ltrx_mha_narrow.hip): ltrx_mha_fwd's arguments and checks, modes 1 / 2 only, and only the
+// shapes ltrx_mha_narrow_fits takes.  ltrx_mha_fwd itself keeps sending these widths to the exact kernels above.
+extern "C" int ltrx_mha_fwd_narrow(const float* q, const float* k, const float* v, const uint8_t* key_pad_mask, int B, int L,
+                                   int h, int d_k, int row_stride, float* o, int o_row_stride, float* lse_out, float p_drop,
+                                   uint32_t seed, const uint32_t* seed_step, const int32_t* cu_seqlens, const int32_t* slate_order,
+                                   int mode, ltrx_stream_t stream) {
+  if (!q || !k || !v || (!key_pad_mask && !cu_seqlens) || !o || !lse_out || !(p_drop >= 0.f) || p_drop >= 1.f) return LTRX_EINVAL;
+  if (mode != 1 && mode != 2) return LTRX_EINVAL;
+  int rc = mha_check(B, L, h, d_k, row_stride, o_row_stride);
+  if (rc != LTRX_OK) return rc;
+  if (!ltrx_mha_narrow_fits(L, d_k)) return LTRX_EUNSUPPORTED;
+  return ltrx_mha_fwd_narrow_launch(q, k, v, key_pad_mask, B, L, h, d_k, row_stride, o, o_row_stride, lse_out, p_drop, seed, seed_step,
+                                    cu_seqlens, slate_order, mode == 2, (hipStream_t)stream);
 }
 
 // The split-bf16 backward hands dS[B, h, LK, LK] (LK = L rounded up to 64) from its dK/dV kernel to its dQ kernel through the

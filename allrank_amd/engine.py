@@ -377,7 +377,7 @@ class FusedTrainer(object):
                  optimizer="Adam", weight_decay=0.0, momentum=0.0, nesterov=False,
                  use_graph=True, gemm="split_bf16", dropout=True, seed=None, gradient_clipping_norm=None, compact=False,
                  weight_images=True, fc_step=True, group_wgrad=True, relu_bits=True, pad_input=True, force_dist=False,
-                 _norm_head=True, ln_in_wgrad=True, wide_heads=False, wide_backward=False):
+                 _norm_head=True, ln_in_wgrad=True, wide_heads=False, wide_backward=False, narrow_heads=False):
         """gemm: "split_bf16" -- libltrx fp32-accurate GEMMs on the bf16 MFMA (3 products), "split_bf16_strict" (6
         products), "hipblaslt" (torch.mm/addmm, exact-fp32 library GEMMs), or "bf16" -- the THROUGHPUT mode: one bf16
         product per contraction in the dense projections AND in attention (fp32 storage, accumulation, LayerNorm, softmax,
@@ -449,7 +449,12 @@ class FusedTrainer(object):
         wide_backward=True (opt-in, independent of ``wide_heads``): the attention BACKWARD at those head widths -- in the padded, compact
         and captured steps alike -- runs the split-bf16 kernels of ltrx_mha_bwd_wide (P recomputed from the saved lse, same dropout draw)
         instead of the exact fp32 arm of ltrx_mha_bwd; it takes the o / lse of either forward.  ``self.attention_backward`` is "wide"
-        where it applies, else "default"; ``meta()`` carries "wide_backward" only when the option is on."""
+        where it applies, else "default"; ``meta()`` carries "wide_backward" only when the option is on.
+        narrow_heads=True (opt-in, independent of both): the attention FORWARD of a model whose head width d_model / h is at most 32 --
+        the training forward, ``score()`` and every FusedScorer -- runs the split-bf16 kernel of ltrx_mha_fwd_narrow instead of the exact
+        fp32 arm ltrx_mha_fwd has for these widths; the backward keeps the exact kernels (same lse and dropout conventions).  A switch
+        because it rounds differently from the exact arm.  ``self.attention_forward`` is "narrow" where it applies; ``meta()`` carries
+        "narrow_heads" only when the option is on."""
         from . import _lib as LB
         from .losses import FusedLoss
         self.LB = LB
@@ -471,6 +476,7 @@ class FusedTrainer(object):
         self._mha_mode = 2 if gemm == "bf16" else 1
         self.wide_heads = bool(wide_heads)
         self.wide_backward = bool(wide_backward)
+        self.narrow_heads = bool(narrow_heads)
         self.model = model
         self.B, self.L, self.M = B, L, B * L
         self.lr, self.betas, self.eps = lr, betas, eps
@@ -800,7 +806,7 @@ class FusedTrainer(object):
             # deferred parameter-gradient partials of up to three LayerNorm backwards per encoder layer (_reduce_flush)
             self.ws_ln_g = [self.ws_ln] + [torch.empty_like(self.ws_ln) for _ in range(2)]
             self.ws_mha = KN.mha_bwd_workspace(self.lib, B, L, self.h, d // self.h, self._mha_mode, self.d_o)
-        self.attention_forward = "wide" if self._wide_fits(L) else "default"
+        self.attention_forward = "wide" if self._wide_fits(L) else ("narrow" if self._narrow_fits(L) else "default")
         self.attention_backward = "wide" if self._wide_bwd_fits(L) else "default"
         no = self.n_out
         if compact:
@@ -1156,6 +1162,10 @@ class FusedTrainer(object):
         """does the attention forward of slates up to ``L`` items run ltrx_mha_fwd_wide?  (``wide_heads``; the head width decides)"""
         return bool(self.wide_heads and self.N and self._mha_mode != 0 and self.LB.mha_wide_fits(L, self.d // self.h))
 
+    def _narrow_fits(self, L):
+        """does the attention forward of slates up to ``L`` items run ltrx_mha_fwd_narrow?  (``narrow_heads``; the head width decides)"""
+        return bool(self.narrow_heads and self.N and self._mha_mode != 0 and self.LB.mha_narrow_fits(L, self.d // self.h))
+
     def _wide_bwd_fits(self, L):
         """does the attention backward of slates up to ``L`` items run ltrx_mha_bwd_wide?  (``wide_backward``; the head width decides)"""
         return bool(self.wide_backward and self.N and self._mha_mode != 0 and self.LB.mha_wide_fits(L, self.d // self.h))
@@ -1170,7 +1180,7 @@ class FusedTrainer(object):
         stream = self._st()                                       # (of the row movers: the pass stays on one stream)
         kpm = bs.mask if bs.layout == "grid" else None            # packed rows are all valid keys
         dp = (lambda p: p) if train else (lambda p: 0.0)          # dropout rate of a site in this pass
-        mha_fwd = KN.mha_fwd_wide if self._wide_fits(L) else KN.mha_fwd
+        mha_fwd = KN.mha_fwd_wide if self._wide_fits(L) else (KN.mha_fwd_narrow if self._narrow_fits(L) else KN.mha_fwd)
         h = bs.x_in
         nm = self.norm_in
         if nm is not None and self._x_pad:                        # ... into the first F columns of the padded operand rows
@@ -1410,6 +1420,8 @@ class FusedTrainer(object):
             meta["wide_heads"] = True
         if getattr(self, "wide_backward", False):
             meta["wide_backward"] = True
+        if getattr(self, "narrow_heads", False):
+            meta["narrow_heads"] = True
         return meta
 
     def state_dict(self):

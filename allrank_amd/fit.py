@@ -273,6 +273,11 @@ def _wide_backward_mode(wide_backward):
     return _wide_heads_mode(wide_backward, "ALLRANK_AMD_WIDE_BACKWARD")
 
 
+def _narrow_heads_mode(narrow_heads):
+    """fit()'s ``narrow_heads`` argument resolved the same way, from ALLRANK_AMD_NARROW_HEADS"""
+    return _wide_heads_mode(narrow_heads, "ALLRANK_AMD_NARROW_HEADS")
+
+
 def _compact_graph_stats(trainer):
     """last_run["compact_graph"]: what the captured variable-length step did so far (None: the mode is not active)"""
     if not getattr(trainer, "compact_graph", False):              # (tools hand it objects that are no trainer)
@@ -457,7 +462,7 @@ def _assert_finite(trainer, loss, epoch, step):
 
 def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, config, gradient_clipping_norm, early_stopping_patience,
         device, output_dir, tensorboard_output_path, use_fused=True, compact=None, gemm="split_bf16", train_metrics=None,
-        check_finite=None, wide_heads=None, wide_backward=None, val_scorer=None, checkpoint_every=None, resume=None):
+        check_finite=None, wide_heads=None, wide_backward=None, narrow_heads=None, val_scorer=None, checkpoint_every=None, resume=None):
     """Same positional / keyword arguments as the reference ``fit``; ``use_fused`` / ``compact`` / ``gemm`` / ``train_metrics`` /
     ``check_finite`` are extensions (compact=None: variable-length execution when less than 80 % of the first batch's slots are valid
     items; compact="graph", or ALLRANK_AMD_COMPACT=graph under main.py (any other value raises): the variable-length step at bucketed
@@ -486,7 +491,9 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
     65..128, in training, validation scoring and ``score()``; ``last_run["attention_forward"]`` = "wide" | "default" then says what ran
     ("default": another head width, or the autograd engine; the key exists only under the option);
     wide_backward=True (None: ALLRANK_AMD_WIDE_BACKWARD=1): FusedTrainer(wide_backward=True) -- the split-bf16 attention backward for
-    the same head widths, independent of ``wide_heads``; ``last_run["attention_backward"]`` = "wide" | "default", only under the option."""
+    the same head widths, independent of ``wide_heads``; ``last_run["attention_backward"]`` = "wide" | "default", only under the option;
+    narrow_heads=True (None: ALLRANK_AMD_NARROW_HEADS=1): FusedTrainer(narrow_heads=True) -- the split-bf16 attention forward for head
+    widths up to 32, independent of both; ``last_run["attention_forward"]`` = "narrow" | "default" (| "wide"), only under an option."""
     import torch.distributed as dist
     device = torch.device(device)
     world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
@@ -527,6 +534,7 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
     compact = _compact_mode(compact)
     wide_heads = _wide_heads_mode(wide_heads)
     wide_backward = _wide_backward_mode(wide_backward)
+    narrow_heads = _narrow_heads_mode(narrow_heads)
     cg_reason = ""
     if spec is not None:
         if compact is None:
@@ -536,7 +544,7 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
         try:
             trainer = FusedTrainer(model, spec[0], spec[1], hi - lo, L, lr=spec[2], world_size=world, use_graph=True,
                                    gradient_clipping_norm=gradient_clipping_norm, compact=compact, gemm=gemm, wide_heads=wide_heads,
-                                   wide_backward=wide_backward, **spec[3])
+                                   wide_backward=wide_backward, narrow_heads=narrow_heads, **spec[3])
             fused = True
             optimizer._opt_called = True   # (torch's "scheduler.step() before optimizer.step()" check: in the fused run the
             #                                 optimizer object only carries the learning rate, its step() is never called)
@@ -551,7 +559,7 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
     last_run.update(engine="fused" if fused else "autograd", compact=bool(trainer.compact), reason=reason,
                     fcstep=trainer.fcstep, sampling=getattr(train_dl, "sampling", None),
                     compact_graph=_compact_graph_stats(trainer), compact_graph_reason=cg_reason)
-    if wide_heads:                            # (only under the option: a run without it reports what it always did)
+    if wide_heads or narrow_heads:            # (only under an option: a run without it reports what it always did)
         last_run["attention_forward"] = getattr(trainer, "attention_forward", "default")
     if wide_backward:
         last_run["attention_backward"] = getattr(trainer, "attention_backward", "default")

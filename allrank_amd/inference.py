@@ -31,6 +31,10 @@ WIDE HEADS.  ``allrank_amd.inference.wide_heads = True`` (or ``Ranker(model, wid
 forward of ltrx_mha_fwd_wide instead of the exact fp32 arm.  ``last_run["attention_forward"]`` ("wide" | "default") records what a
 fused ``rank_slates`` ran.  A switch for the same reason: the scores round differently, near-ties may swap.
 
+NARROW HEADS.  ``allrank_amd.inference.narrow_heads = True`` (or ``Ranker(model, narrow_heads=True)``) does the same with
+``FusedTrainer(narrow_heads=True)`` for head widths up to 32 (ltrx_mha_fwd_narrow; ``last_run["attention_forward"]`` "narrow" |
+"default").  Independent of ``wide_heads``.
+
 A model with a positional encoding is scored with ``indices = ones`` for every item (inference_utils.py:47): a quirk of the
 reference, reproduced.
 """
@@ -40,11 +44,12 @@ from . import _lib as LB
 from .kernels import rank_slates_cu, rank_slates_rows_cu
 from .metrics import PADDED_Y_VALUE
 
-__all__ = ["rank_slates", "rank_batches", "rank_slates_cu", "rank_slates_rows_cu", "last_run", "multi_output", "wide_heads"]
+__all__ = ["rank_slates", "rank_batches", "rank_slates_cu", "rank_slates_rows_cu", "last_run", "multi_output", "wide_heads", "narrow_heads"]
 
 last_run = {"engine": None, "reason": ""}
 multi_output = False          # opt-in: rank models with d_output > 1 on the device (module docstring); read when a Ranker is built
 wide_heads = False            # opt-in: FusedTrainer(wide_heads=True) for the ranking engine (module docstring); read when a Ranker is built
+narrow_heads = False          # opt-in: FusedTrainer(narrow_heads=True) for the ranking engine, likewise
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -75,12 +80,13 @@ class Ranker(object):
     the smallest batch, its step never called (the scorer reads the trainer's flat parameters, weight images and transposes) -- plus
     the ranked output buffers.  ``reason`` != "": the fused engine cannot serve this model, every batch takes the module path."""
 
-    def __init__(self, model, multi_output=None, wide_heads=None):
+    def __init__(self, model, multi_output=None, wide_heads=None, narrow_heads=None):
         self.model, self.trainer, self.reason = model, None, ""
         self._scorers, self._out = {}, {}
         self.head = None                                      # d_output > 1: the head the last ranked batch's scorer ran
         multi_output = globals()["multi_output"] if multi_output is None else multi_output
         wide_heads = globals()["wide_heads"] if wide_heads is None else wide_heads
+        narrow_heads = globals()["narrow_heads"] if narrow_heads is None else narrow_heads
         try:
             p = next(model.parameters())
         except (StopIteration, AttributeError):
@@ -95,7 +101,8 @@ class Ranker(object):
         try:
             from .engine import FusedTrainer
             loss = ("ordinal", {"n": n_out}) if n_out > 1 else ("listNet", {})     # (the loss the engine pairs with the head; never run)
-            self.trainer = FusedTrainer(model, loss[0], loss[1], 1, 8, use_graph=False, fc_step=False, wide_heads=bool(wide_heads))
+            self.trainer = FusedTrainer(model, loss[0], loss[1], 1, 8, use_graph=False, fc_step=False, wide_heads=bool(wide_heads),
+                                        narrow_heads=bool(narrow_heads))
         except NotImplementedError as e:
             self.reason = "the fused engine refuses the model: %s" % (e,)
 
@@ -259,6 +266,6 @@ def rank_slates(datasets, model, config):
         last_run.update(engine="module" if rk.reason else "fused", reason=rk.reason)
     if rk.head is not None:
         last_run.update(head=rk.head, n_out=rk.trainer.n_out)
-    if rk.trainer is not None and rk.trainer.wide_heads:        # (only under the option: the default run reports what it always did)
+    if rk.trainer is not None and (rk.trainer.wide_heads or rk.trainer.narrow_heads):        # (only under the option: the default run reports what it always did)
         last_run.update(attention_forward=rk.trainer.attention_forward)
     return out

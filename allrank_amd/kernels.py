@@ -66,6 +66,12 @@ def mha_fwd_wide(lib, *args):
     mha_fwd(types.SimpleNamespace(ltrx_mha_fwd=lib.ltrx_mha_fwd_wide), *args)
 
 
+def mha_fwd_narrow(lib, *args):
+    """``mha_fwd`` on the opt-in split-bf16 forward for head widths up to 32 (ltrx_mha_fwd_narrow has ltrx_mha_fwd's parameters): the
+    marshalling above against a view of the library whose forward is the narrow entry point, as ``mha_fwd_wide``."""
+    mha_fwd(types.SimpleNamespace(ltrx_mha_fwd=lib.ltrx_mha_fwd_narrow), *args)
+
+
 def mha_bwd_workspace(lib, B, L, h, d_k, mode, like):
     return workspace(lib.ltrx_mha_bwd_workspace_bytes(B, L, h, d_k, mode), like)
 

@@ -401,6 +401,19 @@ int ltrx_mha_fwd_wide(const float* q, const float* k, const float* v, const uint
                       int d_k, int row_stride, float* o, int o_row_stride, float* lse_out, float p_drop, uint32_t seed,
                       const uint32_t* seed_step, const int32_t* cu_seqlens, const int32_t* slate_order, int mode,
                       ltrx_stream_t stream);
+/* Opt-in forward for NARROW heads, d_k <= 32 (d_k % 4 == 0), which ltrx_mha_fwd always runs on the exact fp32 MFMA: the split-bf16
+ * arithmetic of modes 1 / 2 on a kernel that streams K and V through a two-slot ring of 128-key tiles in LDS, walked in 32-key
+ * groups by four-wave workgroups of 128 queries (ltrx_mha_narrow.hip), any slate length, both layouts, dropout included.  Parameters,
+ * argument checks and conventions (lse, dropout draw, fully padded slates = exact zeros) are ltrx_mha_fwd's.  mode must be 1 or 2
+ * (anything else: LTRX_EINVAL); a shape ltrx_mha_narrow_fits refuses returns LTRX_EUNSUPPORTED; a refused call launches nothing and
+ * writes nothing.  Its o / lse feed ltrx_mha_bwd of the same mode (the exact kernels at these widths).  A separate entry point, not
+ * a dispatch arm, because it rounds differently from the exact kernels (within the same split-bf16 bound as 32 < d_k <= 64).
+ * ltrx_mha_narrow_fits: 1 for L > 0, 0 < d_k <= 32, d_k % 4 == 0 and ceil(L / 128) within the grid limit, else 0.  Host only. */
+int ltrx_mha_narrow_fits(int L, int d_k);
+int ltrx_mha_fwd_narrow(const float* q, const float* k, const float* v, const uint8_t* key_pad_mask, int B, int L, int h,
+                        int d_k, int row_stride, float* o, int o_row_stride, float* lse_out, float p_drop, uint32_t seed,
+                        const uint32_t* seed_step, const int32_t* cu_seqlens, const int32_t* slate_order, int mode,
+                        ltrx_stream_t stream);
 /* backward: dq,dk,dv from do.  `ws` holds delta[B,h,L] (rowsum(do*o)) for the exact kernels, or -- in modes 1 / 2 where the
  * LDS-resident kernels run (32 < d_k <= 64, L <= LTRX_MAX_SLATE_LEN) -- the dS exchange between the two backward kernels,
  * B*h*LK*LK floats with LK = L rounded up to 64: S, P, dP and delta are computed once, by the dK/dV kernel, which hands dS to a
