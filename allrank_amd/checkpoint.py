@@ -316,12 +316,8 @@ def check_compatible(saved_meta, live_meta):
             raise ValueError("checkpoint: loss argument %s: stored %r, live %r" % (k, sa.get(k, "<unset>"), la.get(k, "<unset>")))
     if _canon(saved_meta.get("clip")) != _canon(live_meta.get("clip")):
         raise ValueError("checkpoint: gradient_clipping_norm: stored %r, live %r" % (saved_meta.get("clip"), live_meta.get("clip")))
-    if bool(saved_meta.get("wide_heads")) != bool(live_meta.get("wide_heads")):      # (the key exists only where the option is on)
-        raise ValueError("checkpoint: wide_heads (the split-bf16 attention forward for head widths 65..128): stored %r, live %r"
-                         % (bool(saved_meta.get("wide_heads")), bool(live_meta.get("wide_heads"))))
-    if bool(saved_meta.get("wide_backward")) != bool(live_meta.get("wide_backward")):
-        raise ValueError("checkpoint: wide_backward (the split-bf16 attention backward for head widths 65..128): stored %r, live %r"
-                         % (bool(saved_meta.get("wide_backward")), bool(live_meta.get("wide_backward"))))
-    if bool(saved_meta.get("narrow_heads")) != bool(live_meta.get("narrow_heads")):
-        raise ValueError("checkpoint: narrow_heads (the split-bf16 attention forward for head widths up to 32): stored %r, live %r"
-                         % (bool(saved_meta.get("narrow_heads")), bool(live_meta.get("narrow_heads"))))
+    from .engine import ATTENTION_ARMS
+    for arm in ATTENTION_ARMS:
+        stored, live = bool(saved_meta.get(arm.option)), bool(live_meta.get(arm.option))      # (the key exists only where the option is on)
+        if stored != live:
+            raise ValueError("checkpoint: %s (%s): stored %r, live %r" % (arm.option, arm.what, stored, live))

@@ -1,4 +1,5 @@
-// The vocabulary the matrix-core (MFMA) kernels share: ltrx_gemm.hip, ltrx_mha.hip, ltrx_mha_res.hip, ltrx_fcstep.hip.
+// The vocabulary the matrix-core (MFMA) kernels share: ltrx_gemm.hip, ltrx_mha.hip, ltrx_fcstep.hip and, through ltrx_mha_split.h,
+// the split-bf16 attention kernels (ltrx_mha_res.hip, ltrx_mha_wide.hip, ltrx_mha_narrow.hip).
 #pragma once
 #include "ltrx_device.h"
 

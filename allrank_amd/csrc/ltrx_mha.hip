@@ -28,7 +28,7 @@
 //             dV += P^T dO, dK += dS^T Q.  No atomics anywhere: every output element has one owner (deterministic).
 // Arithmetic intensity: 4 L d_k flop per (query, head) against 4 d_k-float rows read once per workgroup -> compute
 // (fp32 MFMA) bound; K/V re-reads by the 2 workgroups of a (slate, head) are served by L2.
-#include "ltrx_mfma.h"
+#include "ltrx_mha_split.h"      // kLog2e, kLn2; the split-bf16 arms' launchers and shape predicates
 
 using namespace ltrx;
 
@@ -180,8 +180,6 @@ __device__ __forceinline__ void store_rows(float* __restrict__ base, int row0, i
 // log2(e)/sqrt(d_k)) instead of the 14-instruction expf expansion, and key padding enters as an additive -inf bias, so
 // masked and out-of-range entries fall out of exp2(-inf) = 0 without compare/select pairs.  The backward kernels recompute
 // P = exp2(s * log2e/sqrt(d_k) - lse * log2e) from the stored natural-log LSE (lse_out keeps its meaning).
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kLn2 = 0.6931471805599453f;
 
 template <int DKP>
 __device__ __forceinline__ void zero_acc(f32x16 (&o)[DKP / 32]) {
@@ -494,25 +492,6 @@ extern "C" int ltrx_selftest_mfma32x32x2(const float* A, const float* Bm, float*
 //   mode 0: exact fp32 MFMA (v_mfma_f32_32x32x2_f32, bit-exact fp32 products) for every shape -- the strict reference.
 //   mode 2: the kernels of mode 1 with ONE bf16 product per contraction (plain bf16 operands, fp32 accumulate and softmax):
 //           the throughput mode, about 2^-9 relative error per product -- NOT the parity arithmetic.
-bool ltrx_mha_res_fits(int L, int dk);
-int ltrx_mha_fwd_res_launch(const float* q, const float* k, const float* v, const uint8_t* kpm, int B, int L, int h, int dk, int rs,
-                            float* o, int ors, float* lse, float p_drop, uint32_t seed, const uint32_t* seed_step, const int* cu,
-                            const int* order, bool plain, hipStream_t s);
-int ltrx_mha_bwd_res_launch(const float* q, const float* k, const float* v, const uint8_t* kpm, const float* o, const float* dout,
-                            const float* lse, int B, int L, int h, int dk, int rs, int ors, float* dq, float* dkk, float* dv, int drs,
-                            void* ws, float p_drop, uint32_t seed, const uint32_t* seed_step, const int* cu, const int* order,
-                            bool plain, hipStream_t s);
-bool ltrx_mha_res_bwd_fits(int L, int dk);
-size_t ltrx_mha_res_bwd_ws_bytes(int B, int L, int h);
-// ltrx_mha_wide.hip: the opt-in split-bf16 forward for 64 < d_k <= 128 (ltrx_mha_fwd_wide below)
-int ltrx_mha_fwd_wide_launch(const float* q, const float* k, const float* v, const uint8_t* kpm, int B, int L, int h, int dk, int rs,
-                             float* o, int ors, float* lse, float p_drop, uint32_t seed, const uint32_t* seed_step, const int* cu,
-                             const int* order, bool plain, hipStream_t s);
-// ltrx_mha_narrow.hip: the opt-in split-bf16 forward for d_k <= 32 (ltrx_mha_fwd_narrow below)
-int ltrx_mha_fwd_narrow_launch(const float* q, const float* k, const float* v, const uint8_t* kpm, int B, int L, int h, int dk, int rs,
-                               float* o, int ors, float* lse, float p_drop, uint32_t seed, const uint32_t* seed_step, const int* cu,
-                               const int* order, bool plain, hipStream_t s);
-
 static int mha_check(int B, int L, int h, int dk, int rs, int ors) {
   if (B <= 0 || L <= 0 || h <= 0 || dk <= 0) return LTRX_EINVAL;
   if (dk % 4 != 0 || dk > 128 || rs % 4 != 0 || ors % 4 != 0 || rs < h * dk || ors < h * dk) return LTRX_EUNSUPPORTED;
@@ -522,6 +501,26 @@ static int mha_check(int B, int L, int h, int dk, int rs, int ors) {
 
 extern "C" int ltrx_mha_head_width_supported(int d_k) { return mha_check(1, 1, 1, d_k, d_k, d_k) == LTRX_OK ? 1 : 0; }
 
+// The argument checks every forward / backward entry point opens with, in the order that decides which code wins: null pointers and
+// p_drop, then the mode (lowest allowed: 0 for ltrx_mha_fwd / ltrx_mha_bwd, 1 for the opt-in arms), then the shape (mha_check), then
+// -- opt-in arms only -- the arm's own `fits`.
+static int mha_fwd_check(bool ptrs, float p_drop, int mode, int mode_lo, int B, int L, int h, int dk, int rs, int ors, int (*fits)(int, int)) {
+  if (!ptrs || !(p_drop >= 0.f) || p_drop >= 1.f) return LTRX_EINVAL;
+  if (mode < mode_lo || mode > 2) return LTRX_EINVAL;
+  const int rc = mha_check(B, L, h, dk, rs, ors);
+  if (rc != LTRX_OK) return rc;
+  return (fits && !fits(L, dk)) ? LTRX_EUNSUPPORTED : LTRX_OK;
+}
+static int mha_bwd_check(bool ptrs, float p_drop, int mode, int mode_lo, int B, int L, int h, int dk, int rs, int ors, int drs,
+                         int (*fits)(int, int)) {
+  const int rc = mha_fwd_check(ptrs, p_drop, mode, mode_lo, B, L, h, dk, rs, ors, nullptr);
+  if (rc != LTRX_OK) return rc;
+  if (drs % 4 != 0 || drs < h * dk) return LTRX_EUNSUPPORTED;
+  return (fits && !fits(L, dk)) ? LTRX_EUNSUPPORTED : LTRX_OK;
+}
+#define LTRX_MHA_FWD_PTRS (q && k && v && (key_pad_mask || cu_seqlens) && o && lse_out)
+#define LTRX_MHA_BWD_PTRS (q && k && v && (key_pad_mask || cu_seqlens) && o && dout && lse && dq && dk && dv && ws)
+
 #define LTRX_DKP_DISPATCH(dk, CALL) \
   do {                              \
     if ((dk) <= 32) { CALL(32); }   \
@@ -530,21 +529,17 @@ extern "C" int ltrx_mha_head_width_supported(int d_k) { return mha_check(1, 1, 1
     else { CALL(128); }             \
   } while (0)
 
-static DropCfg make_drop(float p_drop, uint32_t seed) { return ltrx_make_drop(p_drop, seed); }
-
 extern "C" int ltrx_mha_fwd(const float* q, const float* k, const float* v, const uint8_t* key_pad_mask, int B, int L,
                             int h, int d_k, int row_stride, float* o, int o_row_stride, float* lse_out, float p_drop,
                             uint32_t seed, const uint32_t* seed_step, const int32_t* cu_seqlens, const int32_t* slate_order,
                             int mode, ltrx_stream_t stream) {
-  if (!q || !k || !v || (!key_pad_mask && !cu_seqlens) || !o || !lse_out || !(p_drop >= 0.f) || p_drop >= 1.f) return LTRX_EINVAL;
-  if (mode < 0 || mode > 2) return LTRX_EINVAL;
-  int rc = mha_check(B, L, h, d_k, row_stride, o_row_stride);
+  const int rc = mha_fwd_check(LTRX_MHA_FWD_PTRS, p_drop, mode, 0, B, L, h, d_k, row_stride, o_row_stride, nullptr);
   if (rc != LTRX_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
   if (mode != 0 && ltrx_mha_res_fits(L, d_k))
     return ltrx_mha_fwd_res_launch(q, k, v, key_pad_mask, B, L, h, d_k, row_stride, o, o_row_stride, lse_out, p_drop, seed, seed_step,
                                    cu_seqlens, slate_order, mode == 2, s);
-  const DropCfg drop = make_drop(p_drop, seed);
+  const DropCfg drop = ltrx_make_drop(p_drop, seed);
   const dim3 grid(B * h, (L + 127) / 128);
   const float scale = 1.0f / sqrtf((float)d_k);
 #define CALL(DKP)                                                                                                 \
@@ -566,11 +561,8 @@ extern "C" int ltrx_mha_fwd_wide(const float* q, const float* k, const float* v,
                                  int h, int d_k, int row_stride, float* o, int o_row_stride, float* lse_out, float p_drop,
                                  uint32_t seed, const uint32_t* seed_step, const int32_t* cu_seqlens, const int32_t* slate_order,
                                  int mode, ltrx_stream_t stream) {
-  if (!q || !k || !v || (!key_pad_mask && !cu_seqlens) || !o || !lse_out || !(p_drop >= 0.f) || p_drop >= 1.f) return LTRX_EINVAL;
-  if (mode != 1 && mode != 2) return LTRX_EINVAL;
-  int rc = mha_check(B, L, h, d_k, row_stride, o_row_stride);
+  const int rc = mha_fwd_check(LTRX_MHA_FWD_PTRS, p_drop, mode, 1, B, L, h, d_k, row_stride, o_row_stride, ltrx_mha_wide_fits);
   if (rc != LTRX_OK) return rc;
-  if (!ltrx_mha_wide_fits(L, d_k)) return LTRX_EUNSUPPORTED;
   return ltrx_mha_fwd_wide_launch(q, k, v, key_pad_mask, B, L, h, d_k, row_stride, o, o_row_stride, lse_out, p_drop, seed, seed_step,
                                   cu_seqlens, slate_order, mode == 2, (hipStream_t)stream);
 }
@@ -581,11 +573,8 @@ extern "C" int ltrx_mha_fwd_narrow(const float* q, const float* k, const float* 
                                    int h, int d_k, int row_stride, float* o, int o_row_stride, float* lse_out, float p_drop,
                                    uint32_t seed, const uint32_t* seed_step, const int32_t* cu_seqlens, const int32_t* slate_order,
                                    int mode, ltrx_stream_t stream) {
-  if (!q || !k || !v || (!key_pad_mask && !cu_seqlens) || !o || !lse_out || !(p_drop >= 0.f) || p_drop >= 1.f) return LTRX_EINVAL;
-  if (mode != 1 && mode != 2) return LTRX_EINVAL;
-  int rc = mha_check(B, L, h, d_k, row_stride, o_row_stride);
+  const int rc = mha_fwd_check(LTRX_MHA_FWD_PTRS, p_drop, mode, 1, B, L, h, d_k, row_stride, o_row_stride, ltrx_mha_narrow_fits);
   if (rc != LTRX_OK) return rc;
-  if (!ltrx_mha_narrow_fits(L, d_k)) return LTRX_EUNSUPPORTED;
   return ltrx_mha_fwd_narrow_launch(q, k, v, key_pad_mask, B, L, h, d_k, row_stride, o, o_row_stride, lse_out, p_drop, seed, seed_step,
                                     cu_seqlens, slate_order, mode == 2, (hipStream_t)stream);
 }
@@ -608,18 +597,14 @@ extern "C" int ltrx_mha_bwd(const float* q, const float* k, const float* v, cons
                             int o_row_stride, float* dq, float* dk, float* dv, int d_row_stride, float p_drop,
                             uint32_t seed, const uint32_t* seed_step, const int32_t* cu_seqlens, const int32_t* slate_order,
                             int mode, void* ws, ltrx_stream_t stream) {
-  if (!q || !k || !v || (!key_pad_mask && !cu_seqlens) || !o || !dout || !lse || !dq || !dk || !dv || !ws) return LTRX_EINVAL;
-  if (mode < 0 || mode > 2) return LTRX_EINVAL;
-  if (!(p_drop >= 0.f) || p_drop >= 1.f) return LTRX_EINVAL;
-  int rc = mha_check(B, L, h, d_k, row_stride, o_row_stride);
+  const int rc = mha_bwd_check(LTRX_MHA_BWD_PTRS, p_drop, mode, 0, B, L, h, d_k, row_stride, o_row_stride, d_row_stride, nullptr);
   if (rc != LTRX_OK) return rc;
-  if (d_row_stride % 4 != 0 || d_row_stride < h * d_k) return LTRX_EUNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   float* delta = (float*)ws;
   if (mode != 0 && res_bwd_selected(B, L, h, d_k))
     return ltrx_mha_bwd_res_launch(q, k, v, key_pad_mask, o, dout, lse, B, L, h, d_k, row_stride, o_row_stride, dq, dk, dv, d_row_stride,
                                    ws, p_drop, seed, seed_step, cu_seqlens, slate_order, mode == 2, s);
-  const DropCfg drop = make_drop(p_drop, seed);
+  const DropCfg drop = ltrx_make_drop(p_drop, seed);
   const dim3 grid(B * h, (L + 127) / 128);
   const float scale = 1.0f / sqrtf((float)d_k);
 #define CALLQ(DKP)                                                                                                   \
@@ -648,23 +633,13 @@ extern "C" int ltrx_mha_bwd(const float* q, const float* k, const float* v, cons
 // The opt-in backward for wide heads (ltrx_mha_wide.hip): ltrx_mha_bwd's arguments and checks, modes 1 / 2 only, and only the shapes
 // ltrx_mha_wide_fits takes.  `ws` is the B L h floats (delta) ltrx_mha_bwd_workspace_bytes returns at these widths.  ltrx_mha_bwd
 // itself keeps sending these widths to the exact kernels above.
-int ltrx_mha_bwd_wide_launch(const float* q, const float* k, const float* v, const uint8_t* kpm, const float* o, const float* dout,
-                             const float* lse, int B, int L, int h, int dk, int rs, int ors, float* dq, float* dkk, float* dv, int drs,
-                             float* delta, float p_drop, uint32_t seed, const uint32_t* seed_step, const int* cu, const int* order, bool plain,
-                             hipStream_t s);
-
 extern "C" int ltrx_mha_bwd_wide(const float* q, const float* k, const float* v, const uint8_t* key_pad_mask, const float* o,
                                  const float* dout, const float* lse, int B, int L, int h, int d_k, int row_stride,
                                  int o_row_stride, float* dq, float* dk, float* dv, int d_row_stride, float p_drop,
                                  uint32_t seed, const uint32_t* seed_step, const int32_t* cu_seqlens, const int32_t* slate_order,
                                  int mode, void* ws, ltrx_stream_t stream) {
-  if (!q || !k || !v || (!key_pad_mask && !cu_seqlens) || !o || !dout || !lse || !dq || !dk || !dv || !ws) return LTRX_EINVAL;
-  if (mode != 1 && mode != 2) return LTRX_EINVAL;
-  if (!(p_drop >= 0.f) || p_drop >= 1.f) return LTRX_EINVAL;
-  int rc = mha_check(B, L, h, d_k, row_stride, o_row_stride);
+  const int rc = mha_bwd_check(LTRX_MHA_BWD_PTRS, p_drop, mode, 1, B, L, h, d_k, row_stride, o_row_stride, d_row_stride, ltrx_mha_wide_fits);
   if (rc != LTRX_OK) return rc;
-  if (d_row_stride % 4 != 0 || d_row_stride < h * d_k) return LTRX_EUNSUPPORTED;
-  if (!ltrx_mha_wide_fits(L, d_k)) return LTRX_EUNSUPPORTED;
   return ltrx_mha_bwd_wide_launch(q, k, v, key_pad_mask, o, dout, lse, B, L, h, d_k, row_stride, o_row_stride, dq, dk, dv, d_row_stride,
                                   (float*)ws, p_drop, seed, seed_step, cu_seqlens, slate_order, mode == 2, (hipStream_t)stream);
 }

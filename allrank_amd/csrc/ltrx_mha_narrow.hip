@@ -44,7 +44,7 @@
 //   * barriers.  Every wave takes every barrier.  A wave whose queries lie beyond the slate keeps staging; the only early return is
 //     the workgroup-uniform one before the first barrier.  No thread reads a row at or beyond the slate's length.
 // Compiled without the packed-fp32 VALU instructions (allrank_amd/build.py), and the code uses no two-float vector arithmetic.
-#include "ltrx_mfma.h"
+#include "ltrx_mha_split.h"
 
 using namespace ltrx;
 
@@ -63,42 +63,11 @@ constexpr int SLOTB = 4 * PLANEB;         // K hi, K lo, V hi, V lo
 constexpr int GRPB = 32 * ROWB;           // a 32-key group inside a plane
 constexpr int NPOS = 4;                   // (row, chunk) positions a thread stages per tile: K rows r, r + 64, V rows r, r + 64
 constexpr size_t SMEM = (size_t)NSLOT * SLOTB + NSLOT * TKEYS * sizeof(float) + NSLOT * NGRP * sizeof(int);
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kLn2 = 0.6931471805599453f;
-constexpr float kLazyTau = 8.0f;          // ltrx_mha_res.hip's: a query's reference moves when a group exceeds it by 2^8
 static_assert(NTHREAD * NPOS == 2 * TKEYS * 4, "a tile is 2 x 128 rows x 4 chunks");
 static_assert(NWAVE * 4096 <= SLOTB, "the epilogue's wave-private scratch lives in one slot");
 
 // byte offset of 16-byte chunk `chunk` of row `row` inside one plane of a tile (see the header for why it is conflict-free)
 __device__ __forceinline__ int narrow_off(int row, int chunk) { return row * ROWB + ((chunk ^ ((row >> 2) & 3)) << 4); }
-
-struct Slate {
-  int b, head, bh, Lmax, len;
-  size_t row0;
-};
-__device__ __forceinline__ Slate which_slate(int L, int h, const int* __restrict__ cu, const int* __restrict__ order) {
-  Slate s;
-  s.head = blockIdx.x % h;
-  s.b = order ? order[blockIdx.x / h] : (int)(blockIdx.x / h);
-  s.bh = s.b * h + s.head;
-  s.Lmax = L;
-  s.row0 = cu ? (size_t)cu[s.b] : (size_t)s.b * L;
-  s.len = cu ? cu[s.b + 1] - cu[s.b] : L;
-  return s;
-}
-
-__device__ __forceinline__ float max_across_halves(float x) {     // lane i <-> lane i ^ 32
-  const unsigned u = __float_as_uint(x);
-  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float sum_across_halves(float x) {
-  const unsigned u = __float_as_uint(x);
-  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
-#define LTRX_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
 
 // A thread's staging work.  Position j of 4: rows `row` (j even) / `row + 64` (j odd) of K (j < 2) / V (j >= 2), chunk threadIdx.x & 3.
 struct Stager {
@@ -120,8 +89,7 @@ __device__ __forceinline__ void stager_init(Stager& st, const float* __restrict_
 __device__ __forceinline__ void stager_gload(Stager& st, int tile, int len, int rs) {
 #pragma unroll
   for (int j = 0; j < NPOS; ++j) {
-    const int row = tile * TKEYS + st.row + 64 * (j & 1);
-    const bool ok = row < len;
+    const bool ok = tile * TKEYS + st.row + 64 * (j & 1) < len;
     const float* p = (j < 2 ? st.kp : st.vp) + ((size_t)tile * TKEYS + 64 * (j & 1)) * rs;
     st.a[j] = make_float4(0.f, 0.f, 0.f, 0.f);
     st.b[j] = st.a[j];
@@ -133,12 +101,8 @@ template <bool PL>
 __device__ __forceinline__ void stager_sstore(const Stager& st, unsigned char* slot) {
 #pragma unroll
   for (int j = 0; j < NPOS; ++j) {
-    const float x[8] = {st.a[j].x, st.a[j].y, st.a[j].z, st.a[j].w, st.b[j].x, st.b[j].y, st.b[j].z, st.b[j].w};
     bf16x8 h, l;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      LTRX_SPLIT_BF16(x[e], h[e], l[e]);
-    }
+    split8(st.a[j], st.b[j], h, l);
     unsigned char* at = slot + (j < 2 ? 0 : 2 * PLANEB) + (j & 1) * 64 * ROWB + st.dst;
     *reinterpret_cast<bf16x8*>(at) = h;
     if (!PL) *reinterpret_cast<bf16x8*>(at + PLANEB) = l;
@@ -148,7 +112,7 @@ __device__ __forceinline__ void stager_sstore(const Stager& st, unsigned char* s
 // per-lane byte offsets inside a 32-key group of a slot
 struct GroupOffsets {
   int k[KS];         // K fragment ks: chunk 2 ks + half of row l31 (K hi plane; lo: + PLANEB)
-  int v[2][2];       // V transposed reads [u][rows r0 / r0 + 8] (V hi plane; lo: + PLANEB)
+  int v[2][1][2];    // V transposed reads [u][rows r0 / r0 + 8] (V hi plane; lo: + PLANEB)
 };
 __device__ __forceinline__ GroupOffsets group_offsets() {
   const int lane = threadIdx.x & 63, l31 = lane & 31, half = lane >> 5, i16 = lane & 15, g16 = (lane >> 4) & 1;
@@ -159,28 +123,14 @@ __device__ __forceinline__ GroupOffsets group_offsets() {
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     const int r0 = 16 * u + 4 * half + rsub, chunk = 2 * g16 + c8;
-    f.v[u][0] = 2 * PLANEB + narrow_off(r0, chunk) + b8;
-    f.v[u][1] = 2 * PLANEB + narrow_off(r0 + 8, chunk) + b8;
+    f.v[u][0][0] = 2 * PLANEB + narrow_off(r0, chunk) + b8;
+    f.v[u][0][1] = 2 * PLANEB + narrow_off(r0 + 8, chunk) + b8;
   }
   return f;
 }
 
-// two fp32 values -> one register of two bf16 hi parts and one of two bf16 lo parts
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-template <bool PL>
-__device__ __forceinline__ void split_pair(float x0, float x1, uint32_t& h, uint32_t& l) {
-  const bf16x2 hp = {(__bf16)x0, (__bf16)x1};
-  h = __builtin_bit_cast(uint32_t, hp);
-  if (!PL) {
-    const float d0 = x0 - __uint_as_float(h << 16), d1 = x1 - __uint_as_float(h & 0xffff0000u);
-    const bf16x2 lp = {(__bf16)d0, (__bf16)d1};
-    l = __builtin_bit_cast(uint32_t, lp);
-  }
-}
-
 // the wave's Q fragments: row q0 + l31, columns 16 ks + 8 half + 0..7, times `pre`, split
-__device__ __forceinline__ void q_fragments(bf16x8 (&qh)[KS], bf16x8 (&ql)[KS], const float* __restrict__ qb, int q0, int len, int dk, int rs,
+__device__ __forceinline__ void q_fragments_stepwise(bf16x8 (&qh)[KS], bf16x8 (&ql)[KS], const float* __restrict__ qb, int q0, int len, int dk, int rs,
                                             float pre) {
   const int lane = threadIdx.x & 63, l31 = lane & 31, half = lane >> 5;
   const bool rok = q0 + l31 < len;
@@ -207,7 +157,7 @@ __device__ __forceinline__ void q_fragments(bf16x8 (&qh)[KS], bf16x8 (&ql)[KS], 
 // what a wave carries across the key loop for its query block
 struct Block {
   bf16x8 qh[KS], ql[KS];
-  f32x16 o;                               // O^T[d][query] in the accumulator layout
+  f32x16 o[1];                             // O^T[d][query] in the accumulator layout
   float m, l;                             // log2-domain reference and (this half's part of) the denominator of query l31
   uint32_t drow;
 };
@@ -219,23 +169,7 @@ struct Block {
 template <bool DROP, bool PL>
 __device__ __forceinline__ void key_group(const unsigned char* gs, const float* kb, bool biased, const GroupOffsets& fo, Block& w,
                                           const DropCfg& drop, int key0, int half) {
-  bf16x8 xh[KS], xl[KS];
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) {
-    xh[ks] = *reinterpret_cast<const bf16x8*>(gs + fo.k[ks]);
-    if (!PL) xl[ks] = *reinterpret_cast<const bf16x8*>(gs + fo.k[ks] + PLANEB);
-  }
-  f32x16 s;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) s[r] = 0.f;
-  if (!PL) {
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) s = LTRX_MFMA(xl[ks], w.qh[ks], s);
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) s = LTRX_MFMA(xh[ks], w.ql[ks], s);
-  }
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) s = LTRX_MFMA(xh[ks], w.qh[ks], s);
+  f32x16 s = score_chain<KS, PL>(gs, fo.k, PLANEB, w.qh, w.ql);
   if (biased) {                                     // (wave-uniform) a masked or out-of-range key in this group
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -255,7 +189,7 @@ __device__ __forceinline__ void key_group(const unsigned char* gs, const float* 
     const float alpha = grow ? fast_exp2(w.m - mref) : 1.0f;
     w.l *= alpha;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) w.o[r] *= alpha;
+    for (int r = 0; r < 16; ++r) w.o[0][r] *= alpha;
   }
   w.m = mn;
   f32x16 p;
@@ -272,36 +206,14 @@ __device__ __forceinline__ void key_group(const unsigned char* gs, const float* 
 #pragma unroll
     for (int r = 0; r < 16; ++r) p[r] *= drop_scale_rk(drop, w.drow, key0 + rowmap(r, half));
   }
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    u32x4 hw, lw = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      uint32_t hj, lj = 0u;
-      split_pair<PL>(p[8 * u + 2 * j], p[8 * u + 2 * j + 1], hj, lj);
-      hw[j] = hj;
-      lw[j] = lj;
-    }
-    const bf16x8 ph = __builtin_bit_cast(bf16x8, hw), pl = __builtin_bit_cast(bf16x8, lw);
-    const bf16x4 h0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(gs + fo.v[u][0]));
-    const bf16x4 h1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(gs + fo.v[u][1]));
-    const bf16x8 vh = {h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-    if (!PL) {
-      const bf16x4 l0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(gs + fo.v[u][0] + PLANEB));
-      const bf16x4 l1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(gs + fo.v[u][1] + PLANEB));
-      const bf16x8 vl = {l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
-      w.o = LTRX_MFMA(vl, ph, w.o);
-      w.o = LTRX_MFMA(vh, pl, w.o);
-    }
-    w.o = LTRX_MFMA(vh, ph, w.o);
-  }
+  value_chain<1, PL>(gs, fo.v, PLANEB, p, w.o);
 }
 
 // lane owns output row row0 + l31; register 4 g + e of out is column 8 g + 4 half + e.  Written through a wave-private 4-KB LDS
-// scratch, so that a store instruction covers 8 rows x 128 contiguous bytes (chunk c of row r at c ^ ((r >> 1) & 7), as
-// ltrx_mha_res.hip's store_rows)
-__device__ __forceinline__ void store_rows(float* __restrict__ base, int row0, int nrows, int dk, size_t rs, const f32x16& out, float scale,
-                                           f32x4* scratch) {
+// scratch: ltrx_mha_split.h's store_rows for one 32-column block, written without the block loop -- store_rows<1> compiles to a
+// different instruction order in all four kernels here (profiles/NOTES.md)
+__device__ __forceinline__ void store_rows1(float* __restrict__ base, int row0, int nrows, int dk, size_t rs, const f32x16& out, float scale,
+                                            f32x4* scratch) {
   const int lane = threadIdx.x & 63, l31 = lane & 31, half = lane >> 5;
 #pragma unroll
   for (int g = 0; g < 4; ++g)
@@ -329,7 +241,7 @@ __global__ void __launch_bounds__(NTHREAD) __attribute__((amdgpu_waves_per_eu(2,
   float* kbias = reinterpret_cast<float*>(smem + NSLOT * SLOTB);         // [slot][128]: -inf for a masked or out-of-range key, else 0
   int* kflag = reinterpret_cast<int*>(kbias + NSLOT * TKEYS);            // [slot][group]: 0 no such key, 1 some, 2 all 32
   if (DROP && drop_step) drop.seed ^= drop_step[0] * 0x9E3779B9u;
-  const Slate sl = which_slate(L, h, cu, order);
+  const Slate sl = which_slate(blockIdx.x, L, h, cu, order);
   const int len = sl.len;
   if ((int)(blockIdx.y * QBLK) >= len) return;         // whole workgroup beyond this slate (uniform: before any barrier)
   const int lane = threadIdx.x & 63, half = lane >> 5, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -342,9 +254,9 @@ __global__ void __launch_bounds__(NTHREAD) __attribute__((amdgpu_waves_per_eu(2,
   const int q0 = blockIdx.y * QBLK + wave * 32;
   const bool active = q0 < len;                        // (inactive waves still stage and take every barrier)
   Block w;
-  q_fragments(w.qh, w.ql, q + head0, q0, len, dk, rs, scale * kLog2e);      // S comes out of the MFMAs in the softmax's log2 domain
+  q_fragments_stepwise(w.qh, w.ql, q + head0, q0, len, dk, rs, scale * kLog2e);      // S comes out of the MFMAs in the softmax's log2 domain
 #pragma unroll
-  for (int r = 0; r < 16; ++r) w.o[r] = 0.f;
+  for (int r = 0; r < 16; ++r) w.o[0][r] = 0.f;
   w.m = -INFINITY;
   w.l = 0.f;
   w.drow = DROP ? drop_row_seed(drop, sl.bh, sl.Lmax, q0 + (lane & 31)) : 0u;
@@ -382,7 +294,7 @@ __global__ void __launch_bounds__(NTHREAD) __attribute__((amdgpu_waves_per_eu(2,
   f32x4* scratch = reinterpret_cast<f32x4*>(smem + (((nkt - 1) & (NSLOT - 1)) ^ 1) * SLOTB + wave * 4096);
   const float lt = sum_across_halves(w.l);
   const float inv = (lt > 0.f) ? 1.0f / lt : 0.f;
-  store_rows(o + sl.row0 * ors + (size_t)sl.head * dk, q0, len, dk, ors, w.o, inv, scratch);
+  store_rows1(o + sl.row0 * ors + (size_t)sl.head * dk, q0, len, dk, ors, w.o[0], inv, scratch);
   const int qrow = q0 + (lane & 31);
   if (half == 0 && qrow < len) lse[((size_t)sl.b * h + sl.head) * sl.Lmax + qrow] = (lt > 0.f) ? (w.m + log2f(lt)) * kLn2 : 0.f;
 }

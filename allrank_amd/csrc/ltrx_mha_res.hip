@@ -27,7 +27,7 @@
 // Softmax in the log2 domain, natural-log LSE saved, dropout on P regenerated from (seed, query row, key) -- identical
 // conventions to ltrx_mha.hip, so forward / backward kernels of the two paths are interchangeable.  Variable-length
 // (cu_seqlens) batches: slate b is rows cu[b] .. cu[b+1]-1; waves beyond the slate's length exit after the staging barrier.
-#include "ltrx_mfma.h"
+#include "ltrx_mha_split.h"
 
 using namespace ltrx;
 
@@ -39,8 +39,6 @@ constexpr int PLANE = RMAX * DK * 2;      // bytes of one bf16 plane
 constexpr size_t RES_STATS = 4 * (size_t)PLANE + 3 * RMAX * sizeof(float);   // LDS bytes of the four planes + per-row statistics (the forward: mask bias [RMAX] + 8 tile flags)
 constexpr int XROW = 64;                  // the dS workspace's row stride is a multiple of this (64 floats = 256 bytes)
 constexpr size_t dq_smem(int nw) { return 2 * (size_t)PLANE + (size_t)nw * 32 * 32 * sizeof(float); }     // dQ kernel: 80 KB with 4 waves (two workgroups per CU)
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kLn2 = 0.6931471805599453f;
 
 
 // byte offset of 16-byte chunk `chunk` (8 columns) of row `row` inside a plane
@@ -117,7 +115,6 @@ __device__ __forceinline__ void fixed_finish(bf16x8 (&fh)[4], bf16x8 (&fl)[4], c
   }
 }
 
-#define LTRX_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
 #ifdef LTRX_MHA_STAMP        // lab builds only (tools/lab/lib_variant.sh): cycle stamps of one workgroup of the forward kernel
 __device__ unsigned long long g_mha_stamps[8][40][8];       // (or of the dK/dV kernel with -DLTRX_MHA_STAMP_DKDV)
 #define STAMP_(kt, ph)                                                                 \
@@ -150,55 +147,12 @@ __device__ unsigned long long g_mha_stamps[8][40][8];       // (or of the dK/dV 
 struct ColFrags {
   bf16x8 h[2][2], l[2][2];          // [u][ct]
 };
-// lane owns output row row0 + l31; register 4g + e of out[ct] is column 32 ct + 8 g + 4 half + e.  Written through a wave-private
-// 4-KB LDS scratch, one [32 rows][32 columns] half at a time, so that a store instruction covers 8 rows x 128 contiguous bytes
-// instead of 64 lanes x 16 bytes in 32 different rows (the texture-address unit pays per line: 64 instead of 512 line writes per
-// wave and tensor; round 3).  Scratch layout = the dS exchange of the dQ kernel: chunk c of row r at c ^ ((r >> 1) & 7).
-__device__ __forceinline__ void store_rows(float* __restrict__ base, int row0, int nrows, int dk, size_t rs, const f32x16 (&out)[2],
-                                           float scale, f32x4* scratch) {
-  const int lane = threadIdx.x & 63, l31 = lane & 31, half = lane >> 5;
-#pragma unroll
-  for (int ct = 0; ct < 2; ++ct) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-      scratch[l31 * 8 + ((2 * g + half) ^ ((l31 >> 1) & 7))] =
-          f32x4{out[ct][4 * g + 0] * scale, out[ct][4 * g + 1] * scale, out[ct][4 * g + 2] * scale, out[ct][4 * g + 3] * scale};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int r = (lane >> 3) + 8 * j, c = 32 * ct + 4 * (lane & 7);
-      const f32x4 v = scratch[r * 8 + ((lane & 7) ^ ((r >> 1) & 7))];
-      if (row0 + r < nrows && c < dk) *reinterpret_cast<f32x4*>(base + (size_t)(row0 + r) * rs + c) = v;
-    }
-  }
-}
 // a wave-private 4-KB scratch inside the image planes once the wave has left its tile loop: only the LAST tile's ring slot can
 // still be read by a slower wave (every earlier tile lies behind a barrier this wave has passed), so the half of planes 0 / 1
 // (16 KB each = 8 waves x 4 KB) that does not hold that slot is free
 __device__ __forceinline__ f32x4* end_scratch(unsigned char* smem, int last_tile, int wave) {
   const size_t half_off = (((last_tile & 7) >= 4) ? 0 : PLANE / 2);
   return reinterpret_cast<f32x4*>(smem + (size_t)(wave >> 2) * PLANE + half_off + (size_t)(wave & 3) * 4096);
-}
-
-__device__ __forceinline__ void zero2(f32x16 (&o)[2]) {
-#pragma unroll
-  for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[ct][r] = 0.f;
-}
-
-struct Slate {
-  int b, head, bh, Lmax, len;
-  size_t row0;
-};
-__device__ __forceinline__ Slate which_slate(int L, int h, const int* __restrict__ cu, const int* __restrict__ order) {
-  Slate s;
-  s.head = blockIdx.x % h;
-  s.b = order ? order[blockIdx.x / h] : (int)(blockIdx.x / h);
-  s.bh = s.b * h + s.head;
-  s.Lmax = L;
-  s.row0 = cu ? (size_t)cu[s.b] : (size_t)s.b * L;
-  s.len = cu ? cu[s.b + 1] - cu[s.b] : L;
-  return s;
 }
 
 // The workgroup that will take this CU's place is (about) blockIdx.x + 256 -- one workgroup per CU, 256 CUs, workgroup ids dealt
@@ -262,33 +216,6 @@ __device__ __forceinline__ bool next_slate(int L, int h, const int* __restrict__
 //   * packed fp32 arithmetic (v_pk_add_f32) for S - m, the row sum and the lo part of the P split.
 // The result differs from round 5's kernel in rounding only (summation order of S, reference of the softmax).
 // ------------------------------------------------------------------------------------------------------------------
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-constexpr float kLazyTau = 8.0f;
-__device__ __forceinline__ float max_across_halves(float x) {     // lane i <-> lane i ^ 32: {lo, lo} and {hi, hi} after the swap
-  const unsigned u = __float_as_uint(x);
-  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float sum_across_halves(float x) {
-  const unsigned u = __float_as_uint(x);
-  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-// two fp32 values -> one register of two bf16 hi parts and one of two bf16 lo parts (x = hi + lo to 2^-17 relative): ONE conversion
-// per pair and part, the hi parts widened back with a shift / a mask, the subtraction packed -- 5 instructions per pair
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-template <bool PL>
-__device__ __forceinline__ void split_pair(float x0, float x1, uint32_t& h, uint32_t& l) {
-  const bf16x2 hp = {(__bf16)x0, (__bf16)x1};
-  h = __builtin_bit_cast(uint32_t, hp);
-  if (!PL) {
-    const f32x2 hf = {__uint_as_float(h << 16), __uint_as_float(h & 0xffff0000u)};
-    const f32x2 d = f32x2{x0, x1} - hf;
-    const bf16x2 lp = {(__bf16)d[0], (__bf16)d[1]};
-    l = __builtin_bit_cast(uint32_t, lp);
-  }
-}
 struct TileOffsets {
   int k[4];       // K fragments: byte offset of chunk 2 ks + half of row l31 inside a 32-row tile of the K hi plane (lo plane: + PLANE)
   int v[2][2][2]; // V transposed reads [u][ct][0 / 1]: byte offsets inside a 32-row tile, relative to the V hi plane
@@ -314,24 +241,7 @@ __device__ __forceinline__ TileOffsets tile_offsets() {     // (the same for eve
 // S^T[key = rowmap(r, half)][query = l31] of one tile in one accumulator; `tile` = LDS byte address of the tile's first row in the K hi plane
 template <bool PL>
 __device__ __forceinline__ f32x16 rows_mma(const unsigned char* tile, const TileOffsets& fo, const bf16x8 (&fh)[4], const bf16x8 (&fl)[4]) {
-  bf16x8 xh[4], xl[4];
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) {
-    xh[ks] = *reinterpret_cast<const bf16x8*>(tile + fo.k[ks]);
-    if (!PL) xl[ks] = *reinterpret_cast<const bf16x8*>(tile + fo.k[ks] + PLANE);
-  }
-  f32x16 a;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) a[r] = 0.f;
-  if (!PL) {
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) a = LTRX_MFMA(xl[ks], fh[ks], a);
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) a = LTRX_MFMA(xh[ks], fl[ks], a);
-  }
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) a = LTRX_MFMA(xh[ks], fh[ks], a);
-  return a;
+  return score_chain<4, PL>(tile, fo.k, PLANE, fh, fl);
 }
 // O^T += V^T P^T of one tile; `tile` = LDS byte address of the tile's first row in the V hi plane
 template <bool PL>
@@ -357,7 +267,7 @@ __device__ __forceinline__ void cols_mma(const unsigned char* tile, const TileOf
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       uint32_t hj, lj = 0u;
-      split_pair<PL>(p[8 * u + 2 * j], p[8 * u + 2 * j + 1], hj, lj);
+      split_pair_packed<PL>(p[8 * u + 2 * j], p[8 * u + 2 * j + 1], hj, lj);
       hw[j] = hj;
       lw[j] = lj;
     }
@@ -394,7 +304,7 @@ __global__ void __launch_bounds__(512) ltrx_mha_fwd_res_kernel(const float* __re
   int* kflag = reinterpret_cast<int*>(kbias + RMAX);           // per ring slot: does the tile hold a masked / out-of-range key?
   Touch tch = {{0.f, 0.f}};
   if (DROP && drop_step) drop.seed ^= drop_step[0] * 0x9E3779B9u;
-  const Slate sl = which_slate(L, h, cu, order);
+  const Slate sl = which_slate(blockIdx.x, L, h, cu, order);
   const int lane = threadIdx.x & 63, half = lane >> 5, wave = threadIdx.x >> 6;
   const int len = sl.len;
   const float* qb = q + sl.row0 * rs + (size_t)sl.head * dk;
@@ -419,7 +329,7 @@ __global__ void __launch_bounds__(512) ltrx_mha_fwd_res_kernel(const float* __re
   const TileOffsets fo = tile_offsets();
   if (LTRX_MHA_PRIO_HALF && __builtin_amdgcn_readfirstlane(wave) >= 4) __builtin_amdgcn_s_setprio(1);
   f32x16 oacc[2];
-  zero2(oacc);
+  zero_acc<2>(oacc);
   float m = -INFINITY, l = 0.f;
   const uint32_t drow = DROP ? drop_row_seed(drop, sl.bh, sl.Lmax, q0 + (lane & 31)) : 0u;
   const int nkt = (len + 31) / 32;
@@ -506,7 +416,7 @@ __global__ void __launch_bounds__(512) ltrx_mha_fwd_res_kernel(const float* __re
   }
   const float lt = sum_across_halves(l);
   const float inv = (lt > 0.f) ? 1.0f / lt : 0.f;
-  store_rows(o + sl.row0 * ors + (size_t)sl.head * dk, q0, len, dk, ors, oacc, inv, end_scratch(smem, nkt - 1, wave));
+  store_rows<2>(o + sl.row0 * ors + (size_t)sl.head * dk, q0, len, dk, ors, oacc, inv, end_scratch(smem, nkt - 1, wave));
   const int qrow = q0 + (lane & 31);
   if (half == 0 && qrow < len) lse[((size_t)sl.b * h + sl.head) * sl.Lmax + qrow] = (lt > 0.f) ? (m + log2f(lt)) * kLn2 : 0.f;
   STAMP(34, 0);
@@ -541,7 +451,7 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2,
                                                                   const int* __restrict__ cu, const int* __restrict__ order) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* kimg = smem;
-  const Slate sl = which_slate(L, h, cu, order);
+  const Slate sl = which_slate(blockIdx.x, L, h, cu, order);
   const int lane = threadIdx.x & 63, half = lane >> 5, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), l31 = lane & 31;
   f32x4* xs = reinterpret_cast<f32x4*>(smem + 2 * PLANE) + wave * (32 * 32 / 4);
   const int len = sl.len;
@@ -564,7 +474,7 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2,
       if (s < nkt) ds_gload(dr[s], rows, s, LK);
   }
   f32x16 dqacc[2];
-  zero2(dqacc);
+  zero_acc<2>(dqacc);
   const TileOffsets fo = tile_offsets();
   for (int c = 0; c < nchunk; ++c) {
     if (c > 0) lds_only_barrier();                     // every wave is done with the previous chunk of K
@@ -600,7 +510,7 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2,
     }
   }
   if (!active) return;
-  store_rows(dq + sl.row0 * drs + (size_t)sl.head * dk, q0, len, dk, drs, dqacc, 1.0f, xs);      // (xs: this wave's dS exchange area)
+  store_rows<2>(dq + sl.row0 * drs + (size_t)sl.head * dk, q0, len, dk, drs, dqacc, 1.0f, xs);      // (xs: this wave's dS exchange area)
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -633,7 +543,7 @@ __global__ void __launch_bounds__(512) ltrx_mha_bwd_dkdv_res_kernel(
   float* del_t = lse_t + RMAX;
   uint32_t* drow_t = reinterpret_cast<uint32_t*>(del_t + RMAX);
   if (DROP && drop_step) drop.seed ^= drop_step[0] * 0x9E3779B9u;
-  const Slate sl = which_slate(L, h, cu, order);
+  const Slate sl = which_slate(blockIdx.x, L, h, cu, order);
   // (wave index in a scalar register: `active` below must be a SCALAR branch -- as a divergent one both sides run under exec
   //  masks and the tile loads of the inactive side make the active side wait vmcnt(0) before its own)
   const int lane = threadIdx.x & 63, half = lane >> 5, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -674,8 +584,8 @@ __global__ void __launch_bounds__(512) ltrx_mha_bwd_dkdv_res_kernel(
   const f32x2 kb2 = {kbias, kbias};
   const TileOffsets fo = tile_offsets();
   f32x16 dkacc[2], dvacc[2];
-  zero2(dkacc);
-  zero2(dvacc);
+  zero_acc<2>(dkacc);
+  zero_acc<2>(dvacc);
   const int nqt = (len + 31) / 32;
   if (LTRX_MHA_PRIO_HALF && wave >= 4) __builtin_amdgcn_s_setprio(1);
   // dS tile addressing: a wave-uniform base (scalar registers) + ONE 32-bit per-lane offset, so that the 16 stores of a tile cost
@@ -773,8 +683,8 @@ __global__ void __launch_bounds__(512) ltrx_mha_bwd_dkdv_res_kernel(
   DSTAMP(33, 0);
   if (!active) return;
   f32x4* const es = end_scratch(smem, nqt - 1, wave);
-  store_rows(dkout + sl.row0 * drs + (size_t)sl.head * dk, k0, len, dk, drs, dkacc, 1.0f, es);
-  store_rows(dvout + sl.row0 * drs + (size_t)sl.head * dk, k0, len, dk, drs, dvacc, 1.0f, es);
+  store_rows<2>(dkout + sl.row0 * drs + (size_t)sl.head * dk, k0, len, dk, drs, dkacc, 1.0f, es);
+  store_rows<2>(dvout + sl.row0 * drs + (size_t)sl.head * dk, k0, len, dk, drs, dvacc, 1.0f, es);
   DSTAMP(34, 0);
 }
 

@@ -71,7 +71,7 @@
 //     forward's as well.  The 32-entry statistics of a slot are read as the forward reads kbias (b128, two addresses per wave).
 //   * barriers: every wave takes every barrier, a wave beyond the slate keeps staging, the only early return is the workgroup-uniform
 //     one before the first barrier, and no thread reads a row at or beyond the slate's length (statistics included).
-#include "ltrx_mfma.h"
+#include "ltrx_mha_split.h"
 
 using namespace ltrx;
 
@@ -81,9 +81,6 @@ constexpr int NWAVE = 4;                  // waves of a workgroup
 constexpr int QBLK = 32 * NWAVE;          // queries of a workgroup
 constexpr int NTHREAD = 64 * NWAVE;
 constexpr int NSLOT = 2;                  // tile slots of the ring
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kLn2 = 0.6931471805599453f;
-constexpr float kLazyTau = 8.0f;          // ltrx_mha_res.hip's: a query's reference moves when a tile exceeds it by 2^8
 
 template <int DKP>
 struct Geo {
@@ -105,34 +102,6 @@ __device__ __forceinline__ int wide_off(int row, int chunk) {
   const int s = (DKP == 128) ? (((row & 3) << 2) | ((row >> 2) & 3)) : ((row >> 2) & 3);
   return row * (DKP * 2) + ((chunk ^ s) << 4);
 }
-
-struct Slate {
-  int b, head, bh, Lmax, len;
-  size_t row0;
-};
-__device__ __forceinline__ Slate which_slate(int L, int h, const int* __restrict__ cu, const int* __restrict__ order) {
-  Slate s;
-  s.head = blockIdx.x % h;
-  s.b = order ? order[blockIdx.x / h] : (int)(blockIdx.x / h);
-  s.bh = s.b * h + s.head;
-  s.Lmax = L;
-  s.row0 = cu ? (size_t)cu[s.b] : (size_t)s.b * L;
-  s.len = cu ? cu[s.b + 1] - cu[s.b] : L;
-  return s;
-}
-
-__device__ __forceinline__ float max_across_halves(float x) {     // lane i <-> lane i ^ 32
-  const unsigned u = __float_as_uint(x);
-  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float sum_across_halves(float x) {
-  const unsigned u = __float_as_uint(x);
-  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
-#define LTRX_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
 
 // the tile-invariant part of a thread's staging work: position i = threadIdx.x + 256 j of the 64 CH positions of a tile, K's
 // 32 CH first, then V's
@@ -176,14 +145,38 @@ template <int DKP, bool PL>
 __device__ __forceinline__ void stager_sstore(const Stager<DKP>& st, unsigned char* slot) {
 #pragma unroll
   for (int j = 0; j < Geo<DKP>::NPOS; ++j) {
-    const float x[8] = {st.a[j].x, st.a[j].y, st.a[j].z, st.a[j].w, st.b[j].x, st.b[j].y, st.b[j].z, st.b[j].w};
     bf16x8 h, l;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      LTRX_SPLIT_BF16(x[e], h[e], l[e]);
-    }
+    split8(st.a[j], st.b[j], h, l);
     *reinterpret_cast<bf16x8*>(slot + st.dst[j]) = h;
     if (!PL) *reinterpret_cast<bf16x8*>(slot + st.dst[j] + Geo<DKP>::TILEB) = l;
+  }
+}
+
+// a wave's fixed-operand fragments read straight from memory: row r0 + l31, columns 16 ks + 8 half + 0..7, times `pre`, split.
+// Every load is issued before the first split.
+template <int KS>
+__device__ __forceinline__ void q_fragments(bf16x8 (&qh)[KS], bf16x8 (&ql)[KS], const float* __restrict__ qb, int q0, int len, int dk, int rs,
+                                            float pre) {
+  const int lane = threadIdx.x & 63, l31 = lane & 31, half = lane >> 5;
+  const bool rok = q0 + l31 < len;
+  const float* rowp = qb + (size_t)(rok ? q0 + l31 : 0) * rs;                  // (row 0 exists)
+  f32x4 a[KS], b[KS];
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
+    const int c = 16 * ks + 8 * half;
+    const bool oa = rok && c < dk, ob = rok && c + 4 < dk;
+    const f32x4 va = *reinterpret_cast<const f32x4*>(rowp + (oa ? c : 0));
+    const f32x4 vb = *reinterpret_cast<const f32x4*>(rowp + (ob ? c + 4 : 0));
+    a[ks] = oa ? va : f32x4{0.f, 0.f, 0.f, 0.f};
+    b[ks] = ob ? vb : f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
+    const float x[8] = {a[ks][0] * pre, a[ks][1] * pre, a[ks][2] * pre, a[ks][3] * pre, b[ks][0] * pre, b[ks][1] * pre, b[ks][2] * pre, b[ks][3] * pre};
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      LTRX_SPLIT_BF16(x[e], qh[ks][e], ql[ks][e]);
+    }
   }
 }
 
@@ -212,70 +205,11 @@ __device__ __forceinline__ TileOffsets<DKP> tile_offsets() {
   return f;
 }
 
-// two fp32 values -> one register of two bf16 hi parts and one of two bf16 lo parts
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-template <bool PL>
-__device__ __forceinline__ void split_pair(float x0, float x1, uint32_t& h, uint32_t& l) {
-  const bf16x2 hp = {(__bf16)x0, (__bf16)x1};
-  h = __builtin_bit_cast(uint32_t, hp);
-  if (!PL) {
-    const float d0 = x0 - __uint_as_float(h << 16), d1 = x1 - __uint_as_float(h & 0xffff0000u);
-    const bf16x2 lp = {(__bf16)d0, (__bf16)d1};
-    l = __builtin_bit_cast(uint32_t, lp);
-  }
-}
-
-// the wave's Q fragments: row q0 + l31, columns 16 ks + 8 half + 0..7, times `pre`, split
-template <int DKP>
-__device__ __forceinline__ void q_fragments(bf16x8 (&qh)[Geo<DKP>::KS], bf16x8 (&ql)[Geo<DKP>::KS], const float* __restrict__ qb, int q0, int len,
-                                            int dk, int rs, float pre) {
-  const int lane = threadIdx.x & 63, l31 = lane & 31, half = lane >> 5;
-  const bool rok = q0 + l31 < len;
-  const float* rowp = qb + (size_t)(rok ? q0 + l31 : 0) * rs;                  // (row 0 exists)
-  f32x4 a[Geo<DKP>::KS], b[Geo<DKP>::KS];
-#pragma unroll
-  for (int ks = 0; ks < Geo<DKP>::KS; ++ks) {                                  // every load is issued before the first split
-    const int c = 16 * ks + 8 * half;
-    const bool oa = rok && c < dk, ob = rok && c + 4 < dk;
-    const f32x4 va = *reinterpret_cast<const f32x4*>(rowp + (oa ? c : 0));
-    const f32x4 vb = *reinterpret_cast<const f32x4*>(rowp + (ob ? c + 4 : 0));
-    a[ks] = oa ? va : f32x4{0.f, 0.f, 0.f, 0.f};
-    b[ks] = ob ? vb : f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-#pragma unroll
-  for (int ks = 0; ks < Geo<DKP>::KS; ++ks) {
-    const float x[8] = {a[ks][0] * pre, a[ks][1] * pre, a[ks][2] * pre, a[ks][3] * pre, b[ks][0] * pre, b[ks][1] * pre, b[ks][2] * pre, b[ks][3] * pre};
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      LTRX_SPLIT_BF16(x[e], qh[ks][e], ql[ks][e]);
-    }
-  }
-}
-
 // S^T[key = rowmap(r, half)][query = l31] of the tile in `slot`, in one accumulator
 template <int DKP, bool PL>
 __device__ __forceinline__ f32x16 score_tile(const unsigned char* slot, const TileOffsets<DKP>& fo, const bf16x8 (&qh)[Geo<DKP>::KS],
                                              const bf16x8 (&ql)[Geo<DKP>::KS]) {
-  using G = Geo<DKP>;
-  bf16x8 xh[G::KS], xl[G::KS];
-#pragma unroll
-  for (int ks = 0; ks < G::KS; ++ks) {
-    xh[ks] = *reinterpret_cast<const bf16x8*>(slot + fo.k[ks]);
-    if (!PL) xl[ks] = *reinterpret_cast<const bf16x8*>(slot + fo.k[ks] + G::TILEB);
-  }
-  f32x16 a;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) a[r] = 0.f;
-  if (!PL) {
-#pragma unroll
-    for (int ks = 0; ks < G::KS; ++ks) a = LTRX_MFMA(xl[ks], qh[ks], a);
-#pragma unroll
-    for (int ks = 0; ks < G::KS; ++ks) a = LTRX_MFMA(xh[ks], ql[ks], a);
-  }
-#pragma unroll
-  for (int ks = 0; ks < G::KS; ++ks) a = LTRX_MFMA(xh[ks], qh[ks], a);
-  return a;
+  return score_chain<Geo<DKP>::KS, PL>(slot, fo.k, Geo<DKP>::TILEB, qh, ql);
 }
 
 // O^T[d][query] += V^T[d][key] P^T[key][query] of the tile in `slot` (p in D layout: register r <-> key rowmap(r, half)).  The A
@@ -283,55 +217,7 @@ __device__ __forceinline__ f32x16 score_tile(const unsigned char* slot, const Ti
 // 8 u .. 8 u + 7 hold -- comes from two transposed reads of the row-major image: P never moves between lanes.
 template <int DKP, bool PL>
 __device__ __forceinline__ void value_tile(const unsigned char* slot, const TileOffsets<DKP>& fo, const f32x16& p, f32x16 (&out)[Geo<DKP>::NCT]) {
-  using G = Geo<DKP>;
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    u32x4 hw, lw = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      uint32_t hj, lj = 0u;
-      split_pair<PL>(p[8 * u + 2 * j], p[8 * u + 2 * j + 1], hj, lj);
-      hw[j] = hj;
-      lw[j] = lj;
-    }
-    const bf16x8 ph = __builtin_bit_cast(bf16x8, hw), pl = __builtin_bit_cast(bf16x8, lw);
-#pragma unroll
-    for (int ct = 0; ct < G::NCT; ++ct) {
-      const bf16x4 h0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(slot + fo.v[u][ct][0]));
-      const bf16x4 h1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(slot + fo.v[u][ct][1]));
-      const bf16x8 vh = {h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-      if (!PL) {
-        const bf16x4 l0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(slot + fo.v[u][ct][0] + G::TILEB));
-        const bf16x4 l1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(slot + fo.v[u][ct][1] + G::TILEB));
-        const bf16x8 vl = {l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
-        out[ct] = LTRX_MFMA(vl, ph, out[ct]);
-        out[ct] = LTRX_MFMA(vh, pl, out[ct]);
-      }
-      out[ct] = LTRX_MFMA(vh, ph, out[ct]);
-    }
-  }
-}
-
-// lane owns output row row0 + l31; register 4 g + e of out[ct] is column 32 ct + 8 g + 4 half + e.  Written through a wave-private
-// 4-KB LDS scratch one [32 rows][32 columns] block at a time, so that a store instruction covers 8 rows x 128 contiguous bytes
-// (chunk c of row r at c ^ ((r >> 1) & 7), as ltrx_mha_res.hip's store_rows)
-template <int NCT>
-__device__ __forceinline__ void store_rows(float* __restrict__ base, int row0, int nrows, int dk, size_t rs, const f32x16 (&out)[NCT], float scale,
-                                           f32x4* scratch) {
-  const int lane = threadIdx.x & 63, l31 = lane & 31, half = lane >> 5;
-#pragma unroll
-  for (int ct = 0; ct < NCT; ++ct) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-      scratch[l31 * 8 + ((2 * g + half) ^ ((l31 >> 1) & 7))] =
-          f32x4{out[ct][4 * g + 0] * scale, out[ct][4 * g + 1] * scale, out[ct][4 * g + 2] * scale, out[ct][4 * g + 3] * scale};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int r = (lane >> 3) + 8 * j, c = 32 * ct + 4 * (lane & 7);
-      const f32x4 v = scratch[r * 8 + ((lane & 7) ^ ((r >> 1) & 7))];
-      if (row0 + r < nrows && c < dk) *reinterpret_cast<f32x4*>(base + (size_t)(row0 + r) * rs + c) = v;
-    }
-  }
+  value_chain<Geo<DKP>::NCT, PL>(slot, fo.v, Geo<DKP>::TILEB, p, out);
 }
 
 }  // namespace
@@ -350,7 +236,7 @@ __global__ void __launch_bounds__(NTHREAD) __attribute__((amdgpu_waves_per_eu(Ge
   float* kbias = reinterpret_cast<float*>(smem + NSLOT * G::SLOTB);      // [slot][32]: -inf for a masked or out-of-range key, else 0
   int* kflag = reinterpret_cast<int*>(kbias + NSLOT * 32);               // [slot]: does the tile hold such a key?
   if (DROP && drop_step) drop.seed ^= drop_step[0] * 0x9E3779B9u;
-  const Slate sl = which_slate(L, h, cu, order);
+  const Slate sl = which_slate(blockIdx.x, L, h, cu, order);
   const int len = sl.len;
   if ((int)(blockIdx.y * QBLK) >= len) return;         // whole workgroup beyond this slate (uniform: before any barrier)
   const int lane = threadIdx.x & 63, half = lane >> 5, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -363,7 +249,7 @@ __global__ void __launch_bounds__(NTHREAD) __attribute__((amdgpu_waves_per_eu(Ge
   const int q0 = blockIdx.y * QBLK + wave * 32;
   const bool active = q0 < len;                        // (inactive waves still stage and take every barrier)
   bf16x8 qh[G::KS], ql[G::KS];
-  q_fragments<DKP>(qh, ql, q + head0, q0, len, dk, rs, scale * kLog2e);      // S comes out of the MFMAs in the softmax's log2 domain
+  q_fragments<G::KS>(qh, ql, q + head0, q0, len, dk, rs, scale * kLog2e);      // S comes out of the MFMAs in the softmax's log2 domain
   const TileOffsets<DKP> fo = tile_offsets<DKP>();
   f32x16 oacc[G::NCT];
 #pragma unroll
@@ -508,14 +394,6 @@ __device__ __forceinline__ float do_fragments(bf16x8 (&dh)[Geo<DKP>::KS], bf16x8
   return sum_across_halves(del);
 }
 
-template <int NCT>
-__device__ __forceinline__ void zero_acc(f32x16 (&acc)[NCT]) {
-#pragma unroll
-  for (int ct = 0; ct < NCT; ++ct)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[ct][r] = 0.f;
-}
-
 // two score_tile()s at once, for the kernel that has no registers to spare: X[row][fixed] of the plane pair at `xs` against (xfh, xfl)
 // and of the pair at `ys` against (yfh, yfl).  The streamed fragments are fetched one 16-column step at a time -- 16 registers in
 // flight instead of score_tile's 4 KS per product -- and the two accumulator chains alternate.
@@ -557,7 +435,7 @@ __global__ void __launch_bounds__(NTHREAD) __attribute__((amdgpu_waves_per_eu(1,
   float* kbias = reinterpret_cast<float*>(smem + NSLOT * G::SLOTB);      // [slot][32]: -inf for a masked or out-of-range key, else 0
   int* kflag = reinterpret_cast<int*>(kbias + NSLOT * 32);               // [slot]: does the tile hold such a key?
   if (DROP && drop_step) drop.seed ^= drop_step[0] * 0x9E3779B9u;
-  const Slate sl = which_slate(L, h, cu, order);
+  const Slate sl = which_slate(blockIdx.x, L, h, cu, order);
   const int len = sl.len;
   if ((int)(blockIdx.y * QBLK) >= len) return;         // whole workgroup beyond this slate (uniform: before any barrier)
   const int lane = threadIdx.x & 63, half = lane >> 5, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -570,7 +448,7 @@ __global__ void __launch_bounds__(NTHREAD) __attribute__((amdgpu_waves_per_eu(1,
   const int q0 = blockIdx.y * QBLK + wave * 32;
   const bool active = q0 < len;                        // (inactive waves still stage and take every barrier)
   bf16x8 qh[G::KS], ql[G::KS], dh[G::KS], dl[G::KS];
-  q_fragments<DKP>(qh, ql, q + head0, q0, len, dk, rs, scale * kLog2e);
+  q_fragments<G::KS>(qh, ql, q + head0, q0, len, dk, rs, scale * kLog2e);
   const float del_q = do_fragments<DKP>(dh, dl, dout + ohead0, o + ohead0, q0, len, dk, ors);
   const int qrow = q0 + (lane & 31);
   const size_t stat = (size_t)sl.bh * sl.Lmax + qrow;
@@ -634,7 +512,7 @@ __global__ void __launch_bounds__(NTHREAD) __attribute__((amdgpu_waves_per_eu(1,
   float* del_t = lse_t + NSLOT * 32;                                     // [slot][32]: delta
   uint32_t* seed_t = reinterpret_cast<uint32_t*>(del_t + NSLOT * 32);    // [slot][32]: dropout row seed (DROP)
   if (DROP && drop_step) drop.seed ^= drop_step[0] * 0x9E3779B9u;
-  const Slate sl = which_slate(L, h, cu, order);
+  const Slate sl = which_slate(blockIdx.x, L, h, cu, order);
   const int len = sl.len;
   if ((int)(blockIdx.y * QBLK) >= len) return;         // whole workgroup beyond this slate (uniform: before any barrier)
   const int lane = threadIdx.x & 63, half = lane >> 5, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -651,8 +529,8 @@ __global__ void __launch_bounds__(NTHREAD) __attribute__((amdgpu_waves_per_eu(1,
   const int k0 = blockIdx.y * QBLK + wave * 32;
   const bool active = k0 < len;                        // (inactive waves still stage and take every barrier)
   bf16x8 kh[G::KS], kl[G::KS], vh[G::KS], vl[G::KS];
-  q_fragments<DKP>(kh, kl, k + head0, k0, len, dk, rs, scale * kLog2e);
-  q_fragments<DKP>(vh, vl, v + head0, k0, len, dk, rs, 1.0f);
+  q_fragments<G::KS>(kh, kl, k + head0, k0, len, dk, rs, scale * kLog2e);
+  q_fragments<G::KS>(vh, vl, v + head0, k0, len, dk, rs, 1.0f);
   const int key = k0 + (lane & 31);
   const float kbias = (key >= len || (kpm && kpm[sl.row0 + key])) ? -INFINITY : 0.f;
   const TileOffsets<DKP> fo = tile_offsets<DKP>();

@@ -23,6 +23,21 @@ from .rows import row_bucket, _stage_host, _Stager  # noqa: F401  (their home is
 
 PADDED_Y_VALUE = -1
 
+# The opt-in attention arms, one row each.  ``option`` is the keyword of FusedTrainer / fit() / inference.Ranker, the attribute of the
+# trainer and the key of ``meta()`` (present only when on); ``env`` the variable fit() reads when the keyword is None; ``direction``
+# the pass the arm replaces and ``arm`` what ``attention_forward`` / ``attention_backward`` then say; ``fits`` the _lib predicate over
+# (L, head width) and ``call`` the kernels.py call that runs it; ``what`` the description in error messages.  Where two rows of one
+# direction fit, the earlier wins (wide over narrow; their head widths are disjoint).
+AttentionArm = collections.namedtuple("AttentionArm", "option env direction arm fits call what")
+ATTENTION_ARMS = (
+    AttentionArm("wide_heads", "ALLRANK_AMD_WIDE_HEADS", "forward", "wide", "mha_wide_fits", KN.mha_fwd_wide,
+                 "the split-bf16 attention forward for head widths 65..128"),
+    AttentionArm("wide_backward", "ALLRANK_AMD_WIDE_BACKWARD", "backward", "wide", "mha_wide_fits", KN.mha_bwd_wide,
+                 "the split-bf16 attention backward for head widths 65..128"),
+    AttentionArm("narrow_heads", "ALLRANK_AMD_NARROW_HEADS", "forward", "narrow", "mha_narrow_fits", KN.mha_fwd_narrow,
+                 "the split-bf16 attention forward for head widths up to 32"),
+)
+
 # The step's operands, made once by FusedTrainer.__init__ (the flat buffers are never rebound, so a view or an address stays right):
 #   Param  one per nn.Parameter, ``FusedTrainer.params`` in flat-buffer order: its name, the parameter, its offset, and the views of
 #          flat_p / flat_g shaped like it;
@@ -474,9 +489,9 @@ class FusedTrainer(object):
         # attention arithmetic of THIS trainer, passed with every ltrx_mha_fwd / ltrx_mha_bwd call (the library keeps no mode):
         # 1 = three bf16 products (fp32-class, parity), 2 = one product (the "bf16" throughput mode)
         self._mha_mode = 2 if gemm == "bf16" else 1
-        self.wide_heads = bool(wide_heads)
-        self.wide_backward = bool(wide_backward)
-        self.narrow_heads = bool(narrow_heads)
+        given = locals()
+        for arm in ATTENTION_ARMS:            # self.wide_heads, self.wide_backward, self.narrow_heads
+            setattr(self, arm.option, bool(given[arm.option]))
         self.model = model
         self.B, self.L, self.M = B, L, B * L
         self.lr, self.betas, self.eps = lr, betas, eps
@@ -806,8 +821,8 @@ class FusedTrainer(object):
             # deferred parameter-gradient partials of up to three LayerNorm backwards per encoder layer (_reduce_flush)
             self.ws_ln_g = [self.ws_ln] + [torch.empty_like(self.ws_ln) for _ in range(2)]
             self.ws_mha = KN.mha_bwd_workspace(self.lib, B, L, self.h, d // self.h, self._mha_mode, self.d_o)
-        self.attention_forward = "wide" if self._wide_fits(L) else ("narrow" if self._narrow_fits(L) else "default")
-        self.attention_backward = "wide" if self._wide_bwd_fits(L) else "default"
+        self.attention_forward = getattr(self._attention_arm("forward", L), "arm", "default")
+        self.attention_backward = getattr(self._attention_arm("backward", L), "arm", "default")
         no = self.n_out
         if compact:
             self.dsc_c = torch.zeros(M if no == 1 else (M, no), **f32)
@@ -1158,17 +1173,15 @@ class FusedTrainer(object):
         KN.reduce_group(self.lib, self._st(), q)
         q.clear()
 
-    def _wide_fits(self, L):
-        """does the attention forward of slates up to ``L`` items run ltrx_mha_fwd_wide?  (``wide_heads``; the head width decides)"""
-        return bool(self.wide_heads and self.N and self._mha_mode != 0 and self.LB.mha_wide_fits(L, self.d // self.h))
-
-    def _narrow_fits(self, L):
-        """does the attention forward of slates up to ``L`` items run ltrx_mha_fwd_narrow?  (``narrow_heads``; the head width decides)"""
-        return bool(self.narrow_heads and self.N and self._mha_mode != 0 and self.LB.mha_narrow_fits(L, self.d // self.h))
-
-    def _wide_bwd_fits(self, L):
-        """does the attention backward of slates up to ``L`` items run ltrx_mha_bwd_wide?  (``wide_backward``; the head width decides)"""
-        return bool(self.wide_backward and self.N and self._mha_mode != 0 and self.LB.mha_wide_fits(L, self.d // self.h))
+    def _attention_arm(self, direction, L):
+        """the row of ATTENTION_ARMS whose kernel runs the attention ``direction`` ("forward" / "backward") of slates up to ``L`` items,
+        or None for the default kernels: the first row of that direction that is switched on and whose head width and L fit"""
+        if not self.N or self._mha_mode == 0:
+            return None
+        for arm in ATTENTION_ARMS:
+            if arm.direction == direction and getattr(self, arm.option) and getattr(self.LB, arm.fits)(L, self.d // self.h):
+                return arm
+        return None
 
     # ---- the step body (capturable) ----------------------------------------------------------------------------
     def _forward(self, train=True, bs=None):
@@ -1180,7 +1193,7 @@ class FusedTrainer(object):
         stream = self._st()                                       # (of the row movers: the pass stays on one stream)
         kpm = bs.mask if bs.layout == "grid" else None            # packed rows are all valid keys
         dp = (lambda p: p) if train else (lambda p: 0.0)          # dropout rate of a site in this pass
-        mha_fwd = KN.mha_fwd_wide if self._wide_fits(L) else (KN.mha_fwd_narrow if self._narrow_fits(L) else KN.mha_fwd)
+        mha_fwd = getattr(self._attention_arm("forward", L), "call", KN.mha_fwd)
         h = bs.x_in
         nm = self.norm_in
         if nm is not None and self._x_pad:                        # ... into the first F columns of the padded operand rows
@@ -1288,7 +1301,7 @@ class FusedTrainer(object):
             if not self.norm_head:
                 self._ln_bwd(ga, self.xsum_f, nf, self.mean_f, self.rstd_f, None, gb)
             ds = gb                                               # d loss / d (x1_last + ffn_last)
-            mha_bwd = KN.mha_bwd_wide if self._wide_bwd_fits(L) else KN.mha_bwd
+            mha_bwd = getattr(self._attention_arm("backward", L), "call", KN.mha_bwd)
             other = ga
             for i in range(self.N - 1, -1, -1):
                 st = self.layers[i]
@@ -1416,12 +1429,9 @@ class FusedTrainer(object):
         from . import checkpoint as CK
         meta = CK.make_meta([(r.name, r.p) for r in self._params_named], self.optimizer, self._hyper(), self.loss.name, self._loss_args,
                             self.clip)
-        if self.wide_heads:                   # (only when on: a run without the option writes the block it always wrote)
-            meta["wide_heads"] = True
-        if getattr(self, "wide_backward", False):
-            meta["wide_backward"] = True
-        if getattr(self, "narrow_heads", False):
-            meta["narrow_heads"] = True
+        for arm in ATTENTION_ARMS:            # (only when on: a run without the option writes the block it always wrote)
+            if getattr(self, arm.option, False):
+                meta[arm.option] = True
         return meta
 
     def state_dict(self):

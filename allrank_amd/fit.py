@@ -257,25 +257,17 @@ def _compact_mode(compact):
     return bool(compact)
 
 
-def _wide_heads_mode(wide_heads, name="ALLRANK_AMD_WIDE_HEADS"):
-    """fit()'s ``wide_heads`` argument resolved: None reads ALLRANK_AMD_WIDE_HEADS ("1" = on; unset, "" or "0" = off; anything
-    else raises), so that an unmodified main.py can opt in"""
-    if wide_heads is None:
+def _attention_option(option, value):
+    """fit()'s ``wide_heads`` / ``wide_backward`` / ``narrow_heads`` argument resolved: None reads the variable engine.ATTENTION_ARMS
+    names for ``option`` ("1" = on; unset, "" or "0" = off; anything else raises), so that an unmodified main.py can opt in"""
+    from .engine import ATTENTION_ARMS
+    name = next(arm.env for arm in ATTENTION_ARMS if arm.option == option)
+    if value is None:
         env = os.environ.get(name, "")
         if env not in ("", "0", "1"):
             raise ValueError("%s must be '1', '0' or unset, got %r" % (name, env))
         return env == "1"
-    return bool(wide_heads)
-
-
-def _wide_backward_mode(wide_backward):
-    """fit()'s ``wide_backward`` argument resolved the same way, from ALLRANK_AMD_WIDE_BACKWARD"""
-    return _wide_heads_mode(wide_backward, "ALLRANK_AMD_WIDE_BACKWARD")
-
-
-def _narrow_heads_mode(narrow_heads):
-    """fit()'s ``narrow_heads`` argument resolved the same way, from ALLRANK_AMD_NARROW_HEADS"""
-    return _wide_heads_mode(narrow_heads, "ALLRANK_AMD_NARROW_HEADS")
+    return bool(value)
 
 
 def _compact_graph_stats(trainer):
@@ -532,9 +524,9 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
     B_glob, L, valid_frac = _batch_shape(train_dl)
     lo, hi = shard_slates(B_glob, rank, world)
     compact = _compact_mode(compact)
-    wide_heads = _wide_heads_mode(wide_heads)
-    wide_backward = _wide_backward_mode(wide_backward)
-    narrow_heads = _narrow_heads_mode(narrow_heads)
+    wide_heads = _attention_option("wide_heads", wide_heads)
+    wide_backward = _attention_option("wide_backward", wide_backward)
+    narrow_heads = _attention_option("narrow_heads", narrow_heads)
     cg_reason = ""
     if spec is not None:
         if compact is None:

@@ -85,8 +85,7 @@ class Ranker(object):
         self._scorers, self._out = {}, {}
         self.head = None                                      # d_output > 1: the head the last ranked batch's scorer ran
         multi_output = globals()["multi_output"] if multi_output is None else multi_output
-        wide_heads = globals()["wide_heads"] if wide_heads is None else wide_heads
-        narrow_heads = globals()["narrow_heads"] if narrow_heads is None else narrow_heads
+        given = locals()
         try:
             p = next(model.parameters())
         except (StopIteration, AttributeError):
@@ -99,10 +98,11 @@ class Ranker(object):
             self.reason = "d_output > 1 without the multi_output option"
             return
         try:
-            from .engine import FusedTrainer
+            from .engine import ATTENTION_ARMS, FusedTrainer
             loss = ("ordinal", {"n": n_out}) if n_out > 1 else ("listNet", {})     # (the loss the engine pairs with the head; never run)
-            self.trainer = FusedTrainer(model, loss[0], loss[1], 1, 8, use_graph=False, fc_step=False, wide_heads=bool(wide_heads),
-                                        narrow_heads=bool(narrow_heads))
+            arms = {a.option: bool(globals()[a.option] if given[a.option] is None else given[a.option])      # wide_heads, narrow_heads:
+                    for a in ATTENTION_ARMS if a.direction == "forward"}                                       # ranking runs no backward
+            self.trainer = FusedTrainer(model, loss[0], loss[1], 1, 8, use_graph=False, fc_step=False, **arms)
         except NotImplementedError as e:
             self.reason = "the fused engine refuses the model: %s" % (e,)
 

@@ -55,36 +55,40 @@ def thirds(t):
     return t[..., :d], t[..., d:2 * d], t[..., 2 * d:]
 
 
-def mha_fwd(lib, st, q, k, v, kpm, B, L, h, o, lse, p, seed, drop_step, cu, order, mode):
+def mha_fwd(lib, st, q, k, v, kpm, B, L, h, o, lse, p, seed, drop_step, cu, order, mode, entry="ltrx_mha_fwd"):
+    """``entry``: ltrx_mha_fwd, or an opt-in entry point with its parameters (ltrx_mha_fwd_wide, ltrx_mha_fwd_narrow) -- the call below
+    stays the one written-out statement of all of them and then runs against a view of the library whose forward is ``entry``"""
+    if entry != "ltrx_mha_fwd":
+        lib = types.SimpleNamespace(ltrx_mha_fwd=getattr(lib, entry))
     check(lib.ltrx_mha_fwd(P(q), P(k), P(v), P(kpm), B, L, h, q.shape[-1] // h, q.stride(-2), P(o), o.stride(-2), P(lse), float(p), seed,
                            P(drop_step), P(cu), P(order), mode, st), "mha_fwd")
 
 
 def mha_fwd_wide(lib, *args):
-    """``mha_fwd`` on the opt-in split-bf16 forward for head widths 65..128.  ltrx_mha_fwd_wide has ltrx_mha_fwd's parameters, so the
-    marshalling above stays the one statement of both: it runs against a view of the library whose forward is the wide entry point."""
-    mha_fwd(types.SimpleNamespace(ltrx_mha_fwd=lib.ltrx_mha_fwd_wide), *args)
+    """``mha_fwd`` on the opt-in split-bf16 forward for head widths 65..128"""
+    mha_fwd(lib, *args, entry="ltrx_mha_fwd_wide")
 
 
 def mha_fwd_narrow(lib, *args):
-    """``mha_fwd`` on the opt-in split-bf16 forward for head widths up to 32 (ltrx_mha_fwd_narrow has ltrx_mha_fwd's parameters): the
-    marshalling above against a view of the library whose forward is the narrow entry point, as ``mha_fwd_wide``."""
-    mha_fwd(types.SimpleNamespace(ltrx_mha_fwd=lib.ltrx_mha_fwd_narrow), *args)
+    """``mha_fwd`` on the opt-in split-bf16 forward for head widths up to 32"""
+    mha_fwd(lib, *args, entry="ltrx_mha_fwd_narrow")
 
 
 def mha_bwd_workspace(lib, B, L, h, d_k, mode, like):
     return workspace(lib.ltrx_mha_bwd_workspace_bytes(B, L, h, d_k, mode), like)
 
 
-def mha_bwd(lib, st, q, k, v, kpm, o, do, lse, B, L, h, dq, dk, dv, p, seed, drop_step, cu, order, mode, ws):
+def mha_bwd(lib, st, q, k, v, kpm, o, do, lse, B, L, h, dq, dk, dv, p, seed, drop_step, cu, order, mode, ws, entry="ltrx_mha_bwd"):
+    """``entry``: ltrx_mha_bwd, or the opt-in entry point with its parameters (ltrx_mha_bwd_wide), as ``mha_fwd``"""
+    if entry != "ltrx_mha_bwd":
+        lib = types.SimpleNamespace(ltrx_mha_bwd=getattr(lib, entry))
     check(lib.ltrx_mha_bwd(P(q), P(k), P(v), P(kpm), P(o), P(do), P(lse), B, L, h, q.shape[-1] // h, q.stride(-2), o.stride(-2), P(dq),
                            P(dk), P(dv), dq.stride(-2), float(p), seed, P(drop_step), P(cu), P(order), mode, P(ws), st), "mha_bwd")
 
 
 def mha_bwd_wide(lib, *args):
-    """``mha_bwd`` on the opt-in split-bf16 backward for head widths 65..128 (ltrx_mha_bwd_wide has ltrx_mha_bwd's parameters): the
-    marshalling above against a view of the library whose backward is the wide entry point, as ``mha_fwd_wide``."""
-    mha_bwd(types.SimpleNamespace(ltrx_mha_bwd=lib.ltrx_mha_bwd_wide), *args)
+    """``mha_bwd`` on the opt-in split-bf16 backward for head widths 65..128"""
+    mha_bwd(lib, *args, entry="ltrx_mha_bwd_wide")
 
 
 # ---- LayerNorm (transformer.py:73-81) over rows of x.shape[-1] columns -----------------------------------------------

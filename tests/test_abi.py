@@ -91,6 +91,65 @@ def test_workspace_queries_and_argument_validation_run_without_a_gpu(libpath):
     assert lib.ltrx_mha_fwd(None, None, None, None, 1, 1, 1, 64, 64, None, 64, None, 0.0, 0, None, None, None, 1, None) == -1
 
 
+_MHA_ENTRIES = {"ltrx_mha_fwd": (False, 64), "ltrx_mha_fwd_wide": (False, 96), "ltrx_mha_fwd_narrow": (False, 32),
+                "ltrx_mha_bwd": (True, 64), "ltrx_mha_bwd_wide": (True, 96)}         # name: (backward?, a head width the entry takes)
+
+
+def _mha_rc(lib, entry, null=(), B=2, L=40, h=2, d_k=None, rs=None, ors=None, drs=None, p_drop=0.0, mode=1):
+    """the entry's return code for a call that is valid but for the stated defects; pointers are fake and never dereferenced"""
+    bwd, dk0 = _MHA_ENTRIES[entry]
+    d_k = dk0 if d_k is None else d_k
+    rs, ors, drs = (h * d_k if x is None else x for x in (rs, ors, drs))
+    ptr = lambda name: None if name in null else ctypes.c_void_p(4096)
+    if bwd:
+        return getattr(lib, entry)(ptr("q"), ptr("k"), ptr("v"), ptr("mask"), ptr("o"), ptr("dout"), ptr("lse"), B, L, h, d_k, rs, ors,
+                                   ptr("dq"), ptr("dk"), ptr("dv"), drs, p_drop, 0, None, None, None, mode, ptr("ws"), None)
+    return getattr(lib, entry)(ptr("q"), ptr("k"), ptr("v"), ptr("mask"), B, L, h, d_k, rs, ptr("o"), ors, ptr("lse"), p_drop, 0, None,
+                               None, None, mode, None)
+
+
+# defects that every entry point refuses before any launch, alone and in the pairs that decide which code wins
+_MHA_DEFECTS = [dict(null=("q",)), dict(null=("v",)), dict(null=("mask",)), dict(null=("o",)), dict(null=("lse",)),
+                dict(mode=-1), dict(mode=3), dict(p_drop=-0.1), dict(p_drop=1.0), dict(p_drop=float("nan")),
+                dict(B=0), dict(L=0), dict(h=0), dict(d_k=0), dict(d_k=6), dict(d_k=132), dict(L=128 * 65535 + 1),
+                dict(rs=2 * 64 + 2, d_k=64), dict(rs=2 * 64 - 4, d_k=64), dict(ors=2 * 64 + 2, d_k=64), dict(ors=2 * 64 - 4, d_k=64),
+                dict(mode=3, d_k=6), dict(null=("q",), d_k=6), dict(p_drop=1.0, d_k=132), dict(d_k=0, rs=2), dict(B=0, d_k=6)]
+_MHA_BWD_DEFECTS = [dict(null=("dout",)), dict(null=("dq",)), dict(null=("dv",)), dict(null=("ws",)), dict(drs=2 * 64 + 2, d_k=64),
+                    dict(drs=2 * 64 - 4, d_k=64), dict(mode=3, drs=2), dict(d_k=0, drs=2), dict(d_k=6, drs=2)]
+# the opt-in arms: mode 0 is not theirs, nor are head widths outside their range (wide 65..128, narrow ..32)
+_MHA_ARM_DEFECTS = [dict(mode=0), dict(d_k=64), dict(d_k=64, mode=0), dict(d_k=64, p_drop=1.0), dict(d_k=64, rs=2), dict(d_k=64, drs=2)]
+
+
+def _mha_cases():
+    for entry, (bwd, _) in _MHA_ENTRIES.items():
+        arm = entry.endswith(("_wide", "_narrow"))
+        for kw in _MHA_DEFECTS + (_MHA_BWD_DEFECTS if bwd else []) + (_MHA_ARM_DEFECTS if arm else []):
+            if "drs" in kw and not bwd:
+                continue
+            yield entry, kw
+
+
+# return codes of the library BEFORE the entry points shared their argument checks, in _mha_cases() order (-1 LTRX_EINVAL, -2 LTRX_EUNSUPPORTED)
+_MHA_EXPECTED = [
+    -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -2, -2, -2, -2, -2, -2, -2, -1, -1, -1, -1, -1, -1, -1, -1,
+    -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -2, -2, -2, -2, -2, -2, -2, -1, -1, -1, -1, -1, -1, -2, -1, -1, -2, -1,
+    -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -2, -2, -2, -2, -2, -2, -2, -1, -1, -1, -1, -1, -1, -2, -1, -1,
+    -2, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -2, -2, -2, -2, -2, -2, -2, -1, -1, -1, -1, -1, -1, -1,
+    -1, -1, -2, -2, -1, -1, -2, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -2, -2, -2, -2, -2, -2, -2, -1,
+    -1, -1, -1, -1, -1, -1, -1, -1, -2, -2, -1, -1, -2, -1, -2, -1, -1, -2, -2]
+
+
+def test_attention_entry_points_refuse_bad_arguments_with_the_same_codes(libpath):
+    from allrank_amd import _lib
+    lib = _lib.lib()
+    cases = list(_mha_cases())
+    assert len(cases) == len(_MHA_EXPECTED)
+    got = [_mha_rc(lib, entry, **kw) for entry, kw in cases]
+    wrong = [(entry, kw, g, e) for (entry, kw), g, e in zip(cases, got, _MHA_EXPECTED) if g != e]
+    assert not wrong, wrong
+    assert set(got) == {-1, -2}                        # none of these reached a launch
+
+
 def test_long_slate_loss_workspace_bytes_follow_one_formula(libpath):
     """the four losses that move their per-slate work arrays from LDS to the call's workspace: `per` result floats, then -- only when
     the narr * L + extra work floats of a slate exceed the 159 KB LDS budget -- B blocks of them, each rounded up to 4 floats.

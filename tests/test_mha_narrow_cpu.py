@@ -19,16 +19,16 @@ def test_narrow_fits_truth_table():
 
 
 def test_fit_reads_the_environment_switch(monkeypatch):
-    from allrank_amd.fit import _narrow_heads_mode
+    from allrank_amd.fit import _attention_option
     monkeypatch.delenv("ALLRANK_AMD_NARROW_HEADS", raising=False)
-    assert _narrow_heads_mode(None) is False and _narrow_heads_mode(True) is True
+    assert _attention_option("narrow_heads", None) is False and _attention_option("narrow_heads", True) is True
     monkeypatch.setenv("ALLRANK_AMD_NARROW_HEADS", "0")
-    assert _narrow_heads_mode(None) is False
+    assert _attention_option("narrow_heads", None) is False
     monkeypatch.setenv("ALLRANK_AMD_NARROW_HEADS", "1")
-    assert _narrow_heads_mode(None) is True and _narrow_heads_mode(False) is False      # an explicit argument wins
+    assert _attention_option("narrow_heads", None) is True and _attention_option("narrow_heads", False) is False      # an explicit argument wins
     monkeypatch.setenv("ALLRANK_AMD_NARROW_HEADS", "yes")
     with pytest.raises(ValueError, match="ALLRANK_AMD_NARROW_HEADS"):
-        _narrow_heads_mode(None)
+        _attention_option("narrow_heads", None)
 
 
 def test_meta_carries_the_flag_only_when_it_is_on():

@@ -6,16 +6,16 @@ import pytest
 
 
 def test_fit_reads_the_environment_switch(monkeypatch):
-    from allrank_amd.fit import _wide_backward_mode
+    from allrank_amd.fit import _attention_option
     monkeypatch.delenv("ALLRANK_AMD_WIDE_BACKWARD", raising=False)
-    assert _wide_backward_mode(None) is False and _wide_backward_mode(True) is True
+    assert _attention_option("wide_backward", None) is False and _attention_option("wide_backward", True) is True
     monkeypatch.setenv("ALLRANK_AMD_WIDE_BACKWARD", "0")
-    assert _wide_backward_mode(None) is False
+    assert _attention_option("wide_backward", None) is False
     monkeypatch.setenv("ALLRANK_AMD_WIDE_BACKWARD", "1")
-    assert _wide_backward_mode(None) is True and _wide_backward_mode(False) is False      # an explicit argument wins
+    assert _attention_option("wide_backward", None) is True and _attention_option("wide_backward", False) is False      # an explicit argument wins
     monkeypatch.setenv("ALLRANK_AMD_WIDE_BACKWARD", "yes")
     with pytest.raises(ValueError, match="ALLRANK_AMD_WIDE_BACKWARD"):
-        _wide_backward_mode(None)
+        _attention_option("wide_backward", None)
 
 
 def test_meta_carries_the_flag_only_when_it_is_on():
