@@ -376,6 +376,15 @@ __global__ void __launch_bounds__(256) ltrx_mrr_finalize_kernel(const float* __r
   }
 }
 
+// A slate_order that repeats entries names some slates never: their (best_val, best_idx) are cleared to (0, 0), what an empty slate
+// gives, so the batch sum and the output depend on the visited slates alone.
+__global__ void __launch_bounds__(256) ltrx_mrr_clear_kernel(float* __restrict__ best_val, int* __restrict__ best_idx, int B) {
+  for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < B; b += gridDim.x * blockDim.x) {
+    best_val[b] = 0.f;
+    best_idx[b] = 0;
+  }
+}
+
 extern "C" size_t ltrx_mrr_workspace_bytes(int B, int L, int n_ats) {
   (void)L;
   (void)n_ats;
@@ -386,13 +395,26 @@ extern "C" size_t ltrx_mrr_workspace_bytes(int B, int L, int n_ats) {
 static int mrr_launch(const float* y_pred, const float* y_true, const int32_t* cu, const int32_t* order, int B, int L, const int* ats,
                       int n_ats, float pad_value, float* mrr_out, void* ws, ltrx_stream_t stream) {
   if (!y_pred || !y_true || !ats || !mrr_out || !ws || B <= 0 || L <= 0 || n_ats <= 0) return LTRX_EINVAL;
-  if (n_ats > LTRX_MAX_ATS || L > LTRX_MAX_METRIC_SLATE_LEN) return LTRX_EUNSUPPORTED;   // 8 B of LDS per item: 64 KB at the limit
+  if (n_ats > LTRX_MAX_ATS || L > LTRX_MAX_METRIC_SLATE_LEN) return LTRX_EUNSUPPORTED;
+  // 8 B of LDS per item; above the default allowance (L > 6144) the launch opts in, as ndcg_launch does (ltrx_device.h)
+  if (2 * (size_t)L * sizeof(float) > LTRX_DEFAULT_DYNAMIC_LDS_BYTES) {
+    static std::atomic<uint64_t> attr_done{0};
+    const int arc = ltrx_allow_dynamic_lds(attr_done, {{ltrx_mrr_slate_kernel<false>, 2 * LTRX_MAX_METRIC_SLATE_LEN * sizeof(float)},
+                                                       {ltrx_mrr_slate_kernel<true>, 2 * LTRX_MAX_METRIC_SLATE_LEN * sizeof(float)}});
+    if (arc != LTRX_OK) return arc;
+  }
   hipStream_t s = (hipStream_t)stream;
   float* bv = (float*)ws;
   int* bi = (int*)(bv + B);
   LtrxAts dats;
   dats.n = n_ats;
   for (int i = 0; i < n_ats; ++i) dats.at[i] = ats[i];
+  // only a slate_order can leave a slate unvisited.  The launch costs about 4 us per call (256 slates of 20 .. 240 items, longest first:
+  // median 31.0 us against 27.4 us without a slate_order, 200 calls each, MI355X)
+  if (cu && order) {
+    hipLaunchKernelGGL(ltrx_mrr_clear_kernel, dim3((B + 255) / 256 > 64 ? 64 : (B + 255) / 256), dim3(256), 0, s, bv, bi, B);
+    LTRX_LAUNCH_CHECK();
+  }
   if (cu)
     hipLaunchKernelGGL(ltrx_mrr_slate_kernel<true>, dim3(B), dim3(256), 2 * (size_t)L * sizeof(float), s, y_pred, y_true, L, pad_value,
                        bv, bi, cu, order);

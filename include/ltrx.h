@@ -241,7 +241,8 @@ int ltrx_lambdaloss_fwd_bwd_cu(const float* y_pred, const float* y_true, const i
 int ltrx_ndcg_at_cu(const float* y_pred, const float* y_true, const int32_t* cu_seqlens, const int32_t* slate_order, int B,
                     int max_len, const int* ats, int n_ats, float filler_value, float* ndcg_out, float* dcg_out, int64_t* order_out,
                     void* ws, ltrx_stream_t stream);
-/* the batch-wide rule of metrics.py:108-109 (sum of the slates' maximum labels == 0 -> all zeros) is kept; ws: ltrx_mrr_workspace_bytes */
+/* the batch-wide rule of metrics.py:108-109 (sum of the slates' maximum labels == 0 -> all zeros) is kept; ws: ltrx_mrr_workspace_bytes.
+ * A slate that a repeating slate_order never names counts as an empty one: maximum label 0 at index 0. */
 int ltrx_mrr_at_cu(const float* y_pred, const float* y_true, const int32_t* cu_seqlens, const int32_t* slate_order, int B, int max_len,
                    const int* ats, int n_ats, float* mrr_out, void* ws, ltrx_stream_t stream);
 /* allrank/inference/inference_utils.py:51-56 (padded scores to -inf, sort descending, gather X and y): the slates of a ragged batch in
