@@ -100,7 +100,7 @@ def mha_wide_fits(L, d_k):
 
 
 def mha_narrow_fits(L, d_k):
-    """ltrx_mha_narrow_fits: does ltrx_mha_fwd_narrow take slates of up to ``L`` items at head width ``d_k``?  Host only, launches nothing."""
+    """ltrx_mha_narrow_fits: do ltrx_mha_fwd_narrow / ltrx_mha_bwd_narrow take slates of up to ``L`` items at head width ``d_k``?  Host only, launches nothing."""
     return bool(lib().ltrx_mha_narrow_fits(int(L), int(d_k)))
 
 

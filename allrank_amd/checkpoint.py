@@ -318,6 +318,7 @@ def check_compatible(saved_meta, live_meta):
         raise ValueError("checkpoint: gradient_clipping_norm: stored %r, live %r" % (saved_meta.get("clip"), live_meta.get("clip")))
     from .engine import ATTENTION_ARMS
     for arm in ATTENTION_ARMS:
-        stored, live = bool(saved_meta.get(arm.option)), bool(live_meta.get(arm.option))      # (the key exists only where the option is on)
+        # (the key exists only where the option is on; narrow_heads is True or "both", which differ: another backward)
+        stored, live = saved_meta.get(arm.option) or False, live_meta.get(arm.option) or False
         if stored != live:
             raise ValueError("checkpoint: %s (%s): stored %r, live %r" % (arm.option, arm.what, stored, live))

@@ -643,3 +643,17 @@ extern "C" int ltrx_mha_bwd_wide(const float* q, const float* k, const float* v,
   return ltrx_mha_bwd_wide_launch(q, k, v, key_pad_mask, o, dout, lse, B, L, h, d_k, row_stride, o_row_stride, dq, dk, dv, d_row_stride,
                                   (float*)ws, p_drop, seed, seed_step, cu_seqlens, slate_order, mode == 2, (hipStream_t)stream);
 }
+
+// The opt-in backward for narrow heads (ltrx_mha_narrow.hip): ltrx_mha_bwd's arguments and checks, modes 1 / 2 only, and only the
+// shapes ltrx_mha_narrow_fits takes.  `ws` is the B L h floats (delta) ltrx_mha_bwd_workspace_bytes returns at these widths.
+// ltrx_mha_bwd itself keeps sending these widths to the exact kernels above.
+extern "C" int ltrx_mha_bwd_narrow(const float* q, const float* k, const float* v, const uint8_t* key_pad_mask, const float* o,
+                                   const float* dout, const float* lse, int B, int L, int h, int d_k, int row_stride,
+                                   int o_row_stride, float* dq, float* dk, float* dv, int d_row_stride, float p_drop,
+                                   uint32_t seed, const uint32_t* seed_step, const int32_t* cu_seqlens, const int32_t* slate_order,
+                                   int mode, void* ws, ltrx_stream_t stream) {
+  const int rc = mha_bwd_check(LTRX_MHA_BWD_PTRS, p_drop, mode, 1, B, L, h, d_k, row_stride, o_row_stride, d_row_stride, ltrx_mha_narrow_fits);
+  if (rc != LTRX_OK) return rc;
+  return ltrx_mha_bwd_narrow_launch(q, k, v, key_pad_mask, o, dout, lse, B, L, h, d_k, row_stride, o_row_stride, dq, dk, dv, d_row_stride,
+                                    (float*)ws, p_drop, seed, seed_step, cu_seqlens, slate_order, mode == 2, (hipStream_t)stream);
+}

@@ -29,6 +29,10 @@ int ltrx_mha_bwd_wide_launch(const float* q, const float* k, const float* v, con
                              const float* lse, int B, int L, int h, int dk, int rs, int ors, float* dq, float* dkk, float* dv, int drs,
                              float* delta, float p_drop, uint32_t seed, const uint32_t* seed_step, const int* cu, const int* order,
                              bool plain, hipStream_t s);
+int ltrx_mha_bwd_narrow_launch(const float* q, const float* k, const float* v, const uint8_t* kpm, const float* o, const float* dout,
+                               const float* lse, int B, int L, int h, int dk, int rs, int ors, float* dq, float* dkk, float* dv, int drs,
+                               float* delta, float p_drop, uint32_t seed, const uint32_t* seed_step, const int* cu, const int* order,
+                               bool plain, hipStream_t s);
 
 #define LTRX_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
 

@@ -37,6 +37,10 @@ ATTENTION_ARMS = (
     AttentionArm("narrow_heads", "ALLRANK_AMD_NARROW_HEADS", "forward", "narrow", "mha_narrow_fits", KN.mha_fwd_narrow,
                  "the split-bf16 attention forward for head widths up to 32"),
 )
+# The backward of narrow heads has no option of its own: it is the value "both" of ``narrow_heads`` (True = the forward alone), so
+# it is a record next to the table and not a row of it.
+NARROW_BACKWARD = AttentionArm("narrow_heads", "ALLRANK_AMD_NARROW_HEADS", "backward", "narrow", "mha_narrow_fits", KN.mha_bwd_narrow,
+                               "the split-bf16 attention backward for head widths up to 32")
 
 # The step's operands, made once by FusedTrainer.__init__ (the flat buffers are never rebound, so a view or an address stays right):
 #   Param  one per nn.Parameter, ``FusedTrainer.params`` in flat-buffer order: its name, the parameter, its offset, and the views of
@@ -469,7 +473,11 @@ class FusedTrainer(object):
         the training forward, ``score()`` and every FusedScorer -- runs the split-bf16 kernel of ltrx_mha_fwd_narrow instead of the exact
         fp32 arm ltrx_mha_fwd has for these widths; the backward keeps the exact kernels (same lse and dropout conventions).  A switch
         because it rounds differently from the exact arm.  ``self.attention_forward`` is "narrow" where it applies; ``meta()`` carries
-        "narrow_heads" only when the option is on."""
+        "narrow_heads" only when the option is on.
+        narrow_heads="both": that forward, and the attention BACKWARD at those head widths -- in the padded, compact and captured steps
+        alike -- on the split-bf16 kernels of ltrx_mha_bwd_narrow (P recomputed from the saved lse, same dropout draw) instead of the
+        exact fp32 arm of ltrx_mha_bwd.  ``self.attention_backward`` is then "narrow" where it applies and ``meta()["narrow_heads"]``
+        is "both": a checkpoint of a True run does not resume under "both", nor the other way round.  Any other value raises."""
         from . import _lib as LB
         from .losses import FusedLoss
         self.LB = LB
@@ -490,8 +498,12 @@ class FusedTrainer(object):
         # 1 = three bf16 products (fp32-class, parity), 2 = one product (the "bf16" throughput mode)
         self._mha_mode = 2 if gemm == "bf16" else 1
         given = locals()
+        if narrow_heads not in (False, True, "both"):
+            raise ValueError("FusedTrainer: narrow_heads must be False, True or 'both', got %r" % (narrow_heads,))
         for arm in ATTENTION_ARMS:            # self.wide_heads, self.wide_backward, self.narrow_heads
             setattr(self, arm.option, bool(given[arm.option]))
+        if narrow_heads == "both":            # (True: the forward alone; "both": NARROW_BACKWARD as well)
+            self.narrow_heads = "both"
         self.model = model
         self.B, self.L, self.M = B, L, B * L
         self.lr, self.betas, self.eps = lr, betas, eps
@@ -1175,11 +1187,13 @@ class FusedTrainer(object):
 
     def _attention_arm(self, direction, L):
         """the row of ATTENTION_ARMS whose kernel runs the attention ``direction`` ("forward" / "backward") of slates up to ``L`` items,
-        or None for the default kernels: the first row of that direction that is switched on and whose head width and L fit"""
+        or None for the default kernels: the first row of that direction that is switched on and whose head width and L fit, then
+        NARROW_BACKWARD under ``narrow_heads="both"``"""
         if not self.N or self._mha_mode == 0:
             return None
-        for arm in ATTENTION_ARMS:
-            if arm.direction == direction and getattr(self, arm.option) and getattr(self.LB, arm.fits)(L, self.d // self.h):
+        for arm in ATTENTION_ARMS + (NARROW_BACKWARD,):
+            on = self.narrow_heads == "both" if arm is NARROW_BACKWARD else getattr(self, arm.option)
+            if arm.direction == direction and on and getattr(self.LB, arm.fits)(L, self.d // self.h):
                 return arm
         return None
 
@@ -1431,7 +1445,7 @@ class FusedTrainer(object):
                             self.clip)
         for arm in ATTENTION_ARMS:            # (only when on: a run without the option writes the block it always wrote)
             if getattr(self, arm.option, False):
-                meta[arm.option] = True
+                meta[arm.option] = getattr(self, arm.option)      # True, or "both" for narrow_heads
         return meta
 
     def state_dict(self):

@@ -259,14 +259,22 @@ def _compact_mode(compact):
 
 def _attention_option(option, value):
     """fit()'s ``wide_heads`` / ``wide_backward`` / ``narrow_heads`` argument resolved: None reads the variable engine.ATTENTION_ARMS
-    names for ``option`` ("1" = on; unset, "" or "0" = off; anything else raises), so that an unmodified main.py can opt in"""
+    names for ``option`` ("1" = on; unset, "" or "0" = off; anything else raises), so that an unmodified main.py can opt in.
+    ``narrow_heads`` alone has a third value, "both" (the variable: ``both``): the narrow backward as well as the forward."""
     from .engine import ATTENTION_ARMS
     name = next(arm.env for arm in ATTENTION_ARMS if arm.option == option)
+    both = option == "narrow_heads"
     if value is None:
         env = os.environ.get(name, "")
+        if both and env == "both":
+            return "both"
         if env not in ("", "0", "1"):
-            raise ValueError("%s must be '1', '0' or unset, got %r" % (name, env))
+            raise ValueError("%s must be '1', '0'%s or unset, got %r" % (name, ", 'both'" if both else "", env))
         return env == "1"
+    if isinstance(value, str) and value == "both":
+        if not both:
+            raise ValueError("%s must be True or False, got %r" % (option, value))
+        return "both"
     return bool(value)
 
 
@@ -485,7 +493,9 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
     wide_backward=True (None: ALLRANK_AMD_WIDE_BACKWARD=1): FusedTrainer(wide_backward=True) -- the split-bf16 attention backward for
     the same head widths, independent of ``wide_heads``; ``last_run["attention_backward"]`` = "wide" | "default", only under the option;
     narrow_heads=True (None: ALLRANK_AMD_NARROW_HEADS=1): FusedTrainer(narrow_heads=True) -- the split-bf16 attention forward for head
-    widths up to 32, independent of both; ``last_run["attention_forward"]`` = "narrow" | "default" (| "wide"), only under an option."""
+    widths up to 32, independent of both; ``last_run["attention_forward"]`` = "narrow" | "default" (| "wide"), only under an option;
+    narrow_heads="both" (ALLRANK_AMD_NARROW_HEADS=both): FusedTrainer(narrow_heads="both") -- that forward and the split-bf16 attention
+    backward for the same head widths; ``last_run["attention_backward"]`` = "narrow" | "default" as well."""
     import torch.distributed as dist
     device = torch.device(device)
     world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
@@ -553,7 +563,7 @@ def fit(epochs, model, loss_func, optimizer, scheduler, train_dl, valid_dl, conf
                     compact_graph=_compact_graph_stats(trainer), compact_graph_reason=cg_reason)
     if wide_heads or narrow_heads:            # (only under an option: a run without it reports what it always did)
         last_run["attention_forward"] = getattr(trainer, "attention_forward", "default")
-    if wide_backward:
+    if wide_backward or narrow_heads == "both":
         last_run["attention_backward"] = getattr(trainer, "attention_backward", "default")
     log.info("allrank_amd.fit: %s step%s", last_run["engine"], (" (" + reason + ")") if reason else "")
     normalizer = getattr(getattr(train_dl, "dataset", None), "normalizer", None)      # load_libsvm_dataset(normalize=...) hung it there

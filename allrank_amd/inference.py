@@ -33,7 +33,8 @@ fused ``rank_slates`` ran.  A switch for the same reason: the scores round diffe
 
 NARROW HEADS.  ``allrank_amd.inference.narrow_heads = True`` (or ``Ranker(model, narrow_heads=True)``) does the same with
 ``FusedTrainer(narrow_heads=True)`` for head widths up to 32 (ltrx_mha_fwd_narrow; ``last_run["attention_forward"]`` "narrow" |
-"default").  Independent of ``wide_heads``.
+"default").  Independent of ``wide_heads``.  The trainer's ``narrow_heads="both"`` (the narrow backward too) is read as True here:
+ranking runs no backward.
 
 A model with a positional encoding is scored with ``indices = ones`` for every item (inference_utils.py:47): a quirk of the
 reference, reproduced.

@@ -79,7 +79,7 @@ def mha_bwd_workspace(lib, B, L, h, d_k, mode, like):
 
 
 def mha_bwd(lib, st, q, k, v, kpm, o, do, lse, B, L, h, dq, dk, dv, p, seed, drop_step, cu, order, mode, ws, entry="ltrx_mha_bwd"):
-    """``entry``: ltrx_mha_bwd, or the opt-in entry point with its parameters (ltrx_mha_bwd_wide), as ``mha_fwd``"""
+    """``entry``: ltrx_mha_bwd, or an opt-in entry point with its parameters (ltrx_mha_bwd_wide, ltrx_mha_bwd_narrow), as ``mha_fwd``"""
     if entry != "ltrx_mha_bwd":
         lib = types.SimpleNamespace(ltrx_mha_bwd=getattr(lib, entry))
     check(lib.ltrx_mha_bwd(P(q), P(k), P(v), P(kpm), P(o), P(do), P(lse), B, L, h, q.shape[-1] // h, q.stride(-2), o.stride(-2), P(dq),
@@ -89,6 +89,11 @@ def mha_bwd(lib, st, q, k, v, kpm, o, do, lse, B, L, h, dq, dk, dv, p, seed, dro
 def mha_bwd_wide(lib, *args):
     """``mha_bwd`` on the opt-in split-bf16 backward for head widths 65..128"""
     mha_bwd(lib, *args, entry="ltrx_mha_bwd_wide")
+
+
+def mha_bwd_narrow(lib, *args):
+    """``mha_bwd`` on the opt-in split-bf16 backward for head widths up to 32"""
+    mha_bwd(lib, *args, entry="ltrx_mha_bwd_narrow")
 
 
 # ---- LayerNorm (transformer.py:73-81) over rows of x.shape[-1] columns -----------------------------------------------

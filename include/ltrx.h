@@ -407,8 +407,14 @@ int ltrx_mha_fwd_wide(const float* q, const float* k, const float* v, const uint
  * groups by four-wave workgroups of 128 queries (ltrx_mha_narrow.hip), any slate length, both layouts, dropout included.  Parameters,
  * argument checks and conventions (lse, dropout draw, fully padded slates = exact zeros) are ltrx_mha_fwd's.  mode must be 1 or 2
  * (anything else: LTRX_EINVAL); a shape ltrx_mha_narrow_fits refuses returns LTRX_EUNSUPPORTED; a refused call launches nothing and
- * writes nothing.  Its o / lse feed ltrx_mha_bwd of the same mode (the exact kernels at these widths).  A separate entry point, not
- * a dispatch arm, because it rounds differently from the exact kernels (within the same split-bf16 bound as 32 < d_k <= 64).
+ * writes nothing.  Its o / lse feed ltrx_mha_bwd of the same mode (the exact kernels at these widths) and ltrx_mha_bwd_narrow
+ * (below) alike.  A separate entry point, not a dispatch arm, because it rounds differently from the exact kernels (within the same
+ * split-bf16 bound as 32 < d_k <= 64).
+ * ltrx_mha_bwd_narrow (declared after ltrx_mha_bwd_wide) is the opt-in BACKWARD for the same widths: a dQ kernel and a dK/dV kernel
+ * on the same ring, groups and arithmetic; P is recomputed from lse.  ltrx_mha_bwd's parameters and checks, mode 1 or 2, the shapes
+ * ltrx_mha_narrow_fits takes; `ws` is the B L h floats ltrx_mha_bwd_workspace_bytes returns at these widths (delta), nothing behind
+ * them is written.  It takes o / lse of ltrx_mha_fwd_narrow or of ltrx_mha_fwd of the same mode.  A refused call launches and writes
+ * nothing.
  * ltrx_mha_narrow_fits: 1 for L > 0, 0 < d_k <= 32, d_k % 4 == 0 and ceil(L / 128) within the grid limit, else 0.  Host only. */
 int ltrx_mha_narrow_fits(int L, int d_k);
 int ltrx_mha_fwd_narrow(const float* q, const float* k, const float* v, const uint8_t* key_pad_mask, int B, int L, int h,
@@ -433,6 +439,11 @@ int ltrx_mha_bwd_wide(const float* q, const float* k, const float* v, const uint
                       float* dq, float* dk, float* dv, int d_row_stride, float p_drop, uint32_t seed,
                       const uint32_t* seed_step, const int32_t* cu_seqlens, const int32_t* slate_order, int mode, void* ws,
                       ltrx_stream_t stream);
+int ltrx_mha_bwd_narrow(const float* q, const float* k, const float* v, const uint8_t* key_pad_mask, const float* o,
+                        const float* dout, const float* lse, int B, int L, int h, int d_k, int row_stride, int o_row_stride,
+                        float* dq, float* dk, float* dv, int d_row_stride, float p_drop, uint32_t seed,
+                        const uint32_t* seed_step, const int32_t* cu_seqlens, const int32_t* slate_order, int mode, void* ws,
+                        ltrx_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Training-step glue (allrank/training/train_utils.py:18-29 around the model): the pieces between the library
