@@ -104,6 +104,11 @@ def mha_narrow_fits(L, d_k):
     return bool(lib().ltrx_mha_narrow_fits(int(L), int(d_k)))
 
 
+def mha_xwide_fits(L, d_k):
+    """ltrx_mha_xwide_fits: do ltrx_mha_fwd_xwide / ltrx_mha_bwd_xwide take slates of up to ``L`` items at head width ``d_k`` (132..256)?  Host only, launches nothing."""
+    return bool(lib().ltrx_mha_xwide_fits(int(L), int(d_k)))
+
+
 def check(rc, what):
     if rc != 0:
         kinds = {-1: "invalid argument",

@@ -492,9 +492,10 @@ extern "C" int ltrx_selftest_mfma32x32x2(const float* A, const float* Bm, float*
 //   mode 0: exact fp32 MFMA (v_mfma_f32_32x32x2_f32, bit-exact fp32 products) for every shape -- the strict reference.
 //   mode 2: the kernels of mode 1 with ONE bf16 product per contraction (plain bf16 operands, fp32 accumulate and softmax):
 //           the throughput mode, about 2^-9 relative error per product -- NOT the parity arithmetic.
-static int mha_check(int B, int L, int h, int dk, int rs, int ors) {
+// (dk_max: 128 for every entry point but the extra-wide pair, whose own `fits` then narrows 1..256 to 132..256)
+static int mha_check(int B, int L, int h, int dk, int rs, int ors, int dk_max = 128) {
   if (B <= 0 || L <= 0 || h <= 0 || dk <= 0) return LTRX_EINVAL;
-  if (dk % 4 != 0 || dk > 128 || rs % 4 != 0 || ors % 4 != 0 || rs < h * dk || ors < h * dk) return LTRX_EUNSUPPORTED;
+  if (dk % 4 != 0 || dk > dk_max || rs % 4 != 0 || ors % 4 != 0 || rs < h * dk || ors < h * dk) return LTRX_EUNSUPPORTED;
   if ((long long)B * h > 0x7fffffffLL || (L + 127) / 128 > 65535) return LTRX_EUNSUPPORTED;
   return LTRX_OK;
 }
@@ -504,16 +505,17 @@ extern "C" int ltrx_mha_head_width_supported(int d_k) { return mha_check(1, 1, 1
 // The argument checks every forward / backward entry point opens with, in the order that decides which code wins: null pointers and
 // p_drop, then the mode (lowest allowed: 0 for ltrx_mha_fwd / ltrx_mha_bwd, 1 for the opt-in arms), then the shape (mha_check), then
 // -- opt-in arms only -- the arm's own `fits`.
-static int mha_fwd_check(bool ptrs, float p_drop, int mode, int mode_lo, int B, int L, int h, int dk, int rs, int ors, int (*fits)(int, int)) {
+static int mha_fwd_check(bool ptrs, float p_drop, int mode, int mode_lo, int B, int L, int h, int dk, int rs, int ors, int (*fits)(int, int),
+                         int dk_max = 128) {
   if (!ptrs || !(p_drop >= 0.f) || p_drop >= 1.f) return LTRX_EINVAL;
   if (mode < mode_lo || mode > 2) return LTRX_EINVAL;
-  const int rc = mha_check(B, L, h, dk, rs, ors);
+  const int rc = mha_check(B, L, h, dk, rs, ors, dk_max);
   if (rc != LTRX_OK) return rc;
   return (fits && !fits(L, dk)) ? LTRX_EUNSUPPORTED : LTRX_OK;
 }
 static int mha_bwd_check(bool ptrs, float p_drop, int mode, int mode_lo, int B, int L, int h, int dk, int rs, int ors, int drs,
-                         int (*fits)(int, int)) {
-  const int rc = mha_fwd_check(ptrs, p_drop, mode, mode_lo, B, L, h, dk, rs, ors, nullptr);
+                         int (*fits)(int, int), int dk_max = 128) {
+  const int rc = mha_fwd_check(ptrs, p_drop, mode, mode_lo, B, L, h, dk, rs, ors, nullptr, dk_max);
   if (rc != LTRX_OK) return rc;
   if (drs % 4 != 0 || drs < h * dk) return LTRX_EUNSUPPORTED;
   return (fits && !fits(L, dk)) ? LTRX_EUNSUPPORTED : LTRX_OK;
@@ -577,6 +579,19 @@ extern "C" int ltrx_mha_fwd_narrow(const float* q, const float* k, const float* 
   if (rc != LTRX_OK) return rc;
   return ltrx_mha_fwd_narrow_launch(q, k, v, key_pad_mask, B, L, h, d_k, row_stride, o, o_row_stride, lse_out, p_drop, seed, seed_step,
                                     cu_seqlens, slate_order, mode == 2, (hipStream_t)stream);
+}
+
+// The forward for extra-wide heads (ltrx_mha_xwide.hip), 128 < d_k <= 256: the only kernels at these widths -- ltrx_mha_fwd and the
+// entries above keep refusing them.  ltrx_mha_fwd's arguments and checks (with the width ceiling at 256), modes 1 / 2 only, and only
+// the shapes ltrx_mha_xwide_fits takes.
+extern "C" int ltrx_mha_fwd_xwide(const float* q, const float* k, const float* v, const uint8_t* key_pad_mask, int B, int L,
+                                  int h, int d_k, int row_stride, float* o, int o_row_stride, float* lse_out, float p_drop,
+                                  uint32_t seed, const uint32_t* seed_step, const int32_t* cu_seqlens, const int32_t* slate_order,
+                                  int mode, ltrx_stream_t stream) {
+  const int rc = mha_fwd_check(LTRX_MHA_FWD_PTRS, p_drop, mode, 1, B, L, h, d_k, row_stride, o_row_stride, ltrx_mha_xwide_fits, 256);
+  if (rc != LTRX_OK) return rc;
+  return ltrx_mha_fwd_xwide_launch(q, k, v, key_pad_mask, B, L, h, d_k, row_stride, o, o_row_stride, lse_out, p_drop, seed, seed_step,
+                                   cu_seqlens, slate_order, mode == 2, (hipStream_t)stream);
 }
 
 // The split-bf16 backward hands dS[B, h, LK, LK] (LK = L rounded up to 64) from its dK/dV kernel to its dQ kernel through the
@@ -656,4 +671,18 @@ extern "C" int ltrx_mha_bwd_narrow(const float* q, const float* k, const float* 
   if (rc != LTRX_OK) return rc;
   return ltrx_mha_bwd_narrow_launch(q, k, v, key_pad_mask, o, dout, lse, B, L, h, d_k, row_stride, o_row_stride, dq, dk, dv, d_row_stride,
                                     (float*)ws, p_drop, seed, seed_step, cu_seqlens, slate_order, mode == 2, (hipStream_t)stream);
+}
+
+// The backward for extra-wide heads (ltrx_mha_xwide.hip), 128 < d_k <= 256: ltrx_mha_bwd's arguments and checks (width ceiling 256),
+// modes 1 / 2 only, the shapes ltrx_mha_xwide_fits takes.  `ws` is the B L h floats (delta) ltrx_mha_bwd_workspace_bytes returns at
+// these widths.
+extern "C" int ltrx_mha_bwd_xwide(const float* q, const float* k, const float* v, const uint8_t* key_pad_mask, const float* o,
+                                  const float* dout, const float* lse, int B, int L, int h, int d_k, int row_stride,
+                                  int o_row_stride, float* dq, float* dk, float* dv, int d_row_stride, float p_drop,
+                                  uint32_t seed, const uint32_t* seed_step, const int32_t* cu_seqlens, const int32_t* slate_order,
+                                  int mode, void* ws, ltrx_stream_t stream) {
+  const int rc = mha_bwd_check(LTRX_MHA_BWD_PTRS, p_drop, mode, 1, B, L, h, d_k, row_stride, o_row_stride, d_row_stride, ltrx_mha_xwide_fits, 256);
+  if (rc != LTRX_OK) return rc;
+  return ltrx_mha_bwd_xwide_launch(q, k, v, key_pad_mask, o, dout, lse, B, L, h, d_k, row_stride, o_row_stride, dq, dk, dv, d_row_stride,
+                                   (float*)ws, p_drop, seed, seed_step, cu_seqlens, slate_order, mode == 2, (hipStream_t)stream);
 }

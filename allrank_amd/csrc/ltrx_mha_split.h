@@ -8,7 +8,8 @@
 #pragma once
 #include "ltrx_mfma.h"
 
-// ---- host: the launchers and shape predicates ltrx_mha.hip's C entry points dispatch to (defined in the file the name says) ----
+// ---- host: the launchers and shape predicates ltrx_mha.hip's C entry points dispatch to (defined in the file the name says;
+// ltrx_mha_xwide.hip, 128 < d_k <= 256, is the fourth user of this vocabulary) ----
 bool ltrx_mha_res_fits(int L, int dk);
 bool ltrx_mha_res_bwd_fits(int L, int dk);
 size_t ltrx_mha_res_bwd_ws_bytes(int B, int L, int h);
@@ -33,6 +34,13 @@ int ltrx_mha_bwd_narrow_launch(const float* q, const float* k, const float* v, c
                                const float* lse, int B, int L, int h, int dk, int rs, int ors, float* dq, float* dkk, float* dv, int drs,
                                float* delta, float p_drop, uint32_t seed, const uint32_t* seed_step, const int* cu, const int* order,
                                bool plain, hipStream_t s);
+int ltrx_mha_fwd_xwide_launch(const float* q, const float* k, const float* v, const uint8_t* kpm, int B, int L, int h, int dk, int rs,
+                              float* o, int ors, float* lse, float p_drop, uint32_t seed, const uint32_t* seed_step, const int* cu,
+                              const int* order, bool plain, hipStream_t s);
+int ltrx_mha_bwd_xwide_launch(const float* q, const float* k, const float* v, const uint8_t* kpm, const float* o, const float* dout,
+                              const float* lse, int B, int L, int h, int dk, int rs, int ors, float* dq, float* dkk, float* dv, int drs,
+                              float* delta, float p_drop, uint32_t seed, const uint32_t* seed_step, const int* cu, const int* order,
+                              bool plain, hipStream_t s);
 
 #define LTRX_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
 

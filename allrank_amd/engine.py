@@ -41,6 +41,12 @@ ATTENTION_ARMS = (
 # it is a record next to the table and not a row of it.
 NARROW_BACKWARD = AttentionArm("narrow_heads", "ALLRANK_AMD_NARROW_HEADS", "backward", "narrow", "mha_narrow_fits", KN.mha_bwd_narrow,
                                "the split-bf16 attention backward for head widths up to 32")
+# Head widths 132..256 have one kernel family and no other to opt out of: no option, no variable, no row of the table -- where the width
+# fits, these two records ARE the attention (``option`` / ``env`` None).
+XWIDE_ARMS = (AttentionArm(None, None, "forward", "xwide", "mha_xwide_fits", KN.mha_fwd_xwide,
+                           "the split-bf16 attention forward for head widths 132..256"),
+              AttentionArm(None, None, "backward", "xwide", "mha_xwide_fits", KN.mha_bwd_xwide,
+                           "the split-bf16 attention backward for head widths 132..256"))
 
 # The step's operands, made once by FusedTrainer.__init__ (the flat buffers are never rebound, so a view or an address stays right):
 #   Param  one per nn.Parameter, ``FusedTrainer.params`` in flat-buffer order: its name, the parameter, its offset, and the views of
@@ -700,9 +706,14 @@ class FusedTrainer(object):
         if self.N:
             if self.dff % 4:
                 raise NotImplementedError("FusedTrainer: feed-forward width d_ff = %d is no multiple of 4" % self.dff)
-            if self.d % self.h or not self.lib.ltrx_mha_head_width_supported(self.d // self.h):
+            # 132..256: ltrx_mha_fwd_xwide / ltrx_mha_bwd_xwide (a narrower model makes the calls to the library it always made)
+            xwide = not self.d % self.h and self.d // self.h > 128 and self.LB.mha_xwide_fits(1, self.d // self.h)
+            if xwide and self._mha_mode == 0:
+                raise NotImplementedError("FusedTrainer: head width d_model / h = %d / %d -- above 128 only the split-bf16 kernels exist, "
+                                          "and the exact attention arithmetic (mode 0) has none" % (self.d, self.h))
+            if self.d % self.h or not (xwide or self.lib.ltrx_mha_head_width_supported(self.d // self.h)):
                 raise NotImplementedError("FusedTrainer: head width d_model / h = %d / %d -- the attention kernels take head widths that "
-                                          "are multiples of 4 up to 128" % (self.d, self.h))
+                                          "are multiples of 4 up to 256" % (self.d, self.h))
         if self.in_norm is not None and self.fc_sizes[0] < 2:
             raise NotImplementedError("FusedTrainer: input_norm over %d feature (ltrx_layernorm_bwd needs at least 2 columns)" % self.fc_sizes[0])
 
@@ -1186,11 +1197,15 @@ class FusedTrainer(object):
         q.clear()
 
     def _attention_arm(self, direction, L):
-        """the row of ATTENTION_ARMS whose kernel runs the attention ``direction`` ("forward" / "backward") of slates up to ``L`` items,
-        or None for the default kernels: the first row of that direction that is switched on and whose head width and L fit, then
-        NARROW_BACKWARD under ``narrow_heads="both"``"""
+        """the AttentionArm record whose kernel runs the attention ``direction`` ("forward" / "backward") of slates up to ``L`` items, or
+        None for the default kernels: at head widths 132..256 the record of XWIDE_ARMS (always; its ``option`` and ``env`` are None --
+        callers read ``arm`` and ``call`` only); otherwise the first row of ATTENTION_ARMS of that direction that is switched on and
+        whose head width and L fit, then NARROW_BACKWARD under ``narrow_heads="both"``"""
         if not self.N or self._mha_mode == 0:
             return None
+        for arm in XWIDE_ARMS:                # (no switch: the only kernels at these widths; narrower models never ask the library)
+            if arm.direction == direction and self.d // self.h > 128 and getattr(self.LB, arm.fits)(L, self.d // self.h):
+                return arm
         for arm in ATTENTION_ARMS + (NARROW_BACKWARD,):
             on = self.narrow_heads == "both" if arm is NARROW_BACKWARD else getattr(self, arm.option)
             if arm.direction == direction and on and getattr(self.LB, arm.fits)(L, self.d // self.h):

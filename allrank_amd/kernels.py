@@ -74,6 +74,11 @@ def mha_fwd_narrow(lib, *args):
     mha_fwd(lib, *args, entry="ltrx_mha_fwd_narrow")
 
 
+def mha_fwd_xwide(lib, *args):
+    """``mha_fwd`` on the split-bf16 forward for head widths 132..256, the only kernel at those widths"""
+    mha_fwd(lib, *args, entry="ltrx_mha_fwd_xwide")
+
+
 def mha_bwd_workspace(lib, B, L, h, d_k, mode, like):
     return workspace(lib.ltrx_mha_bwd_workspace_bytes(B, L, h, d_k, mode), like)
 
@@ -94,6 +99,11 @@ def mha_bwd_wide(lib, *args):
 def mha_bwd_narrow(lib, *args):
     """``mha_bwd`` on the opt-in split-bf16 backward for head widths up to 32"""
     mha_bwd(lib, *args, entry="ltrx_mha_bwd_narrow")
+
+
+def mha_bwd_xwide(lib, *args):
+    """``mha_bwd`` on the split-bf16 backward for head widths 132..256"""
+    mha_bwd(lib, *args, entry="ltrx_mha_bwd_xwide")
 
 
 # ---- LayerNorm (transformer.py:73-81) over rows of x.shape[-1] columns -----------------------------------------------

@@ -421,6 +421,23 @@ int ltrx_mha_fwd_narrow(const float* q, const float* k, const float* v, const ui
                         int d_k, int row_stride, float* o, int o_row_stride, float* lse_out, float p_drop, uint32_t seed,
                         const uint32_t* seed_step, const int32_t* cu_seqlens, const int32_t* slate_order, int mode,
                         ltrx_stream_t stream);
+/* Forward for EXTRA-WIDE heads, 128 < d_k <= 256 (d_k % 4 == 0), which ltrx_mha_fwd and the entries above refuse
+ * (ltrx_mha_head_width_supported stays 0 there): the split-bf16 arithmetic of modes 1 / 2 on a kernel that streams K and V through a
+ * two-slot ring of 32-key tiles in LDS and splits the head's COLUMNS across a pair of waves, which exchange their halves of Q K^T
+ * through LDS (ltrx_mha_xwide.hip); any slate length, both layouts, dropout included.  Parameters, argument checks and conventions
+ * (lse, dropout draw and seed step, fully padded slates = exact zeros) are ltrx_mha_fwd's.  mode must be 1 or 2 (anything else, the
+ * exact mode 0 included: LTRX_EINVAL); a width outside 132..256 or a shape ltrx_mha_xwide_fits refuses returns LTRX_EUNSUPPORTED; a
+ * refused call launches nothing and writes nothing.
+ * ltrx_mha_bwd_xwide (declared after ltrx_mha_bwd_narrow) is the BACKWARD for the same widths: a dQ kernel and a dK/dV kernel on the
+ * same ring, column split and arithmetic; P is recomputed from lse; no atomics, deterministic.  ltrx_mha_bwd's parameters and checks,
+ * mode 1 or 2; `ws` is the B L h floats ltrx_mha_bwd_workspace_bytes returns at these widths (delta), nothing behind them is
+ * written.  A refused call launches and writes nothing.
+ * ltrx_mha_xwide_fits: 1 for L > 0, 128 < d_k <= 256, d_k % 4 == 0 and ceil(L / 64) within the grid limit, else 0.  Host only. */
+int ltrx_mha_xwide_fits(int L, int d_k);
+int ltrx_mha_fwd_xwide(const float* q, const float* k, const float* v, const uint8_t* key_pad_mask, int B, int L, int h,
+                       int d_k, int row_stride, float* o, int o_row_stride, float* lse_out, float p_drop, uint32_t seed,
+                       const uint32_t* seed_step, const int32_t* cu_seqlens, const int32_t* slate_order, int mode,
+                       ltrx_stream_t stream);
 /* backward: dq,dk,dv from do.  `ws` holds delta[B,h,L] (rowsum(do*o)) for the exact kernels, or -- in modes 1 / 2 where the
  * LDS-resident kernels run (32 < d_k <= 64, L <= LTRX_MAX_SLATE_LEN) -- the dS exchange between the two backward kernels,
  * B*h*LK*LK floats with LK = L rounded up to 64: S, P, dP and delta are computed once, by the dK/dV kernel, which hands dS to a
@@ -444,6 +461,11 @@ int ltrx_mha_bwd_narrow(const float* q, const float* k, const float* v, const ui
                         float* dq, float* dk, float* dv, int d_row_stride, float p_drop, uint32_t seed,
                         const uint32_t* seed_step, const int32_t* cu_seqlens, const int32_t* slate_order, int mode, void* ws,
                         ltrx_stream_t stream);
+int ltrx_mha_bwd_xwide(const float* q, const float* k, const float* v, const uint8_t* key_pad_mask, const float* o,
+                       const float* dout, const float* lse, int B, int L, int h, int d_k, int row_stride, int o_row_stride,
+                       float* dq, float* dk, float* dv, int d_row_stride, float p_drop, uint32_t seed,
+                       const uint32_t* seed_step, const int32_t* cu_seqlens, const int32_t* slate_order, int mode, void* ws,
+                       ltrx_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Training-step glue (allrank/training/train_utils.py:18-29 around the model): the pieces between the library
